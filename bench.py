@@ -6,7 +6,7 @@ in HBM -> tile-bucketed endpoint records -> LDS difference arrays / prefix sums 
 -> lambda (-> control scaling) -> log-normal -log10 p (-> Fisher over replicates) (-> BH q) -> peak
 sweep -> peak list on the host.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
     --config 2  hg38, 50 M paired fragments, treatment only, -p 0.01          (configs[1], the headline; default)
     --config 3  + a 50 M-fragment uniform control, -q 0.05                    (configs[2])
     --config 4  ATAC -j -d 100 cut-site intervals + -s multimapping weights   (configs[3])
@@ -16,7 +16,13 @@ sweep -> peak list on the host.
          and (with -q) the p-value table, done by the library itself with RCCL on device buffers.
          The genome is fixed, per-GPU work shrinks with N -> "scaling": "strong".
 
-Prints ONE JSON line (rank 0).  Besides the contract's fields:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the contract's fields and `config`.
+  --dump-outputs DIR  after the timed steps, what the last of them handed back, as DIR/<name>.npy (float64 / float32):
+                      the peak list (peaks_<field>) and, with one rank, the final interval table's end / p (/ q) at a
+                      fixed, seeded sample of positions on chr20-chr22 (intervals_<field>).  The inputs are seeded: the
+                      same arguments give the same inputs on every run.
+  --full              everything else as well (the figures below); the --no-* options trim it.
+With --full the timed steps also bracket the roofline kernel's phase with HIP events, and the line also holds:
   gate          the same workload (or its first chromosomes, see cpu_baseline.sample) through the CPU oracle
                 and through the HIP path: narrowpeak_diff (differing narrowPeak lines; must be 0), max_abs_dp /
                 max_abs_dq over every interval
@@ -99,6 +105,44 @@ def decode_path(flags):
 def sig(x, n=4):
     """n significant digits (the short per-config summary at the end of the line)"""
     return None if x is None else float(f"{float(x):.{n}g}")
+
+
+DUMP_CHROMS = (19, 20, 21)   # chr20, chr21, chr22: where --dump-outputs samples the interval table
+DUMP_POSITIONS = 1 << 19     # sampled positions: about 17 MB of .npy files, with the peak list well under 64 MB
+
+
+def interval_sample(gx, lens, qval):
+    """The final interval table (end, p[, q]) of the context's last step at DUMP_POSITIONS positions drawn with a fixed seed
+    on DUMP_CHROMS: for each position, the interval that holds it.  The positions depend on the genome only."""
+    rng = np.random.default_rng(20240601)
+    lens = np.asarray(lens, dtype=np.int64)
+    sel = np.array(DUMP_CHROMS)
+    chrom = np.sort(rng.choice(sel, size=DUMP_POSITIONS, p=lens[sel] / lens[sel].sum()))
+    pos = rng.integers(0, lens[chrom])
+    out = {"chrom": chrom.astype(np.float64), "pos": pos.astype(np.float64), "end": np.zeros(DUMP_POSITIONS),
+           "p": np.zeros(DUMP_POSITIONS, dtype=np.float32)}
+    if qval:
+        out["q"] = np.zeros(DUMP_POSITIONS, dtype=np.float32)
+    for c in DUMP_CHROMS:
+        at = chrom == c
+        ends, cols = gx.get_intervals(-1, c, piles=False)
+        if len(ends) == 0 or int(ends[-1]) < int(lens[c]):
+            raise RuntimeError(f"--dump-outputs: the interval table of chromosome {c} does not cover it ({len(ends)} intervals)")
+        k = np.searchsorted(ends, pos[at], side="right")   # interval k covers [ends[k-1], ends[k])
+        out["end"][at] = ends[k]
+        for f in ("p", "q") if qval else ("p",):
+            out[f][at] = cols[f][k]
+    return out
+
+
+def dump_outputs(path, peaks, intervals):
+    """--dump-outputs: the peak list's fields and the interval sample as <path>/<name>.npy, integers as float64."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"peaks_" + f: peaks[f].astype(np.float64 if peaks.dtype[f].kind in "iu" else np.float32) for f in peaks.dtype.names}
+    if intervals is not None:
+        arrays.update({"intervals_" + k: v for k, v in intervals.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 _PLAIN = {}   # (fragments, seed) -> the plain config-2 stream of that seed: four of the default run's workloads start from seed 1
@@ -411,8 +455,15 @@ def main():
     ap.add_argument("--cpu-chroms", type=int, default=0, help="gate / cpu_baseline on the first K chromosomes (0: per config)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the H2D / end-to-end-from-pinned figures")
     ap.add_argument("--no-materialised", action="store_true", help="skip the second timed loop with the tight interval table written (profiling runs)")
-    ap.add_argument("--no-others", action="store_true", help="headline config only (default: configs 3, 4, 5 ride along, 3 steps each)")
+    ap.add_argument("--no-others", action="store_true", help="with --full: headline config only (else configs 2q, 2E, 3, 4, 5 ride along, 5 steps each)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: gate + CPU baseline, roofline and phases, the materialised / packed / from-pinned "
+                         "steps, the other configs and the end-to-end figures (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # The JSON line must be the only thing on stdout: libraries below Python (RCCL prints a version banner
     # through C stdio, flushed at exit) write to file descriptor 1, so the real stdout is put aside and
     # descriptor 1 joins stderr until the line is written.
@@ -457,8 +508,8 @@ def main():
     cfg["qval"] = cfg["qval"] or args.qval
     cfg["control"] = cfg["control"] or args.control
     out = bench_one(args.config, cfg, args, env, steps=args.steps, warmup=args.warmup, plain=plain,
-                    want_e2e=not args.no_e2e, want_cpu=not args.no_cpu, headline=True)
-    if rank == 0 and world == 1 and args.config == 2 and plain and not args.no_cpu and not args.no_others:
+                    want_e2e=args.full and not args.no_e2e, want_cpu=args.full and not args.no_cpu, headline=True)
+    if args.full and rank == 0 and world == 1 and args.config == 2 and plain and not args.no_cpu and not args.no_others:
         # BASELINE.json's other GPU configs in the same line (the driver runs bench.py once, with defaults)
         detail, brief = {}, {}
         # "2q": the headline workload with -q 0.05 -- north_star's "p + q scan" of one 50 M-fragment sample
@@ -494,7 +545,7 @@ def main():
         others_brief = brief
     else:
         others_brief = None
-    if rank == 0 and world == 1 and args.config == 2 and plain and not args.no_cpu and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and plain and not args.no_cpu and not args.no_e2e:
         try:
             out["e2e_cli"] = e2e_cli(synth.HG38_LENS, args.frags)
         except Exception as e:  # noqa: BLE001
@@ -610,14 +661,17 @@ def bench_one(config, cfg, args, env, steps, warmup, plain, want_e2e, want_cpu, 
     # events on the library's stream (an event record costs the stream a ~5 us bubble); all phases are timed in two extra,
     # untimed steps afterwards.
     # (the headline with -q has a profile of its own: tools/profile_round.sh <tag> 2q)
-    prof = load_profile(cfg.get("profile_as", config), args.frags, world, plain or "profile_as" in cfg)
+    # A plain run (no --full) times the bare steps: no phase is bracketed, and the roofline is not reported.
+    full = args.full
+    prof = load_profile(cfg.get("profile_as", config), args.frags, world, plain or "profile_as" in cfg) if full else None
     dom = prof.get("dominant", {}).get("kernel") if prof else None
     # (the library phase that brackets it -- gx_set_phase_filter -- comes from the profile's own marker trace: the library's roctx
     # ranges, GX_ROCTX; without a profile of this build the tile stage is what is timed)
     dom_phase = prof["kernels"].get(dom, {}).get("phase") if prof and dom else None
     if not dom_phase:
         dom, dom_phase = None, "tile"
-    gx.set_phase_filter(dom_phase)
+    if full:
+        gx.set_phase_filter(dom_phase)
     for _ in range(warmup):
         step()
     barrier()
@@ -625,18 +679,22 @@ def bench_one(config, cfg, args, env, steps, warmup, plain, want_e2e, want_cpu, 
     phase_acc = {}
     for _ in range(steps):
         res = step()
-        collect(phase_acc)
+        if full:
+            collect(phase_acc)
     barrier()
     dt = time.perf_counter() - t0
     path_flags = gx.path_info()   # (after the timed steps: which path THEY took, and whether they wrote pileup floats)
     if force_rccl and cfg["qval"] and not path_flags & (32 | 64):
         raise RuntimeError("GX_BENCH_FORCE_RCCL: the BH exchange did not go through the collectives (path flags %#x)" % path_flags)
+    peaks_local = gx.get_peaks()   # (the last timed step's peak list: what a caller of the path receives)
+    dump = bool(args.dump_outputs) and headline
+    iv_sample = interval_sample(gx, lens, cfg["qval"]) if dump and world == 1 else None
     # The same step with the tight interval table MATERIALISED (GX_NO_LOOSE: lambda only after the tile stage, then
     # k_pack_pval writes (end, p) and the sweep's masks, as every run with -q / a control / a further replicate / -f / -k
     # does): what the default step of a single -p sample leaves out because the sweep reads (end, V) where the tile
     # stage put them.  Only for the headline, one rank.
     mat_ms = None
-    if headline and world == 1 and not cfg["qval"] and not cfg["control"] and cfg["reps"] == 1 and not args.no_materialised:
+    if full and headline and world == 1 and not cfg["qval"] and not cfg["control"] and cfg["reps"] == 1 and not args.no_materialised:
         gx.set_knob("GX_NO_LOOSE", 1)
         try:
             for _ in range(2):
@@ -654,7 +712,7 @@ def bench_one(config, cfg, args, env, steps, warmup, plain, want_e2e, want_cpu, 
     # The same step with the events in their 8-byte form (gx_event8, gx_push_events_packed: half of the step's largest stream),
     # resident in HBM like the 16-byte ones of `value`.  Only for the headline, one rank.
     packed_ms = packed_same = None
-    if headline and world == 1 and not args.no_materialised:
+    if full and headline and world == 1 and not args.no_materialised:
         peaks16 = gx.get_peaks().tobytes()
         p8 = [(pack_events(tv), None if cv is None else pack_events(cv)) for tv, cv in reps_all]
         if all(len(t[1]) == 0 and (c is None or len(c[1]) == 0) for t, c in p8):
@@ -687,13 +745,13 @@ def bench_one(config, cfg, args, env, steps, warmup, plain, want_e2e, want_cpu, 
             packed_same = bool(gx.path_info() & 512) and gx.get_peaks().tobytes() == peaks16
             del d8
             step()
-    gx.set_phase_timing(2)
     all_phases = {}
-    for _ in range(2):
-        step()
-        collect(all_phases)
-    gx.set_phase_timing(0)
-    peaks_local = gx.get_peaks()
+    if full:
+        gx.set_phase_timing(2)
+        for _ in range(2):
+            step()
+            collect(all_phases)
+        gx.set_phase_timing(0)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -817,8 +875,17 @@ def bench_one(config, cfg, args, env, steps, warmup, plain, want_e2e, want_cpu, 
             # (the roofline kernel's phase: HIP events inside the timed region; the others: two extra untimed steps)
             "phases_ms": phases,
         }
-        out["config"]["materialised_ms_per_step"] = mat_ms
-        out["config"]["packed_events_ms_per_step"] = packed_ms
+        if full:
+            out["config"]["materialised_ms_per_step"] = mat_ms
+            out["config"]["packed_events_ms_per_step"] = packed_ms
+        else:   # (a plain run measured none of these: no phase was timed, no other step was run)
+            for k in ("roofline", "materialised", "materialised_ms_per_step", "packed_events", "phases_ms"):
+                del out[k]
+        if dump:
+            peaks_all = np.concatenate(gathered) if world > 1 else peaks_local
+            if world > 1:
+                peaks_all = peaks_all[np.lexsort((peaks_all["start"], peaks_all["chrom"]))]
+            dump_outputs(args.dump_outputs, peaks_all, iv_sample)
         if world == 1 and want_e2e:
             # PCIe upload of the events from pinned host memory, and a step that starts there (gx_push_events)
             pin = [(torch.from_numpy(tv.view(np.uint32).reshape(-1, 4)).pin_memory(),

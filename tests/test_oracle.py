@@ -2,8 +2,8 @@
  * byte-identical narrowPeak / -f / -k text on every committed golden fixture (the fixtures
    are the unmodified reference's own outputs, tests/golden/make_golden.py);
  * the calcPval known answers printed in the reference's README (README.md:243-249);
- * (build container only, marker `ref`) scalar functions and the fraction codec probed
-   against the compiled reference in oracle/_ref/libgenrich_ref.so.
+ * scalar functions and the fraction codec against what the compiled reference returned
+   for the same inputs (tests/golden/ref_probes.npz, tests/golden/make_ref_probes.py).
 """
 import ctypes as C
 import os
@@ -87,76 +87,56 @@ def test_getval_fraction_text():
     assert lib.gxo_getval(120 * 77, C.byref(neg)) == 77.0 and not neg.value
 
 
-# ---- probes against the compiled reference (build container only) ----------------
+# ---- scalar probes of the compiled reference ------------------------------------------
+# tests/golden/ref_probes.npz: fixed inputs and what oracle/_ref/libgenrich_ref.so (the unmodified reference, main renamed)
+# returned for them, recorded by tests/golden/make_ref_probes.py.
 
-def _ref():
-    lib = C.CDLL(B.REF_SO)
-    lib.calcPval.restype = C.c_float
-    lib.calcPval.argtypes = [C.c_float, C.c_float]
-    lib.pchisq.restype = C.c_double
-    lib.pchisq.argtypes = [C.c_double, C.c_int]
-    lib.updateVal.restype = C.c_float
-    lib.updateVal.argtypes = [C.c_int16, C.c_uint8, C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
-    lib.addFrac.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_uint8]
-    lib.subFrac.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_uint8]
-    return lib
+def _probes():
+    return np.load(os.path.join(G.GOLDEN, "ref_probes.npz"))
 
 
-@pytest.mark.ref
 def test_calc_pval_bitexact_vs_reference():
-    ref, lib = _ref(), B.Oracle.lib()
-    rng = np.random.default_rng(5)
-    expt = np.concatenate([rng.integers(0, 3000, 4000) / 120.0 * rng.integers(1, 121, 4000),
-                           rng.random(2000) * 50, [0, 1, 7, 7.0000005, 1e6, 3e38]]).astype(np.float32)
-    ctrl = np.concatenate([rng.random(4000) * 30, rng.random(2000) * 8,
-                           [0, -1, 7, 7.0000005, 1e-30, 6.9999995]]).astype(np.float32)
-    for e, c in zip(expt, ctrl):
-        a, b = ref.calcPval(float(e), float(c)), lib.gxo_calc_pval(float(e), float(c))
+    d, lib = _probes(), B.Oracle.lib()
+    assert len(d["pval_ref"]) == 6006
+    for e, c, a in zip(d["pval_expt"], d["pval_ctrl"], d["pval_ref"]):
+        b = lib.gxo_calc_pval(float(e), float(c))
         assert np.float32(a).tobytes() == np.float32(b).tobytes(), (e, c, a, b)
 
 
-@pytest.mark.ref
 def test_pchisq_bitexact_vs_reference():
-    ref, lib = _ref(), B.Oracle.lib()
-    rng = np.random.default_rng(6)
-    for _ in range(5000):
-        df = int(rng.integers(2, 201)) * 2
-        x = float(rng.random() * (3 * df if rng.random() < 0.8 else 0.9))
-        a, b = ref.pchisq(x, df), lib.gxo_pchisq(x, df)
+    d, lib = _probes(), B.Oracle.lib()
+    assert len(d["chisq_ref"]) == 5000
+    for x, df, a in zip(d["chisq_x"], d["chisq_df"], d["chisq_ref"]):
+        b = lib.gxo_pchisq(float(x), int(df))
         assert a == b or (np.isnan(a) and np.isnan(b)), (x, df, a, b)
 
 
-@pytest.mark.ref
 def test_fraction_codec_is_exact_rational():
     """The (cov, frac) state of the reference after any add/sub sequence, and the running
     state of updateVal, are pure functions of the exact sum in 1/120 units."""
-    ref, lib = _ref(), B.Oracle.lib()
-    rng = np.random.default_rng(7)
-    counts = [2, 3, 4, 5, 6, 8, 10]
+    d, lib = _probes(), B.Oracle.lib()
     neg = C.c_int(0)
-    for _trial in range(300):
-        cov, frac = C.c_int16(0), C.c_uint8(0)   # one diff element
-        rcov, rfrac = C.c_int32(0), C.c_uint8(0)  # running pileup state
+    probed = 0
+    assert d["codec_cov"].shape == (300, 40)
+    for t in range(d["codec_cov"].shape[0]):
         v = 0
-        run_v = int(rng.integers(0, 5)) * 120 * 50
-        # seed the running state with an integer pileup so it never goes negative
-        ref.updateVal(C.c_int16(run_v // 120), C.c_uint8(0), C.byref(rcov), C.byref(rfrac))
-        for _step in range(40):
-            c = counts[rng.integers(0, len(counts))]
-            if rng.random() < 0.5:
-                ref.addFrac(C.byref(cov), C.byref(frac), c)
-                v += 120 // c
-            else:
-                ref.subFrac(C.byref(cov), C.byref(frac), c)
-                v -= 120 // c
+        run_v = int(d["codec_run_v"][t])
+        for s in range(d["codec_cov"].shape[1]):
+            c = int(d["codec_count"][t, s])
+            v += 120 // c if d["codec_add"][t, s] else -(120 // c)
+            cov, frac = int(d["codec_cov"][t, s]), int(d["codec_frac"][t, s])
             # element value must equal v/120 exactly:  cov + e/8 + s/6 + t/10
-            e, s, t = frac.value & 7, (frac.value >> 3) & 3, (frac.value >> 5) & 7
-            assert s < 3 and t < 5
-            assert 120 * cov.value + 15 * e + 20 * s + 12 * t == v
-            assert (cov.value == 0 and frac.value == 0) == (v == 0)
+            e, sx, tn = frac & 7, (frac >> 3) & 3, (frac >> 5) & 7
+            assert sx < 3 and tn < 5
+            assert 120 * cov + 15 * e + 20 * sx + 12 * tn == v
+            assert (cov == 0 and frac == 0) == (v == 0)
         # the reference exit()s on a negative canonical integer part (ERRPILE, 1921/1969), which a
-        # random +/- sequence can reach even for a non-negative total: probe only when it is >= 0
+        # random +/- sequence can reach even for a non-negative total: probed only when it is >= 0
         want = lib.gxo_getval(run_v + v, C.byref(neg))
+        got = d["codec_ref"][t]
         if run_v + v >= 0 and not neg.value:
-            got = ref.updateVal(cov, frac, C.byref(rcov), C.byref(rfrac))
             assert np.float32(got).tobytes() == np.float32(want).tobytes()
+            probed += 1
+        else:
+            assert np.isnan(got)
+    assert probed > 200

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a variant of the library next to the default one, for A/B runs on the GPU box:
 #   tools/build_variant.sh ept64 -DGX_TL_EPT=64      ->  genrich_amd/libgenrich_amd_ept64.so
-#   GENRICH_AMD_LIB=genrich_amd/libgenrich_amd_ept64.so python bench.py --no-cpu
+#   GENRICH_AMD_LIB=genrich_amd/libgenrich_amd_ept64.so python bench.py --full --no-cpu
 # (GX_VARIANT_NOATOMOPT=1: without LLVM's atomic optimizer -- k_sbtile gains 0.01 ms, k_bh_hist's slot counter loses 7 ms at config 5)
 set -e
 name=$1; shift
