@@ -258,6 +258,11 @@ def cases():
         reps=[dict(t=(N2, L2, mf(L2, 1500, 91)), c=None),
               dict(t=(N2, L2, mf(L2, 1500, 92)), c=None)])
 
+    # threshold ties (tests/ties.py): -p / -q at a value present in the run, -a at a peak's exact AUC, -l at a peak's exact
+    # length, -g at the exact distance between two significant runs -- found here, with the oracle, and checked to be live on
+    # the reference alone (tie_args)
+    yield from tie_cases()
+
 
 # -P re-calls on the -f log of a case (callPeaksLog, Genrich.c:1277-1488): new thresholds, new -e / -E
 P_RUNS = {
@@ -265,8 +270,195 @@ P_RUNS = {
     "reps3": [dict(args=["-p", "0.01", "-a", "50"]), dict(args=["-q", "0.3", "-a", "5", "-e", "chr2"])],
     "bedx": [dict(args=["-q", "0.25", "-a", "30"], bed=[("chr1", 3000, 3400), ("chr1", 12000, 12345), ("chr2", 0, 777)])],
     "basic": [dict(args=["-a", "100", "-L", "1000"], bed=[("chrA", 12500, 12520)])],
+    # ties_p / ties_q: -P re-calls at ties of the -f log's printed values (p_run_ties), added when the case is generated
 }
+P_TIES = {"ties_p": ["-p"], "ties_q": ["-p", "-q"]}
 
+
+
+# ---- threshold ties ----------------------------------------------------------------------------------------------------
+
+def _ties():
+    import ties
+    return ties
+
+
+def _ref_coords(args):
+    """the reference's narrowPeak coordinates and summits (columns 1-3, 10) for one command line"""
+    out = args[args.index("-o") + 1]
+    res = subprocess.run([REF] + args, capture_output=True, text=True)
+    if res.returncode != 0:
+        sys.exit("reference failed:\n" + res.stderr)
+    return [(l.split("\t")[0], l.split("\t")[1], l.split("\t")[2], l.split("\t")[9]) for l in open(out).read().splitlines()]
+
+
+def _set(args, flag, value):
+    a = list(args)
+    a[a.index(flag) + 1] = value
+    return a
+
+
+def check_live_on_reference(args, flips, out):
+    """each flip (flag, value one float / one base past the tie) must change the reference's peaks"""
+    full = args + ["-o", out]
+    base = _ref_coords(full)
+    assert base, "the tie case has no peaks"
+    for flag, v in flips:
+        if _ref_coords(_set(full, flag, v)) == base:
+            sys.exit(f"tie {flag} {args[args.index(flag) + 1]} is not live on the reference ({flag} {v} gives the same peaks)")
+
+
+def design_ties(case, qval, lo_t=0.5):
+    """(-p/-q string, min_auc, min_len, max_gap) for one case, every one a live tie on the oracle with the others fixed"""
+    T = _ties()
+    import backends as Bk
+    base = Bk.make_params(pq=0.05 if qval else 0.01, qval=qval, min_auc=0.0, min_len=0, max_gap=100)
+    r0 = T.run_oracle(case, base)
+    col = "q" if qval else "p"
+    bp = {}
+    for c in range(len(case["lens"])):
+        m, ln = T._in_peaks(r0, c)
+        for v, l in zip(r0.cols[c][col][m], ln[m]):
+            if v >= lo_t:
+                bp[float(v)] = bp.get(float(v), 0) + int(l)
+    for t in sorted(bp, key=lambda v: -bp[v])[:40]:
+        s, s_dn = T.pq_string(t), T.pq_string(T.down(t))
+        if s is None or s_dn is None:
+            continue
+        try:
+            g = T.gap_tie(case, T.params(base, thr=t), lo=2, hi=1_000, raise_thr=False)
+        except AssertionError:
+            continue
+        if g.base.thr != np.float32(t):
+            continue
+        gap = int(g.at)
+        P = T.params(base, thr=t, max_gap=gap)
+        r = T.run_oracle(case, P)
+        if len(r.peaks) < 3:
+            continue
+        auc = np.sort(r.peaks["auc"])
+        a = float(auc[len(auc) // 2])
+        keep = r.peaks[r.peaks["auc"] >= np.float32(a)]
+        L = int((keep["end"].astype(np.int64) - keep["start"]).min())
+        P = T.params(P, min_auc=a, min_len=L)
+        k0 = T.run_oracle(case, P).key()
+        flips = dict(thr=T.down(t), min_auc=T.up(a), min_len=L + 1, max_gap=gap - 1)
+        if all(T.run_oracle(case, T.params(P, **{f: v})).key() != k0 for f, v in flips.items()):
+            return dict(pq=s, pq_away=s_dn, auc=a, len=L, gap=gap, t=t)
+    sys.exit("no set of live ties found")
+
+
+def tie_args(ev_t, ev_c, lens, qval):
+    d = design_ties(dict(lens=lens, replicates=[dict(save=None, treat=ev_t, ctrl=ev_c)]), qval)
+    args = ["-q" if qval else "-p", d["pq"], "-a", "%.9g" % d["auc"], "-l", str(d["len"]), "-g", str(d["gap"])]
+    assert float(np.float32(float(args[3]))) == d["auc"]
+    flips = [(args[0], d["pq_away"]), ("-a", "%.9g" % _ties().up(d["auc"])), ("-l", str(d["len"] + 1)), ("-g", str(d["gap"] - 1))]
+    return args, flips
+
+
+def tie_cases():
+    T = _ties()
+    N1, L1 = ["chrA"], [60_000]
+    ev = mf(L1, 3000, 111)
+    args, flips = tie_args(ev, None, L1, False)
+    yield dict(name="ties_p", names=N1, args=args, flips=flips, reps=[dict(t=(N1, L1, ev), c=None)])
+    L2, N2 = [32_000, 20_000], ["chr1", "chr2"]
+    ev, ct = mf(L2, 4000, 121), mf(L2, 2000, 122, uniform_only=True)
+    args, flips = tie_args(ev, ct, L2, True)
+    yield dict(name="ties_q", names=N2, args=args, flips=flips, reps=[dict(t=(N2, L2, ev), c=(N2, L2, ct))])
+    # summits (updatePeak 958-966): plateaus of one height, equal length / the later one longer; in -q mode two plateaus of
+    # different p and equal q -- summitPos moves to the later, longer one, the p reported stays the first one's
+    qp = T.summit_q_pair()
+    ev = T.summit_events(q_pair=qp)
+    yield dict(name="ties_summit", names=N1, args=["-a", "20"], reps=[dict(t=(N1, L1, ev), c=None)])
+    yield dict(name="ties_summit_q", names=N1, args=["-q", "0.05", "-a", "20"], reps=[dict(t=(N1, L1, ev), c=None)])
+
+
+def _log_rows(path):
+    rows = []
+    with open(path) as f:
+        hdr = f.readline().rstrip("\n").split("\t")
+        qcol = hdr.index("-log(q)") if "-log(q)" in hdr else None
+        pcol = hdr.index("-log(p)")
+        for line in f:
+            x = line.rstrip("\n").split("\t")
+            rows.append((x[0], int(x[1]), int(x[2]), x[pcol], x[qcol] if qcol is not None else None))
+    return rows
+
+
+def log_peaks(rows, col, thr, min_auc, min_len, max_gap):
+    """callPeaksLog (Genrich.c:1277-1488) without -E / -e on parsed -f rows: (chrom, start, end, float AUC) of the peaks"""
+    f = np.float32
+    thr = f(thr)
+    out = []
+    state = dict(chrom=None, ps=-1, pe=-1, auc=f(0))
+
+    def check():
+        if state["ps"] != -1 and state["auc"] >= f(min_auc) and state["pe"] - state["ps"] >= min_len:
+            out.append((state["chrom"], state["ps"], state["pe"], float(state["auc"])))
+        state.update(ps=-1, pe=-1, auc=f(0))
+
+    for chrom, s, e, ps, qs in rows:
+        if chrom != state["chrom"]:
+            check()
+            state["chrom"] = chrom
+        st = ps if col == "p" else qs
+        if st == "NA":
+            check()
+            continue
+        v = f(float(np.float32(float(st))))
+        if v > thr:
+            state["auc"] = f(state["auc"] + f(e - s) * f(v - thr))
+            if state["ps"] == -1:
+                state["ps"] = s
+            state["pe"] = e
+        elif e - state["pe"] > max_gap:
+            check()
+    check()
+    return out
+
+
+def p_run_ties(log_path, col, lo_t=0.5):
+    """-P args at ties of the log's printed values: -p/-q at a printed value, -a at a peak's float AUC, -l at a peak's length,
+    -g at a gap between significant runs; with their flips (checked on the reference by the caller)"""
+    T = _ties()
+    rows = _log_rows(log_path)
+    vals = {}
+    for chrom, s, e, ps, qs in rows:
+        st = ps if col == "p" else qs
+        if st not in ("NA", None) and float(st) >= lo_t:
+            vals[st] = vals.get(st, 0) + e - s
+    for st in sorted(vals, key=lambda v: -vals[v])[:60]:
+        t = T.strtof(st)
+        s, s_dn = T.pq_string(t), T.pq_string(T.down(t))
+        if s is None or s_dn is None:
+            continue
+        # gaps between significant runs at thr = t
+        gaps = []
+        prev = None
+        for chrom, a, e, ps, qs in rows:
+            v = ps if col == "p" else qs
+            sig = v != "NA" and np.float32(float(v)) > np.float32(t)
+            if v == "NA":
+                prev = None
+            elif sig:
+                if prev is not None and prev[0] == chrom and a - prev[1] > 1:
+                    gaps.append(a - prev[1])
+                prev = (chrom, e)
+        for gap in sorted(set(g for g in gaps if g <= 1_000), reverse=True)[:8]:
+            pk = log_peaks(rows, col, t, 0.0, 0, gap)
+            if len(pk) < 3:
+                continue
+            L = sorted(e - a for _, a, e, _ in pk)[len(pk) // 2]
+            keep = [x for x in pk if x[2] - x[1] >= L]
+            coords = lambda *arg: [x[:3] for x in log_peaks(rows, col, *arg)]
+            for a in sorted(x[3] for x in keep):   # (AUC: the float sum in interval order, as the reference adds it)
+                pk = coords(t, a, L, gap)
+                if pk not in (coords(T.down(t), a, L, gap), coords(t, T.up(a), L, gap), coords(t, a, L + 1, gap),
+                              coords(t, a, L, gap - 1)):
+                    return (["-" + col, s, "-a", "%.9g" % a, "-l", str(L), "-g", str(gap)],
+                            [("-" + col, s_dn), ("-a", "%.9g" % T.up(a)), ("-l", str(L + 1)), ("-g", str(gap - 1))])
+    sys.exit("no live -P ties")
 
 def write_input(path, names, lens, ev, mixed, seed_off, prefix):
     """The synthetic SAM / BAM input of one sample, by the writer the case asks for."""
@@ -347,6 +539,9 @@ def main():
         if res.returncode != 0:
             sys.exit(f"{case['name']}: reference failed:\n{res.stderr}")
         err = res.stderr
+        if case.get("flips"):   # every tie live on the reference alone: one float / one base away, other peaks
+            ctl = ["-c", ",".join(c if c else "null" for c in cfiles)] if any(cfiles) else []
+            check_live_on_reference(["-t", ",".join(tfiles)] + ctl + case["args"], case["flips"], os.path.join(tmp, "live.narrowPeak"))
         skip = []
         if "-e" in case["args"]:
             skip = case["args"][case["args"].index("-e") + 1].split(",")
@@ -378,8 +573,13 @@ def main():
             src = os.path.join(tmp, fn)
             if os.path.exists(src):
                 gz_copy(src, os.path.join(out_dir, fn + ".gz"))
+        p_runs = list(P_RUNS.get(case["name"], []))
+        for col in P_TIES.get(case["name"], []):   # -P at ties of the printed values, live on the reference
+            pa, pflips = p_run_ties(os.path.join(tmp, "out.log"), col[1])
+            check_live_on_reference(["-P", "-f", os.path.join(tmp, "out.log")] + pa, pflips, os.path.join(tmp, "live.P.narrowPeak"))
+            p_runs.append(dict(args=pa))
         p_meta = []
-        for k, pr in enumerate(P_RUNS.get(case["name"], [])):
+        for k, pr in enumerate(p_runs):
             pargs = [REF, "-P", "-f", os.path.join(tmp, "out.log"), "-o", os.path.join(tmp, f"out.P{k}.narrowPeak")] + pr["args"]
             if pr.get("bed"):
                 bp = os.path.join(tmp, f"xP{k}.bed")

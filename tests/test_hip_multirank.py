@@ -38,6 +38,13 @@ def _scenario(name):
     if name == "noctrl_q":  # one sample without a control, -q: the dense BH exchange
         tr = synth.make_fragments(LENS, 80_000, 23, peak_every=20_000, tower_every=70_000, frac_tower=0.1)
         return B.make_params(pq=0.3, qval=True, min_auc=20.0), [(tr, None)]
+    if name in ("noctrl_q_tie", "ctrl_q_tie"):  # -q at a q present in the run (tests/ties.py): dense / range BH at a live tie
+        import ties as T
+        base, reps = _scenario(name[:-4])
+        case = dict(lens=LENS, replicates=[dict(save=None, treat=tr, ctrl=ct) for tr, ct in reps])
+        (t,) = [t for t in T.pq_ties(case, base) if t.kind == "q_common"]   # (every rank finds the same float)
+        assert t.live()
+        return t.at_params(), reps
     raise KeyError(name)
 
 
@@ -82,7 +89,8 @@ def _worker(rank, world, port, q, name):
 
 
 @pytest.mark.parametrize("name,world", [("ctrl_q", 2), ("atac_multimap", 2), ("reps3_q", 2), ("plain_p", 2), ("noctrl_q", 2),
-                                        ("reps3_q", 3), ("ctrl_q", 4)])
+                                        ("reps3_q", 3), ("ctrl_q", 4),
+                                        ("noctrl_q_tie", 2), ("ctrl_q_tie", 2)])
 def test_two_ranks_equal_one_rank(name, world):
     """(... or three, or four: more ranges of the p axis for the range-partitioned BH exchange, ranks that own a single
     small chromosome)"""
@@ -118,9 +126,9 @@ def test_two_ranks_equal_one_rank(name, world):
         p.join(60)
         assert p.exitcode == 0
     for _, scal, _, flags in res:
-        if name in ("ctrl_q", "reps3_q"):
+        if name in ("ctrl_q", "reps3_q", "ctrl_q_tie"):
             assert flags & 64, "the range-partitioned BH exchange"
-        if name == "noctrl_q":
+        if name in ("noctrl_q", "noctrl_q_tie"):
             assert flags & 32, "the p-value histogram must have travelled as the dense all-reduce"
         if name == "plain_p":
             # lambda reached every rank ahead of the tile stage (the early all-reduce of the closed form of fragLen): the
@@ -285,9 +293,9 @@ def test_rccl_two_gpus_equal_one_rank(name):
         assert nranks == 2
         if name == "plain_p":
             assert flags & 2
-        if name == "noctrl_q":
+        if name in ("noctrl_q", "noctrl_q_tie"):
             assert flags & 32
-        if name in ("ctrl_q", "reps3_q"):
+        if name in ("ctrl_q", "reps3_q", "ctrl_q_tie"):
             assert flags & 64
         for (f, lam, fac), (f1, lam1, fac1) in zip(scal, scal1):
             assert f == f1 and np.float32(lam).tobytes() == np.float32(lam1).tobytes() and np.float32(fac).tobytes() == np.float32(fac1).tobytes()

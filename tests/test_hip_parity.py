@@ -69,7 +69,7 @@ def assert_same_run(o, h, so, sh, case, tol=1e-5):
 
 
 SUPPORTED = ["basic", "atac", "ctrl_q", "multimap", "atac_odd", "reps3", "reps3_p_missing",
-             "ctrl_only_chrom", "nopeaks_log", "bedx", "bedx_noctrl"]
+             "ctrl_only_chrom", "nopeaks_log", "bedx", "bedx_noctrl", "ties_p", "ties_q", "ties_summit", "ties_summit_q"]
 
 
 @pytest.mark.parametrize("name", SUPPORTED)
@@ -541,6 +541,40 @@ def test_random_runs_against_oracle(block):
                 B.run_case(B.Oracle(params), case)
             continue
         assert_same_run(o, h, so, sh, case)
+
+
+# thresholds at and beyond their ends (tools/fuzz_hip_vs_oracle.py --extreme): every -p / -q of the list, both -a and both -g
+# values and -l 100000 are drawn at least once by these eight seeds (checked below)
+_EXTREME_PQ, _EXTREME_AUC, _EXTREME_GAP = (1.0, 0.999, 1e-30, 1e-300), (0.0, 1e6), (0, 100_000)
+
+
+def _extreme_draw(k):
+    rng = np.random.default_rng(7_000 + k)
+    qval = bool(rng.random() < 0.5)
+    return dict(pq=_EXTREME_PQ[k % 4], qval=qval, min_auc=_EXTREME_AUC[(k // 4) % 2 if k % 3 else 1 - (k // 4) % 2],
+                max_gap=_EXTREME_GAP[(k // 2) % 2], min_len=100_000 if k in (3, 6) else int(rng.choice([0, 80])))
+
+
+def test_extreme_draws_cover_every_value():
+    d = [_extreme_draw(k) for k in range(8)]
+    assert {x["pq"] for x in d} == set(_EXTREME_PQ) and {x["min_auc"] for x in d} == set(_EXTREME_AUC)
+    assert {x["max_gap"] for x in d} == set(_EXTREME_GAP) and 100_000 in {x["min_len"] for x in d}
+    assert {x["qval"] for x in d} == {False, True}
+
+
+@pytest.mark.parametrize("k", range(8))
+def test_random_runs_at_extreme_thresholds(k):
+    """-p / -q of 1 (thr -0: every interval with p > 0), 0.999, 1e-30 and 1e-300 (a float 0: thr = inf, no interval), -a 0 / 1e6,
+    -g 0 / 100000, -l 100000 on the random cases of test_random_runs_against_oracle"""
+    case, _ = _random_case(3000 + k)
+    params = B.make_params(**_extreme_draw(k))
+    try:
+        o, h, so, sh = run_both(case, params)
+    except RuntimeError:  # both must refuse the same inputs
+        with pytest.raises(RuntimeError):
+            B.run_case(B.Oracle(params), case)
+        return
+    assert_same_run(o, h, so, sh, case)
 
 
 def _saturating_case(seed, frac):
