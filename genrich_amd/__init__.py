@@ -5,4 +5,4 @@ from genrich_amd/csrc/*.hip; this package is the thin Python host mirror used by
 and bench.py.  It never falls back to a CPU implementation: loading fails loudly when the
 HIP library is missing.
 """
-from .lib import GxParams, Genrich, EVENT_DTYPE, PEAK_DTYPE, load_library, minus_log10f  # noqa: F401
+from .lib import GxParams, Genrich, EVENT_DTYPE, PEAK_DTYPE, GX_PATH_COUNTS, PeakCounts, load_library, minus_log10f  # noqa: F401

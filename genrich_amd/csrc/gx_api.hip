@@ -7,6 +7,7 @@
 #include "gx_host_build.h"
 #include "gx_host_sweep.h"
 #include "gx_host_stats.h"
+#include "gx_host_count.h"
 
 
 // ================================ C ABI ==================================================
@@ -230,6 +231,8 @@ int gx_reset(gx_ctx* ctx) {
   ctx->unpackUsed = 0;
   ctx->evChunkIdx = ctx->evChunkFill = ctx->evPoolUsed = 0;
   ctx->nHostPeaks = 0;
+  drop_kept(ctx);   // (the switch itself stays: gx_set_count_in_peaks)
+  ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
     ctx->statusSeen = 0;
@@ -242,6 +245,7 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   HIPCHECK(hipSetDevice(ctx->device));
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
+    ctx->peaksReady = ctx->countsReady = false;
     // (a further replicate: the previous one's loose slots, tile tables and p(V) table are about to be reused)
     for (size_t r = 0; r < ctx->reps.size(); r++)
       if (ctx->reps[r].loose || ctx->reps[r].pilesPending)
@@ -397,6 +401,7 @@ int gx_sample_end(gx_ctx* ctx, double* frag_len, float* lambda, float* factor) {
     ctx->phase = 4;
   } else
     return GX_ERR_ORDER;
+  if (ctx->countOn) keep_sample(ctx, ctx->phase == 4);
   if (frag_len) *frag_len = ctx->hScal.fragLen;
   if (lambda) *lambda = ctx->hScal.lambda;
   if (factor) *factor = ctx->hScal.factor;
@@ -525,6 +530,7 @@ int gx_pvalues(gx_ctx* ctx) {
 int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* peak_bp) {
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
+  ctx->peaksReady = ctx->countsReady = false;
   hipStream_t s = ctx->stream;
   u32* misc = ctx->misc.as<u32>();
   // One replicate without a control, -p, and the tile stage left the sweep's bits on the loose slots (LooseCtl): the
@@ -645,6 +651,7 @@ int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* 
     return gx_find_peaks(ctx, n_peaks, genome_len, peak_bp);
   }
   if (rcSweep) return rcSweep;
+  ctx->peaksReady = true;
   if (n_peaks) *n_peaks = nPeaks;
   if (genome_len) *genome_len = g;
   if (peak_bp) *peak_bp = ctx->peakBP;
@@ -814,7 +821,36 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
   *flags = (ctx->fusedUsed ? GX_PATH_FUSED : 0u) | (ctx->fusedUsed && ctx->pairsUsed ? GX_PATH_PAIRS : 0u) | (ctx->denseBhUsed ? GX_PATH_DENSE_BH : 0u) | (ctx->rangeBhUsed ? GX_PATH_RANGE_BH : 0u) | (ctx->looseSwept ? GX_PATH_LOOSE_SWEEP : 0u) |
            (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->fusedUsed && ctx->fracPairsUsed ? GX_PATH_FRAC_PAIRS : 0u) |
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
-           (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u);
+           (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
+           (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u);
+  return GX_OK;
+}
+
+int gx_set_count_in_peaks(gx_ctx* ctx, int on) {
+  if (!ctx || ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;   // idle: after gx_create / gx_reset, before a sample
+  ctx->countOn = on != 0;
+  if (!ctx->countOn) drop_kept(ctx);
+  return GX_OK;
+}
+
+int gx_count_in_peaks(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !ctx->countOn || !ctx->peaksReady || ctx->phase != 0) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = count_in_peaks(ctx)) return rc;
+  if (n_samples) *n_samples = (int)ctx->kept.size();
+  return GX_OK;
+}
+
+int gx_get_peak_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
+                       int64_t* in_peaks120) {
+  if (!ctx || !ctx->countsReady || sample < 0 || (size_t)sample >= ctx->kept.size() || (cap && !count120)) return GX_ERR_ORDER;
+  const int64_t* r = static_cast<const int64_t*>(ctx->cntHost.p) + (size_t)sample * (ctx->cntPk + 2);
+  if (rep) *rep = ctx->kept[sample].rep;
+  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
+  const size_t n = std::min<size_t>(cap, ctx->cntPk);
+  if (n) memcpy(count120, r, n * sizeof(int64_t));
+  if (total120) *total120 = r[ctx->cntPk];
+  if (in_peaks120) *in_peaks120 = r[ctx->cntPk + 1];
   return GX_OK;
 }
 

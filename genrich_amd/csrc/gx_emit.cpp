@@ -75,6 +75,53 @@ int gx_write_narrowpeak_group(gx_ctx* const* ctxs, int n_ctx, const char* const*
 
 int gx_write_narrowpeak(gx_ctx* ctx, const char* const* names, FILE* out) { return gx_write_narrowpeak_group(&ctx, 1, names, out); }
 
+// --counts (no Genrich counterpart): the rows of -o -- the same merge of the contexts' peak lists, the same peak_N -- with one
+// column per sample, n / 120 of its count (gx_count_in_peaks on every context first)
+static void put_count(FILE* out, long long n) {
+  if (n % 120 == 0) fprintf(out, "\t%lld", n / 120);
+  else fprintf(out, "\t%.2f", (double)n / 120.0);
+}
+int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_samples,
+                          const char* const* sample_names, FILE* out) {
+  if (n_ctx < 1 || n_samples < 0 || (n_samples && !sample_names)) return GX_ERR_ORDER;
+  std::vector<gx_peak> pk;
+  std::vector<int64_t> cnt;   // [peak][sample], peaks in concatenation order
+  for (int g = 0; g < n_ctx; g++) {
+    size_t k = 0;
+    int rc = gx_peak_count(ctxs[g], &k);
+    if (rc) return rc;
+    const size_t at = pk.size();
+    pk.resize(at + k);
+    if (k && (rc = gx_get_peaks(ctxs[g], pk.data() + at, k))) return rc;
+    cnt.resize(pk.size() * (size_t)n_samples);
+    std::vector<int64_t> one(k);
+    for (int smp = 0; smp < n_samples; smp++) {
+      if ((rc = gx_get_peak_counts(ctxs[g], smp, nullptr, nullptr, one.data(), k, nullptr, nullptr))) return rc;
+      for (size_t i = 0; i < k; i++) cnt[(at + i) * n_samples + smp] = one[i];
+    }
+  }
+  std::vector<size_t> ord(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+  if (n_ctx > 1)
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
+      return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start;
+    });
+  fprintf(out, "chr\tstart\tend\tname");
+  for (int smp = 0; smp < n_samples; smp++) fprintf(out, "\t%s", sample_names[smp]);
+  fprintf(out, "\n");
+  for (size_t i = 0; i < ord.size(); i++) {
+    const gx_peak& k = pk[ord[i]];
+    fprintf(out, "%s\t%ld\t%ld\tpeak_%d", names[k.chrom], (long)k.start, (long)k.end, (int)i);
+    for (int smp = 0; smp < n_samples; smp++) put_count(out, (long long)cnt[ord[i] * n_samples + smp]);
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+int gx_write_counts(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names, FILE* out) {
+  return gx_write_counts_group(&ctx, 1, names, n_samples, sample_names, out);
+}
+
 // -k for replicate `rep` (owner[c] = index into ctxs of the context that computed chromosome c; NULL: ctxs[0])
 int gx_write_pile_group(gx_ctx* const* ctxs, const int* owner, int rep, const char* const* names, int n_chrom,
                         const char* expt_name, const char* ctrl_name, FILE* out) {
@@ -175,6 +222,14 @@ int gx_write_narrowpeak_path(gx_ctx* ctx, const char* const* names, const char* 
   FILE* f = fopen(path, "w");
   if (!f) return GX_ERR_ORDER;
   int rc = gx_write_narrowpeak(ctx, names, f);
+  fclose(f);
+  return rc;
+}
+int gx_write_counts_path(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names,
+                         const char* path) {
+  FILE* f = fopen(path, "w");
+  if (!f) return GX_ERR_ORDER;
+  int rc = gx_write_counts(ctx, names, n_samples, sample_names, f);
   fclose(f);
   return rc;
 }

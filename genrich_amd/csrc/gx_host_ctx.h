@@ -25,6 +25,7 @@
 #include "gx_dups.h"
 #include "gx_bhx.h"
 #include "gx_saturate.h"
+#include "gx_count.h"
 
 using namespace gx;
 
@@ -349,6 +350,23 @@ struct gx_ctx {
   int numCU = 0, resTile = 0, resTileHalf = 0, resTileFast = 0, resSweep = 0;  // co-resident workgroups per kernel class
   // recycled device buffers (gx_reset keeps allocations alive across runs)
   std::vector<DevBuf> pool;
+  // counting in peaks (gx_set_count_in_peaks / gx_count_in_peaks, gx_count.h): every closed sample's events stay where they are
+  struct KeptSample {
+    int rep = 0;
+    bool ctrl = false;
+    std::vector<Seg> segs;          // as gx_sample_end left them (after the int16 rule: the survivors in `sat`)
+    std::vector<uint8_t> save;      // the chromosomes its pileup took (Chrom.save of its replicate's treatment file)
+    std::vector<DevBuf> chunks, unpacks;  // the library's buffers behind `segs`, taken out of evChunks / unpackBufs
+    DevBuf sat;
+  };
+  bool countOn = false;
+  bool peaksReady = false;        // gx_find_peaks has called the peaks of the samples kept so far
+  bool countsReady = false;       // ... and gx_count_in_peaks has counted them
+  std::vector<KeptSample> kept;
+  u32 cntPk = 0;                  // peaks of the last count
+  DevBuf cntIn, cntIdx, cntDiff, cntRes;
+  PinnedBuf cntStage, cntHost;
+  bool cntLdsSet = false;
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

@@ -146,7 +146,8 @@ struct BedRec { std::string name; uint32_t pos[2]; };
 
 struct Opts {
   const char *inFile = nullptr, *ctrlFile = nullptr, *outFile = nullptr, *logFile = nullptr, *pileFile = nullptr,
-             *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr;
+             *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
+             *countsFile = nullptr;  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2470,6 +2471,46 @@ void peaksOnly(State& S, float thr) {
   closeOut(out);
 }
 
+// --counts: every sample's intervals (its -b lines) counted in the peaks just called, one column per sample in run order --
+// for replicate r its treatment, then its control when one was read; with -v the FRiP of each sample
+std::string countText(long long n) {
+  char b[64];
+  if (n % 120 == 0) snprintf(b, sizeof b, "%lld", n / 120);
+  else snprintf(b, sizeof b, "%.2f", (double)n / 120.0);
+  return b;
+}
+void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles,
+                 const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  std::vector<const char*> sampleNames;
+  for (size_t r = 0; r < tFiles.size(); r++) {
+    sampleNames.push_back(tFiles[r].c_str());
+    if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") sampleNames.push_back(cFiles[r].c_str());
+  }
+  const int nS = (int)sampleNames.size();
+  for (gx_ctx* g : S.devs.ctx) {
+    int n = 0;
+    check(S, gx_count_in_peaks(g, &n), g);
+    if (n != nS) die("", "--counts: the library kept another number of samples than were read");
+  }
+  Out out = openWrite(o.countsFile, o.gzOut);
+  check(S, gx_write_counts_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), nS, sampleNames.data(), out.f));
+  closeOut(out);
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++) {
+    long long tot = 0, in = 0;
+    int rep = 0, ctrl = 0;
+    for (gx_ctx* g : S.devs.ctx) {
+      int64_t t = 0, p = 0;
+      check(S, gx_get_peak_counts(g, i, &rep, &ctrl, nullptr, 0, &t, &p), g);
+      tot += t;
+      in += p;
+    }
+    fprintf(stderr, "  Intervals in peaks, %s file #%d: %s of %s (FRiP %f)\n", ctrl ? "control" : "experimental", rep,
+            countText(in).c_str(), countText(tot).c_str(), tot ? (double)in / (double)tot : 0.0);
+  }
+}
+
 void usage() {
   fprintf(stderr,
           "Usage: genrich-amd  -t <file>  -o <file>  [optional arguments]\n"
@@ -2491,6 +2532,7 @@ int main(int argc, char** argv) {
                                      {"device", required_argument, nullptr, 1001},
                                      {"devices", required_argument, nullptr, 1003},
                                      {"threads", required_argument, nullptr, 1002},
+                                     {"counts", required_argument, nullptr, 1004},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2533,6 +2575,7 @@ int main(int argc, char** argv) {
       case 1000: o.eventsOnly = true; break;
       case 1001: o.device = getInt(optarg); break;
       case 1002: g_threads = getInt(optarg); break;
+      case 1004: o.countsFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2553,6 +2596,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "Error! Need input/output files\n");
     usage();
   }
+  // (the counts are counted in the peaks this run calls: nothing to count in with -P, -X or --events-only)
+  if (o.countsFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly)) die("", "--counts needs the peaks of this run (not with -P or -X)");
   if (o.avgExtOpt) { o.singleOpt = true; o.extendOpt = false; }
   if (o.extendOpt) {
     o.singleOpt = true;
@@ -2625,6 +2670,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
+      if (o.countsFile) check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -2784,6 +2830,7 @@ int main(int argc, char** argv) {
     closeOut(out);
     if (o.verbose) fprintf(stderr, "Peaks identified: %d (%ldbp)\n", (int)nPeaks, (long)peakBP);
   }
+  if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);
     check(S, gx_write_log_group(S.devs.ctx.data(), S.devs.owner.data(), S.sample, names.data(), nChrom, o.qvalOpt, o.peaksOpt, thr,

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -33,6 +34,19 @@ def pack_events(ev):
     out["start"] = sel["start"]
     out["lcc"] = ln[fits].astype(np.uint32) | (cls[fits].astype(np.uint32) << 16) | (sel["chrom"].astype(np.uint32) << 19)
     return out, ev[~fits]
+
+GX_PATH_COUNTS = 65536   # gx_path_info bit 16: the run kept its samples' intervals for counting
+
+
+class PeakCounts(NamedTuple):
+    """One sample's counts in the called peaks (gx_get_peak_counts), in 1/120 units: count[k] per peak, the weight of all its
+    intervals (total) and of those that overlap a peak (in_peaks); FRiP = in_peaks / total."""
+    count: np.ndarray
+    total: int
+    in_peaks: int
+    rep: int
+    is_ctrl: bool
+
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
@@ -94,6 +108,13 @@ _SIGS = {
     "gx_selftest2": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
     "gx_selftest_host": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
     "gx_path_info": [C.c_void_p, C.POINTER(C.c_uint)],
+    "gx_set_count_in_peaks": [C.c_void_p, C.c_int],
+    "gx_count_in_peaks": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_peak_counts": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
+                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "gx_write_counts_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_write_counts": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_write_counts_path": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -366,10 +387,35 @@ class Genrich:
         """Which device path the last calls took: GX_PATH_* bits (1 fused tile stage, 2 loose-slot sweep, 4 fell back, 8 page tables grew,
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
-        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots)."""
+        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
+
+    # -- counting in peaks (no Genrich counterpart; include/genrich_amd.h, gx_count_in_peaks) -------------------------
+    def set_count_in_peaks(self, on=True):
+        """Keep every sample's intervals for gx_count_in_peaks (only while idle: after creation / reset, before a sample).
+        Device buffers pushed by pointer must then stay valid until the run's last count_in_peaks."""
+        self._check(self.lib.gx_set_count_in_peaks(self.ctx, int(bool(on))))
+
+    def count_in_peaks(self):
+        """Count every kept sample's intervals in the peaks of the last find_peaks; returns the number of samples."""
+        n = C.c_int(0)
+        self._check(self.lib.gx_count_in_peaks(self.ctx, C.byref(n)))
+        return n.value
+
+    def peak_counts(self, sample):
+        """PeakCounts(count int64[n_peaks], total, in_peaks, rep, is_ctrl) of one sample of the last count_in_peaks."""
+        cnt = np.zeros(self.n_peaks, dtype=np.int64)
+        rep, ctrl, tot, inp = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.gx_get_peak_counts(self.ctx, int(sample), C.byref(rep), C.byref(ctrl), cnt.ctypes.data if cnt.size else None,
+                                                cnt.size, C.byref(tot), C.byref(inp)))
+        return PeakCounts(cnt, tot.value, inp.value, rep.value, bool(ctrl.value))
+
+    def write_counts(self, names, sample_names, path):
+        """--counts' text (gx_write_counts) of this context."""
+        self._check(self.lib.gx_write_counts_path(self.ctx, self._names(names), len(sample_names), self._names(sample_names),
+                                                  path.encode()))
 
     def rccl_nranks(self):
         """Ranks of the library's own RCCL communicator as RCCL reports them (0: none)."""

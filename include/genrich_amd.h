@@ -17,6 +17,7 @@
  *     or      gx_sample_no_control
  *     gx_pvalues
  *   gx_find_peaks -> gx_get_peaks / gx_get_intervals
+ *   (counting on: gx_count_in_peaks -> gx_get_peak_counts / gx_write_counts)
  *   gx_destroy
  */
 #ifndef GENRICH_AMD_H
@@ -123,7 +124,7 @@ int gx_push_events(gx_ctx* ctx, const gx_event* events, size_t n);
 int gx_push_events_pinned(gx_ctx* ctx, const gx_event* events, size_t n);
 
 /* Events already resident in device memory (HIP path only; the pointer must stay
- * valid until gx_sample_end). */
+ * valid until gx_sample_end -- with gx_set_count_in_peaks on, until the run's last gx_count_in_peaks). */
 int gx_push_events_device(gx_ctx* ctx, const gx_event* d_events, size_t n);
 
 /* The same event in 8 bytes (round 6): what saveInterval receives (Genrich.c:2516-2519) is a start, a length that a read pair
@@ -221,6 +222,33 @@ int gx_total_intervals(gx_ctx* ctx, int which, size_t* n_iv); /* over all chromo
 int gx_get_intervals(gx_ctx* ctx, int which, int chrom, size_t cap, uint32_t* end,
                      float* expt, float* ctrl, float* p, float* q);
 
+/* ---- each sample's intervals counted in the called peaks (FRiP, a per-peak count matrix).  Genrich has NO counterpart:
+ *      it prints the intervals (-b: saveInterval / printBED, Genrich.c:2516-2590) and forgets them.  ----
+ * A sample = every gx_sample_end of the run, in call order: for replicate r its treatment, then its control when one was
+ * read (even one without a usable record); gx_sample_no_control is none.  Its intervals are exactly those that entered its
+ * pileup -- the lines -b prints for it: end clamped to the chromosome's length (2536-2544), after the int16 rule's drops
+ * (2558-2573, gx_filter_saturation), none on -e chromosomes (2995) nor on chromosomes this context does not own, empty ones
+ * included -- each with the weight 120 / count (1/120 units, gx_math.h).  Interval [s, e) overlaps peak [ps, pe) (narrowPeak
+ * coordinates) iff s < pe && ps < e, and counts in every peak it overlaps.  Per sample, exact int64 sums in 1/120 units:
+ * count[k] = weight of its intervals that overlap peak k (gx_get_peaks order), total = weight of all of them, in_peaks =
+ * weight of those that overlap at least one peak; FRiP = in_peaks / total.
+ *
+ * gx_set_count_in_peaks: only while idle (after gx_create / gx_reset, before the first gx_sample_begin; else GX_ERR_ORDER);
+ *   off by default.  On, each closed sample keeps its events in device memory until gx_reset (which keeps the switch):
+ *   the library's own copies (host pushes, 16-byte forms of packed pieces, the survivors of the int16 rule) are not reused
+ *   for the next sample, and a caller's DEVICE buffer (gx_push_events_device, gx_push_events_packed(.., GX_EVENTS_DEVICE))
+ *   is read in place, so it must stay valid and unchanged until the run's last gx_count_in_peaks (or gx_reset / gx_destroy)
+ *   instead of until gx_sample_end.  Off, nothing is kept and nothing of a run changes.
+ * gx_count_in_peaks: after gx_find_peaks (else GX_ERR_ORDER); counts every kept sample (*n_samples of them) in one device
+ *   pass and one read-back; may be called again, with the same result.  Under gx_set_owned a context counts the chromosomes
+ *   it owns (an interval and every peak it can touch lie on one chromosome): a host adds the contexts' totals.
+ * gx_get_peak_counts: the last count of one sample (0 .. n_samples-1): its replicate, whether it is a control, min(cap,
+ *   n_peaks) counts (count120 may be NULL when cap is 0) and the two totals (any pointer may be NULL). */
+int gx_set_count_in_peaks(gx_ctx* ctx, int on);
+int gx_count_in_peaks(gx_ctx* ctx, int* n_samples);
+int gx_get_peak_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
+                       int64_t* in_peaks120);
+
 /* ---- host-side text emitters of the drop-in surface (gx_emit.cpp); byte format of the
  *      reference's printf calls.  names[i] = chromosome names in table order. ---- */
 #include <stdio.h>
@@ -242,6 +270,15 @@ int gx_write_pile_group(gx_ctx* const* ctxs, const int* owner, int rep, const ch
 int gx_write_log_group(gx_ctx* const* ctxs, const int* owner, int n_rep, const char* const* names, int n_chrom,
                        int qval_opt, int peaks_opt, float thr, FILE* out);
 int gx_write_narrowpeak_path(gx_ctx* ctx, const char* const* names, const char* path);
+/* --counts (no Genrich counterpart; after gx_count_in_peaks on every context): a header "chr\tstart\tend\tname" and one
+ * column per sample (sample_names[i], n_samples of them), then one row per narrowPeak line (the same peak_N, contexts merged
+ * as gx_write_narrowpeak_group does); a value n (1/120 units) is printed as n / 120 with %lld when n % 120 == 0, else with
+ * %.2f. */
+int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_samples,
+                          const char* const* sample_names, FILE* out);
+int gx_write_counts(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names, FILE* out);
+int gx_write_counts_path(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names,
+                         const char* path);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -328,6 +365,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_LATE_LOOSE 16384u /* bit 14: ... GX_PATH_LOOSE_SWEEP on a sample whose lambda came with its end (fractional weights): the bits and the fillers were written after the tile stage (k_loose_late) */
 #define GX_PATH_Q_LOOSE 32768u /* bit 15: -q on one replicate without control: no tight table -- BH's histogram from the loose slots, q by pileup, the sweep on the loose slots (k_bh_small, k_loose_late, k_peak_both<.., PVQ>) */
 #define GX_PATH_MERGE_P 1024u /* bit 10: the last control merge scored its intervals itself and left (end, p) in its loose slots (k_merge2<.., true> + k_pack_ep2) */
+#define GX_PATH_COUNTS 65536u /* bit 16: this run kept its samples' intervals for counting (gx_set_count_in_peaks) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
