@@ -474,8 +474,11 @@ int build_pileup(gx_ctx* ctx, Pileup& out, int isCtrl, bool reuseSort = false) {
              ctx->fragFused && ctx->fracPairsUsed ? acc : (long long*)nullptr, ctx->hasBed ? bin : BedIn{nullptr, nullptr, nullptr},
              ctx->hasBed ? ff->fragSum : (u64*)nullptr};
     SbtOut so2{to, ctx->tileMeta.as<TileMeta>(), ctx->tileSlot.as<u32>(), ctx->nWide.as<u32>() + 1, ctx->nWide.as<u32>() + 13,
-               ctx->bigBins.as<u32>(), ctx->heavyList.as<u32>(), ctx->nWide.as<u32>() + 2};
+               ctx->bigBins.as<u32>(), ctx->heavyList.as<u32>(), ctx->nWide.as<u32>() + 2, ctx->nWide.as<u32>() + 14};
     const dim3 gAll(std::max(1u, nL1)), gBig(std::max(1u, std::min(nL1, (u32)ctx->numCU)));
+    // the first launch is persistent: a workgroup per CU (160 KiB of LDS: there is room for one), each drawing bins from the
+    // ticket word -- in the arena k_build_init clears, so zero for every sample and every rebuild (GX_SBT_GRID: tests, A/B)
+    const dim3 gPers(std::max(1u, std::min(gBig.x, K.sbtGrid > 0 ? (u32)K.sbtGrid : gBig.x)));
     // a sample so dense that the average bin already holds more keys than the key array (ATAC cut sites of a deep
     // library): every bin takes the rounds of the second launch, the first one would only find that out bin by bin
     const bool dense = ctx->pairsUsed && (size_t)2 * nEv > (size_t)std::max(1u, nL1) * (SBT_KEYCAP - SBT_KEYCAP / 16);
@@ -501,20 +504,20 @@ int build_pileup(gx_ctx* ctx, Pileup& out, int isCtrl, bool reuseSort = false) {
         else hipLaunchKernelGGL((k_sbtile<true, true, false>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
       }
     } else if (ctx->fracPairsUsed) {
-      hipLaunchKernelGGL((k_sbtile<true, false, true>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
+      hipLaunchKernelGGL((k_sbtile<true, false, true>), gPers, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
       hipLaunchKernelGGL((k_sbtile<true, true, true>), gBig, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
     } else if (ctx->pairsUsed && ctx->hasBed) {
       // (-E regions: the bins with an edge tile are the second launch's as well -- every second bin of hg38 with ~800 regions, so
       // a workgroup per bin of the grid, dealt by the dispatcher; the ones beyond the list leave at once)
-      hipLaunchKernelGGL((k_sbtile<true, false, false, SBT_TR, true>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
+      hipLaunchKernelGGL((k_sbtile<true, false, false, SBT_TR, true>), gPers, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
       hipLaunchKernelGGL((k_sbtile<true, true, false, SBT_TR, true>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
     } else if (ctx->pairsUsed) {
-      hipLaunchKernelGGL((k_sbtile<true, false, false>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
+      hipLaunchKernelGGL((k_sbtile<true, false, false>), gPers, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
       // the bins it left on its list (reads piled up: more keys than the key array holds, a tile with thousands of keys):
       // usually none -- an idle launch
       hipLaunchKernelGGL((k_sbtile<true, true, false>), gBig, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
     } else
-      hipLaunchKernelGGL((k_sbtile<false, false, false>), gAll, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
+      hipLaunchKernelGGL((k_sbtile<false, false, false>), gPers, dim3(SBT_NT), SBT_LDS_BYTES, s, si, so2, ctx->dStatus.as<u32>());
   } else if (ctx->hasBed) {
     hipLaunchKernelGGL((k_tile<true, true>), gHalf, dim3(TL_NT), TL_LDS_HALF * 4, s, tin, nTiles, wl, nw, bin, to,
                        ctx->dStatus.as<u32>());

@@ -99,7 +99,12 @@ struct SbtLds {
                                            // TM_ flags | keys of the tile << 8, carry-in pileup (1/120)
   u32 slotOff[2 * SBT_SLOTS];              // first key of a slot, as an index into its stream's page pool
   u32 slotCnt[2 * SBT_SLOTS];
-  u32 pre[2][NXCD + 1];
+  u32 pre[2][2][NXCD + 1];                 // [copy][stream]: records in the lists before list x.  Two copies: a persistent workgroup
+                                           // writes the next bin's while this bin's singles are still read through theirs
+  u32 lenN[2 * NXCD];                      // the next bin's list lengths
+  u32 anyHeavy;                            // the first launch: a tile of the bin is the whole workgroup's (the bin goes to the second launch)
+  u32 segN;                                // the next bin of this workgroup (its ticket; >= nSeg: none)
+  u32 ovfN;                                // the next bin has more slots than descriptors
   __attribute__((aligned(8))) u32 scratch[40];
   u32 work;
   u32 overflow;
@@ -158,6 +163,7 @@ struct SbtOut {
   u32* bigList;
   u32* heavyList;             // fractional pairs: the tiles sbt_heavy took (k_frag_walk adds their fragLen terms), and how many
   u32* nHeavyG;
+  u32* ticket;                // the first launch's bin counter (zero before it: k_build_init)
 };
 
 // LDS operations of ONE wavefront execute in order; what is needed between a wavefront's phases is only that
@@ -171,6 +177,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 // 32-bit byte offsets against a uniform base pointer: one shift instead of 64-bit address arithmetic per store
 __device__ __forceinline__ void st_u32(void* base, u32 index, u32 v) {
   *reinterpret_cast<u32*>(static_cast<char*>(base) + (size_t)(index << 2)) = v;
+}
+
+// A zero the compiler cannot see through.  In a persistent kernel a tuple of zero registers (the operand of a 16-byte store, the
+// initial value of a 16-byte load's destination) is otherwise made once, ahead of the loop over the bins, and kept -- or
+// spilled: the reload in the tile loop then waits for every load in flight, the next bin's records among them.
+__device__ __forceinline__ u32 sbt_zero() {
+  u32 z = 0;
+  asm volatile("" : "+s"(z));
+  return z;
 }
 
 // One tile, one wavefront: the passes of k_tile_fast with the keys in LDS (kl[0 .. n): [11:0] offset, [15] end).
@@ -192,20 +207,22 @@ __device__ __forceinline__ u32 sbt_class_of(int w) {  // weight (> 0) -> class; 
   return c;
 }
 
+// (lane: the caller's lane_id() -- a persistent workgroup hands it over afresh for every bin, so that what the passes derive from it
+// lives as long as a bin's tile loop and not as long as the kernel)
 template <bool FRAC, bool BED>
-__device__ __forceinline__ void sbt_tile(int* lds, const u32 TR_CAP, const uint16_t* __restrict__ kl, u32 n, u32 t, u32 pos0, u32 len, u32 flags,
+__device__ __forceinline__ void sbt_tile(const int lane, int* lds, const u32 TR_CAP, const uint16_t* __restrict__ kl, u32 n, u32 t, u32 pos0, u32 len, u32 flags,
                                          int carry, u32 slot, int vsig, const SbtOut& out, u32& bad, bool fragTerms, long long& fhi,
                                          long long& flo, long long& bedExcl) {
   constexpr u32 NOKEY = FRAC ? SBT_NOKEY_F : SBT_NOKEY;
   if (BED && (flags & TM_BEDIN)) {  // wave-uniform, -E runs only: a tile inside an excluded region -- no interval, its pileup off the closed form
     long long s = 0;
-    for (u32 k = lane_id(); k < n; k += 64) {
+    for (u32 k = lane; k < n; k += 64) {
       const u32 key = kl[k];
       const int w = FRAC ? sbt_weight(key) : ((key & 0x8000u) ? -GX_UNIT : GX_UNIT);
       s += (long long)w * (long long)(TILE - (key & (TILE - 1)));
     }
     bedExcl += wave_sum(s) + (long long)carry * TILE;
-    if (lane_id() == 0) out.to.tileCount[t] = 0;
+    if (lane == 0) out.to.tileCount[t] = 0;
     return;
   }
   // a key's offset with "no key" at 4096 (the dummy bitmap word)
@@ -215,7 +232,6 @@ __device__ __forceinline__ void sbt_tile(int* lds, const u32 TR_CAP, const uint1
   const uint16_t* pre16 = reinterpret_cast<const uint16_t*>(pre);
   int* cnt = lds + SBT_OCCW + SBT_PREW;
   uint16_t* list = reinterpret_cast<uint16_t*>(lds + SBT_OCCW + SBT_PREW + TR_CAP);   // (TR_CAP: a constant in the ordinary launch)
-  const int lane = lane_id();
   if (!(flags & TM_ACTIVE)) {  // wave-uniform: a tile of a chromosome that is not saved -- nothing to emit, nothing touched
     if (lane == 0) out.to.tileCount[t] = 0;
     return;
@@ -330,7 +346,10 @@ __device__ __forceinline__ void sbt_tile(int* lds, const u32 TR_CAP, const uint1
       emit(p, d120, dpp_scan_add(d120));
     }
   }
-  *reinterpret_cast<uint2*>(occ + 2 * lane) = make_uint2(0u, 0u);
+  {
+    const u32 z = sbt_zero();
+    *reinterpret_cast<uint2*>(occ + 2 * lane) = make_uint2(z, z);
+  }
   u32 total = 0;
   if (active) {  // wave-uniform
     total = outCount + (lastTile ? 1u : 0u);
@@ -484,6 +503,29 @@ __device__ __forceinline__ void sbt_heavy(SbtLds& L, const u32 scrWords, const u
   __syncthreads();
 }
 
+// Exclusive scan of two 32-bit values per thread over the workgroup (the tiles' key counts and what they hand on): two DPP scans
+// per level.  (block_excl_scan<u64> shuffles through addresses and masks made from the lane number -- loop invariants that a
+// persistent workgroup would carry in registers through all of its bins.)  `tid`: the caller's thread number.
+__device__ __forceinline__ void sbt_excl_scan2(u32 a, u32 b, uint2* scratch, int tid, u32& exA, u32& exB, u32& totA, u32& totB) {
+  const u32 ia = (u32)dpp_scan_add((int)a), ib = (u32)dpp_scan_add((int)b);
+  const int w = tid >> 6;
+  if ((tid & 63) == 63) scratch[w] = make_uint2(ia, ib);
+  __syncthreads();
+  if (tid < 64) {
+    const uint2 x = tid < SBT_NW ? scratch[tid] : make_uint2(0u, 0u);
+    const u32 xa = (u32)dpp_scan_add((int)x.x), xb = (u32)dpp_scan_add((int)x.y);
+    if (tid < SBT_NW) scratch[tid] = make_uint2(xa - x.x, xb - x.y);
+    if (tid == SBT_NW - 1) scratch[SBT_NW] = make_uint2(xa, xb);
+  }
+  __syncthreads();
+  const uint2 base = scratch[w], tot = scratch[SBT_NW];
+  exA = ia - a + base.x;
+  exB = ib - b + base.y;
+  totA = tot.x;
+  totB = tot.y;
+  __syncthreads();
+}
+
 // PAIRS: level 1 was k_sort1p (gx_sort.h): one 4-byte record per fragment (start within the bin, length) in PS, the few
 // other records ("singles") as 8-byte signed-weight records in PF -- half the bytes to load, one LDS atomic per fragment
 // in the histogram and in the scatter where both ends share a tile (19 of 20).
@@ -491,38 +533,224 @@ __device__ __forceinline__ void sbt_heavy(SbtLds& L, const u32 scrWords, const u
 // array holds (worked off in rounds of tiles), a tile with thousands of keys (sbt_heavy: the whole workgroup), more than
 // 32 K pair records.  It keeps no record in registers (every pass reads the bin's slots from global memory: they are
 // in L2), so that none of this costs the first launch -- the one every bin of an ordinary sample takes -- a register.
+// The FIRST launch is persistent (round 7): min(bins, CUs) workgroups, each of which draws its bins from a ticket counter --
+// 2,946 workgroups of 160 KiB of LDS were one per CU anyway, and a CU took the next one only after the previous one had
+// retired entirely.  What a workgroup knows one bin ahead it asks for under the bin it is working on, so that no global
+// round trip of a bin's prologue (ticket -> list lengths -> page table -> records) is waited for with the whole CU idle:
+//   start of bin i              tid 0 draws the ticket of bin i + 1
+//   end of the histogram        wavefront 0 has the ticket: it asks for that bin's sixteen list lengths, the others for its
+//                               tiles' chromosome numbers (behind the histogram's barrier)
+//   end of the scatter          wavefront 0 leaves the lengths and their prefix in LDS (behind the scatter's barrier)
+//   before the tile loop        every wavefront makes its own slots' descriptors (a wave-local matter) and asks for its
+//                               records: they arrive under the tile loop, which issues no global load of its own, in a
+//                               second set of registers (PAIRS: 32; the start / end key instance holds two streams already
+//                               and loads at the start of the next bin instead)
+//   end of the tile loop        ONE barrier; the registers rotate.
+// No workgroup ever waits for another.  GX_SBT_PREFETCH=0 (tools/build_variant.sh) keeps the persistent loop and runs those
+// steps between the bins instead: the A/B for what the overlap is worth.
+#ifndef GX_SBT_PREFETCH
+#define GX_SBT_PREFETCH 1
+#endif
 template <bool PAIRS, bool BIG, bool FRAC, int TRC, bool BED>
-__device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32* __restrict__ st, const u32 seg, SbtLds& L) {
+__device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32* __restrict__ st, const u32 segArg, SbtLds& L) {
   static_assert(PAIRS || !BIG, "the second launch exists in pair mode only");
   static_assert(PAIRS || !FRAC, "fractional weights ride pair records only");
   static_assert(!BED || (PAIRS && !FRAC), "-E regions: unit-weight pair records (the tiles with an edge are the second launch's)");
   constexpr u32 LENB = FRAC ? 9u : PAIR_LEN_BITS;      // a pair record's length bits (fractional: [11:9] the weight class)
   const bool fragTerms = FRAC && in.fragAcc != nullptr && (u32)__builtin_amdgcn_readfirstlane((int)in.ff->slow) != 0u;
-  long long fhi = 0, flo = 0, bedExcl = 0;
+  long long fhi = 0, flo = 0, bedExcl = 0;   // (a wavefront's sums over all bins of its workgroup: exact integers)
+  u32 bad = 0;
   constexpr int K = BIG ? 0 : (PAIRS ? SBT_KP : SBT_K);   // slots per wavefront of the (first) stream held in registers
   constexpr int KX = BIG ? SBT_KX : K;                    // ... and in all
   constexpr int KR = K ? K : 1;                           // (array sizes)
   constexpr u32 NSLOTS = (u32)KX * SBT_NW;
-  const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+  constexpr bool OVERLAP = !BIG && GX_SBT_PREFETCH != 0;  // the next bin's prologue under this bin
+  constexpr bool PF = PAIRS && OVERLAP;                   // ... down to its records, in registers of their own
+  int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
   // how the LDS behind the tables is split: constants of the instance (runtime values cost the rounds launch 12 %: measured)
   static_assert(TRC % 64 == 0 && TRC >= 192 && TRC <= 448, "touched bases per round");
   constexpr u32 trCap = (u32)TRC;
   constexpr u32 tw = sbt_tw(trCap), scrWords = SBT_NW * tw, keyCap = sbt_keycap(trCap);
+  static_assert(tw % 4 == 0, "a wavefront clears its scratch by 16-byte stores");
   int* const scr = L.dyn;
   uint16_t* const keysL = reinterpret_cast<uint16_t*>(L.dyn + scrWords);
   const u32 nSeg = in.nSeg;
   const u32 nT = 1u << in.sbShift;           // tiles per super-bucket (<= SBT_TILES)
-  const u32 segTileBase = seg << in.sbShift;
-  const int vsig = (int)__builtin_amdgcn_readfirstlane(loose_vsig(out.to.ctl, !BIG && seg == 0 && tid == 0, L.vsRed));
-  // (one workgroup per CU: a global round trip in this prologue is a round trip of the whole CU.  The lists' lengths and the
-  // tiles' chromosome records -- two dependent loads -- are asked for first and arrive while the scratch is cleared)
-  u32 myLen = 0;
+  const int vsig = (int)__builtin_amdgcn_readfirstlane(loose_vsig(out.to.ctl, !BIG && blockIdx.x == 0 && tid == 0, L.vsRed));   // (once per workgroup)
+  const uint4* __restrict__ poolS = reinterpret_cast<const uint4*>(in.PS.pool);
+  const uint4* __restrict__ poolE = reinterpret_cast<const uint4*>(in.PE.pool);
+  constexpr bool hasBed = BED;   // (instances of their own: the plumbing cost the run without regions 0.012 ms as a run-time switch)
+#ifndef GX_SBT_FREG
+#define GX_SBT_FREG 1
+#endif
+  // ---- what a workgroup carries from bin to bin ------------------------------------------------------------------------------
+  u32 seg = 0, segTileBase = 0, par = 0;     // this bin; which copy of L.pre is its
+  u32 ci = 0;                                // thread b: the chromosome of tile b of this bin
+  uint4 kS[KR], kE[PAIRS ? 1 : KR];          // its records
+  u32 segN = 0, ciN = 0, lenRegN = 0;        // the next bin: its number, chromosomes, list lengths (threads 0 .. 15)
+  bool haveN = false;
+  uint4 kN[PF ? KR : 1];                     // ... and its records, on their way under the tile loop
+  u32 tk = 0;                                // (tid 0) the ticket drawn at the start of this bin
+  bool drawn = false;
+  int stage = 0;                             // how far the next bin's prologue has come: 1 lengths asked for, 2 lengths in LDS, 3 records asked for
+#pragma unroll
+  for (int i = 0; i < (PF ? KR : 1); i++) kN[i] = make_uint4(0u, 0u, 0u, 0u);
+  // a wavefront's scratch starts at zero (sbt_tile leaves it so; sbt_heavy clears what it used)
+  auto clearOwn = [&]() {
+    int* mine = scr + (u32)__builtin_amdgcn_readfirstlane(wv) * tw;
+    const int z = (int)sbt_zero();
+    for (u32 i = (u32)lane * 4; i < tw; i += 64 * 4) *reinterpret_cast<int4*>(mine + i) = make_int4(z, z, z, z);
+    wave_lds_sync();
+    if (lane == 0) mine[SBT_OCCW + TILE / 64] = -1;  // the prefix entry of the dummy bitmap word: no rank at all
+  };
+  // the sixteen list lengths of bin sg (wavefront 0; wave-uniform sg)
+  auto askLens = [&](u32 sg) {
+    lenRegN = 0;
+    if (sg < nSeg && tid < 2 * NXCD) {
+      const u32 li = (u32)(tid & (NXCD - 1)) * nSeg + sg;
+      if (PAIRS)
+        lenRegN = tid < NXCD ? list_len<u32>(in.PS, li) : list_len<u64>(in.PF, li);
+      else
+        lenRegN = list_len<u32>(tid < NXCD ? in.PS : in.PE, li);
+    }
+  };
+  // ... and the chromosomes of its tiles (the first of two dependent loads; the second one at the bin's start)
+  auto askChrom = [&]() {
+    haveN = segN < nSeg;
+    ciN = 0;
+    if (haveN && tid < (int)nT) {
+      const u32 t = (segN << in.sbShift) + (u32)tid;
+      if (t < in.nTiles) ciN = in.tileChrom[t];
+    }
+  };
+  // (the scatter cursors are free from the scatter's end to the next bin's scan: the chromosome numbers wait there, not in a
+  // register through the tile loop)
+  auto stashChrom = [&]() {
+    if (tid < (int)nT) L.cur[tid] = ciN;
+  };
+  // the lengths, their prefix and "more slots than descriptors" into LDS (wavefront 0)
+  auto lensToLds = [&]() {
+    if (wv != 0) return;
+    if (tid < 2 * NXCD) L.lenN[tid] = lenRegN;
+    if (tid == 0) L.ovfN = 0;
+    wave_lds_sync();
+    if (tid < 2) {
+      u32 a = 0, ns = 0;
+      for (int x = 0; x < NXCD; x++) {
+        L.pre[par ^ 1u][tid][x] = a;
+        const u32 l = L.lenN[tid * NXCD + x];
+        a += l;
+        ns += (l + SBT_SLOT - 1) / SBT_SLOT;
+      }
+      L.pre[par ^ 1u][tid][NXCD] = a;
+      if (ns > NSLOTS && (tid == 0 || !PAIRS)) L.ovfN = 1;  // more slots than descriptors: the bin does not fit
+    }
+  };
+  // ---- 1: slot descriptors: the bin's sixteen page lists (8 XCD classes x start / end keys) cut into slots of 256 keys.  A
+  // wavefront makes the descriptors of ITS slots (i * SBT_NW + wv: lane i of stream lane / KX) -- nobody else reads them
+  auto descOwn = [&](u32 sg, u32 pr) {
+    constexpr int ND = (PAIRS ? 1 : 2) * KX;
+    static_assert(ND <= 64, "a lane per slot of the wavefront");
+    if (lane < ND) {
+      const int q = lane / KX;
+      const u32 k = (u32)(lane % KX) * SBT_NW + (u32)wv;
+      const PagedStream& P = q ? in.PE : in.PS;
+      const u32* pre = L.pre[pr][q];
+      u32 x = NXCD, k0 = 0, acc = 0;
+      for (u32 y = 0; y < NXCD; y++) {
+        const u32 ns = (pre[y + 1] - pre[y] + SBT_SLOT - 1) / SBT_SLOT;
+        if (x == NXCD && k < acc + ns) {
+          x = y;
+          k0 = acc;
+        }
+        acc += ns;
+      }
+      u32 ptr = 0;
+      u32 cnt = 0;
+      if (x < NXCD) {
+        const u32 off = (k - k0) * SBT_SLOT;
+        const u32 jp = off >> PgCfg<u32>::SHIFT, li = x * nSeg + sg;
+        const u32 page = jp ? P.pt[(size_t)li * P.jmax + jp] - 1u : first_page(li);
+        ptr = (page << PgCfg<u32>::SHIFT) + (off & ((1u << PgCfg<u32>::SHIFT) - 1u));
+        cnt = min(SBT_SLOT, pre[x + 1] - pre[x] - off);
+      }
+      L.slotOff[(u32)q * NSLOTS + k] = ptr;
+      L.slotCnt[(u32)q * NSLOTS + k] = cnt;
+    }
+    wave_lds_sync();
+  };
+  // ---- 2: the bin's keys, all loads in flight together
+  // (have: block-uniform -- no bin, nothing asked for, but every register written: nothing of the next bin's lives across a bin)
+  auto loadRecs = [&](bool have, u32 sg, u32 pr, uint4 (&dS)[KR], uint4 (&dE)[PAIRS ? 1 : KR]) {
+    const bool ov = !have || L.ovfN != 0;
+    const u32 z = PF ? sbt_zero() : 0u;   // (the start / end key instance loads at a bin's start: a plain zero serves it better)
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+      const u32 c = ov ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)L.slotCnt[i * SBT_NW + wv]);  // (wave-uniform)
+      dS[i] = make_uint4(z, z, z, z);
+      if ((u32)lane * 4 < c) dS[i] = poolS[(L.slotOff[i * SBT_NW + wv] >> 2) + lane];
+    }
+#pragma unroll
+    for (int i = 0; i < (PAIRS ? 1 : K); i++) {
+      const u32 c = ov || PAIRS ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)L.slotCnt[NSLOTS + i * SBT_NW + wv]);
+      dE[i] = make_uint4(z, z, z, z);
+      if (!PAIRS && (u32)lane * 4 < c) dE[i] = poolE[(L.slotOff[NSLOTS + i * SBT_NW + wv] >> 2) + lane];
+    }
+  };
+  // what is left of the next bin's prologue, one step after the other (a workgroup's first bin; a bin that left early)
+  auto finishNext = [&]() {
+    if (stage < 1) {
+      if (wv == 0) {
+        if (!drawn && tid == 0) tk = atomicAdd(out.ticket, 1u);
+        const u32 sN = (u32)__builtin_amdgcn_readfirstlane((int)tk);
+        askLens(sN);
+        if (tid == 0) L.segN = sN;
+      }
+      __syncthreads();
+      segN = L.segN;
+      askChrom();
+    }
+    if (GX_EXP_SBT == 4 || GX_EXP_SBT == 5) stashChrom();   // (measurement exits leave before the scan: the cursors are free)
+    if (GX_EXP_SBT == 4) return;
+    if (stage < 2) lensToLds();
+    if (GX_EXP_SBT == 5) return;
+    if (stage < 3) {
+      __syncthreads();
+      if constexpr (PF)
+      {
+        if (haveN) descOwn(segN, par ^ 1u);  // block-uniform
+        loadRecs(haveN, segN, par ^ 1u, kN, kE);
+      }
+      stashChrom();
+    }
+  };
+  auto rotate = [&]() {
+    seg = segN;
+    segTileBase = seg << in.sbShift;
+    if constexpr (!BIG) ci = tid < (int)nT ? L.cur[tid] : 0u;   // (this thread's own word)
+    else ci = ciN;
+    par ^= 1u;
+    if constexpr (PF) {
+#pragma unroll
+      for (int i = 0; i < K; i++) kS[i] = kN[i];
+    }
+  };
+  // ---- one bin ------------------------------------------------------------------------------------------------------------------
+  auto bin = [&]() {
+  if constexpr (!BIG) {
+    // (what is computed from the thread's number is computed anew in every bin: hoisted out of the loop over the bins, the
+    // addresses and masks of all its phases together cost more registers than the kernel has -- scratch, measured at compile time)
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63;
+    wv = tid >> 6;
+  }
+  if (OVERLAP && tid == 0) tk = atomicAdd(out.ticket, 1u);   // the bin after this one: its latency is never waited for
+  drawn = OVERLAP;
   auto loadTi = [&]() {   // the tiles' chromosome records (thread b: tile b of the bin)
     uint4 ti = make_uint4(0u, 0u, 0u, 0u);
     if (tid < (int)nT) {
       const u32 t = segTileBase + tid;
       if (t < in.nTiles) {
-        const u32 ci = in.tileChrom[t];
         const DChrom c = in.chroms[ci];
         const u32 tl = t - c.tileBase;
         ti.x = tl << TB;
@@ -535,7 +763,6 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
   };
   // -E regions: the edges before this thread's tile (they take loose slots of their own) and the tile's kind (TM_BEDX: an edge
   // inside, or a chromosome's last tile that ends inside a region; `inside`: nothing of the tile is saved)
-  constexpr bool hasBed = BED;   // (instances of their own: the plumbing cost the run without regions 0.012 ms as a run-time switch)
   u32 bedBefore = 0, bedMine = 0;
   bool bedInside = false;
   auto loadBed = [&](const uint4& ti) {
@@ -561,70 +788,15 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
       out.to.tileCount[t] = 0;
     }
   };
-  if (GX_EXP_SBT == 4) { expLeave(); return; }   // (measurement: what launching the workgroups costs)
-  if (tid < 2 * NXCD) {
-    const u32 li = (u32)(tid & (NXCD - 1)) * nSeg + seg;
-    if (PAIRS)
-      myLen = tid < NXCD ? list_len<u32>(in.PS, li) : list_len<u64>(in.PF, li);
-    else
-      myLen = list_len<u32>(tid < NXCD ? in.PS : in.PE, li);
+  if (GX_EXP_SBT == 4) { expLeave(); return; }   // (measurement: what handing out the bins costs)
+  // (the records of a bin whose prologue ran between the bins: asked for now)
+  if constexpr (!PF) {
+    descOwn(seg, par);
+    loadRecs(true, seg, par, kS, kE);
   }
   uint4 ti = loadTi();
   const u32 bedx = loadBed(ti);
-  // scratch and tables start at zero
-  for (u32 i = (u32)tid * 4; i < scrWords; i += SBT_NT * 4) *reinterpret_cast<int4*>(scr + i) = make_int4(0, 0, 0, 0);
-  if (tid < SBT_TILES) {
-    L.hist[tid] = 0;
-    if (FRAC) L.netW[tid] = 0;
-  }
-  if (tid == 0) { L.overflow = 0; L.nHeavy = 0; L.nRounds = 0; }
-  if (tid < 2 * NXCD) L.scratch[tid] = myLen;
-  __syncthreads();
-  if (tid < SBT_NW) scr[(u32)tid * tw + SBT_OCCW + TILE / 64] = -1;  // the prefix entry of the dummy bitmap word: no rank at all
-  if (tid < 2) {
-    u32 a = 0;
-    for (int x = 0; x < NXCD; x++) {
-      L.pre[tid][x] = a;
-      a += L.scratch[tid * NXCD + x];
-    }
-    L.pre[tid][NXCD] = a;
-  }
-  __syncthreads();
-  if (GX_EXP_SBT == 5) { expLeave(); return; }   // (measurement: ... and clearing the scratch, the lists' lengths)
-  // ---- 1: slot descriptors (thread k of the first 2 SBT_SLOTS: slot k & 127 of stream k >> 7)
-  if (tid < (PAIRS ? 1 : 2) * (int)NSLOTS) {
-    const int q = tid / (int)NSLOTS;
-    const u32 k = (u32)tid % NSLOTS;
-    const PagedStream& P = q ? in.PE : in.PS;
-    const u32* pre = L.pre[q];
-    u32 x = NXCD, k0 = 0, acc = 0;
-    for (u32 y = 0; y < NXCD; y++) {
-      const u32 ns = (pre[y + 1] - pre[y] + SBT_SLOT - 1) / SBT_SLOT;
-      if (x == NXCD && k < acc + ns) {
-        x = y;
-        k0 = acc;
-      }
-      acc += ns;
-    }
-    if (k == 0 && acc > NSLOTS) L.overflow = 1;  // more slots than descriptors: the bin does not fit
-    u32 ptr = 0;
-    u32 cnt = 0;
-    if (x < NXCD) {
-      const u32 off = (k - k0) * SBT_SLOT;
-      const u32 jp = off >> PgCfg<u32>::SHIFT, li = x * nSeg + seg;
-      const u32 page = jp ? P.pt[(size_t)li * P.jmax + jp] - 1u : first_page(li);
-      ptr = (page << PgCfg<u32>::SHIFT) + (off & ((1u << PgCfg<u32>::SHIFT) - 1u));
-      cnt = min(SBT_SLOT, pre[x + 1] - pre[x] - off);
-    }
-    L.slotOff[tid] = ptr;
-    L.slotCnt[tid] = cnt;
-  }
-  __syncthreads();
-  const bool ovfSlots = L.overflow != 0;
-  // ---- 2: the bin's keys, all loads in flight together
-  const uint4* __restrict__ poolS = reinterpret_cast<const uint4*>(in.PS.pool);
-  const uint4* __restrict__ poolE = reinterpret_cast<const uint4*>(in.PE.pool);
-  uint4 kS[KR], kE[PAIRS ? 1 : KR];
+  const bool ovfSlots = L.ovfN != 0;
   u32 cS[KR], cE[PAIRS ? 1 : KR];
 #pragma unroll
   for (int i = 0; i < K; i++)  // (wave-uniform: scalar registers)
@@ -632,30 +804,29 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
 #pragma unroll
   for (int i = 0; i < (PAIRS ? 1 : K); i++)
     cE[i] = ovfSlots || PAIRS ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)L.slotCnt[NSLOTS + i * SBT_NW + wv]);
-#pragma unroll
-  for (int i = 0; i < K; i++) {
-    kS[i] = make_uint4(0u, 0u, 0u, 0u);
-    if ((u32)lane * 4 < cS[i]) kS[i] = poolS[(L.slotOff[i * SBT_NW + wv] >> 2) + lane];
-  }
-#pragma unroll
-  for (int i = 0; i < (PAIRS ? 1 : K); i++) {
-    kE[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (!PAIRS && (u32)lane * 4 < cE[i]) kE[i] = poolE[(L.slotOff[NSLOTS + i * SBT_NW + wv] >> 2) + lane];
-  }
   // pair mode: the bin's singles (a handful; 8-byte records of weight +-120 = a start / an end key; anything else is a
   // fractional weight: the sample goes to the general chain) are read where they lie, once per pass
-  const BinSrc<u64> srcF{reinterpret_cast<const u64*>(in.PF.pool), in.PF.pt, nSeg, in.PF.jmax, seg, L.pre[1]};
-  const u32 nF = PAIRS && !ovfSlots ? L.pre[1][NXCD] : 0u;
-  // (round 6: a thread's first single is asked for HERE, with the records, and kept for both passes -- read in the histogram's
-  // and in the scatter's loop each was a global round trip of its own, with the whole CU waiting: one workgroup per CU)
-#ifndef GX_SBT_FREG
-#define GX_SBT_FREG 1
-#endif
+  const BinSrc<u64> srcF{reinterpret_cast<const u64*>(in.PF.pool), in.PF.pt, nSeg, in.PF.jmax, seg, L.pre[par][1]};
+  const u32 nF = PAIRS && !ovfSlots ? L.pre[par][1][NXCD] : 0u;
+  // (round 6: a thread's first single is asked for HERE, at the bin's start, and kept for both passes -- read in the histogram's and
+  // in the scatter's loop each was a global round trip of its own; it arrives while the pair records are counted)
   u64 fReg = 0;
   if (GX_SBT_FREG && PAIRS && (u32)tid < nF) fReg = srcF.at((u32)tid);
   auto singleAt = [&](u32 i) -> u64 { return GX_SBT_FREG && i == (u32)tid ? fReg : srcF.at(i); };
-  // (16-bit counts per tile: the bin's pairs and singles together stay below 2^16)
-  if (PAIRS && tid == 0 && (nF > SBT_FCAP || L.pre[0][NXCD] + nF > 65535u)) L.overflow = 1;  // (read behind the histogram's barrier)
+  // tables start at zero
+  if (tid < SBT_TILES) {
+    L.hist[tid] = 0;
+    if (FRAC) L.netW[tid] = 0;
+  }
+  if (tid == 0) {
+    // (16-bit counts per tile: the bin's pairs and singles together stay below 2^16)
+    L.overflow = ovfSlots || (PAIRS && (nF > SBT_FCAP || L.pre[par][0][NXCD] + nF > 65535u)) ? 1u : 0u;
+    L.nHeavy = 0;
+    L.nRounds = 0;
+    L.anyHeavy = 0;
+  }
+  __syncthreads();
+  if (GX_EXP_SBT == 5) { expLeave(); return; }   // (measurement: ... and clearing the tables)
   if (GX_EXP_SBT == 1) {
     u32 x = 0;
 #pragma unroll
@@ -753,26 +924,37 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
     }
   }
   }
+  if (OVERLAP && wv == 0) {   // the next bin's ticket has been on its way since this bin began
+    const u32 sN = (u32)__builtin_amdgcn_readfirstlane((int)tk);
+    askLens(sN);
+    if (tid == 0) L.segN = sN;
+  }
   __syncthreads();
+  if constexpr (OVERLAP) {
+    segN = L.segN;
+    askChrom();
+    stage = 1;
+  }
   {
     u32 h = tid < (int)nT ? L.hist[tid] : 0u;
     const u32 nS = h & 0xFFFFu, nE = h >> 16;
     // (what the tiles before hand on: starts - ends in records; fractional pairs: the net weight itself)
-    const u64 v = (u64)(nS + nE) | ((u64)(u32)(FRAC ? (tid < (int)nT ? L.netW[tid] : 0) : (int)nS - (int)nE) << 32);
-    u64 tot;
-    const u64 ex = block_excl_scan<u64, SBT_NT>(v, reinterpret_cast<u64*>(L.scratch), &tot);
+    u32 totK, totN;
+    u32 exK, exN;
+    sbt_excl_scan2(nS + nE, (u32)(FRAC ? (tid < (int)nT ? L.netW[tid] : 0) : (int)nS - (int)nE), reinterpret_cast<uint2*>(L.scratch), tid, exK, exN,
+                   totK, totN);
     if (tid < (int)nT) {
-      L.startC[tid] = (u32)ex;
-      L.netPref[tid] = (int)(u32)(ex >> 32);
+      L.startC[tid] = exK;
+      L.netPref[tid] = (int)exN;
     }
-    if (tid == 0) L.startC[nT] = (u32)tot;
+    if (tid == 0) L.startC[nT] = totK;
+    // what the first launch does not take: a tile with thousands of keys, or with a -E edge -- the whole workgroup's
+    if (PAIRS && !BIG && (nS + nE > SBT_HEAVY || (bedx & TM_BEDX))) L.anyHeavy = 1;
   }
   __syncthreads();
   if constexpr (PAIRS && !BIG) {
-    // what this launch does not take: it goes on the list of the second one, untouched
-    const u32 hh = tid < (int)nT ? L.hist[tid] : 0u;
-    const bool heavyTile = (hh & 0xFFFFu) + (hh >> 16) > SBT_HEAVY || (bedx & TM_BEDX);   // (a tile with a -E edge: the whole workgroup's too)
-    const bool big = __syncthreads_or((int)heavyTile) || ovfSlots || L.startC[nT] > keyCap || L.overflow == 1;
+    // ... it goes on the list of the second one, untouched
+    const bool big = L.anyHeavy != 0 || ovfSlots || L.startC[nT] > keyCap || L.overflow == 1;
     if (big) {  // block-uniform
       if (tid == 0) out.bigList[atomicAdd(out.nBig, 1u)] = seg;
       return;
@@ -866,7 +1048,6 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
     if (tid < (int)nT && segTileBase + tid < in.nTiles) out.to.tileCount[segTileBase + tid] = 0;
     return;
   }
-  u32 bad = 0;
   // ---- 4: the keys to their tiles' lists in LDS; then the wavefronts take tiles from a counter
   if (tid == 0) L.work = 0;
   __syncthreads();  // the cursors are there
@@ -895,7 +1076,7 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
         continue;
       }
       const u32 bedSlots = hasBed ? (u32)__builtin_amdgcn_readfirstlane(L.netPref[b]) : 0u;
-      sbt_tile<FRAC, BED>(scr + (u32)__builtin_amdgcn_readfirstlane(wv) * tw, trCap, keysL + (sc - keyBase), n, t, tf.x, tf.y, fz & 0xFFu, (int)tf.w,
+      sbt_tile<FRAC, BED>(lane, scr + (u32)__builtin_amdgcn_readfirstlane(wv) * tw, trCap, keysL + (sc - keyBase), n, t, tf.x, tf.y, fz & 0xFFu, (int)tf.w,
                      segSlot + sc + b + bedSlots, vsig, out, bad, fragTerms, fhi, flo, bedExcl);
     }
     if constexpr (BIG) {
@@ -946,12 +1127,24 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
         const u32 off = (u32)(r >> 8) & (TILE - 1);
         keysL[atomicAdd(&L.cur[(u32)(r >> 32) - segTileBase], 1u)] = (uint16_t)(off | ((r & 0x80) ? 0x8000u : 0u) | fCls(r));
       }
+      if constexpr (OVERLAP) {
+        lensToLds();
+        stage = 2;
+      }
       __syncthreads();
       if (GX_EXP_SBT == 3) {
         if (tid < (int)nT && segTileBase + tid < in.nTiles) out.to.tileCount[segTileBase + tid] = keysL[L.startC[tid]] == 0xFFFFu;
         return;
       }
+      // the next bin's records: asked for here, they arrive under the tile loop (which issues no global load of its own)
+      if constexpr (PF) {
+        if (haveN) descOwn(segN, par ^ 1u);  // block-uniform
+        loadRecs(haveN, segN, par ^ 1u, kN, kE);
+        stashChrom();
+        stage = 3;
+      }
       tiles(nT, 0u);
+      clearOwn();
     }
   } else if constexpr (BIG) {
     {
@@ -1006,12 +1199,39 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
         if ((u32)lane * 4 + j < cE[i]) place(keyAt(kE[i], j), (u32)SBT_TILES, 0x8000u);
     }
   }
+  if constexpr (OVERLAP) {
+    lensToLds();
+    stage = 2;
+  }
   __syncthreads();
   if (GX_EXP_SBT == 3) {
     if (tid < (int)nT && segTileBase + tid < in.nTiles) out.to.tileCount[segTileBase + tid] = keysL[L.startC[tid]] == 0xFFFFu;
     return;
   }
   tiles(nT, 0u);
+  clearOwn();
+  }
+  };  // (bin)
+  clearOwn();
+  if constexpr (BIG) {
+    // the second launch: a bin of the list, its prologue step by step
+    askLens(segArg);
+    segN = segArg;
+    askChrom();
+    lensToLds();
+    __syncthreads();
+    rotate();
+    bin();
+  } else {
+    finishNext();
+    for (;;) {
+      __syncthreads();   // (the one barrier between a bin's tile loop and the next bin's tables)
+      rotate();
+      if (seg >= nSeg) break;  // block-uniform
+      stage = 0;
+      bin();
+      finishNext();
+    }
   }
   if (FRAC && fragTerms) {  // wave-uniform
     fhi = wave_sum(fhi);
@@ -1023,16 +1243,17 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
   }
   // (-E: this wavefront's share of the pileup over excluded bases, off the closed form of fragLen -- whole bases with unit weights;
   // with fractional ones the closed form is not used, FRAG_SLOW_FRAC)
-  if (bedExcl && lane == 0) atomicAdd(&in.fragSum[(seg * SBT_NW + (u32)wv) % FRAG_SLOTS], (u64)(-(bedExcl / GX_UNIT)));
+  if (bedExcl && lane == 0) atomicAdd(&in.fragSum[((BIG ? segArg : blockIdx.x) * SBT_NW + (u32)wv) % FRAG_SLOTS], (u64)(-(bedExcl / GX_UNIT)));
   if (bad && lane == 0) atomicOr(st, bad);
 }
 
+// the first launch (!BIG): min(bins, CUs) persistent workgroups; the second one: the bins of the first one's list
 template <bool PAIRS, bool BIG, bool FRAC, int TRC = SBT_TR, bool BED = false>
 __global__ __launch_bounds__(SBT_NT) void k_sbtile(SbtIn in, SbtOut out, u32* __restrict__ st) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sbt_raw[];
   SbtLds& L = *reinterpret_cast<SbtLds*>(sbt_raw);
   if constexpr (!BIG)
-    sbt_bin<PAIRS, false, FRAC, TRC, BED>(in, out, st, blockIdx.x, L);
+    sbt_bin<PAIRS, false, FRAC, TRC, BED>(in, out, st, 0u, L);
   else {
     // (no list: a sample so dense that most bins need rounds -- the host sends every bin here and skips the first launch)
     const u32 nBig = out.bigList ? *out.nBig : in.nSeg;
