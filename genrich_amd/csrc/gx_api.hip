@@ -509,8 +509,8 @@ int gx_pvalues(gx_ctx* ctx) {
     pa.ctrlConst = ctx->hScal.lambda;
     pa.loose = true;
     // (the tile stage wrote the sweep's significance bits, in loose-slot index space: LooseCtl)
-    pa.looseSweep = ctx->looseOk && (!ctx->par.qval_opt || ctx->lateLoose) && !ctx->knob.noLoose;   // (-q: gx_find_peaks' qLoose)
-    pa.latePending = pa.looseSweep && ctx->lateLoose;   // (its bits are still to be written: k_loose_late, by gx_find_peaks)
+    pa.looseSweep = ctx->looseOk && (!ctx->par.qval_opt || ctx->built.wantLate) && !ctx->knob.noLoose;   // (-q: gx_find_peaks' qLoose)
+    pa.latePending = pa.looseSweep && ctx->built.wantLate;   // (its bits are still to be written: k_loose_late, by gx_find_peaks)
     pa.looseStride = ctx->looseStride;
     if (pa.looseSweep) pa.chromLooseOff = std::move(ctx->chromLooseOff);
     ctx->looseOk = false;
@@ -584,38 +584,24 @@ int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* 
   phase_begin(ctx, "sweep");
   SweepSrc src{};
   src.nChrom = nChrom;
-  if (qLoose) {
-    // (q by whole pileup and from which pileup on it passes: k_bh_small, above) the bits on the loose slots
-    HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, fa.looseStride * 8, s));   // (the significance words: a run before may have left its own)
-    hipLaunchKernelGGL(k_loose_late, dim3(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(8 * ctx->numCU)))), dim3(256), 0, s,
-                       ctx->tileSlot.as<u32>(), ctx->tileIvCount.as<u32>(), ctx->tileLastEnd.as<u32>(), ctx->nTiles,
-                       ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->looseCtl.as<LooseCtl>(), ctx->swMask.as<u64>(),
-                       (const u32*)(misc + M_VQ), ctx->dStatus.as<u32>());
-    fa.latePending = false;
-    fa.lateLoose = true;
-    ctx->lateLooseUsed = true;
-    ctx->qLooseUsed = true;
-    src.end = ctx->looseEnd.as<u32>();
-    src.V = ctx->looseV.as<int>();
-    src.p = ctx->pvLut.as<float>();
-    src.qLut = ctx->qLut.as<float>();
-    src.chromOff = fa.chromLooseOff.as<u32>();
-    src.mStride = fa.looseStride;
-    src.nWords = (u32)(fa.looseStride - 2);
-    src.haveMasks = true;
-    src.hasSkip = false;
-  } else if (looseFast) {
-    ctx->lateLooseUsed = fa.lateLoose || fa.latePending;
-    if (fa.latePending) {
+  if (qLoose || looseFast) {
+    // the sweep walks the loose slots; their bits are written now if lambda -- or, with -q, "q passes from this pileup on"
+    // (k_bh_small, above) -- came after the tile stage
+    ctx->lateLooseUsed = qLoose || fa.lateLoose || fa.latePending;
+    ctx->qLooseUsed = qLoose;
+    if (qLoose) HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, fa.looseStride * 8, s));   // (the significance words: a run before may have left its own)
+    if (qLoose || fa.latePending) {
       hipLaunchKernelGGL(k_loose_late, dim3(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(8 * ctx->numCU)))), dim3(256), 0, s,
                          ctx->tileSlot.as<u32>(), ctx->tileIvCount.as<u32>(), ctx->tileLastEnd.as<u32>(), ctx->nTiles,
-                         ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->looseCtl.as<LooseCtl>(), ctx->swMask.as<u64>());
+                         ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->looseCtl.as<LooseCtl>(), ctx->swMask.as<u64>(),
+                         qLoose ? (const u32*)(misc + M_VQ) : (const u32*)nullptr, qLoose ? ctx->dStatus.as<u32>() : (u32*)nullptr);
       fa.latePending = false;
       fa.lateLoose = true;
     }
     src.end = ctx->looseEnd.as<u32>();
     src.V = ctx->looseV.as<int>();
     src.p = ctx->pvLut.as<float>();
+    if (qLoose) src.qLut = ctx->qLut.as<float>();
     src.chromOff = fa.chromLooseOff.as<u32>();
     src.mStride = fa.looseStride;
     src.nWords = (u32)(fa.looseStride - 2);
@@ -818,8 +804,8 @@ int gx_rccl_nranks(gx_ctx* ctx, int* n) {
 
 int gx_path_info(gx_ctx* ctx, unsigned* flags) {
   if (!ctx || !flags) return GX_ERR_ORDER;
-  *flags = (ctx->fusedUsed ? GX_PATH_FUSED : 0u) | (ctx->fusedUsed && ctx->pairsUsed ? GX_PATH_PAIRS : 0u) | (ctx->denseBhUsed ? GX_PATH_DENSE_BH : 0u) | (ctx->rangeBhUsed ? GX_PATH_RANGE_BH : 0u) | (ctx->looseSwept ? GX_PATH_LOOSE_SWEEP : 0u) |
-           (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->fusedUsed && ctx->fracPairsUsed ? GX_PATH_FRAC_PAIRS : 0u) |
+  *flags = (ctx->built.fused ? GX_PATH_FUSED : 0u) | (ctx->built.fused && ctx->built.pairs ? GX_PATH_PAIRS : 0u) | (ctx->denseBhUsed ? GX_PATH_DENSE_BH : 0u) | (ctx->rangeBhUsed ? GX_PATH_RANGE_BH : 0u) | (ctx->looseSwept ? GX_PATH_LOOSE_SWEEP : 0u) |
+           (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->built.fused && ctx->built.fracPairs ? GX_PATH_FRAC_PAIRS : 0u) |
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u);

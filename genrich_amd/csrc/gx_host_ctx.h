@@ -76,7 +76,7 @@ struct HostMail {
   u32 nF, nIv, status, R, nPeaks, nMerged, D, n, hot, bhOvf;
   long long coll[4];   // this rank's / all ranks' {fragLen parts, saturation flag}
   u32 counts[64];      // BH records per rank (all-gather)
-  u32 closeState;      // k_close: 1 the sample is closed, 2 the separate kernels have to run
+  u32 closeState;      // k_scan_iv_close: 1 the sample is closed, 2 the separate kernels have to run
   u32 statusKeep;      // (host -> device: the status bits a repeated tile stage must keep)
   u32 seq;             // k_mail's last write (mail_sync polls it)
 };
@@ -186,6 +186,34 @@ struct Knobs {
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
 };
+// Every decision of one build of a sample, made once (plan_build, gx_host_build.h) before anything is sized, cleared or
+// launched; the stages read it and nothing else decides.  The context keeps the last one (`built`): finish_scalars, the
+// retries, gx_pvalues and gx_path_info ask it what ran.
+struct BuildPlan {
+  int isCtrl = 0;
+  bool reuseSort = false;   // only the tile stage runs again, on the general chain, over level 1's pages (close_sample)
+  u32 nEv = 0;
+  bool unit32 = false;      // tile id + offset fit a 4-byte key
+  bool multiRank = false;
+  bool earlyColl = false;   // the ranks exchange the closed form of fragLen ahead of the tile stage
+  bool fused = false;       // the tile stage is k_sbtile
+  bool pairs = false;       // ... on level 1's pair records (k_sort_a / k_sort_b)
+  bool fracPairs = false;   // ... with a weight class per record (fractional weights)
+  int sbS = 0;              // log2 of the tiles per level-1 bin (the context's, or one less: half-size bins)
+  u32 nL1 = 0;              // level-1 bins
+  u32 nCoarse = 0, jmaxC = 0, nWG1 = 0;   // pair mode's first pass: coarse lists, pages per list, its workgroups over all pieces
+  u32 jmax = 0;             // pages per (XCD class, bin) list
+  u32 poolPages[3] = {0, 0, 0};
+  bool wantEarly = false;   // lambda ahead of the tile stage: it writes the sweep's bits on the loose slots
+  bool wantLate = false;    // ... after the table p(V) (k_loose_late)
+  bool closeInScan = false; // the scan's last workgroup closes the sample (k_scan_iv_close)
+  bool dense = false;       // k_sbtile: one launch takes every bin by rounds
+  bool denseSmall = false;  // ... in the instance with the smaller scratch (SBT_TR_DENSE)
+  bool fragFused = false;   // the tile kernel adds the general fragLen path's terms itself (TileIn::fragAcc)
+  size_t looseCap = 0, ivCap = 0;
+  u32 tChunks = 0;
+  bool masks() const { return wantEarly || wantLate; }   // the sweep's masks are the loose slots'
+};
 struct KnobDef { const char* name; int Knobs::*i; long long Knobs::*ll; };
 const KnobDef KNOBS[] = {
     {"GX_DEBUG", &Knobs::debug, nullptr}, {"GX_DEBUG_RETRY", &Knobs::debugRetry, nullptr}, {"GX_NO_SPIN", &Knobs::noSpin, nullptr},
@@ -269,11 +297,8 @@ struct gx_ctx {
   bool fracHint = false;        // gx_expect_fractional: only selects the kernels that can carry a weight class (k_sort_a<true>,
                                 // k_sbtile<.., true>); on unit-weight data they give what the unit-weight instances give
   bool fusedOff = false;        // this sample: a super-bucket did not fit k_sbtile (the general chain runs instead)
-  bool fusedUsed = false;       // the last build went through k_sbtile
-  bool pairsUsed = false;       // ... on level 1's pair records (k_sort_a / k_sort_b)
-  bool fracPairsUsed = false;   // ... with a weight class per record (fractional weights)
-  bool earlyColl = false;       // this build: the ranks exchange the closed form of fragLen ahead of the tile stage
-  bool earlyOwed = false;       // ... and this rank has not taken part in that all-reduce yet (poison_allreduce)
+  BuildPlan built;              // the last build's plan
+  bool earlyOwed = false;       // built.earlyColl, and this rank has not taken part in that all-reduce yet (poison_allreduce)
   bool earlyPending = false;
   int fusedBackoff[2] = {0, 0}; // treatment / control samples for which k_sbtile is not tried (after one that did not fit)
   bool looseSwept = false;      // the last gx_find_peaks swept the loose slots
@@ -283,14 +308,13 @@ struct gx_ctx {
   bool mergePUsed = false;      // the last control merge wrote p-values into its loose slots (k_merge2<.., true>)
   DevBuf lbSweep, lbSweep2;     // look-back granules of the sweep's one-pass compactions (generation-tagged)
   u32 sweepGen = 0;
-  FragSelect closeSel{};        // the sample's k_frag_select arguments (k_close took them; finish_scalars may need them again)
-  u32 closeSeq = 0;             // sequence number of the mail k_close sends (0: the separate kernels were launched)
+  FragSelect closeSel{};        // the sample's k_frag_select arguments (k_scan_iv_close took them; finish_scalars may need them again)
+  u32 closeSeq = 0;             // sequence number of the mail k_scan_iv_close sends (0: the separate kernels were launched)
   bool beginPending = false;    // gx_sample_begin's clearing of the scalars is still to be done (k_build_init / flush_begin)
   u64 beginGenome = 0;
   bool fellBack = false;        // some sample was sent back from k_sbtile to the general chain
   bool ptGrew = false;          // some sample was built again with larger page tables (RETRY_PT)
   bool packedUsed = false;      // the last build read a piece of 8-byte events in place (k_sort_a<.., PACKED>: gx_path_info)
-  bool fragFused = false;       // the last build's tile kernel adds the general fragLen path's terms itself (TileIn::fragAcc)
   bool looseOk = false;         // the treatment sample's tile stage left valid sweep bits on the loose slots
   bool riskNearThr = false;     // a re-evaluated table entry lies next to the significance threshold
   size_t looseStride = 0;       // words between the sig / brk masks the tile stage wrote into swMask
@@ -300,6 +324,7 @@ struct gx_ctx {
   Stream str[3];  // S (start keys), E (end keys), F (fractional records)
   DevBuf tileCnt[3], tileOff[3];
   DevBuf looseC, looseC2, pairLogE, pairCtab, pairP2d, fragSum, tileDeep, fragList, zeroArena, endAtLen, binNet, curC, ptC, poolC, auxC, nWide, wideList, heavyList;
+  size_t arenaBytes = 0;        // what the views into zeroArena cover: one launch clears it (k_build_init)
   DevBuf tileMeta, tileWsum, tileCarry, lb, misc, dScal, dStatus, looseEnd, looseV, tileIvCount, tileLastEnd, tilePrevEnd;
   Pileup expt, ctrl;
   Scalars hScal{};  // host copy of the device scalars (refreshed from the mail block)
@@ -317,7 +342,6 @@ struct gx_ctx {
   bool qLooseUsed = false;      // the last gx_find_peaks: -q, the sweep on the loose slots (GX_PATH_Q_LOOSE)
   DevBuf qLut;                  // ... its q by whole pileup (k_bh_small)
   bool lateLooseUsed = false;   // ... and the replicate the sweep walked was such a sample (GX_PATH_LATE_LOOSE)
-  bool lateLoose = false;       // this sample: the sweep's bits on the loose slots come after the table p(V) (k_loose_late)
   bool lazyQUsed = false;       // the last -q run took k_sig_from_p / k_q_fill_cands (GX_PATH_LAZY_Q)
   bool bhLive = false;          // the table of the last -q run is still there, with {key, q} of every value (lazy q: ensure_q)
   u32 bhLiveCap = 0;
@@ -410,6 +434,15 @@ enum { M_TICKET = 0, M_NIV = 1, M_BHCOUNT = 5, M_ALLONE = 6, M_BHOVF = 7, M_GENO
        // the sweep's counters are contiguous: one memset clears them
        M_TICKET2 = 16, M_SWCOUNT = 17, M_NPEAKS = 18, M_TICKET3 = 19, M_TICKET4 = 20, M_NHEADS = 21, M_PEAKBP = 22 /* u64 */,
        M_SWEEP_FIRST = 16, M_SWEEP_WORDS = 8, M_WORDS = 32 };
+// the words of the nWide block (u32; in the zero arena: k_build_init clears them for every sample)
+enum { NW_WIDE = 0,        // tiles on wideList (k_tile_meta)
+       NW_HOT = 1,         // a base can reach the reference's int16 limits (level 1 of the sort, k_sbtile, k_hot_check)
+       NW_HEAVY = 2,       // tiles on heavyList
+       NW_CLOSE_TICKET = 8,   // k_scan_iv_close: its workgroups' counter
+       NW_NEED_PAGES = 12, // the pages the longest level-1 list asked for (k_scan_bins: RETRY_PT sizes the table by it)
+       NW_NBIG = 13,       // bins k_sbtile's first launch left to its second
+       NW_SBT_TICKET = 14 };  // k_sbtile's first launch: the bin counter of its persistent workgroups
+u32* nw_word(const gx_ctx* ctx, int w) { return ctx->nWide.as<u32>() + w; }
 
 // GX_DEBUG=1: synchronise after every launch and say which kernel it was (hang / fault triage)
 int dbg_sync(gx_ctx* ctx, const char* what) {
@@ -541,7 +574,7 @@ int mail_sync(gx_ctx* ctx, const Scalars* ds, const u32* hot, const u32* nIv, co
   return mail_wait(ctx, seq);
 }
 
-// (the mail kernel -- k_mail, or k_close -- has been launched with this sequence number)
+// (the mail kernel -- k_mail, or k_scan_iv_close -- has been launched with this sequence number)
 int mail_wait(gx_ctx* ctx, u32 seq) {
   const bool spin = !ctx->knob.noSpin;
   volatile u32* word = &ctx->mail->seq;

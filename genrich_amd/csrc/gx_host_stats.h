@@ -178,50 +178,30 @@ int launch_merge2(gx_ctx* ctx, const Merge2Out& mo, bool pv) {
     ctx->err = "control merge: the two samples are not in the same form";
     return GX_ERR_ORDER;
   }
+  // the two samples where they lie: their loose slots, or their tight arrays
   // (pos0 / len / flags of a tile do not depend on the sample: the control build's descriptors serve)
-  const dim3 gridM(std::min(nTiles, (u32)(8 * ctx->numCU)));
+  const Pileup &E = ctx->expt, &C = ctx->ctrl;
+  const RleIn A = fromLoose ? RleIn{E.looseEnd.as<u32>(), E.looseV.as<int>(), E.tileIvOff.as<u32>(), E.meta.as<TileMeta>()}
+                            : RleIn{E.ivEnd.as<u32>(), E.ivV.as<int>(), E.tileIvOff.as<u32>(), nullptr};
+  const RleIn Bc = fromLoose ? RleIn{C.looseEnd.as<u32>(), C.looseV.as<int>(), C.tileIvOff.as<u32>(), C.meta.as<TileMeta>()}
+                             : RleIn{C.ivEnd.as<u32>(), C.ivV.as<int>(), C.tileIvOff.as<u32>(), nullptr};
+  const TileMeta* meta = fromLoose ? C.meta.as<TileMeta>() : ctx->tileMeta.as<TileMeta>();
   const float* p2d = ctx->pairP2d.as<float>();
+  using MergeKernel = decltype(&k_merge2<false, false>);   // [LOOSE][PV]
   if (!ctx->knob.mergeWg) {
     // one wavefront per tile (round 6): as many workgroups as the CUs hold, each wavefront striding over the tiles
-#define GX_MERGE2W(LOOSE_, PV_, A_, B_, META_)                                                                                        \
-  do {                                                                                                                                \
-    int nb = 0;                                                                                                                       \
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_merge2w<LOOSE_, PV_>, M2W_NW * 64, 0));                              \
-    const u32 want = (nTiles + M2W_NW - 1) / M2W_NW;                                                                                 \
-    hipLaunchKernelGGL((k_merge2w<LOOSE_, PV_>), dim3(std::max(1u, std::min(want, (u32)(std::max(1, std::min(nb, M2W_WGS)) * ctx->numCU)))), \
-                       dim3(M2W_NW * 64), 0, s, A_, B_, ctx->dScal.as<Scalars>(), META_, nTiles, mo, ctx->dStatus.as<u32>(), p2d);   \
-  } while (0)
-    if (fromLoose) {
-      RleIn A{ctx->expt.looseEnd.as<u32>(), ctx->expt.looseV.as<int>(), ctx->expt.tileIvOff.as<u32>(), ctx->expt.meta.as<TileMeta>()};
-      RleIn Bc{ctx->ctrl.looseEnd.as<u32>(), ctx->ctrl.looseV.as<int>(), ctx->ctrl.tileIvOff.as<u32>(), ctx->ctrl.meta.as<TileMeta>()};
-      if (pv) GX_MERGE2W(true, true, A, Bc, ctx->ctrl.meta.as<TileMeta>()); else GX_MERGE2W(true, false, A, Bc, ctx->ctrl.meta.as<TileMeta>());
-    } else {
-      RleIn A{ctx->expt.ivEnd.as<u32>(), ctx->expt.ivV.as<int>(), ctx->expt.tileIvOff.as<u32>(), nullptr};
-      RleIn Bc{ctx->ctrl.ivEnd.as<u32>(), ctx->ctrl.ivV.as<int>(), ctx->ctrl.tileIvOff.as<u32>(), nullptr};
-      if (pv) GX_MERGE2W(false, true, A, Bc, ctx->tileMeta.as<TileMeta>()); else GX_MERGE2W(false, false, A, Bc, ctx->tileMeta.as<TileMeta>());
-    }
-#undef GX_MERGE2W
+    static constexpr MergeKernel WAVE[2][2] = {{k_merge2w<false, false>, k_merge2w<false, true>}, {k_merge2w<true, false>, k_merge2w<true, true>}};
+    const MergeKernel k = WAVE[fromLoose][pv];
+    int nb = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, M2W_NW * 64, 0));
+    const u32 want = (nTiles + M2W_NW - 1) / M2W_NW;
+    hipLaunchKernelGGL(k, dim3(std::max(1u, std::min(want, (u32)(std::max(1, std::min(nb, M2W_WGS)) * ctx->numCU)))), dim3(M2W_NW * 64), 0, s,
+                       A, Bc, ctx->dScal.as<Scalars>(), meta, nTiles, mo, ctx->dStatus.as<u32>(), p2d);
     return dbg_sync(ctx, "k_merge2w");
   }
-  if (fromLoose) {
-    RleIn A{ctx->expt.looseEnd.as<u32>(), ctx->expt.looseV.as<int>(), ctx->expt.tileIvOff.as<u32>(), ctx->expt.meta.as<TileMeta>()};
-    RleIn Bc{ctx->ctrl.looseEnd.as<u32>(), ctx->ctrl.looseV.as<int>(), ctx->ctrl.tileIvOff.as<u32>(), ctx->ctrl.meta.as<TileMeta>()};
-    if (pv)
-      hipLaunchKernelGGL((k_merge2<true, true>), gridM, dim3(MG_NT), 0, s, A, Bc, ctx->dScal.as<Scalars>(), ctx->ctrl.meta.as<TileMeta>(),
-                         nTiles, mo, ctx->dStatus.as<u32>(), p2d);
-    else
-      hipLaunchKernelGGL((k_merge2<true, false>), gridM, dim3(MG_NT), 0, s, A, Bc, ctx->dScal.as<Scalars>(), ctx->ctrl.meta.as<TileMeta>(),
-                         nTiles, mo, ctx->dStatus.as<u32>(), p2d);
-  } else {
-    RleIn A{ctx->expt.ivEnd.as<u32>(), ctx->expt.ivV.as<int>(), ctx->expt.tileIvOff.as<u32>(), nullptr};
-    RleIn Bc{ctx->ctrl.ivEnd.as<u32>(), ctx->ctrl.ivV.as<int>(), ctx->ctrl.tileIvOff.as<u32>(), nullptr};
-    if (pv)
-      hipLaunchKernelGGL((k_merge2<false, true>), gridM, dim3(MG_NT), 0, s, A, Bc, ctx->dScal.as<Scalars>(), ctx->tileMeta.as<TileMeta>(),
-                         nTiles, mo, ctx->dStatus.as<u32>(), p2d);
-    else
-      hipLaunchKernelGGL((k_merge2<false, false>), gridM, dim3(MG_NT), 0, s, A, Bc, ctx->dScal.as<Scalars>(), ctx->tileMeta.as<TileMeta>(),
-                         nTiles, mo, ctx->dStatus.as<u32>(), p2d);
-  }
+  static constexpr MergeKernel GROUP[2][2] = {{k_merge2<false, false>, k_merge2<false, true>}, {k_merge2<true, false>, k_merge2<true, true>}};
+  hipLaunchKernelGGL(GROUP[fromLoose][pv], dim3(std::min(nTiles, (u32)(8 * ctx->numCU))), dim3(MG_NT), 0, s, A, Bc, ctx->dScal.as<Scalars>(), meta,
+                     nTiles, mo, ctx->dStatus.as<u32>(), p2d);
   return dbg_sync(ctx, "k_merge2");
 }
 
