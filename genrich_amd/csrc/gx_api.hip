@@ -8,6 +8,7 @@
 #include "gx_host_sweep.h"
 #include "gx_host_stats.h"
 #include "gx_host_count.h"
+#include "gx_host_regions.h"
 
 
 // ================================ C ABI ==================================================
@@ -808,7 +809,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->built.fused && ctx->built.fracPairs ? GX_PATH_FRAC_PAIRS : 0u) |
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
-           (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u);
+           (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u);
   return GX_OK;
 }
 
@@ -837,6 +838,34 @@ int gx_get_peak_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t*
   if (n) memcpy(count120, r, n * sizeof(int64_t));
   if (total120) *total120 = r[ctx->cntPk];
   if (in_peaks120) *in_peaks120 = r[ctx->cntPk + 1];
+  return GX_OK;
+}
+
+int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_samples) {
+  if (!ctx || !ctx->countOn || ctx->phase == 1 || ctx->phase == 3 || (n && !regions)) return GX_ERR_ORDER;
+  for (size_t k = 0; k < n; k++)
+    if (regions[k].start >= regions[k].end) {
+      ctx->err = "a region with start >= end";
+      return GX_ERR_ORDER;
+    }
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->regionsReady = false;
+  if (int rc = count_in_regions(ctx, regions, n)) return rc;
+  ctx->regionsReady = true;
+  if (n_samples) *n_samples = (int)ctx->regSamples;
+  return GX_OK;
+}
+
+int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
+                         int64_t* in_regions120) {
+  if (!ctx || !ctx->regionsReady || sample < 0 || (u32)sample >= ctx->regSamples || (cap && !count120)) return GX_ERR_ORDER;
+  const int64_t* r = static_cast<const int64_t*>(ctx->regHost.p) + (size_t)sample * (ctx->regN + 2);
+  if (rep) *rep = ctx->kept[sample].rep;
+  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
+  const size_t n = std::min<size_t>(cap, ctx->regN);
+  if (n) memcpy(count120, r, n * sizeof(int64_t));
+  if (total120) *total120 = r[ctx->regN];
+  if (in_regions120) *in_regions120 = r[ctx->regN + 1];
   return GX_OK;
 }
 

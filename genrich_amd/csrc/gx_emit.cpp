@@ -122,6 +122,37 @@ int gx_write_counts(gx_ctx* ctx, const char* const* names, int n_samples, const 
   return gx_write_counts_group(&ctx, 1, names, n_samples, sample_names, out);
 }
 
+// --region-counts: one row per region in the caller's order, the contexts' counts added (a region lies on one chromosome, which
+// one context owns; the others count 0 there)
+int gx_write_region_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_region* regions,
+                                 const char* const* region_names, size_t n, int n_samples, const char* const* sample_names,
+                                 FILE* out) {
+  if (n_ctx < 1 || n_samples < 0 || (n_samples && !sample_names) || (n && !regions)) return GX_ERR_ORDER;
+  std::vector<int64_t> cnt(n * (size_t)n_samples, 0), one(n);   // [sample][region]
+  for (int g = 0; g < n_ctx; g++)
+    for (int smp = 0; smp < n_samples; smp++) {
+      if (int rc = gx_get_region_counts(ctxs[g], smp, nullptr, nullptr, one.data(), n, nullptr, nullptr)) return rc;
+      for (size_t i = 0; i < n; i++) cnt[(size_t)smp * n + i] += one[i];
+    }
+  fprintf(out, "chr\tstart\tend\tname");
+  for (int smp = 0; smp < n_samples; smp++) fprintf(out, "\t%s", sample_names[smp]);
+  fprintf(out, "\n");
+  for (size_t i = 0; i < n; i++) {
+    const gx_region& r = regions[i];
+    fprintf(out, "%s\t%u\t%u\t", names[r.chrom], r.start, r.end);
+    if (region_names && region_names[i]) fprintf(out, "%s", region_names[i]);
+    else fprintf(out, "region_%zu", i);
+    for (int smp = 0; smp < n_samples; smp++) put_count(out, (long long)cnt[(size_t)smp * n + i]);
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+int gx_write_region_counts(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
+                           size_t n, int n_samples, const char* const* sample_names, FILE* out) {
+  return gx_write_region_counts_group(&ctx, 1, names, regions, region_names, n, n_samples, sample_names, out);
+}
+
 // -k for replicate `rep` (owner[c] = index into ctxs of the context that computed chromosome c; NULL: ctxs[0])
 int gx_write_pile_group(gx_ctx* const* ctxs, const int* owner, int rep, const char* const* names, int n_chrom,
                         const char* expt_name, const char* ctrl_name, FILE* out) {
@@ -230,6 +261,14 @@ int gx_write_counts_path(gx_ctx* ctx, const char* const* names, int n_samples, c
   FILE* f = fopen(path, "w");
   if (!f) return GX_ERR_ORDER;
   int rc = gx_write_counts(ctx, names, n_samples, sample_names, f);
+  fclose(f);
+  return rc;
+}
+int gx_write_region_counts_path(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
+                                size_t n, int n_samples, const char* const* sample_names, const char* path) {
+  FILE* f = fopen(path, "w");
+  if (!f) return GX_ERR_ORDER;
+  int rc = gx_write_region_counts(ctx, names, regions, region_names, n, n_samples, sample_names, f);
   fclose(f);
   return rc;
 }

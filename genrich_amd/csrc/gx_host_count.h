@@ -33,7 +33,7 @@ void drop_kept(gx_ctx* ctx) {
     recycle(ctx, k.sat);
   }
   ctx->kept.clear();
-  ctx->countsReady = false;
+  ctx->countsReady = ctx->regionsReady = false;
 }
 
 int count_in_peaks(gx_ctx* ctx) {

@@ -26,6 +26,7 @@
 #include "gx_bhx.h"
 #include "gx_saturate.h"
 #include "gx_count.h"
+#include "gx_regions.h"
 
 using namespace gx;
 
@@ -172,6 +173,7 @@ struct Knobs {
   int noHalfBins = 0;     // GX_NO_HALF_BINS
   int fracHalfBins = 0;   // GX_FRAC_HALF_BINS: half-size bins also for a dense sample with fractional weights (measurements)
   int noEarlyColl = 0;    // GX_NO_EARLY_COLL: no all-reduce of the closed form of fragLen ahead of the tile stage
+  int regWindows = 0;     // GX_REG_WINDOWS: gx_count_in_regions keeps its histograms in LDS up to this many windows (default REG_WIN_MAX; < 0: never)
   int noDenseBh = 0;      // GX_NO_DENSE_BH: the range-partitioned exchange also without a control
   int qtMulti = 0;        // GX_QT_MULTI: the chunked BH table kernels for a small table
   int forceColl = 0;      // GX_FORCE_COLL: run the collectives with a single rank too
@@ -221,7 +223,7 @@ const KnobDef KNOBS[] = {
     {"GX_NO_FUSED", &Knobs::noFused, nullptr}, {"GX_NO_LOOSE", &Knobs::noLoose, nullptr}, {"GX_NO_PAIRS", &Knobs::noPairs, nullptr},
     {"GX_NO_FRAC_PAIRS", &Knobs::noFracPairs, nullptr}, {"GX_NO_BED_FUSED", &Knobs::noBedFused, nullptr}, {"GX_NO_MERGE_P", &Knobs::noMergeP, nullptr}, {"GX_NO_PACK_HIST", &Knobs::noPackHist, nullptr}, {"GX_NO_LAZY_Q", &Knobs::noLazyQ, nullptr}, {"GX_NO_LATE_LOOSE", &Knobs::noLateLoose, nullptr}, {"GX_NO_Q_LOOSE", &Knobs::noQLoose, nullptr}, {"GX_MERGE_WG", &Knobs::mergeWg, nullptr}, {"GX_BH_VARIANT", &Knobs::bhVariant, nullptr}, {"GX_FORCE_HALF_BINS", &Knobs::forceHalfBins, nullptr},
     {"GX_NO_HALF_BINS", &Knobs::noHalfBins, nullptr}, {"GX_FRAC_HALF_BINS", &Knobs::fracHalfBins, nullptr}, {"GX_NO_EARLY_COLL", &Knobs::noEarlyColl, nullptr},
-    {"GX_NO_DENSE_BH", &Knobs::noDenseBh, nullptr}, {"GX_QT_MULTI", &Knobs::qtMulti, nullptr}, {"GX_FORCE_COLL", &Knobs::forceColl, nullptr},
+    {"GX_NO_DENSE_BH", &Knobs::noDenseBh, nullptr}, {"GX_REG_WINDOWS", &Knobs::regWindows, nullptr}, {"GX_QT_MULTI", &Knobs::qtMulti, nullptr}, {"GX_FORCE_COLL", &Knobs::forceColl, nullptr},
     {"GX_SBSHIFT", &Knobs::sbShift, nullptr}, {"GX_RUN_CAP_MIN", nullptr, &Knobs::runCapMin}, {"GX_BH_CAPLOG", &Knobs::bhCapLog, nullptr},
     {"GX_PT_JMAX", &Knobs::ptJmax, nullptr}, {"GX_FAULT", &Knobs::fault, nullptr}, {"GX_SBT_TR", &Knobs::sbtTr, nullptr}, {"GX_SBT_GRID", &Knobs::sbtGrid, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
@@ -393,6 +395,14 @@ struct gx_ctx {
   DevBuf cntIn, cntIdx, cntDiff, cntRes;
   PinnedBuf cntStage, cntHost;
   bool cntLdsSet = false;
+  // counting in regions (gx_count_in_regions, gx_regions.h): the same kept samples, result buffers of its own
+  bool regionsReady = false;      // gx_count_in_regions has counted: regSamples samples in regN regions
+  size_t regN = 0;
+  u32 regSamples = 0;
+  u32 regInvCap = 1u << 14;       // REG_INV_CAP, or more after a pass that met more inverted intervals
+  DevBuf regIn, regIdx, regHist, regSums, regRes, regInv;
+  PinnedBuf regStage, regHost;
+  bool regLdsSet = false;
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

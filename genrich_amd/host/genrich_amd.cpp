@@ -147,7 +147,8 @@ struct BedRec { std::string name; uint32_t pos[2]; };
 struct Opts {
   const char *inFile = nullptr, *ctrlFile = nullptr, *outFile = nullptr, *logFile = nullptr, *pileFile = nullptr,
              *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
-             *countsFile = nullptr;  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
+             *countsFile = nullptr,  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
+             *regionsBed = nullptr, *regionCountsFile = nullptr;  // --count-regions BED --region-counts FILE: ... in given regions
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -233,11 +234,13 @@ struct HotWindows {
   }
 };
 
+struct RegionRow { std::string chrom, name; uint32_t start, end; bool named; };   // a line of --count-regions' BED
 struct State {
   Opts o;
   std::vector<Chrom> chrom;
   std::vector<std::string> xchr;
   std::vector<BedRec> xbed;
+  std::vector<RegionRow> regions;   // --count-regions, in the BED's order
   gx_ctx* gx = nullptr;      // the (first) device context; nullptr with --events-only
   Devs devs;                 // all of them
   bool tableFrozen = false;  // the device already holds the chromosome table
@@ -2479,14 +2482,18 @@ std::string countText(long long n) {
   else snprintf(b, sizeof b, "%.2f", (double)n / 120.0);
   return b;
 }
-void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles,
-                 const std::vector<const char*>& names) {
-  const Opts& o = S.o;
+std::vector<const char*> sampleNamesOf(const State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles) {
   std::vector<const char*> sampleNames;
   for (size_t r = 0; r < tFiles.size(); r++) {
     sampleNames.push_back(tFiles[r].c_str());
-    if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") sampleNames.push_back(cFiles[r].c_str());
+    if (S.o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") sampleNames.push_back(cFiles[r].c_str());
   }
+  return sampleNames;
+}
+void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles,
+                 const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  const std::vector<const char*> sampleNames = sampleNamesOf(S, tFiles, cFiles);
   const int nS = (int)sampleNames.size();
   for (gx_ctx* g : S.devs.ctx) {
     int n = 0;
@@ -2511,12 +2518,86 @@ void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::ve
   }
 }
 
+// --count-regions BED --region-counts FILE: the same intervals counted in the BED's regions, which may overlap and come in any
+// order; exactly one output row per BED line, in the BED's order, so that the files of two runs line up.  The BED is read with
+// -E's rules (loadBED); a 4th column names the row, further columns are ignored (a narrowPeak file is valid input).
+void loadRegions(State& S, const char* fn) {
+  std::vector<char> line(65520);
+  In in;
+  openRead(in, fn);
+  while (in.gets(line.data(), (int)line.size())) {
+    char* name = strtok(line.data(), "\t");
+    if (!name) die(line.data(), ": poorly formatted BED record");
+    char* a = strtok(nullptr, "\t");
+    if (!a) die(line.data(), ": poorly formatted BED record");
+    const int p0 = getInt(a);
+    char* b = strtok(nullptr, "\t\n");
+    if (!b) die(line.data(), ": poorly formatted BED record");
+    const int p1 = getInt(b);
+    if (p1 <= p0 || p0 < 0 || p1 < 0) {
+      char msg[512];
+      snprintf(msg, sizeof msg, "%s, %d - %d", name, p0, p1);
+      die(msg, ": poorly formatted BED record");
+    }
+    const char* rn = strtok(nullptr, "\t\n");
+    S.regions.push_back(RegionRow{name, rn ? rn : "", (uint32_t)p0, (uint32_t)p1, rn != nullptr});
+  }
+  checkIn(in);
+  in.close();
+}
+void writeRegionCounts(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles,
+                       const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  const std::vector<const char*> sampleNames = sampleNamesOf(S, tFiles, cFiles);
+  const int nS = (int)sampleNames.size();
+  // a chromosome that no header names: an index behind the table (the library counts 0 there), its name behind the table's
+  std::vector<const char*> allNames(names);
+  std::unordered_map<std::string, uint32_t> idx;
+  for (size_t c = 0; c < names.size(); c++) idx.emplace(names[c], (uint32_t)c);
+  std::vector<gx_region> reg(S.regions.size());
+  std::vector<const char*> regNames(S.regions.size());
+  for (size_t k = 0; k < S.regions.size(); k++) {
+    const RegionRow& r = S.regions[k];
+    auto it = idx.find(r.chrom);
+    if (it == idx.end()) {
+      it = idx.emplace(r.chrom, (uint32_t)allNames.size()).first;
+      allNames.push_back(r.chrom.c_str());
+    }
+    reg[k] = gx_region{it->second, r.start, r.end};
+    regNames[k] = r.named ? r.name.c_str() : nullptr;
+  }
+  for (gx_ctx* g : S.devs.ctx) {
+    int n = 0;
+    check(S, gx_count_in_regions(g, reg.data(), reg.size(), &n), g);
+    if (n != nS) die("", "--count-regions: the library kept another number of samples than were read");
+  }
+  Out out = openWrite(o.regionCountsFile, o.gzOut);
+  check(S, gx_write_region_counts_group(S.devs.ctx.data(), (int)S.devs.n(), allNames.data(), reg.data(), regNames.data(), reg.size(), nS,
+                                        sampleNames.data(), out.f));
+  closeOut(out);
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++) {
+    long long tot = 0, in = 0;
+    int rep = 0, ctrl = 0;
+    for (gx_ctx* g : S.devs.ctx) {
+      int64_t t = 0, p = 0;
+      check(S, gx_get_region_counts(g, i, &rep, &ctrl, nullptr, 0, &t, &p), g);
+      tot += t;
+      in += p;
+    }
+    fprintf(stderr, "  Intervals in regions, %s file #%d: %s of %s (fraction %f)\n", ctrl ? "control" : "experimental", rep,
+            countText(in).c_str(), countText(tot).c_str(), tot ? (double)in / (double)tot : 0.0);
+  }
+}
+
 void usage() {
   fprintf(stderr,
           "Usage: genrich-amd  -t <file>  -o <file>  [optional arguments]\n"
           "  (same options as Genrich v0.6.2: -t -c -o -f -k -b -z -y -w -x -j -d -D -e -E -m -s\n"
           "   -r -R -p -q -a -l -g -X -P -S -L -v -V)\n"
-          "  --device N | --devices 0-7   GPU(s) to use;  --threads N   BGZF inflate threads\n");
+          "  --device N | --devices 0-7   GPU(s) to use;  --threads N   BGZF inflate threads\n"
+          "  --counts FILE   each sample's intervals counted in the called peaks\n"
+          "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n");
   exit(EXIT_FAILURE);
 }
 
@@ -2533,6 +2614,8 @@ int main(int argc, char** argv) {
                                      {"devices", required_argument, nullptr, 1003},
                                      {"threads", required_argument, nullptr, 1002},
                                      {"counts", required_argument, nullptr, 1004},
+                                     {"count-regions", required_argument, nullptr, 1005},
+                                     {"region-counts", required_argument, nullptr, 1006},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2576,6 +2659,8 @@ int main(int argc, char** argv) {
       case 1001: o.device = getInt(optarg); break;
       case 1002: g_threads = getInt(optarg); break;
       case 1004: o.countsFile = optarg; break;
+      case 1005: o.regionsBed = optarg; break;
+      case 1006: o.regionCountsFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2598,6 +2683,9 @@ int main(int argc, char** argv) {
   }
   // (the counts are counted in the peaks this run calls: nothing to count in with -P, -X or --events-only)
   if (o.countsFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly)) die("", "--counts needs the peaks of this run (not with -P or -X)");
+  if ((o.regionsBed != nullptr) != (o.regionCountsFile != nullptr)) die("", "--count-regions BED and --region-counts FILE need each other");
+  // (the regions count the events the library keeps: none with -P or --events-only; -X is fine)
+  if (o.regionsBed && (o.peaksOnly || o.eventsOnly)) die("", "--count-regions needs the intervals of this run (not with -P or --events-only)");
   if (o.avgExtOpt) { o.singleOpt = true; o.extendOpt = false; }
   if (o.extendOpt) {
     o.singleOpt = true;
@@ -2643,6 +2731,7 @@ int main(int argc, char** argv) {
   const float thr = -log10f(o.pqvalue);
 
   if (o.xFile) loadBED(S, o.xFile);
+  if (o.regionsBed) loadRegions(S, o.regionsBed);
   if (o.peaksOnly) {  // runProgram 5398-5403
     peaksOnly(S, thr);
     return EXIT_SUCCESS;
@@ -2670,7 +2759,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile) check(S, gx_set_count_in_peaks(g, 1), g);
+      if (o.countsFile || o.regionsBed) check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -2831,6 +2920,7 @@ int main(int argc, char** argv) {
     if (o.verbose) fprintf(stderr, "Peaks identified: %d (%ldbp)\n", (int)nPeaks, (long)peakBP);
   }
   if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
+  if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);
     check(S, gx_write_log_group(S.devs.ctx.data(), S.devs.owner.data(), S.sample, names.data(), nChrom, o.qvalOpt, o.peaksOpt, thr,

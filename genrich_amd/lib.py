@@ -48,6 +48,20 @@ class PeakCounts(NamedTuple):
     is_ctrl: bool
 
 
+GX_PATH_REGION_COUNTS = 131072   # gx_path_info bit 17: gx_count_in_regions has counted since the last reset
+REGION_DTYPE = np.dtype([("chrom", "<u4"), ("start", "<u4"), ("end", "<u4")])   # gx_region
+
+
+class RegionCounts(NamedTuple):
+    """One sample's counts in a given region set (gx_get_region_counts), in 1/120 units: count[k] per region in the caller's
+    order, the weight of all its intervals (total) and of those that overlap at least one region (in_regions)."""
+    count: np.ndarray
+    total: int
+    in_regions: int
+    rep: int
+    is_ctrl: bool
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
 
@@ -112,6 +126,12 @@ _SIGS = {
     "gx_count_in_peaks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_get_peak_counts": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "gx_count_in_regions": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)],
+    "gx_get_region_counts": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t,
+                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "gx_write_region_counts_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_write_region_counts": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_write_region_counts_path": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_char_p],
     "gx_write_counts_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts_path": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p],
@@ -387,7 +407,7 @@ class Genrich:
         """Which device path the last calls took: GX_PATH_* bits (1 fused tile stage, 2 loose-slot sweep, 4 fell back, 8 page tables grew,
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
-        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting)."""
+        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -416,6 +436,38 @@ class Genrich:
         """--counts' text (gx_write_counts) of this context."""
         self._check(self.lib.gx_write_counts_path(self.ctx, self._names(names), len(sample_names), self._names(sample_names),
                                                   path.encode()))
+
+    # -- counting in a given region set (include/genrich_amd.h, gx_count_in_regions) ----------------------------------
+    def count_in_regions(self, regions):
+        """Count every sample closed so far in `regions` (REGION_DTYPE, or rows of (chrom, start, end)), which may overlap and
+        come in any order; needs set_count_in_peaks(True), no peaks.  Returns the number of samples."""
+        reg = np.asarray(regions)
+        if reg.dtype != REGION_DTYPE:
+            rows = np.asarray(regions, dtype=np.int64).reshape(-1, 3)
+            reg = np.zeros(len(rows), dtype=REGION_DTYPE)
+            reg["chrom"], reg["start"], reg["end"] = rows[:, 0], rows[:, 1], rows[:, 2]
+        reg = np.ascontiguousarray(reg)
+        n = C.c_int(0)
+        self._check(self.lib.gx_count_in_regions(self.ctx, reg.ctypes.data if reg.size else None, reg.size, C.byref(n)))
+        self._n_regions = int(reg.size)
+        return n.value
+
+    def region_counts(self, sample):
+        """RegionCounts(count int64[n_regions], total, in_regions, rep, is_ctrl) of one sample of the last count_in_regions."""
+        cnt = np.zeros(getattr(self, "_n_regions", 0), dtype=np.int64)
+        rep, ctrl, tot, inr = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.gx_get_region_counts(self.ctx, int(sample), C.byref(rep), C.byref(ctrl), cnt.ctypes.data if cnt.size else None,
+                                                  cnt.size, C.byref(tot), C.byref(inr)))
+        return RegionCounts(cnt, tot.value, inr.value, rep.value, bool(ctrl.value))
+
+    def write_region_counts(self, names, regions, region_names, sample_names, path):
+        """--region-counts' text (gx_write_region_counts) of this context; region_names: a list with None for region_N, or None."""
+        reg = np.ascontiguousarray(np.asarray(regions, dtype=REGION_DTYPE))
+        rn = None
+        if region_names is not None:
+            rn = (C.c_char_p * max(1, len(region_names)))(*[None if x is None else x.encode() for x in region_names])
+        self._check(self.lib.gx_write_region_counts_path(self.ctx, self._names(names), reg.ctypes.data if reg.size else None, rn, reg.size,
+                                                         len(sample_names), self._names(sample_names), path.encode()))
 
     def rccl_nranks(self):
         """Ranks of the library's own RCCL communicator as RCCL reports them (0: none)."""

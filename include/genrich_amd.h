@@ -234,7 +234,8 @@ int gx_get_intervals(gx_ctx* ctx, int which, int chrom, size_t cap, uint32_t* en
  * weight of those that overlap at least one peak; FRiP = in_peaks / total.
  *
  * gx_set_count_in_peaks: only while idle (after gx_create / gx_reset, before the first gx_sample_begin; else GX_ERR_ORDER);
- *   off by default.  On, each closed sample keeps its events in device memory until gx_reset (which keeps the switch):
+ *   off by default.  It is the switch that keeps the events, for gx_count_in_peaks and gx_count_in_regions alike.  On, each
+ *   closed sample keeps its events in device memory until gx_reset (which keeps the switch):
  *   the library's own copies (host pushes, 16-byte forms of packed pieces, the survivors of the int16 rule) are not reused
  *   for the next sample, and a caller's DEVICE buffer (gx_push_events_device, gx_push_events_packed(.., GX_EVENTS_DEVICE))
  *   is read in place, so it must stay valid and unchanged until the run's last gx_count_in_peaks (or gx_reset / gx_destroy)
@@ -248,6 +249,29 @@ int gx_set_count_in_peaks(gx_ctx* ctx, int on);
 int gx_count_in_peaks(gx_ctx* ctx, int* n_samples);
 int gx_get_peak_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
                        int64_t* in_peaks120);
+
+/* ---- counting in a given region set (no Genrich counterpart) ----
+ * The same samples and the same intervals, with the same weights, as gx_count_in_peaks above, counted in regions the caller
+ * names -- a common set for several runs -- instead of the peaks this run called.  Region k is (chrom, start, end), start <
+ * end, in the caller's order; the set may overlap, nest, repeat and be unsorted.  Interval [s, e) on the same chromosome
+ * overlaps it iff s < end && start < e (the predicate of the peaks) and counts in EVERY region it overlaps.  end may lie beyond
+ * the chromosome's length; chrom >= n_chrom (a chromosome the run does not know), a skipped (-e) or un-owned chromosome and
+ * start >= the chromosome's length are legal and count 0.  An interval that ends before it starts (convert_event lets them into
+ * the pileup and the peak counts) is counted by the same predicate.  Per sample, exact int64 sums in 1/120 units: count[k],
+ * total = the value gx_count_in_peaks reports, in_regions = weight of the intervals that overlap at least one region (the
+ * union: an interval in three regions counts once).
+ *
+ * gx_count_in_regions: needs gx_set_count_in_peaks on and no sample open (else GX_ERR_ORDER); it needs no gx_pvalues,
+ *   gx_find_peaks or peak.  Counts every sample closed so far (*n_samples of them, in gx_sample_end order) in one device pass
+ *   and one read-back; may be called again, with other regions; n == 0 is legal.  A region with start >= end: GX_ERR_ORDER,
+ *   and nothing is counted.  The last gx_count_in_peaks result stays readable and vice versa; gx_reset drops both.  Under
+ *   gx_set_owned a context counts the chromosomes it owns: a host adds the contexts' rows and totals.
+ * gx_get_region_counts: the last count of one sample: min(cap, n) counts in the regions' order and the two totals, as
+ *   gx_get_peak_counts. */
+typedef struct { uint32_t chrom, start, end; } gx_region;
+int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_samples);
+int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
+                         int64_t* in_regions120);
 
 /* ---- host-side text emitters of the drop-in surface (gx_emit.cpp); byte format of the
  *      reference's printf calls.  names[i] = chromosome names in table order. ---- */
@@ -279,6 +303,17 @@ int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* nam
 int gx_write_counts(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names, FILE* out);
 int gx_write_counts_path(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names,
                          const char* path);
+/* --region-counts (after gx_count_in_regions with the same regions on every context): the header of --counts, then exactly one
+ * row per region in the caller's order -- names[chrom], start and end as given (not clamped), region_names[k] or, where that (or
+ * region_names) is NULL, region_N with N = k -- with the contexts' counts added, printed as --counts prints them.  names must
+ * reach every chrom the regions use: a caller gives unknown chromosomes indices behind the table and their names there. */
+int gx_write_region_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_region* regions,
+                                 const char* const* region_names, size_t n, int n_samples, const char* const* sample_names,
+                                 FILE* out);
+int gx_write_region_counts(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
+                           size_t n, int n_samples, const char* const* sample_names, FILE* out);
+int gx_write_region_counts_path(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
+                                size_t n, int n_samples, const char* const* sample_names, const char* path);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -366,6 +401,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_Q_LOOSE 32768u /* bit 15: -q on one replicate without control: no tight table -- BH's histogram from the loose slots, q by pileup, the sweep on the loose slots (k_bh_small, k_loose_late, k_peak_both<.., PVQ>) */
 #define GX_PATH_MERGE_P 1024u /* bit 10: the last control merge scored its intervals itself and left (end, p) in its loose slots (k_merge2<.., true> + k_pack_ep2) */
 #define GX_PATH_COUNTS 65536u /* bit 16: this run kept its samples' intervals for counting (gx_set_count_in_peaks) */
+#define GX_PATH_REGION_COUNTS 131072u /* bit 17: gx_count_in_regions has counted the kept samples in a region set since the last gx_reset */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
