@@ -193,6 +193,23 @@ def cases():
               dict(t=(N2[:1], L2[:1], mf(L2[:1], 1500, 62)), c=None),
               dict(t=(N2, L2, mf(L2, 1800, 63)), c=None)])
 
+    # five replicates (combinePval's union beyond four inputs), controls mixed file / null / file / null / file, one replicate
+    # lacks chr2 -- fewer fragments per sample than reps3, so that the directory stays no larger
+    yield dict(
+        name="reps5_mixed", names=N2, args=["-q", "0.2", "-a", "20"],
+        reps=[dict(t=(N2, L2, mf(L2, 800, 131)), c=(N2, L2, mf(L2, 700, 132, uniform_only=True))),
+              dict(t=(N2, L2, mf(L2, 900, 133)), c="null"),
+              dict(t=(N2, L2, mf(L2, 700, 134)), c=(N2, L2, mf(L2, 600, 135, uniform_only=True))),
+              dict(t=(N2[:1], L2[:1], mf(L2[:1], 600, 136)), c="null"),
+              dict(t=(N2, L2, mf(L2, 800, 137)), c=(N2, L2, mf(L2, 700, 138, uniform_only=True)))])
+
+    # nine replicates without controls, p-value mode, one lacks chr2; a -E region on chr1: the intervals inside it are
+    # skipped in every replicate, so the degrees of freedom of multPval vary along the chromosome
+    yield dict(
+        name="reps9", names=N2, args=["-p", "0.01", "-a", "20"], bed=[("chr1", 11_000, 17_500)],
+        reps=[dict(t=((N2[:1], L2[:1], mf(L2[:1], 450, 141 + r)) if r == 6 else (N2, L2, mf(L2, 600 + 40 * r, 141 + r))), c=None)
+              for r in range(9)])
+
     L3 = [30_000, 20_000, 8_000]
     N3 = ["chr1", "chr2", "chrX"]
     yield dict(
@@ -271,6 +288,8 @@ P_RUNS = {
     "bedx": [dict(args=["-q", "0.25", "-a", "30"], bed=[("chr1", 3000, 3400), ("chr1", 12000, 12345), ("chr2", 0, 777)])],
     "basic": [dict(args=["-a", "100", "-L", "1000"], bed=[("chrA", 12500, 12520)])],
     # ties_p / ties_q: -P re-calls at ties of the -f log's printed values (p_run_ties), added when the case is generated
+    # (reps5_mixed / reps9 have none: test_cli_peaks_from_log's ids carry a running index over all cases' re-calls in name
+    # order, and a re-call that sorts before ties_p would rename those that follow)
 }
 P_TIES = {"ties_p": ["-p"], "ties_q": ["-p", "-q"]}
 

@@ -69,7 +69,8 @@ def assert_same_run(o, h, so, sh, case, tol=1e-5):
 
 
 SUPPORTED = ["basic", "atac", "ctrl_q", "multimap", "atac_odd", "reps3", "reps3_p_missing",
-             "ctrl_only_chrom", "nopeaks_log", "bedx", "bedx_noctrl", "ties_p", "ties_q", "ties_summit", "ties_summit_q"]
+             "ctrl_only_chrom", "nopeaks_log", "bedx", "bedx_noctrl", "ties_p", "ties_q", "ties_summit", "ties_summit_q",
+             "reps5_mixed", "reps9"]
 
 
 @pytest.mark.parametrize("name", SUPPORTED)
@@ -488,8 +489,9 @@ def test_events_from_several_host_and_device_segments():
     assert h.n_peaks > 0
 
 
-def _random_case(seed, scale=1):
-    """scale > 1: the same mix on chromosomes / samples `scale` times larger (tools/fuzz_hip_vs_oracle.py)"""
+def _random_case(seed, scale=1, n_reps=None):
+    """scale > 1: the same mix on chromosomes / samples `scale` times larger (tools/fuzz_hip_vs_oracle.py); n_reps = (lo, hi): that
+    many replicates, drawn from a stream of its own (every other draw of a seed stays what it is with 1-3 replicates)"""
     rng = np.random.default_rng(seed)
     nch = int(rng.integers(1, 6))
     lens = [int(x) for x in rng.integers(500 * scale, 120_000 * scale, nch)]
@@ -512,7 +514,10 @@ def _random_case(seed, scale=1):
                 merged.append([s, e])
         beds.append([v for r in merged for v in r])
     reps = []
-    for r in range(int(rng.choice([1, 1, 2, 3]))):
+    nrep = int(rng.choice([1, 1, 2, 3]))
+    if n_reps is not None:
+        nrep = int(np.random.default_rng(seed + 991).integers(n_reps[0], n_reps[1] + 1))
+    for r in range(nrep):
         n = int(rng.integers(200 * scale, 6000 * scale))
         tr = synth.make_fragments(lens, n, seed=seed * 7 + r, frac_peak=0.4, frac_tower=0.2)
         if rng.random() < 0.3:
@@ -528,12 +533,15 @@ def _random_case(seed, scale=1):
     return dict(lens=lens, skip=skip, beds=beds, replicates=reps), params
 
 
-@pytest.mark.parametrize("block", range(4))
+@pytest.mark.parametrize("block", range(5))
 def test_random_runs_against_oracle(block):
-    """40 random runs: 1-5 chromosomes (some skipped, some with -E regions), 1-3 replicates with or
-    without control, multimapping, -p / -q, assorted -a / -l / -g."""
+    """50 random runs: 1-5 chromosomes (some skipped, some with -E regions), 1-3 replicates with or
+    without control, multimapping, -p / -q, assorted -a / -l / -g; the last block with 5-9 replicates (k_mergeN_w<8> and
+    k_mergeN, gx_merge.h: every count of the range is drawn)."""
+    drawn = set()
     for seed in range(block * 10, block * 10 + 10):
-        case, params = _random_case(1000 + seed)
+        case, params = _random_case(1000 + seed, n_reps=(5, 9) if block == 4 else None)
+        drawn.add(len(case["replicates"]))
         try:
             o, h, so, sh = run_both(case, params)
         except RuntimeError as ex:  # both must refuse the same inputs (e.g. a sample without fragments)
@@ -541,6 +549,7 @@ def test_random_runs_against_oracle(block):
                 B.run_case(B.Oracle(params), case)
             continue
         assert_same_run(o, h, so, sh, case)
+    assert block != 4 or drawn == {5, 6, 7, 8, 9}, drawn
 
 
 # thresholds at and beyond their ends (tools/fuzz_hip_vs_oracle.py --extreme): every -p / -q of the list, both -a and both -g

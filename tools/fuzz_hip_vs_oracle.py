@@ -1,7 +1,8 @@
 """GPU box: the HIP library against the CPU oracle on random runs.
 usage: fuzz_hip_vs_oracle.py SEED0 SEED1 [--mid]
 
-default: the generator of tests/test_hip_parity.py::test_random_runs_against_oracle (small runs)
+default: the generator of tests/test_hip_parity.py::test_random_runs_against_oracle (small runs), with 1-9 replicates (the
+         test's blocks draw 1-3 and 5-9: every instance of the replicate merge, gx_merge.h)
 --mid:   1-4 chromosomes of 0.2-6 Mbases, 0.1-0.9 M fragments (deep towers, multimapping, control)
 --extreme: thresholds at and beyond their ends (-p / -q of 1, 0.999, 1e-30, 1e-300; -a 0, 1e6; -g 0,
          100000; -l 100000) on top of whichever generator is chosen
@@ -149,7 +150,7 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
             print("seed", seed, type(ex).__name__, str(ex)[:300], {k: os.environ.get(k) for k in PATH_KNOBS}, flush=True)
             print("   ", describe(mid_case(seed)[0]), flush=True)
         continue
-    case, params = mid_case(seed) if mid else T._random_case(seed, 50 if "--x50" in sys.argv else 1)
+    case, params = mid_case(seed) if mid else T._random_case(seed, 50 if "--x50" in sys.argv else 1, n_reps=(1, 9))
     if "--extreme" in sys.argv:
         r = np.random.default_rng(seed + 77)
         qv = bool(r.random() < 0.5)
