@@ -91,6 +91,18 @@ int gx_create(gx_ctx** out, const gx_params* par) {
       fprintf(stderr, "k_tile workgroups: half %d, wide %d, fast %d\n", ctx->resTileHalf, ctx->resTile, ctx->resTileFast);
     HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scan_iv, STL_NT, 0));
     ctx->resSweep = std::max(1, std::min(nb, 4)) * ctx->numCU;
+    // level 1 of the pair sort: its persistent grids are what the device keeps resident (a multiple of NXCD, so that a chunk's
+    // XCD class is the one a grid of one workgroup per chunk gave it)
+    int nbA = 1 << 30;
+    for (auto k : {k_sort_a<false, false>, k_sort_a<false, true>, k_sort_a<true, false>, k_sort_a<true, true>}) {
+      HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, S2_NT, 0));
+      nbA = std::min(nbA, nb);
+    }
+    auto wholeXcds = [](int g) { return g > NXCD ? g - g % NXCD : std::max(1, g); };
+    ctx->resSortA = wholeXcds(std::max(1, nbA) * ctx->numCU);
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sort_b, S2_NT, 0));
+    ctx->resSortB = wholeXcds(std::max(1, nb) * ctx->numCU);
+    if (ctx->knob.debug) fprintf(stderr, "pair sort workgroups: k_sort_a %d, k_sort_b %d\n", ctx->resSortA, ctx->resSortB);
   }
   HIPCHECK(hipStreamSynchronize(ctx->stream));
   return GX_OK;

@@ -68,18 +68,20 @@ int stash_or_pack(gx_ctx* ctx, Pileup& P) {
   return GX_OK;
 }
 
-// the most level-1 chunks (workgroups of k_sort_a) any XCD class gets: class = blockIdx % NXCD of each piece's launch
-template <typename Segs> static u32 class_chunks(const Segs& segs) {
-  u32 best = 0;
-  for (u32 x = 0; x < (u32)NXCD; x++) {
-    u32 c = 0;
-    for (auto& sg : segs) {
-      const u32 b = (u32)((sg.n + S2_CHUNK - 1) / S2_CHUNK);
-      c += b / NXCD + (b % NXCD > x ? 1u : 0u);
-    }
-    best = std::max(best, c);
+// k_sort_a's persistent grid for a piece of `chunks` chunks: what is resident together (GX_S2_GRID: tests), one chunk each at least
+static u32 sort_a_grid(const gx_ctx* ctx, u32 chunks) {
+  const u32 g = ctx->knob.s2Grid > 0 ? (u32)ctx->knob.s2Grid : (u32)std::max(1, ctx->resSortA);
+  return std::max(1u, std::min(chunks, g));
+}
+// the most level-1 chunks any XCD class gets.  A chunk's class is that of the workgroup that scatters it: workgroup w of a piece's
+// launch (class w % NXCD) takes the chunks w, w + grid, w + 2 grid ... -- ceil((chunks - w) / grid) of them
+static u32 class_chunks(const gx_ctx* ctx) {
+  u32 perClass[NXCD] = {};
+  for (auto& sg : ctx->segs) {
+    const u32 b = (u32)((sg.n + S2_CHUNK - 1) / S2_CHUNK), g = sort_a_grid(ctx, b);
+    for (u32 w = 0; w < g && w < b; w++) perClass[w % NXCD] += (b - w + g - 1) / g;
   }
-  return best;
+  return *std::max_element(perClass, perClass + NXCD);
 }
 
 // Packed pieces (gx_event8) -> 16-byte events, in buffers of the library: for everything that reads gx_event records -- the general
@@ -187,7 +189,7 @@ int plan_build(gx_ctx* ctx, int isCtrl, bool reuseSort) {
   P.poolPages[2] = (u32)(((size_t)2 * nEv) >> PgCfg<u64>::SHIFT) + NXCD * nL1 + 4;
   // pair mode in two passes (k_sort_a / k_sort_b): the coarse lists, and the first pass's workgroups over all pieces
   P.nCoarse = (std::max(1u, nL1) + (1u << s2_fine_shift(nL1)) - 1) >> s2_fine_shift(nL1);
-  P.jmaxC = class_chunks(ctx->segs) + 3;   // (a class's workgroups cannot fill more pages than that in one list)
+  P.jmaxC = class_chunks(ctx) + 3;   // (a class's workgroups cannot fill more pages than that in one list)
   for (auto& sg : ctx->segs) P.nWG1 += (u32)((sg.n + S2_CHUNK - 1) / S2_CHUNK);
   // lambda ahead of the tile stage (closed form of fragLen; LooseCtl): one rank, a treatment sample, -p
   P.wantEarly = !isCtrl && (!P.multiRank || P.earlyColl) && !ctx->par.qval_opt && !ctx->hasBed && unit32 && !noLoose && !forceSlowFrag &&
@@ -357,16 +359,21 @@ int sort_level1(gx_ctx* ctx, const BuildPlan& P) {
     const u32 blocks = (u32)((seg.n + S1_CHUNK - 1) / S1_CHUNK);
     if (P.pairs) {
       // (a piece of 8-byte events by the instance that reads those in place)
-      hipLaunchKernelGGL(SORT_A[P.fracPairs][seg.packed], dim3(blocks), dim3(S2_NT), 0, s, seg.p, (u32)seg.n, ctx->dChrom.as<DChrom>(), ctx->nChrom, P.sbS,
+      hipLaunchKernelGGL(SORT_A[P.fracPairs][seg.packed], dim3(sort_a_grid(ctx, blocks)), dim3(S2_NT), 0, s, seg.p, (u32)seg.n, ctx->dChrom.as<DChrom>(), ctx->nChrom, P.sbS,
                          P.nL1, P.nCoarse, PC, ctx->auxC.as<uint8_t>(), PG2, ctx->binNet.as<int>(), so1, ctx->dStatus.as<u32>());
       ctx->packedUsed |= seg.packed;
     } else
       hipLaunchKernelGGL(P.unit32 ? k_sort1<true> : k_sort1<false>, dim3(blocks), dim3(S1_NT), 0, s, seg.p, (u32)seg.n,
                          ctx->dChrom.as<DChrom>(), ctx->nChrom, P.sbS, P.nL1, PG0, PG1, PG2, so1, ctx->dStatus.as<u32>());
   }
-  if (P.pairs && P.nEv)  // the coarse lists (all pieces' events) -> the fine bins' lists (a class's hold at most its chunks' + one partly filled page each)
-    hipLaunchKernelGGL(k_sort_b, dim3(NXCD * (P.jmaxC - 3 + P.nCoarse)), dim3(S2_NT), 0, s, PC, (const uint8_t*)ctx->auxC.as<uint8_t>(),
+  if (P.pairs && P.nEv) {
+    // the coarse lists (all pieces' events) -> the fine bins' lists.  A class's lists hold at most its chunks' + one partly filled page
+    // each; the resident workgroups (a multiple of NXCD: the same number for every class) share them
+    const u32 want = ctx->knob.s2Grid > 0 ? (u32)ctx->knob.s2Grid : (u32)std::max(1, ctx->resSortB);
+    const u32 gridB = std::min((u32)NXCD * (P.jmaxC - 3 + P.nCoarse), (want + NXCD - 1) / NXCD * NXCD);
+    hipLaunchKernelGGL(k_sort_b, dim3(gridB), dim3(S2_NT), 0, s, PC, (const uint8_t*)ctx->auxC.as<uint8_t>(),
                        P.nCoarse, P.nL1, PG0, ctx->dStatus.as<u32>());
+  }
   return dbg_sync(ctx, "k_sort1");
 }
 

@@ -184,6 +184,8 @@ struct Knobs {
   int sbtTr = 0;          // GX_SBT_TR: 384 / 448: which instance of k_sbtile's dense launch runs (measurements; default: by the sample's density)
   int sbtGrid = 0;        // GX_SBT_GRID: persistent workgroups of k_sbtile's first launch (0: one per CU; a small number makes one workgroup run
                           // many bins in a row: tests, measurements)
+  int s2Grid = 0;         // GX_S2_GRID: persistent workgroups of k_sort_a (per piece) and k_sort_b (0: as many as are resident together; a small
+                          // number makes one workgroup run many chunks / pages in a row: tests, measurements)
   int roctx = 0;          // GX_ROCTX: a roctx range around every phase (rocprofv3 --marker-trace: kernel -> phase attribution)
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
@@ -226,6 +228,7 @@ const KnobDef KNOBS[] = {
     {"GX_NO_DENSE_BH", &Knobs::noDenseBh, nullptr}, {"GX_REG_WINDOWS", &Knobs::regWindows, nullptr}, {"GX_QT_MULTI", &Knobs::qtMulti, nullptr}, {"GX_FORCE_COLL", &Knobs::forceColl, nullptr},
     {"GX_SBSHIFT", &Knobs::sbShift, nullptr}, {"GX_RUN_CAP_MIN", nullptr, &Knobs::runCapMin}, {"GX_BH_CAPLOG", &Knobs::bhCapLog, nullptr},
     {"GX_PT_JMAX", &Knobs::ptJmax, nullptr}, {"GX_FAULT", &Knobs::fault, nullptr}, {"GX_SBT_TR", &Knobs::sbtTr, nullptr}, {"GX_SBT_GRID", &Knobs::sbtGrid, nullptr},
+    {"GX_S2_GRID", &Knobs::s2Grid, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
 };
 // a switch that is merely present counts as 1 (GX_NO_LOOSE= is "on", as it was with getenv() != nullptr), and so does a
@@ -376,6 +379,7 @@ struct gx_ctx {
   bool phaseOpen = false;
   bool roctxOpen = false;       // (GX_ROCTX: the range of the open phase)
   int numCU = 0, resTile = 0, resTileHalf = 0, resTileFast = 0, resSweep = 0;  // co-resident workgroups per kernel class
+  int resSortA = 0, resSortB = 0;   // ... of k_sort_a (the fewest of its four instances: one grid rule for every piece) and k_sort_b
   // recycled device buffers (gx_reset keeps allocations alive across runs)
   std::vector<DevBuf> pool;
   // counting in peaks (gx_set_count_in_peaks / gx_count_in_peaks, gx_count.h): every closed sample's events stay where they are

@@ -23,6 +23,7 @@
 // ST_PT_FULL and the host repeats the sample with a longer table (a pile-up of reads in one spot).
 // Level 2 (k_bucket2p, one workgroup per super-bucket) walks the eight lists of its bin.
 #pragma once
+#include <type_traits>
 #include "gx_kernels.h"
 #include "gx_stats.h"   // (lut_entry: k_bins_lut)
 
@@ -649,6 +650,15 @@ struct S2Lds {
 // The coarse lists' pages hold the 4-byte records at page * 8192 * 4 of `pool` and the bytes at page * 8192 of `aux`.
 // AUX: whether the byte array is written (k_sort_a).  `listBase + key` = the list a key's run goes to.
 // KEYS: 64, or 128 (k_sort_b on a genome of more than 4096 bins): one owner thread per key -- the first wavefront, or two.
+// The thread's index as a value the compiler cannot follow back to threadIdx.x.  The persistent loops of k_sort_a / k_sort_b call
+// scatter64 once per chunk: what depends on the thread alone (sixteen LDS addresses, the loads' offsets) is otherwise computed once
+// ahead of the loop and kept in registers through all of it -- registers the loads in flight need.
+__device__ __forceinline__ u32 fresh_tid() {
+  u32 t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
 template <bool AUX, int KEYS>
 __device__ __forceinline__ void scatter64(const u32 (&rec)[S2_ITEMS], u32 (&ka)[S2_ITEMS], const PagedStream& P,
                                           uint8_t* __restrict__ auxPool, u32 listBase, u32 nKeys, S2Lds& L, u32* __restrict__ st) {
@@ -658,23 +668,25 @@ __device__ __forceinline__ void scatter64(const u32 (&rec)[S2_ITEMS], u32 (&ka)[
   constexpr int SHIFT = PgCfg<u32>::SHIFT;
   constexpr u32 PG = 1u << SHIFT;
   constexpr u32 KM = (u32)KEYS - 1u;
+  const u32 tid = fresh_tid();
 #pragma unroll
   for (int k = 0; k < S2_ITEMS; k++) ka[k] = (ka[k] & 0xFFFFu) | ((rec[k] != NULL32 ? atomicAdd(&L.cnt[ka[k] & KM], 1u) : 0u) << 16);
   __syncthreads();
   // the owners: counts -> reservations on the lists' cursors -> where the runs start in the staged chunk and in the pool.
   // Three steps with workgroup barriers between them (two owner wavefronts: the second needs the first one's total, and
   // every page either of them allocates is published before any of their lanes waits for one)
-  const bool owner = threadIdx.x < (u32)KEYS;
-  const u32 key = threadIdx.x;
+  const bool owner = tid < (u32)KEYS;
+  const u32 key = tid;
   u32 c = 0, o = 0, inc = 0, li = 0;
   if (owner) {
     c = key < nKeys ? L.cnt[key] : 0u;
+    L.cnt[key] = 0;  // (for the caller's next chunk: its first add lies behind the three barriers below)
     li = listBase + key;
     if (c) o = atomicAdd(&P.cursor[li], c);
     inc = (u32)dpp_scan_add((int)c);
     if ((key & 63u) == 63u) L.wtot[key >> 6] = inc;
   }
-  if (KEYS == 64 && threadIdx.x == 0) L.wtot[1] = 0;
+  if (KEYS == 64 && tid == 0) L.wtot[1] = 0;
   __syncthreads();
   const u32 in0 = o & (PG - 1), j0 = o >> SHIFT, j1 = (o + c - 1) >> SHIFT;
   u32* row = P.pt + (size_t)li * P.jmax;
@@ -708,18 +720,19 @@ __device__ __forceinline__ void scatter64(const u32 (&rec)[S2_ITEMS], u32 (&ka)[
   __syncthreads();
   u32* pool = reinterpret_cast<u32*>(P.pool);
   const u32 cnt = L.total;
+  constexpr int SB = 8;   // staged records a thread reads and writes at a time
 #pragma unroll
-  for (int h = 0; h < S2_ITEMS; h += 8) {
-    u32 v[8], kk[8];
+  for (int h = 0; h < S2_ITEMS; h += SB) {
+    u32 v[SB], kk[SB];
 #pragma unroll
-    for (int k = 0; k < 8; k++) {  // (a fixed trip count: the LDS reads of eight records in flight together)
-      const u32 i = (u32)(h + k) * S2_NT + threadIdx.x, ii = i < cnt ? i : 0u;
+    for (int k = 0; k < SB; k++) {  // (a fixed trip count: the LDS reads of SB records in flight together)
+      const u32 i = (u32)(h + k) * S2_NT + tid, ii = i < cnt ? i : 0u;
       v[k] = L.stage[ii];
       kk[k] = L.ka[ii];
     }
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const u32 i = (u32)(h + k) * S2_NT + threadIdx.x;
+    for (int k = 0; k < SB; k++) {
+      const u32 i = (u32)(h + k) * S2_NT + tid;
       const uint4 rn = L.run[kk[k] & KM];
       const u32 r = i - rn.x;
       const u32 dst = r < rn.y ? rn.z + r : rn.w + (r - rn.y);
@@ -752,6 +765,14 @@ __global__ __launch_bounds__(256) void k_unpack_events(const uint2* __restrict__
   }
 }
 
+#ifndef GX_S2_PFL
+#define GX_S2_PFL 4   // 16-byte event loads per thread that k_sort_a keeps ahead of its conversion (a multiple of a batch's)
+#endif
+// PERSISTENT (round 8): workgroup b of a piece's launch takes the chunks b, b + grid, b + 2 grid ... of 8192 events -- static
+// striding: the chunks cost the same, and the host must know which XCD class (b % NXCD) scatters a chunk (class_chunks,
+// gx_host_build.h).  The event loads run GX_S2_PFL loads per thread ahead of the conversion, through a chunk's end into the next
+// chunk: the first batch of the NEXT chunk is asked for ahead of this chunk's scatter and taken after it, so a workgroup that scatters
+// has loads in flight of its own, not only its neighbour's on the CU.
 template <bool FRAC, bool PACKED = false>
 __global__ __launch_bounds__(S2_NT, GX_S2A_WAVES) void k_sort_a(const gx_event* __restrict__ ev, u32 n, const DChrom* __restrict__ chroms,
                                                      u32 nChrom, int sbShift, u32 nBins, u32 nCoarse, PagedStream PC,
@@ -759,61 +780,93 @@ __global__ __launch_bounds__(S2_NT, GX_S2A_WAVES) void k_sort_a(const gx_event* 
                                                      Sort1Out out, u32* __restrict__ st) {
   __shared__ S2Lds L;
   __shared__ DChrom lchrom[S2_LCHROM];
+  // [it & 1]: ST_SB_FRAC as thread 0 found it behind the scatter of the workgroup's it-th chunk; [2]: at the kernel's entry
+  __shared__ u32 sStop[3];
   const int fineShift = s2_fine_shift(nBins);
-  // (unit-weight records and a fractional weight somewhere in the input: the sample is going to be built again on the
-  // general chain whatever this launch still does -- the workgroups that start after the flag went up leave at once)
-  if (!FRAC && (__hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ST_SB_FRAC)) return;
   const bool chromLds = nChrom <= (u32)S2_LCHROM;
   const u32 x = blockIdx.x % NXCD;
-  const u32 begin = blockIdx.x * S2_CHUNK;
+  const u32 nChunks = (n + S2_CHUNK - 1) / S2_CHUNK;   // (the grid is no larger: blockIdx.x < nChunks)
   const u32 binMask = (1u << sbShift) - 1u;
-  u32 bad = 0, slow = 0, fracSeen = 0;
-  u32 covered32 = 0;  // (sixteen lengths below 2^12)
-  u32 rec[S2_ITEMS], ka[S2_ITEMS];
-  if (threadIdx.x < S2_KEYS) L.cnt[threadIdx.x] = 0;
-  const uint4* __restrict__ evb = reinterpret_cast<const uint4*>(ev) + begin;
-  const u32 lastIn = n - 1u - begin;  // (the grid covers the input: begin < n)
-  // (the conversion: see k_sort1p)
-#pragma unroll
-  for (int k0 = 0; k0 < S2_ITEMS; k0 += S2_BATCH) {
-    uint4 e[S2_BATCH];
-    bool have[S2_BATCH];
+  u32 bad = 0, fracSeen = 0;
+  u64 covered = 0;
+  // the 16-byte loads of one batch of events: S2_BATCH events, or (PACKED) two to a load
+  constexpr int NL = PACKED ? S2_BATCH / 2 : S2_BATCH;
+  constexpr int NB = S2_ITEMS / S2_BATCH, PFB = GX_S2_PFL / NL;
+  static_assert(S2_BATCH % 2 == 0, "two packed events per 16-byte load");
+  static_assert(PFB >= 1 && NB % PFB == 0, "a batch's place in the ring is the same in every chunk");
+  auto load_batch = [&](u32 tid, u32 begin, int k0, uint4 (&raw)[NL]) {
+    const u32 lastIn = n - 1u - begin;  // (begin < n: a load past the end of the piece is clamped to its last event)
     if constexpr (PACKED) {
-      static_assert(S2_BATCH % 2 == 0, "two packed events per 16-byte load");
       // (item k of a thread is event 2 ((k / 2) S2_NT + thread) + (k & 1) of the chunk; the array is padded to an even count)
       const uint4* __restrict__ evp = reinterpret_cast<const uint4*>(reinterpret_cast<const uint2*>(ev) + begin);
 #pragma unroll
+      for (int q = 0; q < NL; q++) raw[q] = evp[min(((u32)(k0 >> 1) + q) * S2_NT + tid, lastIn >> 1)];
+    } else {
+      // (a uniform base and a 32-bit offset within the chunk: no 64-bit address per load)
+      const uint4* __restrict__ evb = reinterpret_cast<const uint4*>(ev) + begin;
+#pragma unroll
+      for (int q = 0; q < NL; q++) raw[q] = evb[min((u32)(k0 + q) * S2_NT + tid, lastIn)];  // chrom, start, end, count
+    }
+  };
+  // (unit-weight records and a fractional weight somewhere in the input: the sample is going to be built again on the
+  // general chain whatever this launch still does -- a workgroup that finds the flag up leaves, all of its threads alike)
+  u32 sv = 0;
+  if (!FRAC && threadIdx.x == 0) sv = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x < S2_KEYS) L.cnt[threadIdx.x] = 0;
+  // The event loads run PFB batches ahead of the conversion, through a chunk's end into the next chunk: batch b of a chunk is
+  // loaded into ring[b % PFB] as soon as the batch PFB before it has been converted out of those registers.
+  uint4 ring[PFB][NL];
+#pragma unroll
+  for (int b = 0; b < PFB; b++) load_batch(threadIdx.x, blockIdx.x * S2_CHUNK, b * S2_BATCH, ring[b]);
+  if (chromLds)
+    for (u32 i = threadIdx.x; i < nChrom; i += S2_NT) lchrom[i] = chroms[i];
+  if (!FRAC && threadIdx.x == 0) sStop[2] = sv & ST_SB_FRAC;
+  __syncthreads();
+  if (!FRAC && sStop[2]) return;
+  // (one loop per place the chromosomes' records are read from, chosen here -- not `chromLds ? lchrom[ci] : chroms[ci]`: the compiler
+  // makes ONE load of a selected pointer out of that, a FLAT load, through the texture path and waiting on both counters, for a
+  // record that lies in LDS: round 6, found in the ISA; and not a branch per batch: the batches' conversions are straight-line code
+  // between their loads then, which is what keeps the loads in the order and the registers they are given here)
+  auto chunks = [&](auto inLds) {
+  constexpr bool CLDS = decltype(inLds)::value;
+  u32 it = 0;
+  for (u32 chunk = blockIdx.x; chunk < nChunks; chunk += gridDim.x, it++) {
+  const u32 tid = fresh_tid();
+  const u32 begin = chunk * S2_CHUNK;
+  const u32 lastIn = n - 1u - begin;
+  u32 slow = 0;
+  u32 covered32 = 0;  // (sixteen lengths below 2^12)
+  u32 rec[S2_ITEMS], ka[S2_ITEMS];
+  const u32 next = chunk + gridDim.x;
+  // (the conversion: see k_sort1)
+#pragma unroll
+  for (int k0 = 0; k0 < S2_ITEMS; k0 += S2_BATCH) {
+    // (nothing that touches memory moves across a batch's boundary: the loads stay PFB batches ahead, no more and no less)
+    asm volatile("" ::: "memory");
+    uint4 (&raw)[NL] = ring[(k0 / S2_BATCH) % PFB];
+    uint4 e[S2_BATCH];
+    bool have[S2_BATCH];
+    if constexpr (PACKED) {
+#pragma unroll
       for (int q = 0; q < S2_BATCH; q += 2) {
-        const u32 lp = ((k0 + q) >> 1) * S2_NT + threadIdx.x;
+        const u32 lp = ((k0 + q) >> 1) * S2_NT + tid;
         have[q] = 2u * lp <= lastIn;
         have[q + 1] = 2u * lp + 1u <= lastIn;
-        const uint4 two = evp[min(lp, lastIn >> 1)];
-        e[q] = unpack_event8(two.x, two.y);
-        e[q + 1] = unpack_event8(two.z, two.w);
+        e[q] = unpack_event8(raw[q >> 1].x, raw[q >> 1].y);
+        e[q + 1] = unpack_event8(raw[q >> 1].z, raw[q >> 1].w);
       }
     } else {
 #pragma unroll
-    for (int q = 0; q < S2_BATCH; q++) {
-      // (a uniform base and a 32-bit offset within the chunk: no 64-bit address per load)
-      const u32 li = (k0 + q) * S2_NT + threadIdx.x;
-      have[q] = li <= lastIn;
-      e[q] = evb[min(li, lastIn)];  // chrom, start, end, count
+      for (int q = 0; q < S2_BATCH; q++) {
+        have[q] = (k0 + q) * S2_NT + tid <= lastIn;
+        e[q] = raw[q];
+      }
     }
-    }
-    if (k0 == 0) {
-      if (chromLds)
-        for (u32 i = threadIdx.x; i < nChrom; i += S2_NT) lchrom[i] = chroms[i];
-      __syncthreads();
-    }
-    // (two loops, not `chromLds ? lchrom[ci] : chroms[ci]`: the compiler makes ONE load of a selected pointer out of that -- a
-    // FLAT load, through the texture path and waiting on both counters, for a record that lies in LDS: round 6, found in the ISA)
     DChrom cq[S2_BATCH];
-    if (chromLds) {  // block-uniform
 #pragma unroll
-      for (int q = 0; q < S2_BATCH; q++) cq[q] = lchrom[min(e[q].x, nChrom - 1)];
-    } else {
-#pragma unroll
-      for (int q = 0; q < S2_BATCH; q++) cq[q] = chroms[min(e[q].x, nChrom - 1)];
+    for (int q = 0; q < S2_BATCH; q++) {
+      if constexpr (CLDS) cq[q] = lchrom[min(e[q].x, nChrom - 1)];
+      else cq[q] = chroms[min(e[q].x, nChrom - 1)];
     }
 #pragma unroll
     for (int q = 0; q < S2_BATCH; q++) {
@@ -836,9 +889,20 @@ __global__ __launch_bounds__(S2_NT, GX_S2A_WAVES) void k_sort_a(const gx_event* 
       covered32 += fast && cnt == 1u ? len : 0u;
       slow |= (u32)(!fast && !nothing) << (k0 + q);
     }
-    __builtin_amdgcn_sched_barrier(0);  // (the next batch's loads stay behind this one's conversion: registers)
+    // (the batch's records exist from here on: left alone, the compiler computes them where the scatter first needs them, and the
+    // events and chromosome records of the whole chunk -- eight registers per event -- wait in registers until then)
+#pragma unroll
+    for (int q = 0; q < S2_BATCH; q++) asm volatile("" : "+v"(rec[k0 + q]), "+v"(ka[k0 + q]));
+    asm volatile("" : "+v"(slow), "+v"(covered32), "+v"(fracSeen));
+    // the batch PFB ahead takes the registers this one has left: one of this chunk, or -- the loads that travel while this chunk is
+    // scattered -- one of the first of the chunk to come (nothing to fetch behind the piece's last chunk)
+    if (k0 / S2_BATCH + PFB < NB)
+      load_batch(tid, begin, k0 + PFB * S2_BATCH, raw);
+    else if (next < nChunks)
+      load_batch(tid, next * S2_CHUNK, k0 + PFB * S2_BATCH - S2_ITEMS, raw);
+    __builtin_amdgcn_sched_barrier(0);  // (a batch's conversion is done with before the next one's begins: registers)
   }
-  u64 covered = covered32;
+  covered += covered32;
   scatter64<true, 64>(rec, ka, PC, auxPool, x * nCoarse, nCoarse, L, st);
   // the slow events: loaded again (they are in L2), converted as k_sort1 converts every event, their records appended
   // one by one
@@ -853,10 +917,10 @@ __global__ __launch_bounds__(S2_NT, GX_S2A_WAVES) void k_sort_a(const gx_event* 
       if (mine) {
         uint4 e;
         if constexpr (PACKED) {
-          const uint2 e8 = reinterpret_cast<const uint2*>(ev)[begin + 2u * ((u32)(k >> 1) * S2_NT + threadIdx.x) + (u32)(k & 1)];
+          const uint2 e8 = reinterpret_cast<const uint2*>(ev)[begin + 2u * ((u32)(k >> 1) * S2_NT + tid) + (u32)(k & 1)];
           e = unpack_event8(e8.x, e8.y);
         } else
-          e = reinterpret_cast<const uint4*>(ev)[begin + k * S2_NT + threadIdx.x];
+          e = reinterpret_cast<const uint4*>(ev)[begin + k * S2_NT + tid];
         const Endpoints p = convert_event<true>(e, chroms[min(e.x, nChrom - 1)], true, nChrom, out, bad, covered);
         mine = p.w != 0;  // (else: an event that only raised a status bit, or one without effect)
         if (mine) {
@@ -884,79 +948,107 @@ __global__ __launch_bounds__(S2_NT, GX_S2A_WAVES) void k_sort_a(const gx_event* 
       append_single(PF, l1, r1, h1, st);
     }
   }
+  // The early exit, per chunk and without a barrier of its own: thread 0 posts here, behind the scatter's barriers, whether the
+  // flag is up; everybody takes that word at the end of the NEXT chunk -- behind that one's barriers, and before the word is written
+  // again two chunks on.  (It only spares work: the sample is rebuilt whatever is appended here.)
+  if (!FRAC) {
+    if (tid == 0) sStop[it & 1u] = __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ST_SB_FRAC;
+    if (it && sStop[(it - 1u) & 1u]) break;
+  }
+  }
+  };
+  if (chromLds) chunks(std::true_type{}); else chunks(std::false_type{});
   if (bad) atomicOr(st, bad);
   if (FRAC && __ballot(fracSeen != 0) && lane_id() == 0) atomicOr(out.slowFrag, FRAG_SLOW_FRAC);  // (the closed form of fragLen is off)
   covered = wave_sum(covered);
   if (lane_id() == 0 && covered) atomicAdd(&out.fragSum[(blockIdx.x * 8 + (threadIdx.x >> 6)) % FRAG_SLOTS], covered);
 }
 
-// one workgroup per page of a coarse list -> the fine bins' lists (PP: what k_sbtile<true> reads).  The grid is an
-// upper bound (NXCD x the most pages a class can hold); a workgroup finds its page from its class's cursors: list
-// l = x * nCoarse + cb has ceil(cursor / 8192) pages.
+// The coarse lists' pages -> the fine bins' lists (PP: what k_sbtile<true> reads).  PERSISTENT (round 8): the workgroups of XCD
+// class x = blockIdx % NXCD (the class of the workgroups that filled the lists: the fine lists' cache lines are completed inside
+// one L2, as in the single-pass kernels) share the pages of that class's lists -- list l = x * nCoarse + cb has
+// ceil(cursor / 8192) of them -- by static striding: workgroup b takes the pages b / NXCD, b / NXCD + grid / NXCD ... of the class,
+// counted through its lists in order.  Every wavefront keeps the class's page counts in its lanes (one 64-lane scan at the start)
+// and finds a page's list and length by a ballot: no shared words, no barrier.  A page's table entry is asked for one page ahead
+// of its records.
 __global__ __launch_bounds__(S2_NT, GX_S2B_WAVES) void k_sort_b(PagedStream PC, const uint8_t* __restrict__ auxPool, u32 nCoarse, u32 nBins,
                                                      PagedStream PP, u32* __restrict__ st) {
   constexpr int SHIFT = PgCfg<u32>::SHIFT;
+  constexpr int NQ = S2_ITEMS / 4;  // 16-byte loads of records per thread
   __shared__ S2Lds L;
-  __shared__ u32 sList, sPage, sCount;
-  // workgroup b takes page b / NXCD of XCD class b % NXCD (the class of the workgroups that filled the list: the fine
-  // lists' cache lines are completed inside one L2, as in the single-pass kernels)
-  if (threadIdx.x < 64) {
-    const u32 xc = blockIdx.x % NXCD, q = blockIdx.x / NXCD;
-    const u32 len = threadIdx.x < nCoarse ? PC.cursor[xc * nCoarse + threadIdx.x] : 0u;
-    const u32 np = (len + S2_CHUNK - 1) >> SHIFT;
-    const u32 inc = (u32)dpp_scan_add((int)np), ex = inc - np;
-    if (threadIdx.x == 0) sCount = 0;
-    L.cnt[threadIdx.x] = 0;
-    L.cnt[threadIdx.x + 64] = 0;
-    __builtin_amdgcn_wave_barrier();
-    if (q >= ex && q < inc) {
-      const u32 j = q - ex;
-      sList = xc * nCoarse + threadIdx.x;
-      sPage = j;
-      sCount = min((u32)S2_CHUNK, len - (j << SHIFT));
-    }
-  }
+  const u32 xc = blockIdx.x % NXCD, stride = gridDim.x / NXCD;   // (the grid is a multiple of NXCD)
+  const u32 lane = lane_id();
+  const u32 len = lane < nCoarse ? PC.cursor[xc * nCoarse + lane] : 0u;
+  const u32 np = (len + S2_CHUNK - 1) >> SHIFT;
+  const u32 inc = (u32)dpp_scan_add((int)np), ex = inc - np;
+  const u32 total = (u32)__builtin_amdgcn_readlane((int)inc, 63);
+  if (threadIdx.x < S2_KEYS) L.cnt[threadIdx.x] = 0;
   __syncthreads();
-  const u32 count = sCount;
-  if (count == 0) return;  // (beyond the last page)
-  const u32 li = sList, j = sPage;
-  const u32 x = li / nCoarse, cb = li - x * nCoarse;
-  const u32 page = j ? __hip_atomic_load(&PC.pt[(size_t)li * PC.jmax + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1u : first_page(li);
-  const u32* src = reinterpret_cast<const u32*>(PC.pool) + ((size_t)page << SHIFT);
-  const uint8_t* srcA = auxPool + ((size_t)page << SHIFT);
+  // page q of the class (q < total): its list, its table entry (a list's first page is fixed) and its records
+  struct Page { u32 cb, count, id; };
+  auto find = [&](u32 q) {
+    const int cb = __ffsll((unsigned long long)__ballot(q >= ex && q < inc)) - 1;
+    const u32 j = q - (u32)__builtin_amdgcn_readlane((int)ex, cb), li = xc * nCoarse + (u32)cb;
+    Page p;
+    p.cb = (u32)cb;
+    p.count = min((u32)S2_CHUNK, (u32)__builtin_amdgcn_readlane((int)len, cb) - (j << SHIFT));
+    // (page id + 1, as the table keeps it.  The rows hold every page a class can fill -- class_chunks, gx_host_build.h -- and every
+    // page below a cursor was published in the launches before this one: the sink page stands in for what cannot happen)
+    p.id = j == 0 ? first_page(li) + 1u
+                  : j < PC.jmax ? max(1u, __hip_atomic_load(&PC.pt[(size_t)li * PC.jmax + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 1u;
+    return p;
+  };
   // (thread t: records 16 t .. 16 t + 15 of the page -- four 16-byte loads of records, one of their bytes)
-  u32 rec[S2_ITEMS], ka[S2_ITEMS];
-  {
-    constexpr int NQ = S2_ITEMS / 4;  // 16-byte loads of records per thread
-    uint4 r4[NQ];
+  uint4 r4[NQ], a4 = make_uint4(0u, 0u, 0u, 0u);
+  auto load_page = [&](u32 tid, u32 id) {
+    const u32 page = id - 1u;
+    const u32* src = reinterpret_cast<const u32*>(PC.pool) + ((size_t)page << SHIFT);
+    const uint8_t* srcA = auxPool + ((size_t)page << SHIFT);
 #pragma unroll
-    for (int q = 0; q < NQ; q++) r4[q] = reinterpret_cast<const uint4*>(src)[threadIdx.x * NQ + q];
-    u32 aw[4] = {0u, 0u, 0u, 0u};
-    if (NQ == 4) {
-      const uint4 a4 = reinterpret_cast<const uint4*>(srcA)[threadIdx.x];
-      aw[0] = a4.x; aw[1] = a4.y; aw[2] = a4.z; aw[3] = a4.w;
-    } else {
-      const uint2 a2 = reinterpret_cast<const uint2*>(srcA)[threadIdx.x];
-      aw[0] = a2.x; aw[1] = a2.y;
+    for (int q = 0; q < NQ; q++) r4[q] = reinterpret_cast<const uint4*>(src)[tid * NQ + q];
+    if (NQ == 4)
+      a4 = reinterpret_cast<const uint4*>(srcA)[tid];
+    else {
+      const uint2 a2 = reinterpret_cast<const uint2*>(srcA)[tid];
+      a4.x = a2.x; a4.y = a2.y;
     }
+  };
+  u32 q = blockIdx.x / NXCD;
+  if (q >= total) return;  // (more workgroups than the class has pages)
+  Page cur = find(q), nxt = cur;
+  load_page(threadIdx.x, cur.id);
+  if (q + stride < total) nxt = find(q + stride);
+  const int fineShift = s2_fine_shift(nBins);
+  for (;;) {
+    const u32 tid = fresh_tid();
+    u32 rec[S2_ITEMS], ka[S2_ITEMS];
+    {
+      const u32 aw[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const u32 rw[4] = {r4[q].x, r4[q].y, r4[q].z, r4[q].w};
+      for (int h = 0; h < NQ; h++) {
+        const u32 rw[4] = {r4[h].x, r4[h].y, r4[h].z, r4[h].w};
 #pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const u32 i = threadIdx.x * S2_ITEMS + q * 4 + j;
-        rec[q * 4 + j] = i < count ? rw[j] : NULL32;
-        ka[q * 4 + j] = (aw[q] >> (8 * j)) & 0xFFu;
+        for (int j = 0; j < 4; j++) {
+          const u32 i = tid * S2_ITEMS + h * 4 + j;
+          rec[h * 4 + j] = i < cur.count ? rw[j] : NULL32;
+          ka[h * 4 + j] = (aw[h] >> (8 * j)) & 0xFFu;
+        }
       }
     }
+    // (a pair record is never NULL32: its length is below 2^12 - 1 ... and a page holds only records)
+    const u32 firstBin = cur.cb << fineShift, nk = min(1u << fineShift, nBins - firstBin);
+    if (fineShift == 7)  // block-uniform
+      scatter64<false, 128>(rec, ka, PP, nullptr, xc * nBins + firstBin, nk, L, st);
+    else
+      scatter64<false, 64>(rec, ka, PP, nullptr, xc * nBins + firstBin, nk, L, st);
+    // the next page: its records are asked for behind this page's scatter (ahead of it they cost twenty registers through the
+    // scatter: spills at three workgroups per CU, and slower at two -- round 8), with the table entry of the page after it
+    q += stride;
+    if (q >= total) break;
+    cur = nxt;
+    load_page(tid, cur.id);
+    if (q + stride < total) nxt = find(q + stride);
   }
-  // (a pair record is never NULL32: its length is below 2^12 - 1 ... and a page holds only records)
-  const int fineShift = s2_fine_shift(nBins);
-  const u32 firstBin = cb << fineShift, nk = min(1u << fineShift, nBins - firstBin);
-  if (fineShift == 7)  // block-uniform
-    scatter64<false, 128>(rec, ka, PP, nullptr, x * nBins + firstBin, nk, L, st);
-  else
-    scatter64<false, 64>(rec, ka, PP, nullptr, x * nBins + firstBin, nk, L, st);
 }
 
 // bin totals (over the XCD classes) -> where each super-bucket's records start after level 2; one workgroup per stream.

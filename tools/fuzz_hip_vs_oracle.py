@@ -86,6 +86,11 @@ def run_paths(seed):
                   ("GX_NO_Q_LOOSE", 0.25)):
         if rng.random() < pr:
             knobs[k] = "1"
+    # (round 8) a few persistent workgroups for the pair sort's two passes: one workgroup runs many chunks / pages in a row (a
+    # stream of its own: the other draws of a seed stay what they were)
+    g = np.random.default_rng(seed + 777)
+    if g.random() < 0.5:
+        knobs["GX_S2_GRID"] = str(int(g.choice([1, 2, 3, 7, 16])))
     for k in PATH_KNOBS:
         os.environ.pop(k, None)
     os.environ.update(knobs)
@@ -131,7 +136,7 @@ def describe(case):
     return dict(lens=case["lens"], skip=case.get("skip"), beds=case.get("beds"), reps=reps)
 
 
-PATH_KNOBS = ("GX_SBSHIFT", "GX_FORCE_HALF_BINS", "GX_NO_PAIRS", "GX_NO_FRAC_PAIRS", "GX_NO_LAZY_Q", "GX_NO_PACK_HIST", "GX_MERGE_WG", "GX_NO_MERGE_P", "GX_NO_LATE_LOOSE", "GX_NO_Q_LOOSE")
+PATH_KNOBS = ("GX_SBSHIFT", "GX_FORCE_HALF_BINS", "GX_NO_PAIRS", "GX_NO_FRAC_PAIRS", "GX_NO_LAZY_Q", "GX_NO_PACK_HIST", "GX_MERGE_WG", "GX_NO_MERGE_P", "GX_NO_LATE_LOOSE", "GX_NO_Q_LOOSE", "GX_S2_GRID")
 mid = "--mid" in sys.argv
 paths = "--paths" in sys.argv
 import time  # noqa: E402
