@@ -9,6 +9,7 @@
 #include "gx_host_stats.h"
 #include "gx_host_count.h"
 #include "gx_host_regions.h"
+#include "gx_host_coverage.h"
 
 
 // ================================ C ABI ==================================================
@@ -148,6 +149,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
       ctx->bedGiven = true;
     }
   }
+  ctx->covDirty = true;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -215,6 +217,7 @@ int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   if (!ctx || !owned || ctx->nChrom == 0) return GX_ERR_ORDER;
   if (ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;  // the tile space changes: between runs only
   ctx->owned.assign(owned, owned + ctx->nChrom);
+  ctx->covDirty = true;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -245,6 +248,7 @@ int gx_reset(gx_ctx* ctx) {
   ctx->evChunkIdx = ctx->evChunkFill = ctx->evPoolUsed = 0;
   ctx->nHostPeaks = 0;
   drop_kept(ctx);   // (the switch itself stays: gx_set_count_in_peaks)
+  drop_coverage(ctx);   // (... and gx_set_coverage_bins')
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -414,6 +418,8 @@ int gx_sample_end(gx_ctx* ctx, double* frag_len, float* lambda, float* factor) {
     ctx->phase = 4;
   } else
     return GX_ERR_ORDER;
+  if (ctx->covW)
+    if (int rc = cov_sample(ctx, ctx->phase == 4)) return rc;
   if (ctx->countOn) keep_sample(ctx, ctx->phase == 4);
   if (frag_len) *frag_len = ctx->hScal.fragLen;
   if (lambda) *lambda = ctx->hScal.lambda;
@@ -821,7 +827,8 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->built.fused && ctx->built.fracPairs ? GX_PATH_FRAC_PAIRS : 0u) |
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
-           (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u);
+           (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
+           (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u);
   return GX_OK;
 }
 
@@ -878,6 +885,65 @@ int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_
   if (n) memcpy(count120, r, n * sizeof(int64_t));
   if (total120) *total120 = r[ctx->regN];
   if (in_regions120) *in_regions120 = r[ctx->regN + 1];
+  return GX_OK;
+}
+
+int gx_set_coverage_bins(gx_ctx* ctx, uint32_t bin_size) {
+  if (!ctx || ctx->nChrom == 0 || ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;   // idle, and the table is known
+  if (bin_size > COV_MAX_W) {
+    ctx->err = "coverage bins of more than 2^20 bases";
+    return GX_ERR_ORDER;
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  const u32 before = ctx->covW;
+  drop_coverage(ctx);
+  if (bin_size == before && !ctx->covDirty) return GX_OK;   // (the layout on the device is this one already)
+  ctx->covW = bin_size;
+  ctx->covDirty = true;
+  if (!bin_size) return GX_OK;
+  if (int rc = cov_layout(ctx)) {
+    ctx->covW = before;
+    ctx->covDirty = true;
+    return rc;
+  }
+  return GX_OK;
+}
+
+int gx_coverage_samples(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !n_samples) return GX_ERR_ORDER;
+  *n_samples = (int)ctx->cov.size();
+  return GX_OK;
+}
+
+int gx_coverage_layout(gx_ctx* ctx, int chrom, uint32_t* bin_size, uint32_t* len) {
+  if (!ctx || chrom < 0 || (u32)chrom >= ctx->nChrom) return GX_ERR_ORDER;
+  if (bin_size) *bin_size = ctx->covW;
+  if (len) *len = ctx->len[chrom];
+  return GX_OK;
+}
+
+int gx_coverage_bin_count(gx_ctx* ctx, int chrom, size_t* n_bins) {
+  if (!ctx || !n_bins || chrom < 0 || (u32)chrom >= ctx->nChrom) return GX_ERR_ORDER;
+  *n_bins = 0;
+  if (!ctx->covW) return GX_OK;
+  if (ctx->covDirty)
+    if (int rc = cov_layout(ctx)) return rc;
+  *n_bins = ctx->covOff[chrom + 1] - ctx->covOff[chrom];
+  return GX_OK;
+}
+
+int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, int64_t* sum120, size_t cap) {
+  if (!ctx || ctx->phase == 1 || ctx->phase == 3 || sample < 0 || (size_t)sample >= ctx->cov.size() || chrom < 0 ||
+      (u32)chrom >= ctx->nChrom || (cap && !sum120))
+    return GX_ERR_ORDER;
+  const gx_ctx::CovSample& c = ctx->cov[sample];
+  if (rep) *rep = c.rep;
+  if (is_ctrl) *is_ctrl = c.ctrl ? 1 : 0;
+  const size_t n = std::min(cap, ctx->covOff[chrom + 1] - ctx->covOff[chrom]);
+  if (!n) return GX_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  HIPCHECK(hipMemcpyAsync(sum120, c.bins.as<int64_t>() + ctx->covOff[chrom], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(hipStreamSynchronize(ctx->stream));
   return GX_OK;
 }
 

@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f) and the pileup log (-k).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k) and the binned coverage tracks (--coverage).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -180,6 +180,60 @@ int gx_write_pile(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, c
   return gx_write_pile_group(&ctx, nullptr, rep, names, n_chrom, expt_name, ctrl_name, out);
 }
 
+// --coverage: bedGraph lines of one chromosome's bins.  Adjacent bins with exactly equal means (cross-multiplied in 128 bits:
+// the chromosome's last bin may be short) share a line; a line's value is its sum over its bases.
+int gx_format_coverage(FILE* out, const char* chrom_name, uint32_t len, uint32_t bin_size, const int64_t* sum120, size_t n_bins,
+                       double scale) {
+  if (!out || !chrom_name || !bin_size || (n_bins && !sum120)) return GX_ERR_ORDER;
+  if (n_bins != ((size_t)len + bin_size - 1) / bin_size) return GX_ERR_ORDER;
+  size_t a = 0;
+  while (a < n_bins) {
+    const uint64_t start = (uint64_t)a * bin_size;
+    const uint64_t firstBases = std::min<uint64_t>(start + bin_size, len) - start;
+    __int128 sum = sum120[a];
+    uint64_t bases = firstBases;
+    size_t b = a + 1;
+    for (; b < n_bins; b++) {
+      const uint64_t s0 = (uint64_t)b * bin_size, nb = std::min<uint64_t>(s0 + bin_size, len) - s0;
+      if ((__int128)sum120[a] * (__int128)nb != (__int128)sum120[b] * (__int128)firstBases) break;
+      sum += sum120[b];
+      bases += nb;
+    }
+    const __int128 unit = (__int128)120 * (__int128)bases;
+    if (scale == 1.0 && sum % unit == 0)
+      fprintf(out, "%s\t%llu\t%llu\t%lld\n", chrom_name, (unsigned long long)start, (unsigned long long)(start + bases),
+              (long long)(sum / unit));
+    else
+      fprintf(out, "%s\t%llu\t%llu\t%.4f\n", chrom_name, (unsigned long long)start, (unsigned long long)(start + bases),
+              ((double)sum / (120.0 * (double)bases)) * scale);
+    a = b;
+  }
+  return GX_OK;
+}
+
+int gx_write_coverage_group(gx_ctx* const* ctxs, const int* owner, int sample, const char* const* names, int n_chrom, double scale,
+                            FILE* out) {
+  if (!ctxs || !names || !out) return GX_ERR_ORDER;
+  std::vector<int64_t> sums;
+  for (int c = 0; c < n_chrom; c++) {
+    gx_ctx* ctx = ctxs[owner ? owner[c] : 0];
+    size_t n = 0;
+    uint32_t W = 0, len = 0;
+    int rc = gx_coverage_bin_count(ctx, c, &n);
+    if (!rc) rc = gx_coverage_layout(ctx, c, &W, &len);
+    if (rc) return rc;
+    if (!n) continue;
+    sums.assign(n, 0);
+    if ((rc = gx_get_coverage(ctx, sample, c, nullptr, nullptr, sums.data(), n))) return rc;
+    if ((rc = gx_format_coverage(out, names[c], len, W, sums.data(), n, scale))) return rc;
+  }
+  return GX_OK;
+}
+
+int gx_write_coverage(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, FILE* out) {
+  return gx_write_coverage_group(&ctx, nullptr, sample, names, n_chrom, scale, out);
+}
+
 // -f after gx_find_peaks.  n_rep = number of replicates; peaks_opt = 0 for -X (logIntervals 837).
 // thr / qval_opt as given to gx_create.
 int gx_write_log_group(gx_ctx* const* ctxs, const int* owner, int n_rep, const char* const* names, int n_chrom, int qval_opt,
@@ -277,6 +331,13 @@ int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chr
   FILE* f = fopen(path, append ? "a" : "w");
   if (!f) return GX_ERR_ORDER;
   int rc = gx_write_pile(ctx, rep, names, n_chrom, expt_name, ctrl_name, f);
+  fclose(f);
+  return rc;
+}
+int gx_write_coverage_path(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, const char* path) {
+  FILE* f = fopen(path, "w");
+  if (!f) return GX_ERR_ORDER;
+  int rc = gx_write_coverage(ctx, sample, names, n_chrom, scale, f);
   fclose(f);
   return rc;
 }

@@ -27,6 +27,7 @@
 #include "gx_saturate.h"
 #include "gx_count.h"
 #include "gx_regions.h"
+#include "gx_coverage.h"
 
 using namespace gx;
 
@@ -407,6 +408,17 @@ struct gx_ctx {
   DevBuf regIn, regIdx, regHist, regSums, regRes, regInv;
   PinnedBuf regStage, regHost;
   bool regLdsSet = false;
+  // binned coverage (gx_set_coverage_bins, gx_coverage.h): every closed sample's pileup summed over bins of covW bases
+  struct CovSample {
+    int rep = 0;
+    bool ctrl = false;
+    DevBuf bins;                  // int64 per bin, chromosome c's from covOff[c] on
+  };
+  u32 covW = 0;                   // 0: off
+  bool covDirty = true;           // the chromosome table changed since covOff was laid out
+  std::vector<size_t> covOff;     // [nChrom + 1] first bin of each chromosome (one without bins here: as many as the next)
+  DevBuf covChromBin;             // ... for the device (u32)
+  std::vector<CovSample> cov;     // until gx_reset
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

@@ -148,7 +148,11 @@ struct Opts {
   const char *inFile = nullptr, *ctrlFile = nullptr, *outFile = nullptr, *logFile = nullptr, *pileFile = nullptr,
              *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
              *countsFile = nullptr,  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
-             *regionsBed = nullptr, *regionCountsFile = nullptr;  // --count-regions BED --region-counts FILE: ... in given regions
+             *regionsBed = nullptr, *regionCountsFile = nullptr,  // --count-regions BED --region-counts FILE: ... in given regions
+             *coveragePrefix = nullptr;  // --coverage PREFIX: a binned bedGraph track per sample (no Genrich counterpart)
+  int binSize = 50;             // --bin-size
+  double coverageScale = 1.0;   // --coverage-scale
+  bool binSizeOpt = false, coverageScaleOpt = false;
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2590,6 +2594,48 @@ void writeRegionCounts(State& S, const std::vector<std::string>& tFiles, const s
   }
 }
 
+// --coverage PREFIX: each sample's pileup in bins, one bedGraph file per sample -- PREFIX.t<rep>.bedgraph for a treatment,
+// PREFIX.c<rep>.bedgraph for a control that was read (.gz behind it with -z); with -v the mean of each track
+void writeCoverage(State& S, const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  const int nChrom = (int)names.size();
+  int nS = 0;
+  for (gx_ctx* g : S.devs.ctx) {
+    int n = 0;
+    check(S, gx_coverage_samples(g, &n), g);
+    if (g != S.devs.ctx[0] && n != nS) die("", "--coverage: the devices closed different numbers of samples");
+    nS = n;
+  }
+  std::vector<int64_t> sums;
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    check(S, gx_get_coverage(S.devs.ctx[0], i, 0, &rep, &ctrl, nullptr, 0), S.devs.ctx[0]);
+    const std::string path = std::string(o.coveragePrefix) + (ctrl ? ".c" : ".t") + std::to_string(rep) + ".bedgraph" + (o.gzOut ? ".gz" : "");
+    Out out = openWrite(path.c_str(), o.gzOut);
+    check(S, gx_write_coverage_group(S.devs.ctx.data(), S.devs.owner.data(), i, names.data(), nChrom, o.coverageScale, out.f));
+    closeOut(out);
+    if (!o.verbose) continue;
+    double total = 0.0;   // (sum120 / 120 over the chromosomes written)
+    unsigned long long bp = 0;
+    for (int c = 0; c < nChrom; c++) {
+      gx_ctx* g = S.devs.ctx[S.devs.owner[c]];
+      size_t n = 0;
+      uint32_t len = 0;
+      check(S, gx_coverage_bin_count(g, c, &n), g);
+      if (!n) continue;
+      check(S, gx_coverage_layout(g, c, nullptr, &len), g);
+      sums.assign(n, 0);
+      check(S, gx_get_coverage(g, i, c, nullptr, nullptr, sums.data(), n), g);
+      __int128 sum = 0;
+      for (int64_t v : sums) sum += v;
+      total += (double)sum / 120.0;
+      bp += len;
+    }
+    fprintf(stderr, "  Coverage, %s file #%d: mean %f over %llu bp\n", ctrl ? "control" : "experimental", rep,
+            bp ? total / (double)bp : 0.0, bp);
+  }
+}
+
 void usage() {
   fprintf(stderr,
           "Usage: genrich-amd  -t <file>  -o <file>  [optional arguments]\n"
@@ -2597,7 +2643,9 @@ void usage() {
           "   -r -R -p -q -a -l -g -X -P -S -L -v -V)\n"
           "  --device N | --devices 0-7   GPU(s) to use;  --threads N   BGZF inflate threads\n"
           "  --counts FILE   each sample's intervals counted in the called peaks\n"
-          "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n");
+          "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n"
+          "  --coverage PREFIX [--bin-size N] [--coverage-scale X]   each sample's pileup in bins of N bases (50):\n"
+          "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n");
   exit(EXIT_FAILURE);
 }
 
@@ -2616,6 +2664,9 @@ int main(int argc, char** argv) {
                                      {"counts", required_argument, nullptr, 1004},
                                      {"count-regions", required_argument, nullptr, 1005},
                                      {"region-counts", required_argument, nullptr, 1006},
+                                     {"coverage", required_argument, nullptr, 1007},
+                                     {"bin-size", required_argument, nullptr, 1008},
+                                     {"coverage-scale", required_argument, nullptr, 1009},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2661,6 +2712,15 @@ int main(int argc, char** argv) {
       case 1004: o.countsFile = optarg; break;
       case 1005: o.regionsBed = optarg; break;
       case 1006: o.regionCountsFile = optarg; break;
+      case 1007: o.coveragePrefix = optarg; break;
+      case 1008: o.binSize = getInt(optarg); o.binSizeOpt = true; break;
+      case 1009: {  // (a double: the track's values are computed in doubles)
+        char* end;
+        o.coverageScale = strtod(optarg, &end);
+        if (end == optarg || *end != '\0') die(optarg, ": cannot convert to float");
+        o.coverageScaleOpt = true;
+        break;
+      }
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2686,6 +2746,10 @@ int main(int argc, char** argv) {
   if ((o.regionsBed != nullptr) != (o.regionCountsFile != nullptr)) die("", "--count-regions BED and --region-counts FILE need each other");
   // (the regions count the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.regionsBed && (o.peaksOnly || o.eventsOnly)) die("", "--count-regions needs the intervals of this run (not with -P or --events-only)");
+  // (the tracks are made of the pileups this run builds: none with -P or --events-only; -X is fine)
+  if (o.coveragePrefix && (o.peaksOnly || o.eventsOnly)) die("", "--coverage needs the pileups of this run (not with -P or --events-only)");
+  if ((o.binSizeOpt || o.coverageScaleOpt) && !o.coveragePrefix) die("", "--bin-size and --coverage-scale need --coverage PREFIX");
+  if (o.coveragePrefix && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
   if (o.avgExtOpt) { o.singleOpt = true; o.extendOpt = false; }
   if (o.extendOpt) {
     o.singleOpt = true;
@@ -2801,6 +2865,8 @@ int main(int argc, char** argv) {
     if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") scanHeader(S, cFiles[r].c_str(), true);
   }
   sendChroms(S);
+  if (o.coveragePrefix)
+    for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
   for (size_t r = 0; r < tFiles.size(); r++) {
     for (auto& ch : S.chrom) ch.save = false;
     const char* ctrlName = !o.ctrlFile ? nullptr : (r < cFiles.size() ? cFiles[r].c_str() : nullptr);
@@ -2921,6 +2987,7 @@ int main(int argc, char** argv) {
   }
   if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
+  if (o.coveragePrefix) writeCoverage(S, names);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);
     check(S, gx_write_log_group(S.devs.ctx.data(), S.devs.owner.data(), S.sample, names.data(), nChrom, o.qvalOpt, o.peaksOpt, thr,

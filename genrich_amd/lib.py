@@ -62,6 +62,17 @@ class RegionCounts(NamedTuple):
     is_ctrl: bool
 
 
+GX_PATH_COVERAGE = 262144   # gx_path_info bit 18: the run summed its samples' pileups over bins (gx_set_coverage_bins)
+
+
+class Coverage(NamedTuple):
+    """One sample's binned coverage on one chromosome (gx_get_coverage): sum120[b] = the pileup summed over the bases of bin b,
+    in 1/120 units."""
+    sum120: np.ndarray
+    rep: int
+    is_ctrl: bool
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
 
@@ -135,6 +146,15 @@ _SIGS = {
     "gx_write_counts_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts_path": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p],
+    "gx_set_coverage_bins": [C.c_void_p, C.c_uint32],
+    "gx_coverage_samples": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_coverage_bin_count": [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)],
+    "gx_coverage_layout": [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "gx_get_coverage": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t],
+    "gx_format_coverage": [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_double],
+    "gx_write_coverage_group": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p],
+    "gx_write_coverage": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p],
+    "gx_write_coverage_path": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_char_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -177,6 +197,32 @@ def filter_saturation(events, lens):
     if rc < 0:
         raise RuntimeError(f"gx_filter_saturation: {rc}")
     return keep, int(rc)
+
+
+def format_coverage(chrom_name, length, bin_size, sum120, scale=1.0) -> bytes:
+    """--coverage's bedGraph lines of one chromosome's bins (gx_format_coverage); host-only, needs no GPU."""
+    lib = load_library()
+    libc = C.CDLL(None)
+    libc.tmpfile.restype = C.c_void_p
+    libc.fclose.argtypes = [C.c_void_p]
+    libc.fflush.argtypes = [C.c_void_p]
+    libc.fileno.argtypes = [C.c_void_p]
+    a = np.ascontiguousarray(sum120, dtype=np.int64)
+    f = libc.tmpfile()
+    if not f:
+        raise RuntimeError("tmpfile failed")
+    try:
+        rc = lib.gx_format_coverage(f, chrom_name.encode(), int(length), int(bin_size), a.ctypes.data if a.size else None, a.size,
+                                    float(scale))
+        if rc:
+            raise RuntimeError(f"gx_format_coverage: {rc}")
+        libc.fflush(f)
+        fd = os.dup(libc.fileno(f))
+    finally:
+        libc.fclose(f)
+    with os.fdopen(fd, "rb") as g:
+        g.seek(0)
+        return g.read()
 
 
 def rccl_unique_id() -> bytes:
@@ -407,7 +453,8 @@ class Genrich:
         """Which device path the last calls took: GX_PATH_* bits (1 fused tile stage, 2 loose-slot sweep, 4 fell back, 8 page tables grew,
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
-        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set)."""
+        where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
+        262144 pileups summed over coverage bins)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -468,6 +515,33 @@ class Genrich:
             rn = (C.c_char_p * max(1, len(region_names)))(*[None if x is None else x.encode() for x in region_names])
         self._check(self.lib.gx_write_region_counts_path(self.ctx, self._names(names), reg.ctypes.data if reg.size else None, rn, reg.size,
                                                          len(sample_names), self._names(sample_names), path.encode()))
+
+    # -- binned coverage tracks (include/genrich_amd.h, gx_set_coverage_bins) ------------------------------------------
+    def set_coverage_bins(self, bin_size):
+        """Sum every closed sample's pileup over bins of bin_size bases (0: off); only while idle, after set_chroms."""
+        self._check(self.lib.gx_set_coverage_bins(self.ctx, int(bin_size)))
+
+    def coverage_samples(self):
+        n = C.c_int(0)
+        self._check(self.lib.gx_coverage_samples(self.ctx, C.byref(n)))
+        return n.value
+
+    def coverage_bin_count(self, chrom):
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_coverage_bin_count(self.ctx, int(chrom), C.byref(n)))
+        return n.value
+
+    def coverage(self, sample, chrom):
+        """Coverage(sum120 int64[n_bins], rep, is_ctrl) of one closed sample on one chromosome."""
+        out = np.zeros(self.coverage_bin_count(chrom), dtype=np.int64)
+        rep, ctrl = C.c_int(0), C.c_int(0)
+        self._check(self.lib.gx_get_coverage(self.ctx, int(sample), int(chrom), C.byref(rep), C.byref(ctrl),
+                                             out.ctypes.data if out.size else None, out.size))
+        return Coverage(out, rep.value, bool(ctrl.value))
+
+    def write_coverage(self, sample, names, path, scale=1.0):
+        """--coverage's bedGraph (gx_write_coverage) of one sample of this context."""
+        self._check(self.lib.gx_write_coverage_path(self.ctx, int(sample), self._names(names), len(names), float(scale), path.encode()))
 
     def rccl_nranks(self):
         """Ranks of the library's own RCCL communicator as RCCL reports them (0: none)."""

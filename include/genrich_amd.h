@@ -18,6 +18,7 @@
  *     gx_pvalues
  *   gx_find_peaks -> gx_get_peaks / gx_get_intervals
  *   (counting on: gx_count_in_peaks -> gx_get_peak_counts / gx_write_counts)
+ *   (coverage on, any time after a gx_sample_end: gx_get_coverage / gx_write_coverage)
  *   gx_destroy
  */
 #ifndef GENRICH_AMD_H
@@ -273,6 +274,35 @@ int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_
 int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
                          int64_t* in_regions120);
 
+/* ---- binned coverage tracks per sample (no Genrich counterpart: -k, printPile Genrich.c:1697-1715, prints a replicate's pileups
+ *      per run-length interval, the control's already scaled and floored; a track wants each sample's own pileup in bins) ----
+ * A sample = every gx_sample_end of the run, in call order, as for gx_count_in_peaks: for replicate r its treatment, then its
+ * control when one was read; gx_sample_no_control is none.  Its pileup at a base, in 1/120 units (gx_math.h), is what its
+ * run-length pileup holds there: the `experimental` column of -k for a treatment (printPile 1697); the control file's own
+ * pileup, before factor and lambda, for a control; 0 inside -E regions (-k prints 0.000000 there) and on a chromosome the
+ * replicate's treatment header does not list (save[c] == 0) -- after the int16 rule's drops and after every rebuild, because
+ * it is read from the pileup the run uses.  With bin size W, chromosome c has ceil(len / W) bins, bin b covers
+ * [b W, min((b + 1) W, len)), and sum120[b] is the sum of the pileup over its bases, an exact int64.  Chromosomes that are
+ * skipped (-e), empty or not owned by this context (gx_set_owned) have no bins on this context.
+ *
+ * gx_set_coverage_bins: bin_size 0 = off (default).  Only while idle (after gx_create / gx_reset, before the first
+ *   gx_sample_begin) and after gx_set_chroms, else GX_ERR_ORDER; bin_size > 2^20, or more than 2^30 bins in total:
+ *   GX_ERR_ORDER.  Survives gx_reset, like gx_set_count_in_peaks.  On, every gx_sample_end runs one more kernel (k_cov_bins,
+ *   gx_coverage.h) over the pileup it has just closed and keeps one int64 per bin in device memory until gx_reset (a failed
+ *   allocation: GX_ERR_MEM); off, a run launches and allocates nothing for it.
+ * gx_coverage_samples: samples closed since the last gx_reset.
+ * gx_coverage_bin_count: bins of one chromosome; 0 for a chromosome this context does not compute.
+ * gx_coverage_layout: the bin size in effect and the chromosome's length as given to gx_set_chroms (what a formatter needs
+ *   besides the sums; either pointer may be NULL).
+ * gx_get_coverage: min(cap, n_bins) sums of one sample (0 .. n_samples-1) on one chromosome, its replicate and whether it is a
+ *   control (any pointer may be NULL; sum120 when cap is 0).  No sample open, else GX_ERR_ORDER, as for a bad index; it needs
+ *   no gx_pvalues and no gx_find_peaks. */
+int gx_set_coverage_bins(gx_ctx* ctx, uint32_t bin_size);
+int gx_coverage_samples(gx_ctx* ctx, int* n_samples);
+int gx_coverage_bin_count(gx_ctx* ctx, int chrom, size_t* n_bins);
+int gx_coverage_layout(gx_ctx* ctx, int chrom, uint32_t* bin_size, uint32_t* len);
+int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, int64_t* sum120, size_t cap);
+
 /* ---- host-side text emitters of the drop-in surface (gx_emit.cpp); byte format of the
  *      reference's printf calls.  names[i] = chromosome names in table order. ---- */
 #include <stdio.h>
@@ -314,6 +344,21 @@ int gx_write_region_counts(gx_ctx* ctx, const char* const* names, const gx_regio
                            size_t n, int n_samples, const char* const* sample_names, FILE* out);
 int gx_write_region_counts_path(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
                                 size_t n, int n_samples, const char* const* sample_names, const char* path);
+/* --coverage (no Genrich counterpart; printPile 1697 is what -k prints instead): bedGraph without a header line.
+ * gx_format_coverage: host only, no context.  One chromosome's bins (n_bins = ceil(len / bin_size) sums in 1/120 units) as lines
+ * "chrom\tstart\tend\tvalue\n" that tile [0, len) with no gap and no overlap, zero runs included.  Adjacent bins are merged
+ * into one line iff their means are exactly equal (sum_a * bases_b == sum_b * bases_a, compared in 128-bit integers).  The
+ * value of a line over `bases` bases with the sum `sum`: when scale == 1.0 and sum % (120 * bases) == 0 the integer
+ * sum / (120 * bases) with %lld, otherwise %.4f of ((double)sum / (120.0 * (double)bases)) * scale, evaluated in that order.
+ * n_bins != ceil(len / bin_size), bin_size == 0 or a missing pointer: GX_ERR_ORDER, nothing written.
+ * gx_write_coverage: one sample (gx_get_coverage's index) over the chromosomes in table order, those without bins left out;
+ * _group: owner[c] = index into ctxs of the context that computed chromosome c (NULL: ctxs[0]), as gx_write_pile_group. */
+int gx_format_coverage(FILE* out, const char* chrom_name, uint32_t len, uint32_t bin_size, const int64_t* sum120,
+                       size_t n_bins, double scale);
+int gx_write_coverage_group(gx_ctx* const* ctxs, const int* owner, int sample, const char* const* names, int n_chrom,
+                            double scale, FILE* out);
+int gx_write_coverage(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, FILE* out);
+int gx_write_coverage_path(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, const char* path);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -365,7 +410,7 @@ int gx_set_keep_pileups(gx_ctx* ctx, int keep);
  * --kernel-trace run attributes every kernel to its phase (tools/make_counters_json.py; host-side markers, no stream
  * bubble; the roctx library is opened at run time and its absence is not an error). */
 int gx_set_phase_timing(gx_ctx* ctx, int level);
-/* Like level 1, for another phase: only the phases called `name` ("sort1", "tile", "bucket" -- per sample, reported
+/* Like level 1, for another phase: only the phases called `name` ("sort1", "tile", "bucket", "cover" -- per sample, reported
  * as "t.<name>" / "c.<name>" --, "pval", "merge", "fisher", "bh", "sweep") are bracketed by events.  bench.py times
  * the phase of its roofline kernel this way inside the timed region. */
 int gx_set_phase_filter(gx_ctx* ctx, const char* name);
@@ -402,6 +447,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_MERGE_P 1024u /* bit 10: the last control merge scored its intervals itself and left (end, p) in its loose slots (k_merge2<.., true> + k_pack_ep2) */
 #define GX_PATH_COUNTS 65536u /* bit 16: this run kept its samples' intervals for counting (gx_set_count_in_peaks) */
 #define GX_PATH_REGION_COUNTS 131072u /* bit 17: gx_count_in_regions has counted the kept samples in a region set since the last gx_reset */
+#define GX_PATH_COVERAGE 262144u /* bit 18: this run summed its samples' pileups over bins (gx_set_coverage_bins; a sample was closed since the last gx_reset) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
