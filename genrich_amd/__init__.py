@@ -8,3 +8,4 @@ HIP library is missing.
 from .lib import GxParams, Genrich, EVENT_DTYPE, PEAK_DTYPE, GX_PATH_COUNTS, PeakCounts, load_library, minus_log10f  # noqa: F401
 from .lib import GX_PATH_REGION_COUNTS, REGION_DTYPE, RegionCounts  # noqa: F401
 from .lib import GX_PATH_COVERAGE, Coverage, format_coverage  # noqa: F401
+from .lib import GX_PATH_PROFILE, ANCHOR_DTYPE, Profile, format_profile, format_profile_rows  # noqa: F401

@@ -10,6 +10,7 @@
 #include "gx_host_count.h"
 #include "gx_host_regions.h"
 #include "gx_host_coverage.h"
+#include "gx_host_profile.h"
 
 
 // ================================ C ABI ==================================================
@@ -150,6 +151,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
     }
   }
   ctx->covDirty = true;
+  ctx->profDirty = true;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -218,6 +220,7 @@ int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   if (ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;  // the tile space changes: between runs only
   ctx->owned.assign(owned, owned + ctx->nChrom);
   ctx->covDirty = true;
+  ctx->profDirty = true;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -249,6 +252,7 @@ int gx_reset(gx_ctx* ctx) {
   ctx->nHostPeaks = 0;
   drop_kept(ctx);   // (the switch itself stays: gx_set_count_in_peaks)
   drop_coverage(ctx);   // (... and gx_set_coverage_bins')
+  drop_profile(ctx);    // (... and gx_set_profile's)
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -420,6 +424,8 @@ int gx_sample_end(gx_ctx* ctx, double* frag_len, float* lambda, float* factor) {
     return GX_ERR_ORDER;
   if (ctx->covW)
     if (int rc = cov_sample(ctx, ctx->phase == 4)) return rc;
+  if (!ctx->profAnchors.empty())
+    if (int rc = prof_sample(ctx, ctx->phase == 4)) return rc;
   if (ctx->countOn) keep_sample(ctx, ctx->phase == 4);
   if (frag_len) *frag_len = ctx->hScal.fragLen;
   if (lambda) *lambda = ctx->hScal.lambda;
@@ -828,7 +834,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
-           (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u);
+           (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u);
   return GX_OK;
 }
 
@@ -944,6 +950,113 @@ int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, 
   HIPCHECK(hipSetDevice(ctx->device));
   HIPCHECK(hipMemcpyAsync(sum120, c.bins.as<int64_t>() + ctx->covOff[chrom], n * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(hipStreamSynchronize(ctx->stream));
+  return GX_OK;
+}
+
+int gx_set_profile(gx_ctx* ctx, const gx_anchor* anchors, size_t n, uint32_t flank, uint32_t bin_size, int keep_matrix) {
+  if (!ctx || ctx->nChrom == 0 || ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;   // idle, and the table is known
+  if (n == 0) {   // off
+    drop_profile(ctx);
+    ctx->profAnchors.clear();
+    ctx->profF = ctx->profB = ctx->profNb = 0;
+    ctx->profKeep = false;
+    return GX_OK;
+  }
+  const char* why = nullptr;
+  if (!anchors) why = "no anchors";
+  else if (bin_size == 0) why = "profile bins of 0 bases";
+  else if (flank == 0 || flank > PROF_MAX_F) why = "a profile flank outside [1, 2^20]";
+  else if (flank % bin_size != 0) why = "the profile's flank is no multiple of its bin size";
+  else if (2 * flank / bin_size > PROF_MAX_NB) why = "more than 1024 profile bins";
+  else if (n > 0xFFFFFFFFull) why = "more than 2^32 - 1 anchors";
+  else if (keep_matrix && (u64)n * (2 * flank / bin_size) > PROF_MAX_CELLS) why = "a profile matrix of more than 2^26 cells";
+  for (size_t i = 0; !why && i < n; i++)
+    if (anchors[i].strand != 1 && anchors[i].strand != -1) why = "an anchor's strand is neither +1 nor -1";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  drop_profile(ctx);
+  ctx->profAnchors.assign(anchors, anchors + n);   // (a copy: the caller's array may go away)
+  ctx->profF = flank;
+  ctx->profB = bin_size;
+  ctx->profNb = 2 * flank / bin_size;
+  ctx->profKeep = keep_matrix != 0;
+  ctx->profDirty = true;
+  return prof_layout(ctx);
+}
+
+int gx_profile_samples(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !n_samples) return GX_ERR_ORDER;
+  *n_samples = (int)ctx->prof.size();
+  return GX_OK;
+}
+
+int gx_profile_layout(gx_ctx* ctx, size_t* n_anchors, uint32_t* n_bins, uint32_t* flank, uint32_t* bin_size, int* has_matrix) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (n_anchors) *n_anchors = ctx->profAnchors.size();
+  if (n_bins) *n_bins = ctx->profNb;
+  if (flank) *flank = ctx->profF;
+  if (bin_size) *bin_size = ctx->profB;
+  if (has_matrix) *has_matrix = ctx->profKeep ? 1 : 0;
+  return GX_OK;
+}
+
+int gx_get_profile(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* agg120, int64_t* cell120, size_t first_anchor,
+                   size_t n_rows) {
+  if (!ctx || ctx->phase == 1 || ctx->phase == 3 || sample < 0 || (size_t)sample >= ctx->prof.size()) return GX_ERR_ORDER;
+  const gx_ctx::ProfSample& p = ctx->prof[sample];
+  const size_t nA = ctx->profAnchors.size(), nb = ctx->profNb;
+  if (cell120 && (!p.cells.p || first_anchor > nA || n_rows > nA - first_anchor)) return GX_ERR_ORDER;
+  if (rep) *rep = p.rep;
+  if (is_ctrl) *is_ctrl = p.ctrl ? 1 : 0;
+  if (!agg120 && !(cell120 && n_rows)) return GX_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (agg120) HIPCHECK(hipMemcpyAsync(agg120, p.agg.p, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (cell120 && n_rows)
+    HIPCHECK(hipMemcpyAsync(cell120, p.cells.as<int64_t>() + first_anchor * nb, n_rows * nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHECK(hipStreamSynchronize(ctx->stream));
+  return GX_OK;
+}
+
+// The writers over contexts live here, not in gx_emit.cpp: that file links on its own, against the entries its stand-alone
+// test programs define.
+int gx_write_profile_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, size_t n_anchors_counted,
+                           FILE* out) {
+  if (!ctxs || n_ctx < 1 || !out || n_samples < 0 || (n_samples && !sample_names)) return GX_ERR_ORDER;
+  uint32_t nb = 0, F = 0, B = 0;
+  if (int rc = gx_profile_layout(ctxs[0], nullptr, &nb, &F, &B, nullptr)) return rc;
+  std::vector<int64_t> agg((size_t)n_samples * nb, 0), one(nb);
+  for (int g = 0; g < n_ctx; g++)
+    for (int smp = 0; smp < n_samples; smp++) {
+      if (int rc = gx_get_profile(ctxs[g], smp, nullptr, nullptr, one.data(), nullptr, 0, 0)) return rc;
+      for (uint32_t j = 0; j < nb; j++) agg[(size_t)smp * nb + j] += one[j];
+    }
+  std::vector<const int64_t*> rows((size_t)n_samples);
+  for (int smp = 0; smp < n_samples; smp++) rows[smp] = agg.data() + (size_t)smp * nb;
+  return gx_format_profile(out, n_samples, sample_names, rows.data(), n_anchors_counted, nb, F, B);
+}
+
+int gx_write_profile_rows_group(gx_ctx* const* ctxs, int n_ctx, int sample, const char* const* names, const gx_region* regions,
+                                const char* const* row_names, const gx_anchor* anchors, FILE* out) {
+  if (!ctxs || n_ctx < 1 || !out) return GX_ERR_ORDER;
+  size_t nA = 0;
+  uint32_t nb = 0, B = 0;
+  if (int rc = gx_profile_layout(ctxs[0], &nA, &nb, nullptr, &B, nullptr)) return rc;
+  if (!nb) return GX_ERR_ORDER;
+  const size_t chunk = std::max<size_t>(1, (1u << 20) / nb);   // (8 MiB of cells at a time)
+  std::vector<int64_t> sum, one;
+  for (size_t first = 0; first < nA; first += chunk) {
+    const size_t rows = std::min(chunk, nA - first);
+    sum.assign(rows * nb, 0);
+    one.resize(rows * nb);
+    for (int g = 0; g < n_ctx; g++) {
+      if (int rc = gx_get_profile(ctxs[g], sample, nullptr, nullptr, nullptr, one.data(), first, rows)) return rc;
+      for (size_t k = 0; k < rows * nb; k++) sum[k] += one[k];
+    }
+    if (int rc = gx_format_profile_rows(out, names, regions, row_names, anchors, first, rows, nb, B, sum.data())) return rc;
+  }
   return GX_OK;
 }
 

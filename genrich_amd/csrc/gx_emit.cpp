@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k) and the binned coverage tracks (--coverage).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage) and the profile tables (--profile).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -232,6 +232,47 @@ int gx_write_coverage_group(gx_ctx* const* ctxs, const int* owner, int sample, c
 
 int gx_write_coverage(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, FILE* out) {
   return gx_write_coverage_group(&ctx, nullptr, sample, names, n_chrom, scale, out);
+}
+
+// --profile: the aggregate table, one column per sample
+int gx_format_profile(FILE* out, int n_samples, const char* const* sample_names, const int64_t* const* agg120, size_t n_anchors_counted,
+                      uint32_t n_bins, uint32_t flank, uint32_t bin_size) {
+  if (!out || n_samples < 0 || (n_samples && (!sample_names || !agg120)) || !n_bins || !bin_size) return GX_ERR_ORDER;
+  for (int smp = 0; smp < n_samples; smp++)
+    if (!sample_names[smp] || !agg120[smp]) return GX_ERR_ORDER;
+  fprintf(out, "offset");
+  for (int smp = 0; smp < n_samples; smp++) fprintf(out, "\t%s", sample_names[smp]);
+  fprintf(out, "\n");
+  for (uint32_t j = 0; j < n_bins; j++) {
+    fprintf(out, "%lld", (long long)j * (long long)bin_size - (long long)flank);
+    for (int smp = 0; smp < n_samples; smp++)
+      fprintf(out, "\t%.6f", n_anchors_counted ? (double)agg120[smp][j] / (120.0 * bin_size * n_anchors_counted) : 0.0);
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// ... and rows of a sample's matrix, one per anchor (--coverage's value rule over bin_size bases)
+int gx_format_profile_rows(FILE* out, const char* const* names, const gx_region* regions, const char* const* row_names,
+                           const gx_anchor* anchors, size_t first, size_t n_rows, uint32_t n_bins, uint32_t bin_size,
+                           const int64_t* cell120) {
+  if (!out || !n_bins || !bin_size || (n_rows && (!names || !regions || !anchors || !cell120))) return GX_ERR_ORDER;
+  const long long unit = 120ll * (long long)bin_size;
+  for (size_t i = 0; i < n_rows; i++) {
+    const size_t a = first + i;
+    const gx_region& r = regions[a];
+    fprintf(out, "%s\t%u\t%u\t", names[r.chrom], r.start, r.end);
+    if (row_names && row_names[a]) fprintf(out, "%s", row_names[a]);
+    else fprintf(out, "anchor_%zu", a);
+    fprintf(out, "\t%c", anchors[a].strand < 0 ? '-' : '+');
+    const int64_t* row = cell120 + i * (size_t)n_bins;
+    for (uint32_t j = 0; j < n_bins; j++) {
+      if (row[j] % unit == 0) fprintf(out, "\t%lld", (long long)(row[j] / unit));
+      else fprintf(out, "\t%.4f", (double)row[j] / (120.0 * (double)bin_size));
+    }
+    fprintf(out, "\n");
+  }
+  return GX_OK;
 }
 
 // -f after gx_find_peaks.  n_rep = number of replicates; peaks_opt = 0 for -X (logIntervals 837).

@@ -28,6 +28,7 @@
 #include "gx_count.h"
 #include "gx_regions.h"
 #include "gx_coverage.h"
+#include "gx_profile.h"
 
 using namespace gx;
 
@@ -419,6 +420,20 @@ struct gx_ctx {
   std::vector<size_t> covOff;     // [nChrom + 1] first bin of each chromosome (one without bins here: as many as the next)
   DevBuf covChromBin;             // ... for the device (u32)
   std::vector<CovSample> cov;     // until gx_reset
+  // profiles around anchors (gx_set_profile, gx_profile.h): every closed sample's pileup summed over windows around them
+  struct ProfSample {
+    int rep = 0;
+    bool ctrl = false;
+    DevBuf agg;                   // int64 per bin
+    DevBuf cells;                 // int64 per anchor and bin, in the caller's anchor order (profKeep)
+  };
+  std::vector<gx_anchor> profAnchors;   // empty: off
+  u32 profF = 0, profB = 0, profNb = 0;
+  bool profKeep = false;
+  bool profDirty = true;          // the chromosome table changed since profDev was made
+  DevBuf profDev;                 // ProfAnchor per anchor
+  DevBuf profPartial;             // k_profile's workgroups' sums
+  std::vector<ProfSample> prof;   // until gx_reset
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

@@ -149,7 +149,10 @@ struct Opts {
              *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
              *countsFile = nullptr,  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
              *regionsBed = nullptr, *regionCountsFile = nullptr,  // --count-regions BED --region-counts FILE: ... in given regions
-             *coveragePrefix = nullptr;  // --coverage PREFIX: a binned bedGraph track per sample (no Genrich counterpart)
+             *coveragePrefix = nullptr,  // --coverage PREFIX: a binned bedGraph track per sample (no Genrich counterpart)
+             *profileBed = nullptr, *profilePrefix = nullptr;  // --profile BED --profile-out PREFIX: signal around anchor sites
+  int flank = 2000, profileBin = 10;   // --flank, --profile-bin
+  bool flankOpt = false, profileBinOpt = false, profileAtOpt = false, profileCenter = false, profileMatrix = false;
   int binSize = 50;             // --bin-size
   double coverageScale = 1.0;   // --coverage-scale
   bool binSizeOpt = false, coverageScaleOpt = false;
@@ -245,6 +248,8 @@ struct State {
   std::vector<std::string> xchr;
   std::vector<BedRec> xbed;
   std::vector<RegionRow> regions;   // --count-regions, in the BED's order
+  std::vector<RegionRow> anchorRows;   // --profile, in the BED's order ...
+  std::vector<int> anchorStrand;       // ... and each line's strand, +1 / -1
   gx_ctx* gx = nullptr;      // the (first) device context; nullptr with --events-only
   Devs devs;                 // all of them
   bool tableFrozen = false;  // the device already holds the chromosome table
@@ -2525,7 +2530,8 @@ void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::ve
 // --count-regions BED --region-counts FILE: the same intervals counted in the BED's regions, which may overlap and come in any
 // order; exactly one output row per BED line, in the BED's order, so that the files of two runs line up.  The BED is read with
 // -E's rules (loadBED); a 4th column names the row, further columns are ignored (a narrowPeak file is valid input).
-void loadRegions(State& S, const char* fn) {
+// (--profile reads its BED by the same rules; there column 6 gives the strand: + and - as given, . or no column 6 means +)
+void loadRegionRows(const char* fn, std::vector<RegionRow>& rows, std::vector<int>* strands) {
   std::vector<char> line(65520);
   In in;
   openRead(in, fn);
@@ -2544,11 +2550,20 @@ void loadRegions(State& S, const char* fn) {
       die(msg, ": poorly formatted BED record");
     }
     const char* rn = strtok(nullptr, "\t\n");
-    S.regions.push_back(RegionRow{name, rn ? rn : "", (uint32_t)p0, (uint32_t)p1, rn != nullptr});
+    rows.push_back(RegionRow{name, rn ? rn : "", (uint32_t)p0, (uint32_t)p1, rn != nullptr});
+    if (!strands) continue;
+    const char* st = rn && strtok(nullptr, "\t\n") ? strtok(nullptr, "\t\n") : nullptr;   // (behind the score)
+    if (st && strcmp(st, "+") && strcmp(st, "-") && strcmp(st, ".")) {
+      char msg[512];
+      snprintf(msg, sizeof msg, "%s, %d - %d, strand %s", rows.back().chrom.c_str(), p0, p1, st);
+      die(msg, ": poorly formatted BED record");
+    }
+    strands->push_back(st && st[0] == '-' ? -1 : 1);
   }
   checkIn(in);
   in.close();
 }
+void loadRegions(State& S, const char* fn) { loadRegionRows(fn, S.regions, nullptr); }
 void writeRegionCounts(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles,
                        const std::vector<const char*>& names) {
   const Opts& o = S.o;
@@ -2636,6 +2651,90 @@ void writeCoverage(State& S, const std::vector<const char*>& names) {
   }
 }
 
+// --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
+// every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
+// offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
+// row per BED line, in the BED's order; with -v the enrichment of each sample
+struct ProfilePlan {
+  std::vector<const char*> allNames;   // the table's names, then those of chromosomes that no header names
+  std::vector<gx_anchor> anchors;
+  std::vector<gx_region> regions;
+  std::vector<const char*> rowNames;
+  size_t counted = 0;                  // anchors on chromosomes the run computes: known, not -e skipped, not empty
+};
+ProfilePlan planProfile(State& S) {
+  ProfilePlan P;
+  std::unordered_map<std::string, uint32_t> idx;
+  for (size_t c = 0; c < S.chrom.size(); c++) {
+    P.allNames.push_back(S.chrom[c].name.c_str());
+    idx.emplace(S.chrom[c].name, (uint32_t)c);
+  }
+  const size_t n = S.anchorRows.size();
+  P.anchors.resize(n);
+  P.regions.resize(n);
+  P.rowNames.resize(n);
+  for (size_t k = 0; k < n; k++) {
+    const RegionRow& r = S.anchorRows[k];
+    auto it = idx.find(r.chrom);
+    if (it == idx.end()) {   // (an index behind the table: the library's row is zero)
+      it = idx.emplace(r.chrom, (uint32_t)P.allNames.size()).first;
+      P.allNames.push_back(r.chrom.c_str());
+    }
+    const int strand = S.anchorStrand[k];
+    const uint32_t pos = S.o.profileCenter ? (uint32_t)(((uint64_t)r.start + r.end) / 2) : strand > 0 ? r.start : r.end - 1;
+    P.anchors[k] = gx_anchor{it->second, pos, strand};
+    P.regions[k] = gx_region{it->second, r.start, r.end};
+    P.rowNames[k] = r.named ? r.name.c_str() : nullptr;
+    if (it->second < S.chrom.size() && !S.chrom[it->second].skip && S.chrom[it->second].len != 0) P.counted++;
+  }
+  return P;
+}
+void writeProfile(State& S, const ProfilePlan& P, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles) {
+  const Opts& o = S.o;
+  const std::vector<const char*> sampleNames = sampleNamesOf(S, tFiles, cFiles);
+  const int nS = (int)sampleNames.size();
+  for (gx_ctx* g : S.devs.ctx) {
+    int n = 0;
+    check(S, gx_profile_samples(g, &n), g);
+    if (n != nS) die("", "--profile: the library closed another number of samples than were read");
+  }
+  {
+    const std::string path = std::string(o.profilePrefix) + ".profile.tsv";
+    Out out = openWrite(path.c_str(), o.gzOut);
+    check(S, gx_write_profile_group(S.devs.ctx.data(), (int)S.devs.n(), nS, sampleNames.data(), P.counted, out.f));
+    closeOut(out);
+  }
+  const uint32_t nb = (uint32_t)(2 * o.flank / o.profileBin);
+  std::vector<int64_t> agg(nb), one(nb);
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    std::fill(agg.begin(), agg.end(), 0);
+    for (gx_ctx* g : S.devs.ctx) {
+      check(S, gx_get_profile(g, i, &rep, &ctrl, one.data(), nullptr, 0, 0), g);
+      for (uint32_t j = 0; j < nb; j++) agg[j] += one[j];
+    }
+    if (o.profileMatrix) {
+      const std::string path = std::string(o.profilePrefix) + (ctrl ? ".c" : ".t") + std::to_string(rep) + ".matrix.tsv";
+      Out out = openWrite(path.c_str(), o.gzOut);
+      check(S, gx_write_profile_rows_group(S.devs.ctx.data(), (int)S.devs.n(), i, P.allNames.data(), P.regions.data(), P.rowNames.data(),
+                                           P.anchors.data(), out.f));
+      closeOut(out);
+    }
+    if (!o.verbose) continue;
+    // the highest bin over the mean of the first and the last ne bins (100 bases at each end, at least one bin, at most a
+    // quarter of the bins): with the defaults ENCODE's TSS-enrichment construction, unsmoothed
+    const uint32_t ne = std::max(1u, std::min(nb / 4, (uint32_t)((100 + o.profileBin - 1) / o.profileBin)));
+    __int128 edge = 0;
+    int64_t top = agg[0];
+    for (uint32_t j = 0; j < nb; j++) {
+      top = std::max(top, agg[j]);
+      if (j < ne || j >= nb - ne) edge += agg[j];
+    }
+    fprintf(stderr, "  Profile, %s file #%d: enrichment %f over %zu anchors\n", ctrl ? "control" : "experimental", rep,
+            edge ? (double)top * (2.0 * ne) / (double)edge : 0.0, P.counted);
+  }
+}
+
 void usage() {
   fprintf(stderr,
           "Usage: genrich-amd  -t <file>  -o <file>  [optional arguments]\n"
@@ -2645,7 +2744,13 @@ void usage() {
           "  --counts FILE   each sample's intervals counted in the called peaks\n"
           "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n"
           "  --coverage PREFIX [--bin-size N] [--coverage-scale X]   each sample's pileup in bins of N bases (50):\n"
-          "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n");
+          "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n"
+          "  --profile BED --profile-out PREFIX [--flank N] [--profile-bin N] [--profile-at tss|center] [--profile-matrix]\n"
+          "                  each sample's pileup around the BED's sites, N (2000) bases to either side in bins of N (10) bases,\n"
+          "                  oriented by column 6: PREFIX.profile.tsv, the mean per base and site at every offset; a site is the\n"
+          "                  line's 5' end (tss) or its middle (center); --profile-matrix: one row per site and sample in\n"
+          "                  PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv; -v: the highest bin over the mean of the 100\n"
+          "                  bases at either end -- with the defaults ENCODE's TSS enrichment, unsmoothed\n");
   exit(EXIT_FAILURE);
 }
 
@@ -2667,6 +2772,12 @@ int main(int argc, char** argv) {
                                      {"coverage", required_argument, nullptr, 1007},
                                      {"bin-size", required_argument, nullptr, 1008},
                                      {"coverage-scale", required_argument, nullptr, 1009},
+                                     {"profile", required_argument, nullptr, 1010},
+                                     {"profile-out", required_argument, nullptr, 1011},
+                                     {"flank", required_argument, nullptr, 1012},
+                                     {"profile-bin", required_argument, nullptr, 1013},
+                                     {"profile-at", required_argument, nullptr, 1014},
+                                     {"profile-matrix", no_argument, nullptr, 1015},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2721,6 +2832,16 @@ int main(int argc, char** argv) {
         o.coverageScaleOpt = true;
         break;
       }
+      case 1010: o.profileBed = optarg; break;
+      case 1011: o.profilePrefix = optarg; break;
+      case 1012: o.flank = getInt(optarg); o.flankOpt = true; break;
+      case 1013: o.profileBin = getInt(optarg); o.profileBinOpt = true; break;
+      case 1014:
+        if (strcmp(optarg, "tss") && strcmp(optarg, "center")) die(optarg, ": --profile-at takes tss or center");
+        o.profileCenter = !strcmp(optarg, "center");
+        o.profileAtOpt = true;
+        break;
+      case 1015: o.profileMatrix = true; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2750,6 +2871,17 @@ int main(int argc, char** argv) {
   if (o.coveragePrefix && (o.peaksOnly || o.eventsOnly)) die("", "--coverage needs the pileups of this run (not with -P or --events-only)");
   if ((o.binSizeOpt || o.coverageScaleOpt) && !o.coveragePrefix) die("", "--bin-size and --coverage-scale need --coverage PREFIX");
   if (o.coveragePrefix && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
+  if ((o.profileBed != nullptr) != (o.profilePrefix != nullptr)) die("", "--profile BED and --profile-out PREFIX need each other");
+  if ((o.flankOpt || o.profileBinOpt || o.profileAtOpt || o.profileMatrix) && !o.profileBed)
+    die("", "--flank, --profile-bin, --profile-at and --profile-matrix need --profile BED");
+  // (the profiles are made of the pileups this run builds: none with -P or --events-only; -X is fine)
+  if (o.profileBed && (o.peaksOnly || o.eventsOnly)) die("", "--profile needs the pileups of this run (not with -P or --events-only)");
+  if (o.profileBed) {   // (the library's limits: gx_set_profile)
+    if (o.profileBin < 1) die("", "--profile: --profile-bin must be at least 1");
+    if (o.flank < 1 || o.flank > (1 << 20)) die("", "--profile: --flank must be in [1, 1048576]");
+    if (o.flank % o.profileBin) die("", "--profile: --flank must be a multiple of --profile-bin");
+    if (2 * o.flank / o.profileBin > 1024) die("", "--profile: at most 1024 bins (2 * flank / profile-bin)");
+  }
   if (o.avgExtOpt) { o.singleOpt = true; o.extendOpt = false; }
   if (o.extendOpt) {
     o.singleOpt = true;
@@ -2796,6 +2928,12 @@ int main(int argc, char** argv) {
 
   if (o.xFile) loadBED(S, o.xFile);
   if (o.regionsBed) loadRegions(S, o.regionsBed);
+  if (o.profileBed && !o.peaksOnly) {
+    loadRegionRows(o.profileBed, S.anchorRows, &S.anchorStrand);
+    if (S.anchorRows.empty()) die(o.profileBed, ": --profile: no anchors");
+    if (o.profileMatrix && S.anchorRows.size() * (size_t)(2 * o.flank / o.profileBin) > ((size_t)1 << 26))
+      die("", "--profile-matrix: more than 2^26 cells (BED lines times bins)");
+  }
   if (o.peaksOnly) {  // runProgram 5398-5403
     peaksOnly(S, thr);
     return EXIT_SUCCESS;
@@ -2867,6 +3005,13 @@ int main(int argc, char** argv) {
   sendChroms(S);
   if (o.coveragePrefix)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
+  ProfilePlan profilePlan;
+  if (o.profileBed) {
+    profilePlan = planProfile(S);
+    for (gx_ctx* g : S.devs.ctx)
+      check(S, gx_set_profile(g, profilePlan.anchors.data(), profilePlan.anchors.size(), (uint32_t)o.flank, (uint32_t)o.profileBin,
+                              o.profileMatrix), g);
+  }
   for (size_t r = 0; r < tFiles.size(); r++) {
     for (auto& ch : S.chrom) ch.save = false;
     const char* ctrlName = !o.ctrlFile ? nullptr : (r < cFiles.size() ? cFiles[r].c_str() : nullptr);
@@ -2988,6 +3133,7 @@ int main(int argc, char** argv) {
   if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.coveragePrefix) writeCoverage(S, names);
+  if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);
     check(S, gx_write_log_group(S.devs.ctx.data(), S.devs.owner.data(), S.sample, names.data(), nChrom, o.qvalOpt, o.peaksOpt, thr,

@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -69,6 +69,19 @@ class Coverage(NamedTuple):
     """One sample's binned coverage on one chromosome (gx_get_coverage): sum120[b] = the pileup summed over the bases of bin b,
     in 1/120 units."""
     sum120: np.ndarray
+    rep: int
+    is_ctrl: bool
+
+
+GX_PATH_PROFILE = 524288    # gx_path_info bit 19: the run summed its samples' pileups around anchors (gx_set_profile)
+ANCHOR_DTYPE = np.dtype([("chrom", "<u4"), ("pos", "<u4"), ("strand", "<i4")])   # gx_anchor
+
+
+class Profile(NamedTuple):
+    """One sample's profile around the anchors (gx_get_profile): agg120[j] = the pileup summed over bin j of every anchor, in
+    1/120 units; cell120[a][j] the same per anchor, in the caller's anchor order (None when no matrix was kept or asked for)."""
+    agg120: np.ndarray
+    cell120: Optional[np.ndarray]
     rep: int
     is_ctrl: bool
 
@@ -155,6 +168,16 @@ _SIGS = {
     "gx_write_coverage_group": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p],
     "gx_write_coverage": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p],
     "gx_write_coverage_path": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_char_p],
+    "gx_set_profile": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int],
+    "gx_profile_samples": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_profile_layout": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                          C.POINTER(C.c_int)],
+    "gx_get_profile": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t],
+    "gx_format_profile": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32],
+    "gx_format_profile_rows": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                               C.c_uint32, C.c_void_p],
+    "gx_write_profile_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+    "gx_write_profile_rows_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -223,6 +246,61 @@ def format_coverage(chrom_name, length, bin_size, sum120, scale=1.0) -> bytes:
     with os.fdopen(fd, "rb") as g:
         g.seek(0)
         return g.read()
+
+
+def _to_tmpfile(call) -> bytes:
+    """What call(FILE*) writes (a host-only writer of gx_emit.cpp); raises when it returns an error."""
+    libc = C.CDLL(None)
+    libc.tmpfile.restype = C.c_void_p
+    libc.fclose.argtypes = [C.c_void_p]
+    libc.fflush.argtypes = [C.c_void_p]
+    libc.fileno.argtypes = [C.c_void_p]
+    f = libc.tmpfile()
+    if not f:
+        raise RuntimeError("tmpfile failed")
+    try:
+        rc = call(f)
+        if rc:
+            raise RuntimeError(f"writer: {rc}")
+        libc.fflush(f)
+        fd = os.dup(libc.fileno(f))
+    finally:
+        libc.fclose(f)
+    with os.fdopen(fd, "rb") as g:
+        g.seek(0)
+        return g.read()
+
+
+def _c_names(names):
+    arr = (C.c_char_p * max(len(names), 1))()
+    for i, n in enumerate(names):
+        arr[i] = None if n is None else n.encode()
+    return arr
+
+
+def format_profile(sample_names, agg120, n_anchors_counted, flank, bin_size) -> bytes:
+    """--profile's aggregate table (gx_format_profile) of the samples' aggregates agg120[s]; host-only, needs no GPU."""
+    lib = load_library()
+    rows = [np.ascontiguousarray(a, dtype=np.int64) for a in agg120]
+    n_bins = len(rows[0]) if rows else 2 * int(flank) // max(int(bin_size), 1)
+    ptrs = (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows])
+    names = _c_names(list(sample_names))
+    return _to_tmpfile(lambda f: lib.gx_format_profile(f, len(rows), names, ptrs, int(n_anchors_counted), int(n_bins), int(flank),
+                                                       int(bin_size)))
+
+
+def format_profile_rows(names, regions, row_names, anchors, first, cell120, bin_size) -> bytes:
+    """--profile-matrix's rows (gx_format_profile_rows): regions (REGION_DTYPE), row_names (None: anchor_N) and anchors
+    (ANCHOR_DTYPE) are indexed by anchor, cell120 holds the rows first .. first + len(cell120) - 1; host-only."""
+    lib = load_library()
+    reg = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+    anc = np.ascontiguousarray(anchors, dtype=ANCHOR_DTYPE)
+    cells = np.ascontiguousarray(cell120, dtype=np.int64)
+    n_rows, n_bins = cells.shape
+    cn = _c_names(list(names))
+    rn = _c_names(list(row_names)) if row_names is not None else None
+    return _to_tmpfile(lambda f: lib.gx_format_profile_rows(f, cn, reg.ctypes.data, rn, anc.ctypes.data, int(first), n_rows, n_bins,
+                                                            int(bin_size), cells.ctypes.data))
 
 
 def rccl_unique_id() -> bytes:
@@ -454,7 +532,7 @@ class Genrich:
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
-        262144 pileups summed over coverage bins)."""
+        262144 pileups summed over coverage bins, 524288 pileups summed around anchors)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -542,6 +620,39 @@ class Genrich:
     def write_coverage(self, sample, names, path, scale=1.0):
         """--coverage's bedGraph (gx_write_coverage) of one sample of this context."""
         self._check(self.lib.gx_write_coverage_path(self.ctx, int(sample), self._names(names), len(names), float(scale), path.encode()))
+
+    # -- profiles around anchors (include/genrich_amd.h, gx_set_profile) -------------------------------------------------
+    def set_profile(self, anchors, flank, bin_size, keep_matrix=False):
+        """Sum every closed sample's pileup over 2 * flank / bin_size bins around the anchors (ANCHOR_DTYPE; none: off); only
+        while idle, after set_chroms."""
+        a = np.ascontiguousarray(anchors, dtype=ANCHOR_DTYPE)
+        self._check(self.lib.gx_set_profile(self.ctx, a.ctypes.data if a.size else None, a.size, int(flank), int(bin_size),
+                                            int(bool(keep_matrix))))
+
+    def profile_samples(self):
+        n = C.c_int(0)
+        self._check(self.lib.gx_profile_samples(self.ctx, C.byref(n)))
+        return n.value
+
+    def profile_layout(self):
+        """(n_anchors, n_bins, flank, bin_size, has_matrix) as given to set_profile; zeros while off."""
+        n, nb, f, b, m = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+        self._check(self.lib.gx_profile_layout(self.ctx, C.byref(n), C.byref(nb), C.byref(f), C.byref(b), C.byref(m)))
+        return n.value, nb.value, f.value, b.value, bool(m.value)
+
+    def profile(self, sample, rows=None):
+        """Profile(agg120 int64[n_bins], cell120 int64[n_rows, n_bins] | None, rep, is_ctrl) of one closed sample; rows = None:
+        the whole matrix when one was kept, else (first_anchor, n_rows)."""
+        n, nb, _, _, has = self.profile_layout()
+        agg = np.zeros(nb, dtype=np.int64)
+        if rows is None:
+            rows = (0, n) if has else None
+        cells = np.zeros((rows[1], nb), dtype=np.int64) if rows is not None else None
+        rep, ctrl = C.c_int(0), C.c_int(0)
+        self._check(self.lib.gx_get_profile(self.ctx, int(sample), C.byref(rep), C.byref(ctrl), agg.ctypes.data,
+                                            cells.ctypes.data if cells is not None else None, rows[0] if rows else 0,
+                                            rows[1] if rows else 0))
+        return Profile(agg, cells, rep.value, bool(ctrl.value))
 
     def rccl_nranks(self):
         """Ranks of the library's own RCCL communicator as RCCL reports them (0: none)."""

@@ -19,6 +19,7 @@
  *   gx_find_peaks -> gx_get_peaks / gx_get_intervals
  *   (counting on: gx_count_in_peaks -> gx_get_peak_counts / gx_write_counts)
  *   (coverage on, any time after a gx_sample_end: gx_get_coverage / gx_write_coverage)
+ *   (profile on, any time after a gx_sample_end: gx_get_profile / gx_write_profile_group)
  *   gx_destroy
  */
 #ifndef GENRICH_AMD_H
@@ -303,6 +304,45 @@ int gx_coverage_bin_count(gx_ctx* ctx, int chrom, size_t* n_bins);
 int gx_coverage_layout(gx_ctx* ctx, int chrom, uint32_t* bin_size, uint32_t* len);
 int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, int64_t* sum120, size_t cap);
 
+/* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
+ *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
+ *      start sites is the TSS-enrichment curve) ----
+ * An anchor is (chrom, pos, strand), strand +1 or -1.  With the flank F and the bin size B (B >= 1, F % B == 0) an anchor has
+ * nb = 2 F / B bins (nb <= 1024).  Bin j (0 <= j < nb) covers these bases x of the anchor's chromosome:
+ *     strand +:  pos - F + j B       <= x <  pos - F + (j + 1) B
+ *     strand -:  pos + F - (j + 1) B <  x <= pos + F - j B            (the mirror image)
+ * so that on both strands the anchor base is the first base, in reading direction, of bin nb / 2.
+ * cell120[a][j] is the sum over the bases of bin j of anchor a of the sample's pileup there, in 1/120 units, an exact int64.
+ * The pileup is the one gx_get_coverage integrates: a treatment's `experimental` pileup; a control's own raw pileup, before
+ * factor and lambda; 0 inside -E regions.  Bases x < 0 or x >= len count 0.  A row is all zeros when the anchor's chromosome is
+ * skipped (-e), empty or not owned by this context (gx_set_owned), when the replicate's save mask leaves it out, or when its
+ * index lies behind the table (chrom >= nChrom); an anchor with pos >= len on a known chromosome is legal and covers whatever
+ * part of its window is inside.  agg120[j] is the sum of cell120[a][j] over all anchors.  Everything is an integer: a result
+ * does not depend on the grid, on the order of the adds or on the number of contexts, and a host adds the contexts' rows and
+ * aggregates as it does for region counts.  A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.
+ *
+ * gx_set_profile: n == 0 = off (default).  Only while idle (after gx_create / gx_reset, before the first gx_sample_begin) and
+ *   after gx_set_chroms, else GX_ERR_ORDER; also GX_ERR_ORDER: bin_size == 0, flank == 0 or flank > 2^20,
+ *   flank % bin_size != 0, nb > 1024, a strand other than +1 / -1, with keep_matrix more than 2^26 cells (n * nb).  The anchors
+ *   are copied.  Survives gx_reset, like gx_set_coverage_bins.  On, every gx_sample_end runs k_profile and k_profile_sum
+ *   (gx_profile.h) over the pileup it has just closed and keeps nb int64 -- with keep_matrix n * nb more -- in device memory
+ *   until gx_reset (a failed allocation: GX_ERR_MEM); off, a run launches and allocates nothing for it.
+ * gx_profile_samples: samples closed with the profile on since the last gx_reset.
+ * gx_profile_layout: what gx_set_profile was given (any pointer may be NULL); all zero while off.
+ * gx_get_profile: one sample's (0 .. n_samples-1) replicate, whether it is a control, its aggregate (n_bins values, or NULL) and
+ *   n_rows rows of its matrix from first_anchor on, in the caller's anchor order (n_rows * n_bins values, or NULL).  Rows when no
+ *   matrix was kept, rows beyond the anchors, a bad index or a sample still open: GX_ERR_ORDER.  It needs no gx_pvalues and no
+ *   gx_find_peaks. */
+typedef struct {
+  uint32_t chrom, pos;
+  int32_t strand;
+} gx_anchor;
+int gx_set_profile(gx_ctx* ctx, const gx_anchor* anchors, size_t n, uint32_t flank, uint32_t bin_size, int keep_matrix);
+int gx_profile_samples(gx_ctx* ctx, int* n_samples);
+int gx_profile_layout(gx_ctx* ctx, size_t* n_anchors, uint32_t* n_bins, uint32_t* flank, uint32_t* bin_size, int* has_matrix);
+int gx_get_profile(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* agg120, int64_t* cell120, size_t first_anchor,
+                   size_t n_rows);
+
 /* ---- host-side text emitters of the drop-in surface (gx_emit.cpp); byte format of the
  *      reference's printf calls.  names[i] = chromosome names in table order. ---- */
 #include <stdio.h>
@@ -359,6 +399,26 @@ int gx_write_coverage_group(gx_ctx* const* ctxs, const int* owner, int sample, c
                             double scale, FILE* out);
 int gx_write_coverage(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, FILE* out);
 int gx_write_coverage_path(gx_ctx* ctx, int sample, const char* const* names, int n_chrom, double scale, const char* path);
+/* --profile (no Genrich counterpart).  gx_format_profile and gx_format_profile_rows: host only, no context.
+ * gx_format_profile: the aggregate table -- "offset" and one column per sample, then n_bins rows: the bin's first offset
+ * -flank + j bin_size, then per sample %.6f of (double)agg120[s][j] / (120.0 * bin_size * n_anchors_counted), evaluated in that
+ * order (0.000000 when n_anchors_counted is 0).  n_anchors_counted is the caller's: the anchors on chromosomes the run computes.
+ * gx_format_profile_rows: n_rows matrix rows, anchors first .. first + n_rows - 1 (regions, row_names and anchors are indexed by
+ * anchor, cell120 by row): "chrom\tstart\tend\tname\tstrand" of the anchor's BED line -- names[regions[a].chrom], the name
+ * "anchor_<a>" where row_names or row_names[a] is NULL, the strand "+" or "-" -- then n_bins values: the integer
+ * cell / (120 bin_size) with %lld when it is one, else %.4f of (double)cell / (120.0 * bin_size).
+ * A missing pointer, n_bins == 0 or bin_size == 0: GX_ERR_ORDER, nothing written.
+ * _group (gx_api.hip: they read contexts): the contexts' aggregates / rows added, as gx_write_region_counts_group adds counts;
+ * the layout is ctxs[0]'s. */
+int gx_format_profile(FILE* out, int n_samples, const char* const* sample_names, const int64_t* const* agg120,
+                      size_t n_anchors_counted, uint32_t n_bins, uint32_t flank, uint32_t bin_size);
+int gx_format_profile_rows(FILE* out, const char* const* names, const gx_region* regions, const char* const* row_names,
+                           const gx_anchor* anchors, size_t first, size_t n_rows, uint32_t n_bins, uint32_t bin_size,
+                           const int64_t* cell120);
+int gx_write_profile_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names,
+                           size_t n_anchors_counted, FILE* out);
+int gx_write_profile_rows_group(gx_ctx* const* ctxs, int n_ctx, int sample, const char* const* names, const gx_region* regions,
+                                const char* const* row_names, const gx_anchor* anchors, FILE* out);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -410,7 +470,7 @@ int gx_set_keep_pileups(gx_ctx* ctx, int keep);
  * --kernel-trace run attributes every kernel to its phase (tools/make_counters_json.py; host-side markers, no stream
  * bubble; the roctx library is opened at run time and its absence is not an error). */
 int gx_set_phase_timing(gx_ctx* ctx, int level);
-/* Like level 1, for another phase: only the phases called `name` ("sort1", "tile", "bucket", "cover" -- per sample, reported
+/* Like level 1, for another phase: only the phases called `name` ("sort1", "tile", "bucket", "cover", "profile" -- per sample, reported
  * as "t.<name>" / "c.<name>" --, "pval", "merge", "fisher", "bh", "sweep") are bracketed by events.  bench.py times
  * the phase of its roofline kernel this way inside the timed region. */
 int gx_set_phase_filter(gx_ctx* ctx, const char* name);
@@ -448,6 +508,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_COUNTS 65536u /* bit 16: this run kept its samples' intervals for counting (gx_set_count_in_peaks) */
 #define GX_PATH_REGION_COUNTS 131072u /* bit 17: gx_count_in_regions has counted the kept samples in a region set since the last gx_reset */
 #define GX_PATH_COVERAGE 262144u /* bit 18: this run summed its samples' pileups over bins (gx_set_coverage_bins; a sample was closed since the last gx_reset) */
+#define GX_PATH_PROFILE 524288u /* bit 19: this run summed its samples' pileups around anchors (gx_set_profile; a sample was closed with it on since the last gx_reset) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
