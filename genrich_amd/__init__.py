@@ -9,3 +9,4 @@ from .lib import GxParams, Genrich, EVENT_DTYPE, PEAK_DTYPE, GX_PATH_COUNTS, Pea
 from .lib import GX_PATH_REGION_COUNTS, REGION_DTYPE, RegionCounts  # noqa: F401
 from .lib import GX_PATH_COVERAGE, Coverage, format_coverage  # noqa: F401
 from .lib import GX_PATH_PROFILE, ANCHOR_DTYPE, Profile, format_profile, format_profile_rows  # noqa: F401
+from .lib import GX_PATH_GRAM, U128_DTYPE, correlation_matrix, format_correlation, gram_geometry  # noqa: F401

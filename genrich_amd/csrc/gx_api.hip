@@ -11,6 +11,7 @@
 #include "gx_host_regions.h"
 #include "gx_host_coverage.h"
 #include "gx_host_profile.h"
+#include "gx_host_gram.h"
 
 
 // ================================ C ABI ==================================================
@@ -253,6 +254,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_kept(ctx);   // (the switch itself stays: gx_set_count_in_peaks)
   drop_coverage(ctx);   // (... and gx_set_coverage_bins')
   drop_profile(ctx);    // (... and gx_set_profile's)
+  ctx->gramUsed = false;
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -834,7 +836,8 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
-           (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u);
+           (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
+           (ctx->gramUsed ? GX_PATH_GRAM : 0u);
   return GX_OK;
 }
 
@@ -1058,6 +1061,112 @@ int gx_write_profile_rows_group(gx_ctx* const* ctxs, int n_ctx, int sample, cons
     if (int rc = gx_format_profile_rows(out, names, regions, row_names, anchors, first, rows, nb, B, sum.data())) return rc;
   }
   return GX_OK;
+}
+
+int gx_coverage_gram(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram, int cap) {
+  if (!ctx || !ctx->covW || ctx->cov.empty() || ctx->phase == 1 || ctx->phase == 3) return GX_ERR_ORDER;
+  const size_t S = ctx->cov.size();
+  const char* why = nullptr;
+  if (S > GRAM_MAX_S) why = "more than 32 samples for the correlation";
+  else if ((sum || gram) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_gram: cap is smaller than the number of samples";
+  if (!why && ctx->covDirty)
+    if (int rc = cov_layout(ctx)) return rc;
+  u64 G = 0;   // (the lengths are u32, a table has fewer than 2^31 entries: no overflow)
+  for (u32 c = 0; c < ctx->nChrom; c++)
+    if (cov_has_bins(ctx, c)) G += ctx->len[c];
+  if (!why && (u128)ctx->covW * (u128)G > ((u128)1 << 64)) why = "bin size times genome length above 2^64: the correlation's sums could overflow";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<const void*> rows(S);
+  for (size_t i = 0; i < S; i++) rows[i] = ctx->cov[i].bins.p;
+  const u64 n = ctx->covOff[ctx->nChrom];
+  u64 nz = 0;
+  std::vector<gx_u128> s1, g1;
+  if (int rc = gram_pass(ctx, rows, n, 0, &nz, s1, g1)) return rc;
+  if (n_samples) *n_samples = (int)S;
+  if (n_bins) *n_bins = n;
+  if (n_zero) *n_zero = nz;
+  if (sum) std::copy(s1.begin(), s1.end(), sum);
+  if (gram)
+    for (size_t i = 0; i < S; i++) std::copy(g1.begin() + i * S, g1.begin() + (i + 1) * S, gram + i * (size_t)cap);
+  return GX_OK;
+}
+
+int gx_gram_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* n_zero, gx_u128* sum, gx_u128* gram) {
+  if (!ctx) return GX_ERR_ORDER;
+  const char* why = nullptr;
+  if (n_rows < 1 || n_rows > (int)GRAM_MAX_S) why = "gx_gram_u64: the number of rows is outside [1, 32]";
+  else if (n > ((size_t)1 << 24)) why = "gx_gram_u64: more than 2^24 values a row";
+  else if (n && !rows) why = "gx_gram_u64: no rows";
+  else if (grid > GRAM_MAX_GRID) why = "gx_gram_u64: a grid of more than 65535 workgroups";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  for (size_t k = 0; k < (size_t)n_rows * n; k++)
+    if (rows[k] >> 51) {
+      ctx->err = "gx_gram_u64: a value of 2^51 or more";
+      return GX_ERR_ORDER;
+    }
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<const void*> dev((size_t)n_rows, nullptr);
+  if (n) {
+    if (pooled(ctx, ctx->gramIn, (size_t)n_rows * n * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "Cannot allocate memory";
+      return GX_ERR_MEM;
+    }
+    HIPCHECK(hipMemcpyAsync(ctx->gramIn.p, rows, (size_t)n_rows * n * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int r = 0; r < n_rows; r++) dev[r] = ctx->gramIn.as<uint64_t>() + (size_t)r * n;
+  }
+  u64 nz = 0;
+  std::vector<gx_u128> s1, g1;
+  if (int rc = gram_pass(ctx, dev, n, grid, &nz, s1, g1)) return rc;
+  if (n_zero) *n_zero = nz;
+  if (sum) std::copy(s1.begin(), s1.end(), sum);
+  if (gram) std::copy(g1.begin(), g1.end(), gram);
+  return GX_OK;
+}
+
+int gx_gram_geometry(int* tile, int* lanes, int* grid) {
+  if (tile) *tile = GRAM_T;
+  if (lanes) *lanes = GRAM_NW * 64;
+  if (grid) *grid = (int)GRAM_GRID;
+  return GX_OK;
+}
+
+// (the two over contexts live here, not in gx_emit.cpp, like the profile's group writers: they read contexts)
+int gx_coverage_gram_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram) {
+  if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)GRAM_MAX_S || !sum || !gram) return GX_ERR_ORDER;
+  const size_t S = (size_t)n_samples;
+  std::vector<u128> st(S, 0), gt(S * S, 0);
+  uint64_t n = 0, nz = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int s = 0;
+    uint64_t n1 = 0, nz1 = 0;
+    if (int rc = gx_coverage_gram(ctxs[g], &s, &n1, &nz1, sum, gram, n_samples)) return rc;
+    if (s != n_samples) return GX_ERR_ORDER;
+    n += n1;
+    nz += nz1;
+    for (size_t k = 0; k < S; k++) st[k] += ((u128)sum[k].hi << 64) | sum[k].lo;
+    for (size_t k = 0; k < S * S; k++) gt[k] += ((u128)gram[k].hi << 64) | gram[k].lo;
+  }
+  for (size_t k = 0; k < S; k++) sum[k] = gx_u128{(uint64_t)st[k], (uint64_t)(st[k] >> 64)};
+  for (size_t k = 0; k < S * S; k++) gram[k] = gx_u128{(uint64_t)gt[k], (uint64_t)(gt[k] >> 64)};
+  if (n_bins) *n_bins = n;
+  if (n_zero) *n_zero = nz;
+  return GX_OK;
+}
+
+int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros, FILE* out) {
+  if (!out || !sample_names || n_samples < 1 || n_samples > (int)GRAM_MAX_S) return GX_ERR_ORDER;
+  std::vector<gx_u128> s1((size_t)n_samples), g1((size_t)n_samples * n_samples);
+  uint64_t n = 0, nz = 0;
+  if (int rc = gx_coverage_gram_group(ctxs, n_ctx, n_samples, &n, &nz, s1.data(), g1.data())) return rc;
+  return gx_format_correlation(out, n_samples, sample_names, n, nz, s1.data(), g1.data(), skip_zeros);
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

@@ -1,10 +1,11 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage) and the profile tables (--profile).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile) and the correlation matrix (--correlation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
 //   printPileHeader 1680-1691              printPile      1697-1715
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -18,6 +19,57 @@ struct Iv {
   std::vector<float> expt, ctrl, p, q;
   size_t n = 0;
 };
+
+// --correlation's exact arithmetic: unsigned 256-bit integers, words least significant first
+typedef unsigned __int128 u128_t;
+struct U256 {
+  uint64_t w[4] = {0, 0, 0, 0};
+};
+U256 mul128(u128_t a, u128_t b) {   // (schoolbook over 64-bit words; the top word cannot overflow)
+  const uint64_t x[2] = {(uint64_t)a, (uint64_t)(a >> 64)}, y[2] = {(uint64_t)b, (uint64_t)(b >> 64)};
+  U256 r;
+  for (int i = 0; i < 2; i++) {
+    uint64_t carry = 0;
+    for (int j = 0; j < 2; j++) {
+      const u128_t t = (u128_t)x[i] * y[j] + r.w[i + j] + carry;
+      r.w[i + j] = (uint64_t)t;
+      carry = (uint64_t)(t >> 64);
+    }
+    r.w[i + 2] = carry;
+  }
+  return r;
+}
+int cmp256(const U256& a, const U256& b) {
+  for (int k = 3; k >= 0; k--)
+    if (a.w[k] != b.w[k]) return a.w[k] < b.w[k] ? -1 : 1;
+  return 0;
+}
+U256 sub256(const U256& a, const U256& b) {   // a >= b
+  U256 r;
+  uint64_t borrow = 0;
+  for (int k = 0; k < 4; k++) {
+    const u128_t t = (u128_t)a.w[k] - b.w[k] - borrow;
+    r.w[k] = (uint64_t)t;
+    borrow = (uint64_t)(t >> 64) & 1;
+  }
+  return r;
+}
+double to_double(const U256& a) {   // the leading 64 bits, rounded once by the conversion, scaled
+  int top = 3;
+  while (top >= 0 && !a.w[top]) top--;
+  if (top < 0) return 0.0;
+  const int lz = __builtin_clzll(a.w[top]);
+  uint64_t m = a.w[top] << lz;
+  if (lz && top > 0) m |= a.w[top - 1] >> (64 - lz);
+  return std::ldexp((double)m, 64 * top - lz);
+}
+// a - b as a double, the difference itself exact; *zero: it is 0
+double diff256(const U256& a, const U256& b, bool* zero) {
+  const int c = cmp256(a, b);
+  if (zero) *zero = c == 0;
+  if (c == 0) return 0.0;
+  return c > 0 ? to_double(sub256(a, b)) : -to_double(sub256(b, a));
+}
 
 int fetch(gx_ctx* ctx, int which, int chrom, Iv& iv, bool piles, bool qv) {
   size_t n = 0;
@@ -269,6 +321,51 @@ int gx_format_profile_rows(FILE* out, const char* const* names, const gx_region*
     for (uint32_t j = 0; j < n_bins; j++) {
       if (row[j] % unit == 0) fprintf(out, "\t%lld", (long long)(row[j] / unit));
       else fprintf(out, "\t%.4f", (double)row[j] / (120.0 * (double)bin_size));
+    }
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// --correlation: the Pearson matrix from the exact sums; NaN where there is no correlation
+int gx_correlation_matrix(int n_samples, uint64_t n, uint64_t n_zero, const gx_u128* sum, const gx_u128* gram, int skip_zeros, double* r) {
+  if (n_samples < 1 || !sum || !gram || !r || n_zero > n) return GX_ERR_ORDER;
+  const size_t S = (size_t)n_samples;
+  const uint64_t N = skip_zeros ? n - n_zero : n;
+  auto v = [](const gx_u128& x) { return ((u128_t)x.hi << 64) | x.lo; };
+  std::vector<double> var(S);
+  std::vector<char> flat(S);
+  for (size_t i = 0; i < S; i++) {
+    bool zero = false;
+    var[i] = diff256(mul128(N, v(gram[i * S + i])), mul128(v(sum[i]), v(sum[i])), &zero);
+    flat[i] = zero || N < 2;
+  }
+  for (size_t i = 0; i < S; i++)
+    for (size_t j = 0; j < S; j++) {
+      if (i == j) r[i * S + j] = 1.0;
+      else if (flat[i] || flat[j]) r[i * S + j] = std::nan("");
+      else r[i * S + j] = diff256(mul128(N, v(gram[i * S + j])), mul128(v(sum[i]), v(sum[j])), nullptr) / std::sqrt(var[i] * var[j]);
+    }
+  return GX_OK;
+}
+
+// ... and its text
+int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_names, uint64_t n, uint64_t n_zero, const gx_u128* sum,
+                          const gx_u128* gram, int skip_zeros) {
+  if (!out || n_samples < 1 || !sample_names) return GX_ERR_ORDER;
+  const size_t S = (size_t)n_samples;
+  for (size_t i = 0; i < S; i++)
+    if (!sample_names[i]) return GX_ERR_ORDER;
+  std::vector<double> r(S * S);
+  if (int rc = gx_correlation_matrix(n_samples, n, n_zero, sum, gram, skip_zeros, r.data())) return rc;
+  for (size_t j = 0; j < S; j++) fprintf(out, "\t%s", sample_names[j]);
+  fprintf(out, "\n");
+  for (size_t i = 0; i < S; i++) {
+    fprintf(out, "%s", sample_names[i]);
+    for (size_t j = 0; j < S; j++) {
+      if (i == j) fprintf(out, "\t1.000000");
+      else if (std::isnan(r[i * S + j])) fprintf(out, "\tnan");
+      else fprintf(out, "\t%.6f", r[i * S + j]);
     }
     fprintf(out, "\n");
   }

@@ -29,6 +29,7 @@
 #include "gx_regions.h"
 #include "gx_coverage.h"
 #include "gx_profile.h"
+#include "gx_gram.h"
 
 using namespace gx;
 
@@ -434,6 +435,11 @@ struct gx_ctx {
   DevBuf profDev;                 // ProfAnchor per anchor
   DevBuf profPartial;             // k_profile's workgroups' sums
   std::vector<ProfSample> prof;   // until gx_reset
+  // the samples' Gram sums (gx_coverage_gram / gx_gram_u64, gx_gram.h): nothing here exists before the first call
+  DevBuf gramRows;                // the row pointers for the device
+  DevBuf gramIn;                  // gx_gram_u64's copy of the caller's rows
+  DevBuf gramPartial, gramOut;    // k_gram's workgroups' sums, k_gram_sum's totals
+  bool gramUsed = false;          // the kernels ran since the last gx_reset
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

@@ -156,6 +156,8 @@ struct Opts {
   int binSize = 50;             // --bin-size
   double coverageScale = 1.0;   // --coverage-scale
   bool binSizeOpt = false, coverageScaleOpt = false;
+  const char* correlationFile = nullptr;   // --correlation FILE: the samples' Pearson matrix from the coverage bins
+  bool corrSkipZeros = false;              // --corr-skip-zeros
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2651,6 +2653,43 @@ void writeCoverage(State& S, const std::vector<const char*>& names) {
   }
 }
 
+// --correlation FILE: the Pearson matrix of the samples' coverage bins (all bins, or with --corr-skip-zeros those that are not
+// zero in every sample), a TSV labelled t<rep> / c<rep> like --coverage's files (.gz'd with -z); with -v the bins and the
+// least alike pair
+void writeCorrelation(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  int nS = 0;
+  check(S, gx_coverage_samples(g0, &nS), g0);
+  std::vector<std::string> labels;
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
+    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
+  }
+  std::vector<const char*> names;
+  for (const std::string& l : labels) names.push_back(l.c_str());
+  // one pass per context; the matrix is formatted, and with -v searched, from the added sums
+  std::vector<gx_u128> sum((size_t)nS), gram((size_t)nS * nS);
+  uint64_t bins = 0, zeros = 0;
+  check(S, gx_coverage_gram_group(S.devs.ctx.data(), (int)S.devs.n(), nS, &bins, &zeros, sum.data(), gram.data()), g0);
+  Out out = openWrite(o.correlationFile, o.gzOut);
+  check(S, gx_format_correlation(out.f, nS, names.data(), bins, zeros, sum.data(), gram.data(), o.corrSkipZeros ? 1 : 0), g0);
+  closeOut(out);
+  if (!o.verbose) return;
+  std::vector<double> r((size_t)nS * nS);
+  check(S, gx_correlation_matrix(nS, bins, zeros, sum.data(), gram.data(), o.corrSkipZeros ? 1 : 0, r.data()), g0);
+  int li = -1, lj = -1;
+  for (int i = 0; i < nS; i++)
+    for (int j = i + 1; j < nS; j++)
+      if (r[(size_t)i * nS + j] == r[(size_t)i * nS + j] && (li < 0 || r[(size_t)i * nS + j] < r[(size_t)li * nS + lj])) { li = i; lj = j; }
+  if (li >= 0)
+    fprintf(stderr, "  Correlation: %llu bins, %llu all zero; smallest r %f (%s, %s)\n", (unsigned long long)bins, (unsigned long long)zeros,
+            r[(size_t)li * nS + lj], names[li], names[lj]);
+  else
+    fprintf(stderr, "  Correlation: %llu bins, %llu all zero; no pair with a correlation\n", (unsigned long long)bins, (unsigned long long)zeros);
+}
+
 // --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
@@ -2745,6 +2784,8 @@ void usage() {
           "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n"
           "  --coverage PREFIX [--bin-size N] [--coverage-scale X]   each sample's pileup in bins of N bases (50):\n"
           "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n"
+          "  --correlation FILE [--corr-skip-zeros]   the samples' Pearson correlation matrix over their bins of --bin-size N (50)\n"
+          "                  bases, a TSV labelled t<rep> / c<rep>; --corr-skip-zeros leaves out the bins that are 0 in every sample\n"
           "  --profile BED --profile-out PREFIX [--flank N] [--profile-bin N] [--profile-at tss|center] [--profile-matrix]\n"
           "                  each sample's pileup around the BED's sites, N (2000) bases to either side in bins of N (10) bases,\n"
           "                  oriented by column 6: PREFIX.profile.tsv, the mean per base and site at every offset; a site is the\n"
@@ -2778,6 +2819,8 @@ int main(int argc, char** argv) {
                                      {"profile-bin", required_argument, nullptr, 1013},
                                      {"profile-at", required_argument, nullptr, 1014},
                                      {"profile-matrix", no_argument, nullptr, 1015},
+                                     {"correlation", required_argument, nullptr, 1016},
+                                     {"corr-skip-zeros", no_argument, nullptr, 1017},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2842,6 +2885,8 @@ int main(int argc, char** argv) {
         o.profileAtOpt = true;
         break;
       case 1015: o.profileMatrix = true; break;
+      case 1016: o.correlationFile = optarg; break;
+      case 1017: o.corrSkipZeros = true; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2869,8 +2914,24 @@ int main(int argc, char** argv) {
   if (o.regionsBed && (o.peaksOnly || o.eventsOnly)) die("", "--count-regions needs the intervals of this run (not with -P or --events-only)");
   // (the tracks are made of the pileups this run builds: none with -P or --events-only; -X is fine)
   if (o.coveragePrefix && (o.peaksOnly || o.eventsOnly)) die("", "--coverage needs the pileups of this run (not with -P or --events-only)");
-  if ((o.binSizeOpt || o.coverageScaleOpt) && !o.coveragePrefix) die("", "--bin-size and --coverage-scale need --coverage PREFIX");
-  if (o.coveragePrefix && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
+  // (the matrix is made of the same bins: one bin size per run)
+  if (o.correlationFile && (o.peaksOnly || o.eventsOnly)) die("", "--correlation needs the pileups of this run (not with -P or --events-only)");
+  if (o.corrSkipZeros && !o.correlationFile) die("", "--corr-skip-zeros needs --correlation FILE");
+  if (o.correlationFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
+    auto split = [](const char* list) {
+      std::vector<std::string> out;
+      std::string l(list ? list : "");
+      for (char* t = strtok(l.data(), ", "); t; t = strtok(nullptr, ", ")) out.push_back(t);
+      return out;
+    };
+    const std::vector<std::string> t = split(o.inFile), c = split(o.ctrlFile);
+    size_t n = t.size();
+    for (size_t r = 0; r < t.size() && r < c.size(); r++) n += c[r] != "null";
+    if (n > 32) die("", "--correlation takes at most 32 samples");
+  }
+  if ((o.coverageScaleOpt && !o.coveragePrefix) || (o.binSizeOpt && !o.coveragePrefix && !o.correlationFile))
+    die("", "--bin-size and --coverage-scale need --coverage PREFIX");
+  if ((o.coveragePrefix || o.correlationFile) && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
   if ((o.profileBed != nullptr) != (o.profilePrefix != nullptr)) die("", "--profile BED and --profile-out PREFIX need each other");
   if ((o.flankOpt || o.profileBinOpt || o.profileAtOpt || o.profileMatrix) && !o.profileBed)
     die("", "--flank, --profile-bin, --profile-at and --profile-matrix need --profile BED");
@@ -3003,7 +3064,7 @@ int main(int argc, char** argv) {
     if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") scanHeader(S, cFiles[r].c_str(), true);
   }
   sendChroms(S);
-  if (o.coveragePrefix)
+  if (o.coveragePrefix || o.correlationFile)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
   ProfilePlan profilePlan;
   if (o.profileBed) {
@@ -3133,6 +3194,7 @@ int main(int argc, char** argv) {
   if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.coveragePrefix) writeCoverage(S, names);
+  if (o.correlationFile) writeCorrelation(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);

@@ -86,6 +86,29 @@ class Profile(NamedTuple):
     is_ctrl: bool
 
 
+GX_PATH_GRAM = 1048576     # gx_path_info bit 20: k_gram / k_gram_sum ran (gx_coverage_gram, gx_gram_u64)
+U128_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])   # gx_u128
+
+
+def _join128(a):
+    """gx_u128 records -> an object array of Python ints of the same shape."""
+    out = np.empty(a.shape, dtype=object)
+    for k in np.ndindex(a.shape):
+        out[k] = int(a[k]["lo"]) | (int(a[k]["hi"]) << 64)
+    return out
+
+
+def _split128(values, shape):
+    out = np.zeros(shape, dtype=U128_DTYPE)
+    flat = out.reshape(-1)
+    for k, v in enumerate(np.asarray(values, dtype=object).reshape(-1)):
+        v = int(v)
+        if not 0 <= v < 1 << 128:
+            raise ValueError("not an unsigned 128-bit integer")
+        flat[k] = (v & 0xFFFFFFFFFFFFFFFF, v >> 64)
+    return out
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
 
@@ -178,6 +201,13 @@ _SIGS = {
                                C.c_uint32, C.c_void_p],
     "gx_write_profile_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
     "gx_write_profile_rows_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_coverage_gram": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int],
+    "gx_gram_u64": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
+    "gx_format_correlation": [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int],
+    "gx_write_correlation_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_gram_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "gx_correlation_matrix": [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_coverage_gram_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -301,6 +331,39 @@ def format_profile_rows(names, regions, row_names, anchors, first, cell120, bin_
     rn = _c_names(list(row_names)) if row_names is not None else None
     return _to_tmpfile(lambda f: lib.gx_format_profile_rows(f, cn, reg.ctypes.data, rn, anc.ctypes.data, int(first), n_rows, n_bins,
                                                             int(bin_size), cells.ctypes.data))
+
+
+def gram_geometry():
+    """(tile, lanes, grid) of k_gram as the library was built (gx_gram_geometry): the samples along a tile's edge, the lanes of a
+    workgroup, the most workgroups along the bin axis by default."""
+    lib = load_library()
+    t, l, g = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib.gx_gram_geometry(C.byref(t), C.byref(l), C.byref(g))
+    return t.value, l.value, g.value
+
+
+def correlation_matrix(n, n_zero, sums, gram, skip_zeros=False):
+    """The Pearson matrix as float64 [S, S] (gx_correlation_matrix), NaN where there is none; host-only."""
+    lib = load_library()
+    S = len(sums)
+    s, g = _split128(sums, (S,)), _split128(gram, (S, S))
+    r = np.zeros((S, S), dtype=np.float64)
+    rc = lib.gx_correlation_matrix(S, int(n), int(n_zero), s.ctypes.data, g.ctypes.data, int(bool(skip_zeros)), r.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_correlation_matrix: {rc}")
+    return r
+
+
+def format_correlation(sample_names, n, n_zero, sums, gram, skip_zeros=False) -> bytes:
+    """--correlation's matrix (gx_format_correlation) from the exact sums: sums[S] and gram[S][S] as Python ints; host-only,
+    needs no GPU."""
+    lib = load_library()
+    S = len(sample_names)
+    s = _split128(sums, (S,))
+    g = _split128(gram, (S, S))
+    names = _c_names(list(sample_names))
+    return _to_tmpfile(lambda f: lib.gx_format_correlation(f, S, names, int(n), int(n_zero), s.ctypes.data, g.ctypes.data,
+                                                           int(bool(skip_zeros))))
 
 
 def rccl_unique_id() -> bytes:
@@ -532,7 +595,7 @@ class Genrich:
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
-        262144 pileups summed over coverage bins, 524288 pileups summed around anchors)."""
+        262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -620,6 +683,26 @@ class Genrich:
     def write_coverage(self, sample, names, path, scale=1.0):
         """--coverage's bedGraph (gx_write_coverage) of one sample of this context."""
         self._check(self.lib.gx_write_coverage_path(self.ctx, int(sample), self._names(names), len(names), float(scale), path.encode()))
+
+    # -- correlation of the samples' bins (include/genrich_amd.h, gx_coverage_gram) --------------------------------------
+    def coverage_gram(self):
+        """(n, n_zero, sum, gram) of the samples closed since the last reset: Python ints, sum an object array [S], gram [S, S]."""
+        S = self.coverage_samples()
+        s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+        ns, n, nz = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_coverage_gram(self.ctx, C.byref(ns), C.byref(n), C.byref(nz), s.ctypes.data, g.ctypes.data, max(S, 1)))
+        return n.value, nz.value, _join128(s[:ns.value]), _join128(g[:ns.value, :ns.value])
+
+    def gram_u64(self, rows, grid=0):
+        """(n_zero, sum, gram) of the rows (uint64 [n_rows, n], every value < 2^51) by the same kernels (gx_gram_u64); grid = 0:
+        the library's geometry, else that many workgroups along the bin axis."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        n_rows, n = r.shape
+        s, g = np.zeros(max(n_rows, 1), dtype=U128_DTYPE), np.zeros((max(n_rows, 1), max(n_rows, 1)), dtype=U128_DTYPE)
+        nz = C.c_uint64(0)
+        self._check(self.lib.gx_gram_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), C.byref(nz), s.ctypes.data,
+                                         g.ctypes.data))
+        return nz.value, _join128(s[:n_rows]), _join128(g[:n_rows, :n_rows])
 
     # -- profiles around anchors (include/genrich_amd.h, gx_set_profile) -------------------------------------------------
     def set_profile(self, anchors, flank, bin_size, keep_matrix=False):

@@ -20,6 +20,7 @@
  *   (counting on: gx_count_in_peaks -> gx_get_peak_counts / gx_write_counts)
  *   (coverage on, any time after a gx_sample_end: gx_get_coverage / gx_write_coverage)
  *   (profile on, any time after a gx_sample_end: gx_get_profile / gx_write_profile_group)
+ *   (coverage on, between samples or after them: gx_coverage_gram / gx_write_correlation_group)
  *   gx_destroy
  */
 #ifndef GENRICH_AMD_H
@@ -304,6 +305,41 @@ int gx_coverage_bin_count(gx_ctx* ctx, int chrom, size_t* n_bins);
 int gx_coverage_layout(gx_ctx* ctx, int chrom, uint32_t* bin_size, uint32_t* len);
 int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, int64_t* sum120, size_t cap);
 
+/* ---- pairwise correlation of the samples from their coverage bins (no Genrich counterpart: the sums deepTools'
+ *      multiBamSummary + plotCorrelation take from a second reading of every BAM) ----
+ * Samples are 0 .. S-1, the gx_sample_end order of gx_get_coverage.  x_s[b] is sample s's sum120 of bin b over ALL bins of this
+ * context: every chromosome that has bins, in table order, the short last bin of a chromosome as it is; bins inside -E regions
+ * and of chromosomes a replicate's save mask omits are 0.  With n = the number of bins:
+ *     n_zero     = the number of bins b with x_s[b] == 0 for every s
+ *     sum[s]     = sum over b of x_s[b]
+ *     gram[i][j] = sum over b of x_i[b] x_j[b]              (symmetric; the diagonal is the sum of squares)
+ * all exact unsigned 128-bit integers (gx_u128: lo + 2^64 hi).  The bound that makes them exact: x_s[b] <= (2^31 - 1) w_b with
+ * w_b <= W the bases of the bin, so a sum of products is at most 2^62 sum w_b^2 <= 2^62 W G, G = the total length of the
+ * chromosomes that have bins; the pass is refused (GX_ERR_ORDER) when W G > 2^64, which leaves every sum below 2^126 (hg38 at the
+ * largest W = 2^20: W G = 2^52).  Leaving out the all-zero bins changes only n, to n - n_zero: they add nothing to any sum.
+ * Everything is an integer: a result does not depend on the grid or on the number of contexts, and a host adds the contexts'
+ * n, n_zero, sum and gram (with carries) as it adds region counts; gx_write_correlation_group does.
+ *
+ * gx_coverage_gram: the pass (k_gram, k_gram_sum: gx_gram.h) over the samples closed since the last gx_reset.  It needs
+ *   gx_set_coverage_bins on and at least one closed sample, else GX_ERR_ORDER; also GX_ERR_ORDER: a sample is open, more than
+ *   32 samples, the bound above broken, cap < S while sum or gram is given.  sum[cap] and gram[cap * cap] (row-major, row i at
+ *   gram + i * cap, both halves filled) may both be NULL: only the counts.  It needs no gx_pvalues and no gx_find_peaks, and may be
+ *   called again: the same answer.  A context without bins (it owns no chromosome) answers zeros.  A failed allocation:
+ *   GX_ERR_MEM.  Nothing of it is allocated or launched before the first call.
+ * gx_gram_u64: the same two kernels over n_rows rows of n values each that the caller gives (host memory, row after row; copied
+ *   to the device by this call).  Domain: every value < 2^51, n <= 2^24, 1 <= n_rows <= 32, else GX_ERR_ORDER before anything
+ *   is launched.  grid = 0: the library's geometry; else that many workgroups along the bin axis (at most 65535).  n_zero, sum[n_rows] and
+ *   gram[n_rows * n_rows] may each be NULL.  For tests and measurements: values and sizes no small pileup produces. */
+typedef struct {
+  uint64_t lo, hi;
+} gx_u128;
+int gx_coverage_gram(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram, int cap);
+int gx_gram_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* n_zero, gx_u128* sum,
+                gx_u128* gram);
+/* What gx_gram_u64's edge cases depend on: the samples along a tile's edge, the lanes of a workgroup, the most workgroups
+ * along the bin axis with grid = 0 (any pointer may be NULL). */
+int gx_gram_geometry(int* tile, int* lanes, int* grid);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -419,6 +455,24 @@ int gx_write_profile_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const 
                            size_t n_anchors_counted, FILE* out);
 int gx_write_profile_rows_group(gx_ctx* const* ctxs, int n_ctx, int sample, const char* const* names, const gx_region* regions,
                                 const char* const* row_names, const gx_anchor* anchors, FILE* out);
+/* --correlation (no Genrich counterpart).  gx_format_correlation: host only, no context.  The Pearson matrix of the sums of
+ * gx_coverage_gram (gram[n_samples * n_samples], row-major): with N = n, or n - n_zero when skip_zeros,
+ *     r_ij = (N g_ij - s_i s_j) / sqrt((N g_ii - s_i^2) (N g_jj - s_j^2)).
+ * The three differences are exact 256-bit integers (N g < 2^156, s_i s_j < 2^162: two numbers of 150 bits cancel there); only
+ * they are converted to double.  A TSV: the header line is a tab and the sample names, then per sample its name and S values
+ * %.6f; the diagonal is 1.000000; a pair with a sample of zero variance, and every pair when N < 2, is "nan".
+ * A missing pointer or n_samples < 1: GX_ERR_ORDER, nothing written.
+ * gx_correlation_matrix: the same r as doubles, r[n_samples * n_samples] row-major, NaN where the text says "nan" (host only).
+ * gx_coverage_gram_group (gx_api.hip: it reads contexts): gx_coverage_gram of every context, added with carries; sum[n_samples]
+ * and gram[n_samples * n_samples] are required.  gx_write_correlation_group: that, then gx_format_correlation. */
+int gx_correlation_matrix(int n_samples, uint64_t n, uint64_t n_zero, const gx_u128* sum, const gx_u128* gram, int skip_zeros,
+                          double* r);
+int gx_coverage_gram_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum,
+                           gx_u128* gram);
+int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_names, uint64_t n, uint64_t n_zero,
+                          const gx_u128* sum, const gx_u128* gram, int skip_zeros);
+int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros,
+                               FILE* out);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -509,6 +563,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_REGION_COUNTS 131072u /* bit 17: gx_count_in_regions has counted the kept samples in a region set since the last gx_reset */
 #define GX_PATH_COVERAGE 262144u /* bit 18: this run summed its samples' pileups over bins (gx_set_coverage_bins; a sample was closed since the last gx_reset) */
 #define GX_PATH_PROFILE 524288u /* bit 19: this run summed its samples' pileups around anchors (gx_set_profile; a sample was closed with it on since the last gx_reset) */
+#define GX_PATH_GRAM 1048576u /* bit 20: k_gram / k_gram_sum ran since the last gx_reset (gx_coverage_gram, gx_gram_u64) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
