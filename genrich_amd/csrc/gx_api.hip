@@ -12,6 +12,7 @@
 #include "gx_host_coverage.h"
 #include "gx_host_profile.h"
 #include "gx_host_gram.h"
+#include "gx_host_fingerprint.h"
 
 
 // ================================ C ABI ==================================================
@@ -255,6 +256,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_coverage(ctx);   // (... and gx_set_coverage_bins')
   drop_profile(ctx);    // (... and gx_set_profile's)
   ctx->gramUsed = false;
+  ctx->fpUsed = false;
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -837,7 +839,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
-           (ctx->gramUsed ? GX_PATH_GRAM : 0u);
+           (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u);
   return GX_OK;
 }
 
@@ -1167,6 +1169,121 @@ int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, co
   uint64_t n = 0, nz = 0;
   if (int rc = gx_coverage_gram_group(ctxs, n_ctx, n_samples, &n, &nz, s1.data(), g1.data())) return rc;
   return gx_format_correlation(out, n_samples, sample_names, n, nz, s1.data(), g1.data(), skip_zeros);
+}
+
+int gx_coverage_fingerprint(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum, int cap) {
+  if (!ctx || !ctx->covW || ctx->cov.empty() || ctx->phase == 1 || ctx->phase == 3) return GX_ERR_ORDER;
+  const size_t S = ctx->cov.size();
+  const char* why = nullptr;
+  if (S > FP_MAX_S) why = "more than 32 samples for the fingerprint";
+  else if ((count || sum) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_fingerprint: cap is smaller than the number of samples";
+  if (!why && ctx->covDirty)
+    if (int rc = cov_layout(ctx)) return rc;
+  u64 G = 0;   // (the lengths are u32, a table has fewer than 2^31 entries: no overflow)
+  for (u32 c = 0; c < ctx->nChrom; c++)
+    if (cov_has_bins(ctx, c)) G += ctx->len[c];
+  if (!why && G >= ((u64)1 << 33)) why = "a genome of 2^33 bases or more: the fingerprint's sums could overflow";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<const void*> rows(S);
+  for (size_t i = 0; i < S; i++) rows[i] = ctx->cov[i].bins.p;   // (each the start of an allocation: aligned)
+  const u64 n = ctx->covOff[ctx->nChrom];
+  std::vector<uint64_t> c1, s1;
+  if (int rc = fp_pass(ctx, rows, n, 0, c1, s1)) return rc;
+  if (n_samples) *n_samples = (int)S;
+  if (n_bins) *n_bins = n;
+  if (count) std::copy(c1.begin(), c1.end(), count);
+  if (sum) std::copy(s1.begin(), s1.end(), sum);
+  return GX_OK;
+}
+
+int gx_fp_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* count, uint64_t* sum) {
+  if (!ctx) return GX_ERR_ORDER;
+  const char* why = nullptr;
+  if (n_rows < 1 || n_rows > (int)FP_MAX_S) why = "gx_fp_u64: the number of rows is outside [1, 32]";
+  else if (n > ((size_t)1 << 24)) why = "gx_fp_u64: more than 2^24 values a row";
+  else if (n && !rows) why = "gx_fp_u64: no rows";
+  else if (grid > FP_MAX_GRID) why = "gx_fp_u64: a grid of more than 65535 workgroups";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  // the device's rows start 16 bytes apart at least: an odd n is padded by one value no lane reads.  Every row is added in
+  // 128 bits on its way into the staging copy; a total of 2^64 or more is refused before anything reaches the device
+  const size_t pitch = (n + 1) & ~(size_t)1;
+  std::vector<uint64_t> staged((size_t)n_rows * pitch, 0);
+  for (int r = 0; r < n_rows; r++) {
+    u128 t = 0;
+    for (size_t k = 0; k < n; k++) {
+      const uint64_t v = rows[(size_t)r * n + k];
+      staged[(size_t)r * pitch + k] = v;
+      t += v;
+    }
+    if (t >> 64) {
+      ctx->err = "gx_fp_u64: a row's total of 2^64 or more";
+      return GX_ERR_ORDER;
+    }
+  }
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<const void*> dev((size_t)n_rows, nullptr);
+  if (n) {
+    if (pooled(ctx, ctx->fpIn, staged.size() * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "Cannot allocate memory";
+      return GX_ERR_MEM;
+    }
+    HIPCHECK(hipMemcpyAsync(ctx->fpIn.p, staged.data(), staged.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));   // (`staged` is this call's)
+    for (int r = 0; r < n_rows; r++) dev[r] = ctx->fpIn.as<uint64_t>() + (size_t)r * pitch;
+  }
+  std::vector<uint64_t> c1, s1;
+  if (int rc = fp_pass(ctx, dev, n, grid, c1, s1)) return rc;
+  if (count) std::copy(c1.begin(), c1.end(), count);
+  if (sum) std::copy(s1.begin(), s1.end(), sum);
+  return GX_OK;
+}
+
+int gx_fp_geometry(int* n_classes, int* sub_log, int* lanes, int* grid) {
+  if (n_classes) *n_classes = FP_NC;
+  if (sub_log) *sub_log = GX_FP_SUB_LOG;
+  if (lanes) *lanes = FP_NW * 64;
+  if (grid) *grid = (int)FP_GRID;
+  return GX_OK;
+}
+
+// (the two over contexts live here, not in gx_emit.cpp, like the correlation's: they read contexts)
+int gx_coverage_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum) {
+  if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)FP_MAX_S || !count || !sum) return GX_ERR_ORDER;
+  const size_t N = (size_t)n_samples * FP_NC;
+  std::vector<uint64_t> ct(N, 0), st(N, 0);
+  uint64_t n = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int s = 0;
+    uint64_t n1 = 0;
+    if (int rc = gx_coverage_fingerprint(ctxs[g], &s, &n1, count, sum, n_samples)) return rc;
+    if (s != n_samples) return GX_ERR_ORDER;
+    n += n1;
+    for (size_t k = 0; k < N; k++) {
+      ct[k] += count[k];
+      st[k] += sum[k];
+    }
+  }
+  std::copy(ct.begin(), ct.end(), count);
+  std::copy(st.begin(), st.end(), sum);
+  if (n_bins) *n_bins = n;
+  return GX_OK;
+}
+
+int gx_write_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, const int* ctrl_of, FILE* curve,
+                               FILE* metrics) {
+  if (!curve || !sample_names || n_samples < 1 || n_samples > (int)FP_MAX_S) return GX_ERR_ORDER;
+  std::vector<uint64_t> c1((size_t)n_samples * FP_NC), s1((size_t)n_samples * FP_NC);
+  if (int rc = gx_coverage_fingerprint_group(ctxs, n_ctx, n_samples, nullptr, c1.data(), s1.data())) return rc;
+  if (int rc = gx_format_fingerprint(curve, n_samples, sample_names, c1.data(), s1.data())) return rc;
+  return metrics ? gx_format_fingerprint_metrics(metrics, n_samples, sample_names, c1.data(), s1.data(), ctrl_of) : GX_OK;
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile) and the correlation matrix (--correlation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation) and the fingerprint tables (--fingerprint).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -8,9 +8,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/genrich_amd.h"
+#include "gx_fp_class.h"
 
 namespace {
 
@@ -86,6 +88,34 @@ int fetch(gx_ctx* ctx, int which, int chrom, Iv& iv, bool piles, bool qv) {
                           piles ? iv.ctrl.data() : nullptr, iv.p.data(), qv ? iv.q.data() : nullptr);
 }
 
+// --fingerprint
+// a sample's n = sum of its counts and T = sum of its sums: 128 bits, so that histograms a caller makes up cannot wrap them
+struct FpTotals {
+  u128_t n = 0, T = 0;
+};
+FpTotals fp_totals(const uint64_t* count, const uint64_t* sum) {
+  FpTotals t;
+  for (int k = 0; k < GX_FP_NC; k++) {
+    t.n += count[k];
+    if (count[k]) t.T += sum[k];
+  }
+  return t;
+}
+std::string dec128(u128_t v) {
+  char buf[40];
+  int at = 40;
+  do {
+    buf[--at] = (char)('0' + (int)(v % 10));
+    v /= 10;
+  } while (v);
+  return std::string(buf + at, buf + 40);
+}
+// one division of two integers (long double: 64 bits of each are kept)
+long double ratio(u128_t a, u128_t b) { return (long double)a / (long double)b; }
+void put_fraction(FILE* out, double v) {
+  if (std::isnan(v)) fprintf(out, "\tnan");
+  else fprintf(out, "\t%.6f", v);
+}
 }  // namespace
 
 extern "C" {
@@ -367,6 +397,105 @@ int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_na
       else if (std::isnan(r[i * S + j])) fprintf(out, "\tnan");
       else fprintf(out, "\t%.6f", r[i * S + j]);
     }
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// --fingerprint: the value classes (gx_fp_class.h) behind the C ABI
+uint32_t gx_fp_class(uint64_t x) { return gx::fp_class(x); }
+uint64_t gx_fp_class_lo(uint32_t k) { return k < (uint32_t)GX_FP_NC ? gx::fp_class_lo(k) : 0; }
+uint64_t gx_fp_class_hi(uint32_t k) { return k < (uint32_t)GX_FP_NC ? gx::fp_class_hi(k) : 0; }
+
+// --fingerprint's figures, from the integers alone: NaN where a definition divides by 0
+int gx_fingerprint_metrics(int n_samples, const uint64_t* count, const uint64_t* sum, const int* ctrl_of, gx_fp_metrics* out) {
+  if (n_samples < 1 || !count || !sum || !out) return GX_ERR_ORDER;
+  const double nan = std::nan("");
+  for (int s = 0; s < n_samples; s++) {
+    if (ctrl_of && (ctrl_of[s] >= n_samples || ctrl_of[s] == s)) return GX_ERR_ORDER;
+    const uint64_t* c = count + (size_t)s * GX_FP_NC;
+    const uint64_t* v = sum + (size_t)s * GX_FP_NC;
+    const FpTotals t = fp_totals(c, v);
+    gx_fp_metrics m{nan, nan, nan, nan, nan, nan};
+    if (t.n) m.zero_fraction = (double)ratio(c[0], t.n);
+    if (t.n && t.T) {
+      long double auc = 0, p0 = 0, l0 = 0, best = -1;
+      u128_t C = 0, L = 0;
+      for (int k = 0; k < GX_FP_NC; k++) {
+        if (!c[k]) continue;
+        C += c[k];
+        L += v[k];
+        const long double p = ratio(C, t.n), l = ratio(L, t.T);
+        auc += (p - p0) * (l + l0) / 2;
+        if (p - l > best) {
+          best = p - l;
+          m.elbow_bins = (double)p;
+          m.elbow_gap = (double)(p - l);
+        }
+        p0 = p;
+        l0 = l;
+      }
+      m.auc = (double)auc;
+      m.gini = (double)(1 - 2 * auc);
+    }
+    const int ct = ctrl_of ? ctrl_of[s] : -1;
+    if (ct >= 0 && t.n) {
+      const uint64_t* cc = count + (size_t)ct * GX_FP_NC;
+      const FpTotals tc = fp_totals(cc, sum + (size_t)ct * GX_FP_NC);
+      if (tc.n) {
+        long double js = 0;
+        for (int k = 0; k < GX_FP_NC; k++) {
+          if (!c[k] && !cc[k]) continue;
+          const long double p = ratio(c[k], t.n), q = ratio(cc[k], tc.n), mid = (p + q) / 2;
+          if (c[k]) js += p * std::log2(p / mid) / 2;
+          if (cc[k]) js += q * std::log2(q / mid) / 2;
+        }
+        m.jsd_control = (double)std::sqrt(std::max<long double>(js, 0));
+      }
+    }
+    out[s] = m;
+  }
+  return GX_OK;
+}
+
+// ... the curve table: one row per sample and non-empty class
+int gx_format_fingerprint(FILE* out, int n_samples, const char* const* sample_names, const uint64_t* count, const uint64_t* sum) {
+  if (!out || n_samples < 1 || !sample_names || !count || !sum) return GX_ERR_ORDER;
+  for (int s = 0; s < n_samples; s++)
+    if (!sample_names[s]) return GX_ERR_ORDER;
+  fprintf(out, "sample\tlo120\thi120\tbins\tsum120\tcum_bins\tcum_signal\n");
+  for (int s = 0; s < n_samples; s++) {
+    const uint64_t* c = count + (size_t)s * GX_FP_NC;
+    const uint64_t* v = sum + (size_t)s * GX_FP_NC;
+    const FpTotals t = fp_totals(c, v);
+    u128_t C = 0, L = 0;
+    for (int k = 0; k < GX_FP_NC; k++) {
+      if (!c[k]) continue;
+      C += c[k];
+      L += v[k];
+      fprintf(out, "%s\t%llu\t%llu\t%llu\t%llu", sample_names[s], (unsigned long long)gx::fp_class_lo((uint32_t)k),
+              (unsigned long long)gx::fp_class_hi((uint32_t)k), (unsigned long long)c[k], (unsigned long long)v[k]);
+      put_fraction(out, (double)ratio(C, t.n));
+      put_fraction(out, t.T ? (double)ratio(L, t.T) : std::nan(""));
+      fprintf(out, "\n");
+    }
+  }
+  return GX_OK;
+}
+
+// ... and the figures, one row per sample
+int gx_format_fingerprint_metrics(FILE* out, int n_samples, const char* const* sample_names, const uint64_t* count, const uint64_t* sum,
+                                  const int* ctrl_of) {
+  if (!out || n_samples < 1 || !sample_names || !count || !sum) return GX_ERR_ORDER;
+  for (int s = 0; s < n_samples; s++)
+    if (!sample_names[s]) return GX_ERR_ORDER;
+  std::vector<gx_fp_metrics> m((size_t)n_samples);
+  if (int rc = gx_fingerprint_metrics(n_samples, count, sum, ctrl_of, m.data())) return rc;
+  fprintf(out, "sample\tbins\tzero_bins\tsum120\tzero_fraction\tauc\tgini\telbow_bins\telbow_gap\tjsd_control\n");
+  for (int s = 0; s < n_samples; s++) {
+    const FpTotals t = fp_totals(count + (size_t)s * GX_FP_NC, sum + (size_t)s * GX_FP_NC);
+    fprintf(out, "%s\t%s\t%llu\t%s", sample_names[s], dec128(t.n).c_str(), (unsigned long long)count[(size_t)s * GX_FP_NC], dec128(t.T).c_str());
+    for (double v : {m[s].zero_fraction, m[s].auc, m[s].gini, m[s].elbow_bins, m[s].elbow_gap, m[s].jsd_control}) put_fraction(out, v);
     fprintf(out, "\n");
   }
   return GX_OK;

@@ -30,6 +30,7 @@
 #include "gx_coverage.h"
 #include "gx_profile.h"
 #include "gx_gram.h"
+#include "gx_fingerprint.h"
 
 using namespace gx;
 
@@ -189,6 +190,7 @@ struct Knobs {
                           // many bins in a row: tests, measurements)
   int s2Grid = 0;         // GX_S2_GRID: persistent workgroups of k_sort_a (per piece) and k_sort_b (0: as many as are resident together; a small
                           // number makes one workgroup run many chunks / pages in a row: tests, measurements)
+  int fpAgg = 0;          // GX_FP_AGG: k_fp_hist aggregates equal classes inside the wavefront before LDS (measurements; default: an atomic pair per lane)
   int roctx = 0;          // GX_ROCTX: a roctx range around every phase (rocprofv3 --marker-trace: kernel -> phase attribution)
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
@@ -232,6 +234,7 @@ const KnobDef KNOBS[] = {
     {"GX_SBSHIFT", &Knobs::sbShift, nullptr}, {"GX_RUN_CAP_MIN", nullptr, &Knobs::runCapMin}, {"GX_BH_CAPLOG", &Knobs::bhCapLog, nullptr},
     {"GX_PT_JMAX", &Knobs::ptJmax, nullptr}, {"GX_FAULT", &Knobs::fault, nullptr}, {"GX_SBT_TR", &Knobs::sbtTr, nullptr}, {"GX_SBT_GRID", &Knobs::sbtGrid, nullptr},
     {"GX_S2_GRID", &Knobs::s2Grid, nullptr},
+    {"GX_FP_AGG", &Knobs::fpAgg, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
 };
 // a switch that is merely present counts as 1 (GX_NO_LOOSE= is "on", as it was with getenv() != nullptr), and so does a
@@ -440,6 +443,11 @@ struct gx_ctx {
   DevBuf gramIn;                  // gx_gram_u64's copy of the caller's rows
   DevBuf gramPartial, gramOut;    // k_gram's workgroups' sums, k_gram_sum's totals
   bool gramUsed = false;          // the kernels ran since the last gx_reset
+  // the samples' fingerprint histograms (gx_coverage_fingerprint / gx_fp_u64, gx_fingerprint.h): nothing here exists before the first call
+  DevBuf fpRows;                  // the row pointers for the device
+  DevBuf fpIn;                    // gx_fp_u64's copy of the caller's rows
+  DevBuf fpOut;                   // count[S][FP_NC], sum[S][FP_NC]
+  bool fpUsed = false;            // the kernel ran since the last gx_reset
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

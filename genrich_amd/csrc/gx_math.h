@@ -21,6 +21,7 @@
 #define GX_UNIT 120
 #define GX_SKIPF (-1.0f)
 #define GX_HD __host__ __device__
+#include "gx_fp_class.h"   // fp_class / fp_class_lo / fp_class_hi: the fingerprint's value classes (GX_FP_SUB_LOG, GX_FP_NC)
 
 namespace gx {
 

@@ -158,6 +158,8 @@ struct Opts {
   bool binSizeOpt = false, coverageScaleOpt = false;
   const char* correlationFile = nullptr;   // --correlation FILE: the samples' Pearson matrix from the coverage bins
   bool corrSkipZeros = false;              // --corr-skip-zeros
+  const char* fingerprintFile = nullptr;   // --fingerprint FILE: each sample's Lorenz curve from the coverage bins
+  const char* fingerprintMetricsFile = nullptr;   // --fingerprint-metrics FILE: ... and its figures
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2690,6 +2692,48 @@ void writeCorrelation(State& S) {
     fprintf(stderr, "  Correlation: %llu bins, %llu all zero; no pair with a correlation\n", (unsigned long long)bins, (unsigned long long)zeros);
 }
 
+// --fingerprint FILE [--fingerprint-metrics FILE]: each sample's bins reduced to value classes (one pass per context, added),
+// the Lorenz curve's points per sample and non-empty class as a TSV labelled t<rep> / c<rep> like --correlation's, and the
+// figures made of them (zero fraction, area, Gini, elbow, the divergence from the replicate's control); with -v the figures
+// on stderr too
+void writeFingerprint(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  int nS = 0;
+  check(S, gx_coverage_samples(g0, &nS), g0);
+  std::vector<std::string> labels;
+  std::vector<int> reps, ctrls;
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
+    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
+    reps.push_back(rep);
+    ctrls.push_back(ctrl);
+  }
+  std::vector<const char*> names;
+  for (const std::string& l : labels) names.push_back(l.c_str());
+  std::vector<int> ctrlOf((size_t)nS, -1);   // a treatment's control: the control sample of the same replicate
+  for (int i = 0; i < nS; i++)
+    for (int j = 0; j < nS && !ctrls[i]; j++)
+      if (ctrls[j] && reps[j] == reps[i]) ctrlOf[i] = j;
+  std::vector<uint64_t> count((size_t)nS * GX_FP_NC), sum((size_t)nS * GX_FP_NC);
+  check(S, gx_coverage_fingerprint_group(S.devs.ctx.data(), (int)S.devs.n(), nS, nullptr, count.data(), sum.data()), g0);
+  Out out = openWrite(o.fingerprintFile, o.gzOut);
+  check(S, gx_format_fingerprint(out.f, nS, names.data(), count.data(), sum.data()), g0);
+  closeOut(out);
+  if (o.fingerprintMetricsFile) {
+    Out m = openWrite(o.fingerprintMetricsFile, o.gzOut);
+    check(S, gx_format_fingerprint_metrics(m.f, nS, names.data(), count.data(), sum.data(), ctrlOf.data()), g0);
+    closeOut(m);
+  }
+  if (!o.verbose) return;
+  std::vector<gx_fp_metrics> m((size_t)nS);
+  check(S, gx_fingerprint_metrics(nS, count.data(), sum.data(), ctrlOf.data(), m.data()), g0);
+  for (int i = 0; i < nS; i++)
+    fprintf(stderr, "  Fingerprint %s: zero fraction %f, auc %f, gini %f, elbow at %f of the bins (gap %f), jsd to control %f\n", names[i],
+            m[i].zero_fraction, m[i].auc, m[i].gini, m[i].elbow_bins, m[i].elbow_gap, m[i].jsd_control);
+}
+
 // --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
@@ -2786,6 +2830,9 @@ void usage() {
           "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n"
           "  --correlation FILE [--corr-skip-zeros]   the samples' Pearson correlation matrix over their bins of --bin-size N (50)\n"
           "                  bases, a TSV labelled t<rep> / c<rep>; --corr-skip-zeros leaves out the bins that are 0 in every sample\n"
+          "  --fingerprint FILE [--fingerprint-metrics FILE]   each sample's fingerprint (Lorenz curve) over its bins of --bin-size N (50)\n"
+          "                  bases: a TSV of cumulative bins and signal per value class; the metrics file has the zero fraction, area,\n"
+          "                  Gini, elbow and the divergence from the replicate's control per sample\n"
           "  --profile BED --profile-out PREFIX [--flank N] [--profile-bin N] [--profile-at tss|center] [--profile-matrix]\n"
           "                  each sample's pileup around the BED's sites, N (2000) bases to either side in bins of N (10) bases,\n"
           "                  oriented by column 6: PREFIX.profile.tsv, the mean per base and site at every offset; a site is the\n"
@@ -2821,6 +2868,8 @@ int main(int argc, char** argv) {
                                      {"profile-matrix", no_argument, nullptr, 1015},
                                      {"correlation", required_argument, nullptr, 1016},
                                      {"corr-skip-zeros", no_argument, nullptr, 1017},
+                                     {"fingerprint", required_argument, nullptr, 1018},
+                                     {"fingerprint-metrics", required_argument, nullptr, 1019},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2887,6 +2936,8 @@ int main(int argc, char** argv) {
       case 1015: o.profileMatrix = true; break;
       case 1016: o.correlationFile = optarg; break;
       case 1017: o.corrSkipZeros = true; break;
+      case 1018: o.fingerprintFile = optarg; break;
+      case 1019: o.fingerprintMetricsFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2917,7 +2968,9 @@ int main(int argc, char** argv) {
   // (the matrix is made of the same bins: one bin size per run)
   if (o.correlationFile && (o.peaksOnly || o.eventsOnly)) die("", "--correlation needs the pileups of this run (not with -P or --events-only)");
   if (o.corrSkipZeros && !o.correlationFile) die("", "--corr-skip-zeros needs --correlation FILE");
-  if (o.correlationFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
+  if (o.fingerprintFile && (o.peaksOnly || o.eventsOnly)) die("", "--fingerprint needs the pileups of this run (not with -P or --events-only)");
+  if (o.fingerprintMetricsFile && !o.fingerprintFile) die("", "--fingerprint-metrics needs --fingerprint FILE");
+  if (o.correlationFile || o.fingerprintFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
     auto split = [](const char* list) {
       std::vector<std::string> out;
       std::string l(list ? list : "");
@@ -2927,11 +2980,12 @@ int main(int argc, char** argv) {
     const std::vector<std::string> t = split(o.inFile), c = split(o.ctrlFile);
     size_t n = t.size();
     for (size_t r = 0; r < t.size() && r < c.size(); r++) n += c[r] != "null";
-    if (n > 32) die("", "--correlation takes at most 32 samples");
+    if (n > 32 && o.correlationFile) die("", "--correlation takes at most 32 samples");
+    if (n > 32) die("", "--fingerprint takes at most 32 samples");
   }
-  if ((o.coverageScaleOpt && !o.coveragePrefix) || (o.binSizeOpt && !o.coveragePrefix && !o.correlationFile))
+  if ((o.coverageScaleOpt && !o.coveragePrefix) || (o.binSizeOpt && !o.coveragePrefix && !o.correlationFile && !o.fingerprintFile))
     die("", "--bin-size and --coverage-scale need --coverage PREFIX");
-  if ((o.coveragePrefix || o.correlationFile) && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
+  if ((o.coveragePrefix || o.correlationFile || o.fingerprintFile) && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
   if ((o.profileBed != nullptr) != (o.profilePrefix != nullptr)) die("", "--profile BED and --profile-out PREFIX need each other");
   if ((o.flankOpt || o.profileBinOpt || o.profileAtOpt || o.profileMatrix) && !o.profileBed)
     die("", "--flank, --profile-bin, --profile-at and --profile-matrix need --profile BED");
@@ -3064,7 +3118,7 @@ int main(int argc, char** argv) {
     if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") scanHeader(S, cFiles[r].c_str(), true);
   }
   sendChroms(S);
-  if (o.coveragePrefix || o.correlationFile)
+  if (o.coveragePrefix || o.correlationFile || o.fingerprintFile)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
   ProfilePlan profilePlan;
   if (o.profileBed) {
@@ -3195,6 +3249,7 @@ int main(int argc, char** argv) {
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.coveragePrefix) writeCoverage(S, names);
   if (o.correlationFile) writeCorrelation(S);
+  if (o.fingerprintFile) writeFingerprint(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);

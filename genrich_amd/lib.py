@@ -109,6 +109,12 @@ def _split128(values, shape):
     return out
 
 
+GX_PATH_FINGERPRINT = 2097152   # gx_path_info bit 21: k_fp_hist ran (gx_coverage_fingerprint, gx_fp_u64)
+FP_NC = 3776                    # GX_FP_NC: the fingerprint's value classes
+FP_SUB_LOG = 6                  # GX_FP_SUB_LOG
+FP_METRICS_DTYPE = np.dtype([(k, "<f8") for k in ("zero_fraction", "auc", "gini", "elbow_bins", "elbow_gap", "jsd_control")])   # gx_fp_metrics
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
 
@@ -208,6 +214,14 @@ _SIGS = {
     "gx_gram_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "gx_correlation_matrix": [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "gx_coverage_gram_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
+    "gx_coverage_fingerprint": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int],
+    "gx_fp_u64": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p],
+    "gx_fp_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "gx_fingerprint_metrics": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_format_fingerprint": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_format_fingerprint_metrics": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_coverage_fingerprint_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
+    "gx_write_fingerprint_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -234,6 +248,9 @@ def load_library(path: str = os.environ.get("GENRICH_AMD_LIB", LIB_PATH)):
     lib.gx_strerror.argtypes = [C.c_int]
     lib.gx_filter_saturation.restype = C.c_longlong
     lib.gx_filter_saturation.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    lib.gx_fp_class.restype, lib.gx_fp_class.argtypes = C.c_uint32, [C.c_uint64]
+    lib.gx_fp_class_lo.restype, lib.gx_fp_class_lo.argtypes = C.c_uint64, [C.c_uint32]
+    lib.gx_fp_class_hi.restype, lib.gx_fp_class_hi.argtypes = C.c_uint64, [C.c_uint32]
     _lib = lib
     return lib
 
@@ -364,6 +381,73 @@ def format_correlation(sample_names, n, n_zero, sums, gram, skip_zeros=False) ->
     names = _c_names(list(sample_names))
     return _to_tmpfile(lambda f: lib.gx_format_correlation(f, S, names, int(n), int(n_zero), s.ctypes.data, g.ctypes.data,
                                                            int(bool(skip_zeros))))
+
+
+def fp_geometry():
+    """(n_classes, sub_log, lanes, grid) of k_fp_hist as the library was built (gx_fp_geometry): the value classes, log2 of the
+    classes per octave, the lanes of a workgroup, the most workgroups of a launch by default."""
+    lib = load_library()
+    v = [C.c_int(0) for _ in range(4)]
+    lib.gx_fp_geometry(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def fp_class(x):
+    return int(load_library().gx_fp_class(int(x)))
+
+
+def fp_class_lo(k):
+    return int(load_library().gx_fp_class_lo(int(k)))
+
+
+def fp_class_hi(k):
+    return int(load_library().gx_fp_class_hi(int(k)))
+
+
+def _fp_arrays(count, total):
+    c = np.ascontiguousarray(count, dtype=np.uint64)
+    t = np.ascontiguousarray(total, dtype=np.uint64)
+    if c.ndim != 2 or c.shape[1] != FP_NC or t.shape != c.shape:
+        raise ValueError("count and sum must be [S, FP_NC]")
+    return c, t
+
+
+def _fp_ctrl(ctrl_of, S):
+    if ctrl_of is None:
+        return None, None
+    a = np.ascontiguousarray(ctrl_of, dtype=np.int32)
+    if a.shape != (S,):
+        raise ValueError("ctrl_of must have one entry per sample")
+    return a, a.ctypes.data
+
+
+def fingerprint_metrics(count, total, ctrl_of=None):
+    """The figures of gx_fingerprint_metrics as a FP_METRICS_DTYPE array [S]; count / total: uint64 [S, FP_NC]; host-only."""
+    lib = load_library()
+    c, t = _fp_arrays(count, total)
+    keep, cp = _fp_ctrl(ctrl_of, len(c))
+    out = np.zeros(len(c), dtype=FP_METRICS_DTYPE)
+    rc = lib.gx_fingerprint_metrics(len(c), c.ctypes.data, t.ctypes.data, cp, out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_fingerprint_metrics: {rc}")
+    return out
+
+
+def format_fingerprint(sample_names, count, total) -> bytes:
+    """--fingerprint's curve table (gx_format_fingerprint); host-only, needs no GPU."""
+    lib = load_library()
+    c, t = _fp_arrays(count, total)
+    names = _c_names(list(sample_names))
+    return _to_tmpfile(lambda f: lib.gx_format_fingerprint(f, len(c), names, c.ctypes.data, t.ctypes.data))
+
+
+def format_fingerprint_metrics(sample_names, count, total, ctrl_of=None) -> bytes:
+    """--fingerprint-metrics' table (gx_format_fingerprint_metrics); host-only, needs no GPU."""
+    lib = load_library()
+    c, t = _fp_arrays(count, total)
+    keep, cp = _fp_ctrl(ctrl_of, len(c))
+    names = _c_names(list(sample_names))
+    return _to_tmpfile(lambda f: lib.gx_format_fingerprint_metrics(f, len(c), names, c.ctypes.data, t.ctypes.data, cp))
 
 
 def rccl_unique_id() -> bytes:
@@ -595,7 +679,8 @@ class Genrich:
         16 pair records, 32 dense BH all-reduce, 64 range BH exchange, 128 fractional pair records, 256 pileup floats written, 512 8-byte
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
-        262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran)."""
+        262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
+        2097152 the fingerprint kernel ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -703,6 +788,24 @@ class Genrich:
         self._check(self.lib.gx_gram_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), C.byref(nz), s.ctypes.data,
                                          g.ctypes.data))
         return nz.value, _join128(s[:n_rows]), _join128(g[:n_rows, :n_rows])
+
+    # -- fingerprint of the samples' bins (include/genrich_amd.h, gx_coverage_fingerprint) -------------------------------
+    def coverage_fingerprint(self):
+        """(n, count, sum) of the samples closed since the last reset: count and sum uint64 [S, FP_NC]."""
+        S = max(self.coverage_samples(), 1)
+        c, t = np.zeros((S, FP_NC), dtype=np.uint64), np.zeros((S, FP_NC), dtype=np.uint64)
+        ns, n = C.c_int(0), C.c_uint64(0)
+        self._check(self.lib.gx_coverage_fingerprint(self.ctx, C.byref(ns), C.byref(n), c.ctypes.data, t.ctypes.data, S))
+        return n.value, c[:ns.value], t[:ns.value]
+
+    def fp_u64(self, rows, grid=0):
+        """(count, sum), uint64 [n_rows, FP_NC], of the rows (uint64 [n_rows, n]) by the same kernel (gx_fp_u64); grid = 0: the
+        library's geometry, else that many workgroups along the bin axis."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        n_rows, n = r.shape
+        c, t = np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64), np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64)
+        self._check(self.lib.gx_fp_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), c.ctypes.data, t.ctypes.data))
+        return c[:n_rows], t[:n_rows]
 
     # -- profiles around anchors (include/genrich_amd.h, gx_set_profile) -------------------------------------------------
     def set_profile(self, anchors, flank, bin_size, keep_matrix=False):

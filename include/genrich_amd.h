@@ -21,6 +21,7 @@
  *   (coverage on, any time after a gx_sample_end: gx_get_coverage / gx_write_coverage)
  *   (profile on, any time after a gx_sample_end: gx_get_profile / gx_write_profile_group)
  *   (coverage on, between samples or after them: gx_coverage_gram / gx_write_correlation_group)
+ *   (coverage on, between samples or after them: gx_coverage_fingerprint / gx_write_fingerprint_group)
  *   gx_destroy
  */
 #ifndef GENRICH_AMD_H
@@ -340,6 +341,62 @@ int gx_gram_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigne
  * along the bin axis with grid = 0 (any pointer may be NULL). */
 int gx_gram_geometry(int* tile, int* lanes, int* grid);
 
+/* ---- fingerprint (Lorenz curve) of each sample from its coverage bins (no Genrich counterpart: what deepTools'
+ *      plotFingerprint takes from another reading of every BAM) ----
+ * Samples and x_s[b] are gx_coverage_gram's: all bins of this context, a chromosome's short last bin as it is, 0 inside -E
+ * regions and where a replicate's save mask omits the chromosome.  A fingerprint is a function of the distribution of a
+ * sample's values only, so the pass reduces every sample to a histogram over value classes.  With M = GX_FP_SUB_LOG = 6:
+ *     x < 64:  class(x) = x;     else  e = 63 - clz(x),  class(x) = (e - 6) 64 + (x >> (e - 6))
+ * which is continuous and monotone: values below 128 have a class of their own, above that an octave has 64 classes, so a
+ * class's values differ by less than 1 / 64 relative; GX_FP_NC = 3776 classes cover uint64 (class(2^64 - 1) = 3775).  The
+ * inverse: k < 128: lo(k) = hi(k) = k; else q = k / 64 - 1, lo(k) = (k - 64 q) << q, hi(k) = lo(k) + 2^q - 1.
+ *     count[s][k] = the number of bins b with class(x_s[b]) == k
+ *     sum[s][k]   = the sum of those x_s[b]
+ * both exact uint64.  The bound: x_s[b] <= (2^31 - 1) w_b, so a sample's total is below 2^31 G, G = the total length of the
+ * chromosomes that have bins; the pass is refused (GX_ERR_ORDER) when G >= 2^33 (hg38: below 2^32).  A context has at most
+ * 2^30 bins, so a count fits 32 bits anywhere on the device.  Integer adds only: a result does not depend on the grid or on
+ * the number of contexts, and a host adds the contexts' count and sum class by class (gx_coverage_fingerprint_group does; the
+ * bound is then the caller's to keep over all contexts).
+ *
+ * The curve and the figures are host-only doubles made from those integers (gx_fingerprint_metrics, gx_format_fingerprint).
+ * With n = sum_k count[k], T = sum_k sum[k] and C_k, T_k the inclusive running sums, the curve starts at (0, 0) and passes
+ * through (p_k, L_k) = (C_k / n, T_k / T) for each non-empty class in ascending order.  These points lie exactly on the
+ * sample's Lorenz curve (all bins of a class and below, and all their signal); between two of them the true curve is convex
+ * and the polyline lies above it by at most what a spread of 1 / 64 inside one class allows (none below 128).
+ *     zero_fraction = count[0] / n            auc  = the polyline's trapezoid sum            gini = 1 - 2 auc
+ *     elbow_bins, elbow_gap = p_i and p_i - L_i at the first point where p_i - L_i is largest
+ *     jsd_control = for a treatment whose control was read: the square root of the base-2 Jensen-Shannon divergence between
+ *                   count_t[k] / n_t and count_c[k] / n_c over the classes; NaN for a control or without one
+ * With T == 0 every figure that divides by T is NaN (n == 0: all of them).  Each ratio is one division of integer running
+ * sums in long double; auc is added in ascending order in long double.
+ *
+ * gx_coverage_fingerprint: the pass (k_fp_hist: gx_fingerprint.h) over the samples closed since the last gx_reset.  It needs
+ *   gx_set_coverage_bins on and at least one closed sample, else GX_ERR_ORDER; also GX_ERR_ORDER: a sample is open, more than
+ *   32 samples, the bound above broken, cap < S while count or sum is given.  count[cap * GX_FP_NC] and sum[cap * GX_FP_NC]
+ *   (sample s's row at + s * GX_FP_NC) may each be NULL.  It needs no gx_pvalues and no gx_find_peaks, and may be called
+ *   between samples, after them and again: the same answer.  A context without bins answers zeros.  A failed allocation:
+ *   GX_ERR_MEM.  Nothing of it is allocated or launched before the first call.
+ * gx_fp_u64: the same kernel over n_rows rows of n values each that the caller gives (host memory, row after row; copied to
+ *   the device by this call, which adds each row in 128 bits on the way).  Domain: 1 <= n_rows <= 32, n <= 2^24, grid <= 65535,
+ *   every row's total below 2^64, else GX_ERR_ORDER before anything is launched; a single value may be anything up to
+ *   2^64 - 1.  grid = 0: the library's geometry; else that many workgroups along the bin axis.  count[n_rows * GX_FP_NC] and
+ *   sum[n_rows * GX_FP_NC] may each be NULL.  For tests and measurements: values and sizes no small pileup produces.
+ * gx_fp_geometry: what gx_fp_u64's edge cases depend on: GX_FP_NC, GX_FP_SUB_LOG, the lanes of a workgroup (each takes two
+ *   values a step), the most workgroups of a launch with grid = 0 (with S rows: that divided by S along the bin axis).  Any
+ *   pointer may be NULL.
+ * gx_fp_class / gx_fp_class_lo / gx_fp_class_hi: class(), lo() and hi() above (host only; lo / hi of k >= GX_FP_NC: 0). */
+#define GX_FP_SUB_LOG 6
+#define GX_FP_NC ((64 - GX_FP_SUB_LOG + 1) << GX_FP_SUB_LOG)
+typedef struct {
+  double zero_fraction, auc, gini, elbow_bins, elbow_gap, jsd_control;
+} gx_fp_metrics;
+int gx_coverage_fingerprint(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum, int cap);
+int gx_fp_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* count, uint64_t* sum);
+int gx_fp_geometry(int* n_classes, int* sub_log, int* lanes, int* grid);
+uint32_t gx_fp_class(uint64_t x);
+uint64_t gx_fp_class_lo(uint32_t k);
+uint64_t gx_fp_class_hi(uint32_t k);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -473,6 +530,24 @@ int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_na
                           const gx_u128* sum, const gx_u128* gram, int skip_zeros);
 int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros,
                                FILE* out);
+/* --fingerprint (no Genrich counterpart).  The first three: host only, no context; count and sum are [n_samples][GX_FP_NC] as
+ * gx_coverage_fingerprint gives them, ctrl_of[s] is the sample index of s's control or -1 (ctrl_of == NULL: all -1).
+ * gx_fingerprint_metrics: the figures defined above, NaN where they are not.
+ * gx_format_fingerprint: a TSV with the header "sample lo120 hi120 bins sum120 cum_bins cum_signal" and one row per sample and
+ *   non-empty class in ascending order: the class's lo and hi, its count and sum as integers, C_k / n and T_k / T as %.6f
+ *   ("nan" with T == 0).
+ * gx_format_fingerprint_metrics: header "sample bins zero_bins sum120 zero_fraction auc gini elbow_bins elbow_gap jsd_control",
+ *   one row per sample: n, count[0] and T as integers, the figures as %.6f or "nan".
+ * A missing pointer, n_samples < 1 or a ctrl_of entry that is not a sample other than s: GX_ERR_ORDER, nothing written.
+ * gx_coverage_fingerprint_group (gx_api.hip: it reads contexts): gx_coverage_fingerprint of every context, added; count and
+ * sum are required.  gx_write_fingerprint_group: that, then the curve table to `curve` and, unless NULL, the figures to `metrics`. */
+int gx_fingerprint_metrics(int n_samples, const uint64_t* count, const uint64_t* sum, const int* ctrl_of, gx_fp_metrics* out);
+int gx_format_fingerprint(FILE* out, int n_samples, const char* const* sample_names, const uint64_t* count, const uint64_t* sum);
+int gx_format_fingerprint_metrics(FILE* out, int n_samples, const char* const* sample_names, const uint64_t* count,
+                                  const uint64_t* sum, const int* ctrl_of);
+int gx_coverage_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum);
+int gx_write_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, const int* ctrl_of,
+                               FILE* curve, FILE* metrics);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -564,6 +639,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_COVERAGE 262144u /* bit 18: this run summed its samples' pileups over bins (gx_set_coverage_bins; a sample was closed since the last gx_reset) */
 #define GX_PATH_PROFILE 524288u /* bit 19: this run summed its samples' pileups around anchors (gx_set_profile; a sample was closed with it on since the last gx_reset) */
 #define GX_PATH_GRAM 1048576u /* bit 20: k_gram / k_gram_sum ran since the last gx_reset (gx_coverage_gram, gx_gram_u64) */
+#define GX_PATH_FINGERPRINT 2097152u /* bit 21: k_fp_hist ran since the last gx_reset (gx_coverage_fingerprint, gx_fp_u64) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
