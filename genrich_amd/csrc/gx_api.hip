@@ -13,6 +13,7 @@
 #include "gx_host_profile.h"
 #include "gx_host_gram.h"
 #include "gx_host_fingerprint.h"
+#include "gx_host_rank.h"
 
 
 // ================================ C ABI ==================================================
@@ -257,6 +258,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_profile(ctx);    // (... and gx_set_profile's)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
+  ctx->rankUsed = false;
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -839,7 +841,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
-           (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u);
+           (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u);
   return GX_OK;
 }
 
@@ -1284,6 +1286,203 @@ int gx_write_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, co
   if (int rc = gx_coverage_fingerprint_group(ctxs, n_ctx, n_samples, nullptr, c1.data(), s1.data())) return rc;
   if (int rc = gx_format_fingerprint(curve, n_samples, sample_names, c1.data(), s1.data())) return rc;
   return metrics ? gx_format_fingerprint_metrics(metrics, n_samples, sample_names, c1.data(), s1.data(), ctrl_of) : GX_OK;
+}
+
+int gx_coverage_distinct(gx_ctx* ctx, int sample, uint64_t* value, uint64_t* count, size_t cap, size_t* n_distinct) {
+  std::vector<const void*> rows;
+  u64 n = 0;
+  if (int rc = rank_cov_rows(ctx, rows, &n)) return rc;
+  if (sample < 0 || (size_t)sample >= rows.size() || (cap && (!value || !count))) return GX_ERR_ORDER;
+  std::vector<uint64_t> v, c;
+  if (int rc = rank_distinct_pass(ctx, rows[sample], n, 0, v, c)) return rc;
+  return rank_give_table(ctx, "gx_coverage_distinct", v, c, value, count, cap, n_distinct);
+}
+
+int gx_distinct_u64(gx_ctx* ctx, const uint64_t* row, size_t n, unsigned grid, uint64_t* value, uint64_t* count, size_t cap,
+                    size_t* n_distinct) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (const char* why = rank_u64_domain(row, 1, n, grid)) {
+    ctx->err = std::string("gx_distinct_u64: ") + why;
+    return GX_ERR_ORDER;
+  }
+  if (cap && (!value || !count)) return GX_ERR_ORDER;
+  std::vector<const void*> dev;
+  if (int rc = rank_stage_rows(ctx, row, 1, n, dev)) return rc;
+  std::vector<uint64_t> v, c;
+  if (int rc = rank_distinct_pass(ctx, dev[0], n, grid, v, c)) return rc;
+  return rank_give_table(ctx, "gx_distinct_u64", v, c, value, count, cap, n_distinct);
+}
+
+int gx_rank_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, int skip_zeros, uint64_t* rank2, uint64_t* n_zero) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (const char* why = rank_u64_domain(rows, n_rows, n, grid)) {
+    ctx->err = std::string("gx_rank_u64: ") + why;
+    return GX_ERR_ORDER;
+  }
+  const size_t S = (size_t)n_rows;
+  std::vector<const void*> dev;
+  if (int rc = rank_stage_rows(ctx, rows, n_rows, n, dev)) return rc;
+  u64 nz = 0;
+  if (skip_zeros)
+    if (int rc = rank_nzero_pass(ctx, dev, n, &nz)) return rc;
+  std::vector<std::vector<uint64_t>> v(S), c(S), lv(S), lr(S);
+  std::vector<gx_rank_table> tabs(S);
+  size_t most = 0;
+  for (size_t i = 0; i < S; i++) {
+    if (int rc = rank_distinct_pass(ctx, dev[i], n, grid, v[i], c[i])) return rc;
+    tabs[i] = gx_rank_table{v[i].data(), c[i].data(), v[i].size()};
+    most = std::max(most, v[i].size());
+  }
+  std::vector<uint64_t*> pv(S), pr(S);
+  for (size_t i = 0; i < S; i++) {
+    lv[i].resize(most);
+    lr[i].resize(most);
+    pv[i] = lv[i].data();
+    pr[i] = lr[i].data();
+  }
+  std::vector<size_t> nOut(S, 0);
+  if (int rc = gx_rank_tables(1, n_rows, tabs.data(), nz, pv.data(), pr.data(), most, nOut.data(), nullptr)) {
+    ctx->err = "gx_rank_u64: the rows' tables do not make rank tables";
+    return rc;
+  }
+  std::vector<gx_rank_lut> lut(S);
+  for (size_t i = 0; i < S; i++) lut[i] = gx_rank_lut{lv[i].data(), lr[i].data(), nOut[i]};
+  std::vector<const void*> out;
+  u64 nz2 = 0;
+  if (int rc = rank_rows_pass(ctx, dev, n, grid, skip_zeros != 0, lut.data(), out, &nz2)) return rc;
+  if (n_zero) *n_zero = nz2;
+  if (rank2 && n) {
+    for (size_t i = 0; i < S; i++)
+      HIPCHECK(hipMemcpyAsync(rank2 + i * n, out[i], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+  }
+  return GX_OK;
+}
+
+int gx_rank_geometry(int* lanes, int* grid, int* cache_entries, size_t* first_capacity, size_t* load_limit) {
+  if (lanes) *lanes = RK_NW * 64;
+  if (grid) *grid = (int)RK_GRID;
+  if (cache_entries) *cache_entries = (int)RK_CACHE;
+  if (first_capacity) *first_capacity = (size_t)1 << RK_CAP_LOG;
+  if (load_limit) *load_limit = ((size_t)1 << RK_CAP_LOG) / RK_LOAD_DIV;
+  return GX_OK;
+}
+
+int gx_rank_last(gx_ctx* ctx, size_t* capacity, int* n_grown) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (capacity) *capacity = ctx->rankLastCapLog ? (size_t)1 << ctx->rankLastCapLog : 0;
+  if (n_grown) *n_grown = (int)ctx->rankLastGrown;
+  return GX_OK;
+}
+
+int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros, int* n_samples, uint64_t* n_bins, uint64_t* n_zero,
+                          gx_u128* sum, gx_u128* gram, int cap) {
+  std::vector<const void*> rows;
+  u64 n = 0;
+  if (int rc = rank_cov_rows(ctx, rows, &n)) return rc;
+  const size_t S = rows.size();
+  const char* why = nullptr;
+  if (!tables || !rank_lut_ok(tables, S)) why = "gx_coverage_rank_gram: a table is not ascending, holds the value 2^64 - 1, or a rank is outside [1, 2^42)";
+  else if ((sum || gram) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_rank_gram: cap is smaller than the number of samples";
+  if (why) {
+    ctx->err = why;
+    return GX_ERR_ORDER;
+  }
+  std::vector<const void*> ranks;
+  u64 nz = 0, nzGram = 0;
+  if (int rc = rank_rows_pass(ctx, rows, n, 0, skip_zeros != 0, tables, ranks, &nz)) return rc;
+  std::vector<gx_u128> s1, g1;
+  if (int rc = gram_pass(ctx, ranks, n, 0, &nzGram, s1, g1)) return rc;
+  if (skip_zeros && nzGram != nz) {   // (a rank is at least 1: the rows that are 0 everywhere are the bins left out)
+    ctx->err = "gx_coverage_rank_gram: the rank rows' zero bins are not the bins left out";
+    return GX_ERR_DEVICE;
+  }
+  if (n_samples) *n_samples = (int)S;
+  if (n_bins) *n_bins = n;
+  if (n_zero) *n_zero = nz;
+  if (sum) std::copy(s1.begin(), s1.end(), sum);
+  if (gram)
+    for (size_t i = 0; i < S; i++) std::copy(g1.begin() + i * S, g1.begin() + (i + 1) * S, gram + i * (size_t)cap);
+  return GX_OK;
+}
+
+// (the two over contexts live here, not in gx_emit.cpp, like the correlation's: they read contexts)
+int gx_coverage_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, int skip_zeros, uint64_t* n_ranked, gx_u128* sum, gx_u128* gram,
+                               uint64_t* n_distinct) {
+  if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)RK_MAX_S || !sum || !gram) return GX_ERR_ORDER;
+  const size_t S = (size_t)n_samples, G = (size_t)n_ctx;
+  // 1. every context's tables, and with skip_zeros its all-zero bins
+  std::vector<std::vector<uint64_t>> v(G * S), c(G * S);
+  std::vector<gx_rank_table> tabs(G * S);
+  uint64_t nzAll = 0;
+  std::vector<size_t> room(S, 0);
+  for (size_t g = 0; g < G; g++) {
+    std::vector<const void*> rows;
+    u64 n = 0;
+    if (int rc = rank_cov_rows(ctxs[g], rows, &n)) return rc;
+    if (rows.size() != S) {
+      ctxs[g]->err = "gx_coverage_spearman_group: a context has another number of samples";
+      return GX_ERR_ORDER;
+    }
+    if (skip_zeros) {
+      u64 nz = 0;
+      if (int rc = rank_nzero_pass(ctxs[g], rows, n, &nz)) return rc;
+      nzAll += nz;
+    }
+    for (size_t i = 0; i < S; i++) {
+      const size_t k = g * S + i;
+      if (int rc = rank_distinct_pass(ctxs[g], rows[i], n, 0, v[k], c[k])) return rc;
+      tabs[k] = gx_rank_table{v[k].data(), c[k].data(), v[k].size()};
+      room[i] += v[k].size();
+    }
+  }
+  // 2. the rank tables over all contexts
+  const size_t most = *std::max_element(room.begin(), room.end());
+  std::vector<std::vector<uint64_t>> lv(S), lr(S);
+  std::vector<uint64_t*> pv(S), pr(S);
+  for (size_t i = 0; i < S; i++) {
+    lv[i].resize(most);
+    lr[i].resize(most);
+    pv[i] = lv[i].data();
+    pr[i] = lr[i].data();
+  }
+  std::vector<size_t> nOut(S, 0);
+  uint64_t N = 0;
+  if (int rc = gx_rank_tables(n_ctx, n_samples, tabs.data(), nzAll, pv.data(), pr.data(), most, nOut.data(), &N)) {
+    for (size_t g = 0; g < G; g++) ctxs[g]->err = "the contexts' tables do not make rank tables (more than 2^41 bins?)";
+    return rc;
+  }
+  std::vector<gx_rank_lut> lut(S);
+  for (size_t i = 0; i < S; i++) lut[i] = gx_rank_lut{lv[i].data(), lr[i].data(), nOut[i]};
+  // 3. every context's rank rows and their sums, added with carries
+  std::vector<u128> st(S, 0), gt(S * S, 0);
+  uint64_t nzSeen = 0;
+  for (size_t g = 0; g < G; g++) {
+    int s = 0;
+    uint64_t nz1 = 0;
+    if (int rc = gx_coverage_rank_gram(ctxs[g], lut.data(), skip_zeros, &s, nullptr, &nz1, sum, gram, n_samples)) return rc;
+    nzSeen += nz1;
+    for (size_t k = 0; k < S; k++) st[k] += ((u128)sum[k].hi << 64) | sum[k].lo;
+    for (size_t k = 0; k < S * S; k++) gt[k] += ((u128)gram[k].hi << 64) | gram[k].lo;
+  }
+  if (skip_zeros && nzSeen != nzAll) {
+    for (size_t g = 0; g < G; g++) ctxs[g]->err = "gx_coverage_spearman_group: the bins left out are not the all-zero bins counted";
+    return GX_ERR_DEVICE;
+  }
+  for (size_t k = 0; k < S; k++) sum[k] = gx_u128{(uint64_t)st[k], (uint64_t)(st[k] >> 64)};
+  for (size_t k = 0; k < S * S; k++) gram[k] = gx_u128{(uint64_t)gt[k], (uint64_t)(gt[k] >> 64)};
+  if (n_ranked) *n_ranked = N;
+  if (n_distinct)
+    for (size_t i = 0; i < S; i++) n_distinct[i] = nOut[i];
+  return GX_OK;
+}
+
+int gx_write_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros, FILE* out) {
+  if (!out || !sample_names || n_samples < 1 || n_samples > (int)RK_MAX_S) return GX_ERR_ORDER;
+  std::vector<gx_u128> s1((size_t)n_samples), g1((size_t)n_samples * n_samples);
+  uint64_t N = 0;
+  if (int rc = gx_coverage_spearman_group(ctxs, n_ctx, n_samples, skip_zeros, &N, s1.data(), g1.data(), nullptr)) return rc;
+  return gx_format_correlation(out, n_samples, sample_names, N, 0, s1.data(), g1.data(), 0);
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

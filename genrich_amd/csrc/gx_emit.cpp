@@ -402,6 +402,56 @@ int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_na
   return GX_OK;
 }
 
+// --spearman: the contexts' (value, count) tables of every sample merged into one table (value, rank2) per sample
+int gx_rank_tables(int n_ctx, int n_samples, const gx_rank_table* tables, uint64_t n_zero_to_drop, uint64_t* const* value,
+                   uint64_t* const* rank2, size_t cap, size_t* n_out, uint64_t* n_ranked) {
+  if (n_ctx < 1 || n_samples < 1 || n_samples > 32 || !tables || !n_out || ((value == nullptr) != (rank2 == nullptr))) return GX_ERR_ORDER;
+  const size_t S = (size_t)n_samples, G = (size_t)n_ctx;
+  uint64_t N = 0;
+  std::vector<std::pair<uint64_t, uint64_t>> all, merged;
+  for (size_t s = 0; s < S; s++) {
+    all.clear();
+    merged.clear();
+    for (size_t g = 0; g < G; g++) {
+      const gx_rank_table& t = tables[g * S + s];
+      if (t.n && (!t.value || !t.count)) return GX_ERR_ORDER;
+      for (size_t k = 0; k < t.n; k++) {
+        if ((k && t.value[k - 1] >= t.value[k]) || !t.count[k] || t.count[k] >> 41) return GX_ERR_ORDER;
+        all.emplace_back(t.value[k], t.count[k]);
+      }
+    }
+    std::sort(all.begin(), all.end());
+    for (const auto& p : all) {
+      if (!merged.empty() && merged.back().first == p.first) merged.back().second += p.second;
+      else merged.push_back(p);
+      if (merged.back().second >> 41) return GX_ERR_ORDER;
+    }
+    if (n_zero_to_drop) {   // (the bins that are 0 in every sample are 0 in this one)
+      if (merged.empty() || merged[0].first != 0 || merged[0].second < n_zero_to_drop) return GX_ERR_ORDER;
+      merged[0].second -= n_zero_to_drop;
+      if (!merged[0].second) merged.erase(merged.begin());
+    }
+    uint64_t total = 0;
+    for (const auto& p : merged) {
+      total += p.second;
+      if (total >> 41) return GX_ERR_ORDER;   // N < 2^41: a rank below 2^42, a sum of products below 2^125
+    }
+    if (s == 0) N = total;
+    else if (total != N) return GX_ERR_ORDER;   // (every sample has the same bins)
+    n_out[s] = merged.size();
+    if (!value) continue;
+    if (merged.size() > cap || (!merged.empty() && (!value[s] || !rank2[s]))) return GX_ERR_ORDER;
+    uint64_t less = 0;
+    for (size_t k = 0; k < merged.size(); k++) {
+      value[s][k] = merged[k].first;
+      rank2[s][k] = 2 * less + merged[k].second + 1;
+      less += merged[k].second;
+    }
+  }
+  if (n_ranked) *n_ranked = N;
+  return GX_OK;
+}
+
 // --fingerprint: the value classes (gx_fp_class.h) behind the C ABI
 uint32_t gx_fp_class(uint64_t x) { return gx::fp_class(x); }
 uint64_t gx_fp_class_lo(uint32_t k) { return k < (uint32_t)GX_FP_NC ? gx::fp_class_lo(k) : 0; }

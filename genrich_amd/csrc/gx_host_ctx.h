@@ -31,6 +31,7 @@
 #include "gx_profile.h"
 #include "gx_gram.h"
 #include "gx_fingerprint.h"
+#include "gx_rank.h"
 
 using namespace gx;
 
@@ -191,6 +192,8 @@ struct Knobs {
   int s2Grid = 0;         // GX_S2_GRID: persistent workgroups of k_sort_a (per piece) and k_sort_b (0: as many as are resident together; a small
                           // number makes one workgroup run many chunks / pages in a row: tests, measurements)
   int fpAgg = 0;          // GX_FP_AGG: k_fp_hist aggregates equal classes inside the wavefront before LDS (measurements; default: an atomic pair per lane)
+  int rankCapLog = 0;     // GX_RANK_CAP_LOG: log2 of the first capacity of k_rank_distinct's table (default RK_CAP_LOG; tests: the growth path with a few thousand values)
+  int rankLookup = 0;     // GX_RANK_LOOKUP: k_rank's lookup: 1 binary search in the sorted table, 2 probing a hashed one (measurements; default RK_LOOKUP)
   int roctx = 0;          // GX_ROCTX: a roctx range around every phase (rocprofv3 --marker-trace: kernel -> phase attribution)
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
@@ -235,6 +238,8 @@ const KnobDef KNOBS[] = {
     {"GX_PT_JMAX", &Knobs::ptJmax, nullptr}, {"GX_FAULT", &Knobs::fault, nullptr}, {"GX_SBT_TR", &Knobs::sbtTr, nullptr}, {"GX_SBT_GRID", &Knobs::sbtGrid, nullptr},
     {"GX_S2_GRID", &Knobs::s2Grid, nullptr},
     {"GX_FP_AGG", &Knobs::fpAgg, nullptr},
+    {"GX_RANK_CAP_LOG", &Knobs::rankCapLog, nullptr},
+    {"GX_RANK_LOOKUP", &Knobs::rankLookup, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
 };
 // a switch that is merely present counts as 1 (GX_NO_LOOSE= is "on", as it was with getenv() != nullptr), and so does a
@@ -448,6 +453,16 @@ struct gx_ctx {
   DevBuf fpIn;                    // gx_fp_u64's copy of the caller's rows
   DevBuf fpOut;                   // count[S][FP_NC], sum[S][FP_NC]
   bool fpUsed = false;            // the kernel ran since the last gx_reset
+  // the samples' rank rows (gx_coverage_distinct / gx_coverage_rank_gram / gx_distinct_u64 / gx_rank_u64, gx_rank.h): nothing
+  // here exists before the first call
+  DevBuf rankRows;                // the row pointers for the device: the S rows read, then the S rows written
+  DevBuf rankIn;                  // gx_distinct_u64's / gx_rank_u64's copy of the caller's rows
+  DevBuf rankTab, rankCtl;        // k_rank_distinct's table (keys, then counts) and the control words (RKC_*)
+  DevBuf rankPairs;               // k_rank_compact's (value, count) pairs
+  DevBuf rankLut;                 // k_rank's tables: the samples' values, their rank2, the offsets
+  DevBuf rankOut;                 // the rank rows k_gram reads
+  bool rankUsed = false;          // k_rank ran since the last gx_reset
+  u32 rankLastCapLog = 0, rankLastGrown = 0;   // the last k_rank_distinct pass: log2 of the capacity it ended with, how often it grew (gx_rank_last)
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

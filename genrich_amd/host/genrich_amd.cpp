@@ -157,7 +157,8 @@ struct Opts {
   double coverageScale = 1.0;   // --coverage-scale
   bool binSizeOpt = false, coverageScaleOpt = false;
   const char* correlationFile = nullptr;   // --correlation FILE: the samples' Pearson matrix from the coverage bins
-  bool corrSkipZeros = false;              // --corr-skip-zeros
+  bool corrSkipZeros = false;              // --corr-skip-zeros (both matrices)
+  const char* spearmanFile = nullptr;      // --spearman FILE: the samples' Spearman matrix from the coverage bins
   const char* fingerprintFile = nullptr;   // --fingerprint FILE: each sample's Lorenz curve from the coverage bins
   const char* fingerprintMetricsFile = nullptr;   // --fingerprint-metrics FILE: ... and its figures
   uint64_t genomeLen = 0;
@@ -2692,6 +2693,45 @@ void writeCorrelation(State& S) {
     fprintf(stderr, "  Correlation: %llu bins, %llu all zero; no pair with a correlation\n", (unsigned long long)bins, (unsigned long long)zeros);
 }
 
+// --spearman FILE: the Spearman matrix of the same bins (with --corr-skip-zeros: of those that are not zero in every sample, taken
+// out before ranking), --correlation's TSV; with -v the bins ranked, the most distinct values a sample has and the least alike pair
+void writeSpearman(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  int nS = 0;
+  check(S, gx_coverage_samples(g0, &nS), g0);
+  std::vector<std::string> labels;
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
+    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
+  }
+  std::vector<const char*> names;
+  for (const std::string& l : labels) names.push_back(l.c_str());
+  // every context's value tables, one ranking over all of them, one pass per context over its rank rows; the sums are added
+  std::vector<gx_u128> sum((size_t)nS), gram((size_t)nS * nS);
+  std::vector<uint64_t> distinct((size_t)nS);
+  uint64_t ranked = 0;
+  check(S, gx_coverage_spearman_group(S.devs.ctx.data(), (int)S.devs.n(), nS, o.corrSkipZeros ? 1 : 0, &ranked, sum.data(), gram.data(),
+                                      distinct.data()), g0);
+  Out out = openWrite(o.spearmanFile, o.gzOut);
+  check(S, gx_format_correlation(out.f, nS, names.data(), ranked, 0, sum.data(), gram.data(), 0), g0);
+  closeOut(out);
+  if (!o.verbose) return;
+  std::vector<double> r((size_t)nS * nS);
+  check(S, gx_correlation_matrix(nS, ranked, 0, sum.data(), gram.data(), 0, r.data()), g0);
+  int li = -1, lj = -1;
+  for (int i = 0; i < nS; i++)
+    for (int j = i + 1; j < nS; j++)
+      if (r[(size_t)i * nS + j] == r[(size_t)i * nS + j] && (li < 0 || r[(size_t)i * nS + j] < r[(size_t)li * nS + lj])) { li = i; lj = j; }
+  const unsigned long long most = nS ? (unsigned long long)*std::max_element(distinct.begin(), distinct.end()) : 0ull;
+  if (li >= 0)
+    fprintf(stderr, "  Spearman: %llu bins ranked, at most %llu distinct values a sample; smallest rho %f (%s, %s)\n", (unsigned long long)ranked,
+            most, r[(size_t)li * nS + lj], names[li], names[lj]);
+  else
+    fprintf(stderr, "  Spearman: %llu bins ranked, at most %llu distinct values a sample; no pair with a correlation\n", (unsigned long long)ranked, most);
+}
+
 // --fingerprint FILE [--fingerprint-metrics FILE]: each sample's bins reduced to value classes (one pass per context, added),
 // the Lorenz curve's points per sample and non-empty class as a TSV labelled t<rep> / c<rep> like --correlation's, and the
 // figures made of them (zero fraction, area, Gini, elbow, the divergence from the replicate's control); with -v the figures
@@ -2830,6 +2870,9 @@ void usage() {
           "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n"
           "  --correlation FILE [--corr-skip-zeros]   the samples' Pearson correlation matrix over their bins of --bin-size N (50)\n"
           "                  bases, a TSV labelled t<rep> / c<rep>; --corr-skip-zeros leaves out the bins that are 0 in every sample\n"
+          "  --spearman FILE [--corr-skip-zeros]   the samples' Spearman correlation matrix over their bins of --bin-size N (50)\n"
+          "                  bases, a TSV labelled t<rep> / c<rep>; --corr-skip-zeros leaves out the bins that are 0 in every sample\n"
+          "                  before they are ranked\n"
           "  --fingerprint FILE [--fingerprint-metrics FILE]   each sample's fingerprint (Lorenz curve) over its bins of --bin-size N (50)\n"
           "                  bases: a TSV of cumulative bins and signal per value class; the metrics file has the zero fraction, area,\n"
           "                  Gini, elbow and the divergence from the replicate's control per sample\n"
@@ -2870,6 +2913,7 @@ int main(int argc, char** argv) {
                                      {"corr-skip-zeros", no_argument, nullptr, 1017},
                                      {"fingerprint", required_argument, nullptr, 1018},
                                      {"fingerprint-metrics", required_argument, nullptr, 1019},
+                                     {"spearman", required_argument, nullptr, 1020},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2938,6 +2982,7 @@ int main(int argc, char** argv) {
       case 1017: o.corrSkipZeros = true; break;
       case 1018: o.fingerprintFile = optarg; break;
       case 1019: o.fingerprintMetricsFile = optarg; break;
+      case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
         for (char* t = strtok(list.data(), ","); t; t = strtok(nullptr, ",")) {
@@ -2967,10 +3012,11 @@ int main(int argc, char** argv) {
   if (o.coveragePrefix && (o.peaksOnly || o.eventsOnly)) die("", "--coverage needs the pileups of this run (not with -P or --events-only)");
   // (the matrix is made of the same bins: one bin size per run)
   if (o.correlationFile && (o.peaksOnly || o.eventsOnly)) die("", "--correlation needs the pileups of this run (not with -P or --events-only)");
-  if (o.corrSkipZeros && !o.correlationFile) die("", "--corr-skip-zeros needs --correlation FILE");
+  if (o.spearmanFile && (o.peaksOnly || o.eventsOnly)) die("", "--spearman needs the pileups of this run (not with -P or --events-only)");
+  if (o.corrSkipZeros && !o.correlationFile && !o.spearmanFile) die("", "--corr-skip-zeros needs --correlation FILE or --spearman FILE");
   if (o.fingerprintFile && (o.peaksOnly || o.eventsOnly)) die("", "--fingerprint needs the pileups of this run (not with -P or --events-only)");
   if (o.fingerprintMetricsFile && !o.fingerprintFile) die("", "--fingerprint-metrics needs --fingerprint FILE");
-  if (o.correlationFile || o.fingerprintFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
+  if (o.correlationFile || o.fingerprintFile || o.spearmanFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
     auto split = [](const char* list) {
       std::vector<std::string> out;
       std::string l(list ? list : "");
@@ -2981,11 +3027,12 @@ int main(int argc, char** argv) {
     size_t n = t.size();
     for (size_t r = 0; r < t.size() && r < c.size(); r++) n += c[r] != "null";
     if (n > 32 && o.correlationFile) die("", "--correlation takes at most 32 samples");
+    if (n > 32 && o.spearmanFile) die("", "--spearman takes at most 32 samples");
     if (n > 32) die("", "--fingerprint takes at most 32 samples");
   }
-  if ((o.coverageScaleOpt && !o.coveragePrefix) || (o.binSizeOpt && !o.coveragePrefix && !o.correlationFile && !o.fingerprintFile))
+  if ((o.coverageScaleOpt && !o.coveragePrefix) || (o.binSizeOpt && !o.coveragePrefix && !o.correlationFile && !o.fingerprintFile && !o.spearmanFile))
     die("", "--bin-size and --coverage-scale need --coverage PREFIX");
-  if ((o.coveragePrefix || o.correlationFile || o.fingerprintFile) && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
+  if ((o.coveragePrefix || o.correlationFile || o.fingerprintFile || o.spearmanFile) && (o.binSize < 1 || o.binSize > (1 << 20))) die("", "--bin-size must be in [1, 1048576]");
   if ((o.profileBed != nullptr) != (o.profilePrefix != nullptr)) die("", "--profile BED and --profile-out PREFIX need each other");
   if ((o.flankOpt || o.profileBinOpt || o.profileAtOpt || o.profileMatrix) && !o.profileBed)
     die("", "--flank, --profile-bin, --profile-at and --profile-matrix need --profile BED");
@@ -3118,7 +3165,7 @@ int main(int argc, char** argv) {
     if (o.ctrlFile && r < cFiles.size() && cFiles[r] != "null") scanHeader(S, cFiles[r].c_str(), true);
   }
   sendChroms(S);
-  if (o.coveragePrefix || o.correlationFile || o.fingerprintFile)
+  if (o.coveragePrefix || o.correlationFile || o.fingerprintFile || o.spearmanFile)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
   ProfilePlan profilePlan;
   if (o.profileBed) {
@@ -3249,6 +3296,7 @@ int main(int argc, char** argv) {
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.coveragePrefix) writeCoverage(S, names);
   if (o.correlationFile) writeCorrelation(S);
+  if (o.spearmanFile) writeSpearman(S);
   if (o.fingerprintFile) writeFingerprint(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {

@@ -115,6 +115,14 @@ FP_SUB_LOG = 6                  # GX_FP_SUB_LOG
 FP_METRICS_DTYPE = np.dtype([(k, "<f8") for k in ("zero_fraction", "auc", "gini", "elbow_bins", "elbow_gap", "jsd_control")])   # gx_fp_metrics
 
 
+GX_PATH_SPEARMAN = 4194304      # gx_path_info bit 22: k_rank ran (gx_coverage_rank_gram, gx_rank_u64)
+
+
+class RankTable(C.Structure):
+    """gx_rank_table (value ascending, count) and gx_rank_lut (value ascending, rank2): the same layout."""
+    _fields_ = [("value", C.c_void_p), ("second", C.c_void_p), ("n", C.c_size_t)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int64), C.c_size_t, C.c_void_p)
 
 
@@ -222,6 +230,16 @@ _SIGS = {
     "gx_format_fingerprint_metrics": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "gx_coverage_fingerprint_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p],
     "gx_write_fingerprint_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_coverage_distinct": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_rank_tables": [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint64)],
+    "gx_coverage_rank_gram": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
+                              C.c_void_p, C.c_int],
+    "gx_coverage_spearman_group": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_write_spearman_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_distinct_u64": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_rank_u64": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)],
+    "gx_rank_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "gx_rank_last": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -381,6 +399,76 @@ def format_correlation(sample_names, n, n_zero, sums, gram, skip_zeros=False) ->
     names = _c_names(list(sample_names))
     return _to_tmpfile(lambda f: lib.gx_format_correlation(f, S, names, int(n), int(n_zero), s.ctypes.data, g.ctypes.data,
                                                            int(bool(skip_zeros))))
+
+
+def rank_geometry():
+    """(lanes, grid, cache_entries, first_capacity, load_limit) of k_rank_distinct as the library was built (gx_rank_geometry):
+    the lanes of a workgroup (two values each a step), the most workgroups by default, the entries of a workgroup's LDS cache,
+    the table's first capacity and the distinct non-zero values it takes before it grows (half of any capacity)."""
+    lib = load_library()
+    l, g, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    cap, lim = C.c_size_t(0), C.c_size_t(0)
+    lib.gx_rank_geometry(C.byref(l), C.byref(g), C.byref(c), C.byref(cap), C.byref(lim))
+    return l.value, g.value, c.value, cap.value, lim.value
+
+
+def _rank_structs(pairs):
+    """[(first, second)] -> (a RankTable array, the arrays it points to)."""
+    keep = []
+    arr = (RankTable * max(len(pairs), 1))()
+    for k, (a, b) in enumerate(pairs):
+        a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("a table is two equally long vectors")
+        keep += [a, b]
+        arr[k] = RankTable(a.ctypes.data if a.size else None, b.ctypes.data if b.size else None, a.size)
+    return arr, keep
+
+
+def rank_tables(tables, n_zero_to_drop=0):
+    """gx_rank_tables: tables[g][s] = (values ascending, counts) of context g's sample s -> (N, [(values, rank2) per sample]);
+    host-only, needs no GPU.  Raises where the library refuses."""
+    lib = load_library()
+    G, S = len(tables), len(tables[0]) if tables else 0
+    if any(len(t) != S for t in tables):
+        raise ValueError("every context has one table per sample")
+    arr, keep = _rank_structs([t for ctx in tables for t in ctx])
+    n_out = np.zeros(max(S, 1), dtype=np.uintp)
+    N = C.c_uint64(0)
+    rc = lib.gx_rank_tables(G, S, C.addressof(arr), int(n_zero_to_drop), None, None, 0, n_out.ctypes.data, C.byref(N))
+    if rc:
+        raise RuntimeError(f"gx_rank_tables: {rc}")
+    cap = int(n_out[:S].max()) if S else 0
+    vals = [np.zeros(cap, dtype=np.uint64) for _ in range(S)]
+    ranks = [np.zeros(cap, dtype=np.uint64) for _ in range(S)]
+    pv = (C.c_void_p * max(S, 1))(*[v.ctypes.data for v in vals])
+    pr = (C.c_void_p * max(S, 1))(*[r.ctypes.data for r in ranks])
+    rc = lib.gx_rank_tables(G, S, C.addressof(arr), int(n_zero_to_drop), pv, pr, cap, n_out.ctypes.data, C.byref(N))
+    if rc:
+        raise RuntimeError(f"gx_rank_tables: {rc}")
+    return N.value, [(vals[s][:int(n_out[s])], ranks[s][:int(n_out[s])]) for s in range(S)]
+
+
+def coverage_spearman_group(ctxs, skip_zeros=False):
+    """(N, sum, gram, n_distinct) of the rank rows over the contexts of a run (gx_coverage_spearman_group): Python ints, sum an
+    object array [S], gram [S, S], n_distinct the entries of each sample's merged table."""
+    lib = load_library()
+    S = ctxs[0].coverage_samples()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+    nd = np.zeros(max(S, 1), dtype=np.uint64)
+    N = C.c_uint64(0)
+    ctxs[0]._check(lib.gx_coverage_spearman_group(arr, len(ctxs), S, int(bool(skip_zeros)), C.byref(N), s.ctypes.data, g.ctypes.data,
+                                                  nd.ctypes.data))
+    return N.value, _join128(s[:S]), _join128(g[:S, :S]), [int(v) for v in nd[:S]]
+
+
+def spearman_text(ctxs, sample_names, skip_zeros=False) -> bytes:
+    """--spearman's matrix over the contexts of a run (gx_write_spearman_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    names = _c_names(list(sample_names))
+    return _to_tmpfile(lambda f: lib.gx_write_spearman_group(arr, len(ctxs), len(sample_names), names, int(bool(skip_zeros)), f))
 
 
 def fp_geometry():
@@ -680,7 +768,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -806,6 +894,56 @@ class Genrich:
         c, t = np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64), np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64)
         self._check(self.lib.gx_fp_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), c.ctypes.data, t.ctypes.data))
         return c[:n_rows], t[:n_rows]
+
+    # -- rank correlation of the samples' bins (include/genrich_amd.h, gx_coverage_distinct) -------------------------------
+    def coverage_distinct(self, sample):
+        """(values ascending, counts), uint64, of one closed sample's bins in this context (gx_coverage_distinct)."""
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_coverage_distinct(self.ctx, int(sample), None, None, 0, C.byref(n)))
+        v, c = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            self._check(self.lib.gx_coverage_distinct(self.ctx, int(sample), v.ctypes.data, c.ctypes.data, n.value, C.byref(n)))
+        return v, c
+
+    def coverage_rank_gram(self, luts, skip_zeros=False):
+        """(n, n_zero, sum, gram) of this context's rank rows by the samples' tables luts[s] = (values ascending, rank2)
+        (gx_coverage_rank_gram): Python ints, sum an object array [S], gram [S, S]."""
+        S = self.coverage_samples()
+        arr, keep = _rank_structs(list(luts))
+        s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+        ns, n, nz = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        if len(luts) != S:
+            raise ValueError("one table per sample")
+        self._check(self.lib.gx_coverage_rank_gram(self.ctx, C.addressof(arr), int(bool(skip_zeros)), C.byref(ns), C.byref(n), C.byref(nz),
+                                                   s.ctypes.data, g.ctypes.data, max(S, 1)))
+        return n.value, nz.value, _join128(s[:ns.value]), _join128(g[:ns.value, :ns.value])
+
+    def distinct_u64(self, row, grid=0):
+        """(values ascending, counts) of the row (uint64 [n], every value < 2^51) by the same kernels (gx_distinct_u64); grid = 0:
+        the library's geometry, else that many workgroups."""
+        r = np.ascontiguousarray(row, dtype=np.uint64)
+        n = C.c_size_t(0)
+        v, c = np.zeros(max(r.size, 1), dtype=np.uint64), np.zeros(max(r.size, 1), dtype=np.uint64)
+        self._check(self.lib.gx_distinct_u64(self.ctx, r.ctypes.data if r.size else None, r.size, int(grid), v.ctypes.data, c.ctypes.data,
+                                             v.size, C.byref(n)))
+        return v[:n.value], c[:n.value]
+
+    def rank_u64(self, rows, grid=0, skip_zeros=False):
+        """(rank2 uint64 [n_rows, n], n_zero) of the rows (uint64 [n_rows, n], every value < 2^51) ranked as the samples of one
+        context (gx_rank_u64); grid = 0: the library's geometry."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        n_rows, n = r.shape
+        out = np.zeros((n_rows, n), dtype=np.uint64)
+        nz = C.c_uint64(0)
+        self._check(self.lib.gx_rank_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), int(bool(skip_zeros)),
+                                         out.ctypes.data if out.size else None, C.byref(nz)))
+        return out, nz.value
+
+    def rank_last(self):
+        """(capacity, n_grown) of this context's last k_rank_distinct pass (gx_rank_last); capacity 0: none yet."""
+        cap, g = C.c_size_t(0), C.c_int(0)
+        self._check(self.lib.gx_rank_last(self.ctx, C.byref(cap), C.byref(g)))
+        return cap.value, g.value
 
     # -- profiles around anchors (include/genrich_amd.h, gx_set_profile) -------------------------------------------------
     def set_profile(self, anchors, flank, bin_size, keep_matrix=False):

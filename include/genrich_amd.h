@@ -397,6 +397,77 @@ uint32_t gx_fp_class(uint64_t x);
 uint64_t gx_fp_class_lo(uint32_t k);
 uint64_t gx_fp_class_hi(uint32_t k);
 
+/* ---- Spearman (rank) correlation of the samples from their coverage bins (no Genrich counterpart: what deepTools'
+ *      multiBamSummary + plotCorrelation --corMethod spearman take from a second reading of every BAM) ----
+ * Samples and x_s[b] are gx_coverage_gram's, over all bins of ALL contexts, a chromosome's short last bin as it is.  Let B be the
+ * set of ranked bins: all n of them, or with skip_zeros the n - n_zero bins that are not 0 in every sample (they are taken out
+ * BEFORE ranking, as deepTools does: unlike Pearson's sums, the ranks of the bins that stay change).  For a value v of sample s
+ *     less_s(v)  = #{b in B : x_s[b] <  v}
+ *     equal_s(v) = #{b in B : x_s[b] == v}
+ *     R_s[b]     = 2 less_s(x_s[b]) + equal_s(x_s[b]) + 1      for b in B;        R_s[b] = 0 for b outside B
+ * R_s[b] is twice the average rank of bin b (ranks counted from 1, ties sharing their mean): an integer, so ties need no
+ * fractions, and a correlation does not change when both of its rows are doubled.  A rank is at least 1, so a bin outside B
+ * adds nothing to any sum and the Gram pass's own count of all-zero rows counts exactly the bins left out.  Spearman's rho is
+ * Pearson's r of the rank rows over B: with N = |B| and sum / gram the exact sums of R over all contexts
+ *     rho = gx_correlation_matrix(S, N, 0, sum, gram, 0)
+ * Bounds, each refused with GX_ERR_ORDER: at most 32 samples; at most 2^30 bins in a context; N < 2^41 over all contexts, so
+ * that R <= 2 N < 2^42 and a sum of products is at most N (2 N)^2 = 4 N^3 < 2^125, inside gx_u128 (4 N^3 < 2^128 needs
+ * N < 2^42); N gram < 4 N^4 < 2^166 and sum_i sum_j <= (N (2 N))^2 < 2^166 are inside gx_correlation_matrix's 256-bit
+ * differences (they would be up to N < 2^63).  Everything is an integer: a result depends neither on the launch geometry nor
+ * on the number of contexts nor on the order in which a table on the device was filled (tables are sorted by value before
+ * anything leaves the library).
+ *
+ * gx_coverage_distinct: one closed sample's distinct bin values over this context's bins, ascending, and how many bins hold
+ *   each (k_rank_distinct, k_rank_compact: gx_rank.h).  Order rules: gx_coverage_gram's (coverage bins on, a closed sample, no
+ *   sample open, at most 32 samples), a sample index outside the closed samples: GX_ERR_ORDER.  cap = 0: only *n_distinct; else
+ *   value[cap] and count[cap] are filled, GX_ERR_ORDER (with *n_distinct set) when cap is too small.  A context without bins: 0.
+ * gx_rank_tables: host only, no context.  tables[g * n_samples + s] is context g's table of sample s as gx_coverage_distinct
+ *   gives it (strictly ascending values, counts in [1, 2^41)).  Per sample the contexts' tables are merged (equal values add),
+ *   n_zero_to_drop is taken off the count of value 0 (0 without skip_zeros; an entry that reaches 0 disappears), and
+ *   value[s][k], rank2[s][k] = the merged values ascending and 2 less + equal + 1 of each; n_out[s] = how many.  value and rank2
+ *   hold cap entries per sample; both NULL: only n_out and *n_ranked (= N, the same for every sample).  GX_ERR_ORDER: a table
+ *   out of order, a count of 0, more to drop than a sample has zeros, samples that differ in N, N >= 2^41, cap too small.
+ * gx_coverage_rank_gram: k_rank over this context's bins with the given tables (n_samples of them; value ascending and
+ *   never 2^64 - 1, rank2 in [1, 2^42); else GX_ERR_ORDER), then the Gram pass (k_gram, k_gram_sum) over the rank rows: sum and gram as gx_coverage_gram lays them out.
+ *   *n_zero = the bins of this context that are 0 in every sample, counted by k_rank itself whether or not they are left out.
+ *   A bin's value that is not in its sample's table: GX_ERR_ORDER.  Order rules: gx_coverage_gram's.
+ * gx_coverage_spearman_group: the whole pass over the contexts of a run: every context's tables (and with skip_zeros its
+ *   all-zero bins, k_rank_nzero), gx_rank_tables, every context's gx_coverage_rank_gram, added with carries.  *n_ranked = N;
+ *   n_distinct[n_samples] (may be NULL) = the entries of each sample's merged table.  sum and gram are required.
+ * gx_write_spearman_group: that, then gx_format_correlation(out, S, names, N, 0, sum, gram, 0): --correlation's text rules.
+ * gx_distinct_u64 / gx_rank_u64: the same kernels over rows the caller gives (host memory; n_rows rows of n values, row after
+ *   row; copied to the device by the call).  Domain: every value < 2^51, n <= 2^24, 1 <= n_rows <= 32, grid <= 65535, else
+ *   GX_ERR_ORDER before anything is launched.  grid = 0: the library's geometry, else that many workgroups.  gx_rank_u64 ranks
+ *   the rows as the samples of one context (rank2[n_rows * n], may be NULL) and gives the all-zero bins in *n_zero.
+ * gx_rank_geometry: what their edge cases depend on: the lanes of a workgroup of k_rank_distinct (each takes two values a
+ *   step), the most workgroups with grid = 0, the entries of a workgroup's LDS cache, the table's first capacity and the most
+ *   distinct non-zero values it takes before it grows (the same half of every capacity).  Any pointer may be NULL.
+ * gx_rank_last: the capacity the last k_rank_distinct pass of this context ended with (0: none yet) and how often it grew.
+ * Nothing of all this is allocated or launched before the first call. */
+typedef struct {
+  const uint64_t* value;   /* ascending */
+  const uint64_t* count;
+  size_t n;
+} gx_rank_table;
+typedef struct {
+  const uint64_t* value;   /* ascending */
+  const uint64_t* rank2;
+  size_t n;
+} gx_rank_lut;
+int gx_coverage_distinct(gx_ctx* ctx, int sample, uint64_t* value, uint64_t* count, size_t cap, size_t* n_distinct);
+int gx_rank_tables(int n_ctx, int n_samples, const gx_rank_table* tables, uint64_t n_zero_to_drop, uint64_t* const* value,
+                   uint64_t* const* rank2, size_t cap, size_t* n_out, uint64_t* n_ranked);
+int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros, int* n_samples, uint64_t* n_bins, uint64_t* n_zero,
+                          gx_u128* sum, gx_u128* gram, int cap);
+int gx_coverage_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, int skip_zeros, uint64_t* n_ranked, gx_u128* sum,
+                               gx_u128* gram, uint64_t* n_distinct);
+int gx_distinct_u64(gx_ctx* ctx, const uint64_t* row, size_t n, unsigned grid, uint64_t* value, uint64_t* count, size_t cap,
+                    size_t* n_distinct);
+int gx_rank_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, int skip_zeros, uint64_t* rank2,
+                uint64_t* n_zero);
+int gx_rank_geometry(int* lanes, int* grid, int* cache_entries, size_t* first_capacity, size_t* load_limit);
+int gx_rank_last(gx_ctx* ctx, size_t* capacity, int* n_grown);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -530,6 +601,8 @@ int gx_format_correlation(FILE* out, int n_samples, const char* const* sample_na
                           const gx_u128* sum, const gx_u128* gram, int skip_zeros);
 int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros,
                                FILE* out);
+/* --spearman (no Genrich counterpart; defined with gx_coverage_spearman_group above): --correlation's text, of the rank rows */
+int gx_write_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, int skip_zeros, FILE* out);
 /* --fingerprint (no Genrich counterpart).  The first three: host only, no context; count and sum are [n_samples][GX_FP_NC] as
  * gx_coverage_fingerprint gives them, ctrl_of[s] is the sample index of s's control or -1 (ctrl_of == NULL: all -1).
  * gx_fingerprint_metrics: the figures defined above, NaN where they are not.
@@ -640,6 +713,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_PROFILE 524288u /* bit 19: this run summed its samples' pileups around anchors (gx_set_profile; a sample was closed with it on since the last gx_reset) */
 #define GX_PATH_GRAM 1048576u /* bit 20: k_gram / k_gram_sum ran since the last gx_reset (gx_coverage_gram, gx_gram_u64) */
 #define GX_PATH_FINGERPRINT 2097152u /* bit 21: k_fp_hist ran since the last gx_reset (gx_coverage_fingerprint, gx_fp_u64) */
+#define GX_PATH_SPEARMAN 4194304u /* bit 22: k_rank ran since the last gx_reset (gx_coverage_rank_gram, gx_rank_u64) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
