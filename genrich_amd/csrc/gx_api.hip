@@ -11,6 +11,7 @@
 #include "gx_host_regions.h"
 #include "gx_host_coverage.h"
 #include "gx_host_profile.h"
+#include "gx_host_binstat.h"
 #include "gx_host_gram.h"
 #include "gx_host_fingerprint.h"
 #include "gx_host_rank.h"
@@ -1068,70 +1069,31 @@ int gx_write_profile_rows_group(gx_ctx* const* ctxs, int n_ctx, int sample, cons
 }
 
 int gx_coverage_gram(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram, int cap) {
-  if (!ctx || !ctx->covW || ctx->cov.empty() || ctx->phase == 1 || ctx->phase == 3) return GX_ERR_ORDER;
-  const size_t S = ctx->cov.size();
-  const char* why = nullptr;
-  if (S > GRAM_MAX_S) why = "more than 32 samples for the correlation";
-  else if ((sum || gram) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_gram: cap is smaller than the number of samples";
-  if (!why && ctx->covDirty)
-    if (int rc = cov_layout(ctx)) return rc;
-  u64 G = 0;   // (the lengths are u32, a table has fewer than 2^31 entries: no overflow)
-  for (u32 c = 0; c < ctx->nChrom; c++)
-    if (cov_has_bins(ctx, c)) G += ctx->len[c];
-  if (!why && (u128)ctx->covW * (u128)G > ((u128)1 << 64)) why = "bin size times genome length above 2^64: the correlation's sums could overflow";
-  if (why) {
-    ctx->err = why;
-    return GX_ERR_ORDER;
-  }
+  BinRows b;
+  if (int rc = stat_cov_rows(ctx, "the correlation", b)) return rc;
+  if (int rc = stat_cap(ctx, "gx_coverage_gram", sum || gram, cap, b.rows.size())) return rc;
+  if ((u128)ctx->covW * (u128)b.G > ((u128)1 << 64))
+    return stat_refuse(ctx, "bin size times genome length above 2^64: the correlation's sums could overflow");
   HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<const void*> rows(S);
-  for (size_t i = 0; i < S; i++) rows[i] = ctx->cov[i].bins.p;
-  const u64 n = ctx->covOff[ctx->nChrom];
   u64 nz = 0;
   std::vector<gx_u128> s1, g1;
-  if (int rc = gram_pass(ctx, rows, n, 0, &nz, s1, g1)) return rc;
-  if (n_samples) *n_samples = (int)S;
-  if (n_bins) *n_bins = n;
+  if (int rc = gram_pass(ctx, b.rows, b.n, 0, &nz, s1, g1)) return rc;
+  if (n_samples) *n_samples = (int)b.rows.size();
+  if (n_bins) *n_bins = b.n;
   if (n_zero) *n_zero = nz;
-  if (sum) std::copy(s1.begin(), s1.end(), sum);
-  if (gram)
-    for (size_t i = 0; i < S; i++) std::copy(g1.begin() + i * S, g1.begin() + (i + 1) * S, gram + i * (size_t)cap);
+  stat_give_sums(s1, g1, sum, gram, (size_t)cap);
   return GX_OK;
 }
 
 int gx_gram_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* n_zero, gx_u128* sum, gx_u128* gram) {
-  if (!ctx) return GX_ERR_ORDER;
-  const char* why = nullptr;
-  if (n_rows < 1 || n_rows > (int)GRAM_MAX_S) why = "gx_gram_u64: the number of rows is outside [1, 32]";
-  else if (n > ((size_t)1 << 24)) why = "gx_gram_u64: more than 2^24 values a row";
-  else if (n && !rows) why = "gx_gram_u64: no rows";
-  else if (grid > GRAM_MAX_GRID) why = "gx_gram_u64: a grid of more than 65535 workgroups";
-  if (why) {
-    ctx->err = why;
-    return GX_ERR_ORDER;
-  }
-  for (size_t k = 0; k < (size_t)n_rows * n; k++)
-    if (rows[k] >> 51) {
-      ctx->err = "gx_gram_u64: a value of 2^51 or more";
-      return GX_ERR_ORDER;
-    }
-  HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<const void*> dev((size_t)n_rows, nullptr);
-  if (n) {
-    if (pooled(ctx, ctx->gramIn, (size_t)n_rows * n * 8) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->err = "Cannot allocate memory";
-      return GX_ERR_MEM;
-    }
-    HIPCHECK(hipMemcpyAsync(ctx->gramIn.p, rows, (size_t)n_rows * n * 8, hipMemcpyHostToDevice, ctx->stream));
-    for (int r = 0; r < n_rows; r++) dev[r] = ctx->gramIn.as<uint64_t>() + (size_t)r * n;
-  }
+  if (int rc = stat_u64_domain(ctx, "gx_gram_u64", rows, n_rows, n, grid, true)) return rc;
+  std::vector<const void*> dev;
+  if (int rc = stat_stage_rows(ctx, rows, n_rows, n, dev)) return rc;
   u64 nz = 0;
   std::vector<gx_u128> s1, g1;
   if (int rc = gram_pass(ctx, dev, n, grid, &nz, s1, g1)) return rc;
   if (n_zero) *n_zero = nz;
-  if (sum) std::copy(s1.begin(), s1.end(), sum);
-  if (gram) std::copy(g1.begin(), g1.end(), gram);
+  stat_give_sums(s1, g1, sum, gram, (size_t)n_rows);
   return GX_OK;
 }
 
@@ -1145,8 +1107,7 @@ int gx_gram_geometry(int* tile, int* lanes, int* grid) {
 // (the two over contexts live here, not in gx_emit.cpp, like the profile's group writers: they read contexts)
 int gx_coverage_gram_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram) {
   if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)GRAM_MAX_S || !sum || !gram) return GX_ERR_ORDER;
-  const size_t S = (size_t)n_samples;
-  std::vector<u128> st(S, 0), gt(S * S, 0);
+  Sums128 total((size_t)n_samples);
   uint64_t n = 0, nz = 0;
   for (int g = 0; g < n_ctx; g++) {
     int s = 0;
@@ -1155,11 +1116,9 @@ int gx_coverage_gram_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64
     if (s != n_samples) return GX_ERR_ORDER;
     n += n1;
     nz += nz1;
-    for (size_t k = 0; k < S; k++) st[k] += ((u128)sum[k].hi << 64) | sum[k].lo;
-    for (size_t k = 0; k < S * S; k++) gt[k] += ((u128)gram[k].hi << 64) | gram[k].lo;
+    total.add(sum, gram);
   }
-  for (size_t k = 0; k < S; k++) sum[k] = gx_u128{(uint64_t)st[k], (uint64_t)(st[k] >> 64)};
-  for (size_t k = 0; k < S * S; k++) gram[k] = gx_u128{(uint64_t)gt[k], (uint64_t)(gt[k] >> 64)};
+  total.give(sum, gram);
   if (n_bins) *n_bins = n;
   if (n_zero) *n_zero = nz;
   return GX_OK;
@@ -1174,73 +1133,30 @@ int gx_write_correlation_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, co
 }
 
 int gx_coverage_fingerprint(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum, int cap) {
-  if (!ctx || !ctx->covW || ctx->cov.empty() || ctx->phase == 1 || ctx->phase == 3) return GX_ERR_ORDER;
-  const size_t S = ctx->cov.size();
-  const char* why = nullptr;
-  if (S > FP_MAX_S) why = "more than 32 samples for the fingerprint";
-  else if ((count || sum) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_fingerprint: cap is smaller than the number of samples";
-  if (!why && ctx->covDirty)
-    if (int rc = cov_layout(ctx)) return rc;
-  u64 G = 0;   // (the lengths are u32, a table has fewer than 2^31 entries: no overflow)
-  for (u32 c = 0; c < ctx->nChrom; c++)
-    if (cov_has_bins(ctx, c)) G += ctx->len[c];
-  if (!why && G >= ((u64)1 << 33)) why = "a genome of 2^33 bases or more: the fingerprint's sums could overflow";
-  if (why) {
-    ctx->err = why;
-    return GX_ERR_ORDER;
-  }
+  BinRows b;
+  if (int rc = stat_cov_rows(ctx, "the fingerprint", b)) return rc;
+  if (int rc = stat_cap(ctx, "gx_coverage_fingerprint", count || sum, cap, b.rows.size())) return rc;
+  if (b.G >= ((u64)1 << 33)) return stat_refuse(ctx, "a genome of 2^33 bases or more: the fingerprint's sums could overflow");
   HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<const void*> rows(S);
-  for (size_t i = 0; i < S; i++) rows[i] = ctx->cov[i].bins.p;   // (each the start of an allocation: aligned)
-  const u64 n = ctx->covOff[ctx->nChrom];
   std::vector<uint64_t> c1, s1;
-  if (int rc = fp_pass(ctx, rows, n, 0, c1, s1)) return rc;
-  if (n_samples) *n_samples = (int)S;
-  if (n_bins) *n_bins = n;
+  if (int rc = fp_pass(ctx, b.rows, b.n, 0, c1, s1)) return rc;
+  if (n_samples) *n_samples = (int)b.rows.size();
+  if (n_bins) *n_bins = b.n;
   if (count) std::copy(c1.begin(), c1.end(), count);
   if (sum) std::copy(s1.begin(), s1.end(), sum);
   return GX_OK;
 }
 
 int gx_fp_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, uint64_t* count, uint64_t* sum) {
-  if (!ctx) return GX_ERR_ORDER;
-  const char* why = nullptr;
-  if (n_rows < 1 || n_rows > (int)FP_MAX_S) why = "gx_fp_u64: the number of rows is outside [1, 32]";
-  else if (n > ((size_t)1 << 24)) why = "gx_fp_u64: more than 2^24 values a row";
-  else if (n && !rows) why = "gx_fp_u64: no rows";
-  else if (grid > FP_MAX_GRID) why = "gx_fp_u64: a grid of more than 65535 workgroups";
-  if (why) {
-    ctx->err = why;
-    return GX_ERR_ORDER;
-  }
-  // the device's rows start 16 bytes apart at least: an odd n is padded by one value no lane reads.  Every row is added in
-  // 128 bits on its way into the staging copy; a total of 2^64 or more is refused before anything reaches the device
-  const size_t pitch = (n + 1) & ~(size_t)1;
-  std::vector<uint64_t> staged((size_t)n_rows * pitch, 0);
+  if (int rc = stat_u64_domain(ctx, "gx_fp_u64", rows, n_rows, n, grid, false)) return rc;
+  // every row is added in 128 bits: a total of 2^64 or more is refused before anything reaches the device
   for (int r = 0; r < n_rows; r++) {
     u128 t = 0;
-    for (size_t k = 0; k < n; k++) {
-      const uint64_t v = rows[(size_t)r * n + k];
-      staged[(size_t)r * pitch + k] = v;
-      t += v;
-    }
-    if (t >> 64) {
-      ctx->err = "gx_fp_u64: a row's total of 2^64 or more";
-      return GX_ERR_ORDER;
-    }
+    for (size_t k = 0; k < n; k++) t += rows[(size_t)r * n + k];
+    if (t >> 64) return stat_refuse(ctx, "gx_fp_u64: a row's total of 2^64 or more");
   }
-  HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<const void*> dev((size_t)n_rows, nullptr);
-  if (n) {
-    if (pooled(ctx, ctx->fpIn, staged.size() * 8) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->err = "Cannot allocate memory";
-      return GX_ERR_MEM;
-    }
-    HIPCHECK(hipMemcpyAsync(ctx->fpIn.p, staged.data(), staged.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(hipStreamSynchronize(ctx->stream));   // (`staged` is this call's)
-    for (int r = 0; r < n_rows; r++) dev[r] = ctx->fpIn.as<uint64_t>() + (size_t)r * pitch;
-  }
+  std::vector<const void*> dev;
+  if (int rc = stat_stage_rows(ctx, rows, n_rows, n, dev)) return rc;
   std::vector<uint64_t> c1, s1;
   if (int rc = fp_pass(ctx, dev, n, grid, c1, s1)) return rc;
   if (count) std::copy(c1.begin(), c1.end(), count);
@@ -1289,71 +1205,38 @@ int gx_write_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, co
 }
 
 int gx_coverage_distinct(gx_ctx* ctx, int sample, uint64_t* value, uint64_t* count, size_t cap, size_t* n_distinct) {
-  std::vector<const void*> rows;
-  u64 n = 0;
-  if (int rc = rank_cov_rows(ctx, rows, &n)) return rc;
-  if (sample < 0 || (size_t)sample >= rows.size() || (cap && (!value || !count))) return GX_ERR_ORDER;
+  BinRows b;
+  if (int rc = rank_cov_rows(ctx, b)) return rc;
+  if (sample < 0 || (size_t)sample >= b.rows.size() || (cap && (!value || !count))) return GX_ERR_ORDER;
   std::vector<uint64_t> v, c;
-  if (int rc = rank_distinct_pass(ctx, rows[sample], n, 0, v, c)) return rc;
+  if (int rc = rank_distinct_pass(ctx, b.rows[sample], b.n, 0, v, c)) return rc;
   return rank_give_table(ctx, "gx_coverage_distinct", v, c, value, count, cap, n_distinct);
 }
 
 int gx_distinct_u64(gx_ctx* ctx, const uint64_t* row, size_t n, unsigned grid, uint64_t* value, uint64_t* count, size_t cap,
                     size_t* n_distinct) {
-  if (!ctx) return GX_ERR_ORDER;
-  if (const char* why = rank_u64_domain(row, 1, n, grid)) {
-    ctx->err = std::string("gx_distinct_u64: ") + why;
-    return GX_ERR_ORDER;
-  }
+  if (int rc = stat_u64_domain(ctx, "gx_distinct_u64", row, 1, n, grid, true)) return rc;
   if (cap && (!value || !count)) return GX_ERR_ORDER;
   std::vector<const void*> dev;
-  if (int rc = rank_stage_rows(ctx, row, 1, n, dev)) return rc;
+  if (int rc = stat_stage_rows(ctx, row, 1, n, dev)) return rc;
   std::vector<uint64_t> v, c;
   if (int rc = rank_distinct_pass(ctx, dev[0], n, grid, v, c)) return rc;
   return rank_give_table(ctx, "gx_distinct_u64", v, c, value, count, cap, n_distinct);
 }
 
 int gx_rank_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned grid, int skip_zeros, uint64_t* rank2, uint64_t* n_zero) {
-  if (!ctx) return GX_ERR_ORDER;
-  if (const char* why = rank_u64_domain(rows, n_rows, n, grid)) {
-    ctx->err = std::string("gx_rank_u64: ") + why;
-    return GX_ERR_ORDER;
-  }
-  const size_t S = (size_t)n_rows;
-  std::vector<const void*> dev;
-  if (int rc = rank_stage_rows(ctx, rows, n_rows, n, dev)) return rc;
-  u64 nz = 0;
-  if (skip_zeros)
-    if (int rc = rank_nzero_pass(ctx, dev, n, &nz)) return rc;
-  std::vector<std::vector<uint64_t>> v(S), c(S), lv(S), lr(S);
-  std::vector<gx_rank_table> tabs(S);
-  size_t most = 0;
-  for (size_t i = 0; i < S; i++) {
-    if (int rc = rank_distinct_pass(ctx, dev[i], n, grid, v[i], c[i])) return rc;
-    tabs[i] = gx_rank_table{v[i].data(), c[i].data(), v[i].size()};
-    most = std::max(most, v[i].size());
-  }
-  std::vector<uint64_t*> pv(S), pr(S);
-  for (size_t i = 0; i < S; i++) {
-    lv[i].resize(most);
-    lr[i].resize(most);
-    pv[i] = lv[i].data();
-    pr[i] = lr[i].data();
-  }
-  std::vector<size_t> nOut(S, 0);
-  if (int rc = gx_rank_tables(1, n_rows, tabs.data(), nz, pv.data(), pr.data(), most, nOut.data(), nullptr)) {
-    ctx->err = "gx_rank_u64: the rows' tables do not make rank tables";
-    return rc;
-  }
-  std::vector<gx_rank_lut> lut(S);
-  for (size_t i = 0; i < S; i++) lut[i] = gx_rank_lut{lv[i].data(), lr[i].data(), nOut[i]};
+  if (int rc = stat_u64_domain(ctx, "gx_rank_u64", rows, n_rows, n, grid, true)) return rc;
+  std::vector<RankGroup> one(1, RankGroup{ctx, {}, n});
+  if (int rc = stat_stage_rows(ctx, rows, n_rows, n, one[0].rows)) return rc;
+  RankTables t;
+  if (int rc = rank_make_tables(one, grid, skip_zeros != 0, "gx_rank_u64: the rows' tables do not make rank tables", t)) return rc;
   std::vector<const void*> out;
-  u64 nz2 = 0;
-  if (int rc = rank_rows_pass(ctx, dev, n, grid, skip_zeros != 0, lut.data(), out, &nz2)) return rc;
-  if (n_zero) *n_zero = nz2;
+  u64 nz = 0;
+  if (int rc = rank_rows_pass(ctx, one[0].rows, n, grid, skip_zeros != 0, t.lut.data(), out, &nz)) return rc;
+  if (n_zero) *n_zero = nz;
   if (rank2 && n) {
-    for (size_t i = 0; i < S; i++)
-      HIPCHECK(hipMemcpyAsync(rank2 + i * n, out[i], n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    for (int i = 0; i < n_rows; i++)
+      HIPCHECK(hipMemcpyAsync(rank2 + (size_t)i * n, out[i], n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(hipStreamSynchronize(ctx->stream));
   }
   return GX_OK;
@@ -1377,32 +1260,25 @@ int gx_rank_last(gx_ctx* ctx, size_t* capacity, int* n_grown) {
 
 int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros, int* n_samples, uint64_t* n_bins, uint64_t* n_zero,
                           gx_u128* sum, gx_u128* gram, int cap) {
-  std::vector<const void*> rows;
-  u64 n = 0;
-  if (int rc = rank_cov_rows(ctx, rows, &n)) return rc;
-  const size_t S = rows.size();
-  const char* why = nullptr;
-  if (!tables || !rank_lut_ok(tables, S)) why = "gx_coverage_rank_gram: a table is not ascending, holds the value 2^64 - 1, or a rank is outside [1, 2^42)";
-  else if ((sum || gram) && (cap < 0 || (size_t)cap < S)) why = "gx_coverage_rank_gram: cap is smaller than the number of samples";
-  if (why) {
-    ctx->err = why;
-    return GX_ERR_ORDER;
-  }
+  BinRows b;
+  if (int rc = rank_cov_rows(ctx, b)) return rc;
+  const size_t S = b.rows.size();
+  if (!tables || !rank_lut_ok(tables, S))
+    return stat_refuse(ctx, "gx_coverage_rank_gram: a table is not ascending, holds the value 2^64 - 1, or a rank is outside [1, 2^42)");
+  if (int rc = stat_cap(ctx, "gx_coverage_rank_gram", sum || gram, cap, S)) return rc;
   std::vector<const void*> ranks;
   u64 nz = 0, nzGram = 0;
-  if (int rc = rank_rows_pass(ctx, rows, n, 0, skip_zeros != 0, tables, ranks, &nz)) return rc;
+  if (int rc = rank_rows_pass(ctx, b.rows, b.n, 0, skip_zeros != 0, tables, ranks, &nz)) return rc;
   std::vector<gx_u128> s1, g1;
-  if (int rc = gram_pass(ctx, ranks, n, 0, &nzGram, s1, g1)) return rc;
+  if (int rc = gram_pass(ctx, ranks, b.n, 0, &nzGram, s1, g1)) return rc;
   if (skip_zeros && nzGram != nz) {   // (a rank is at least 1: the rows that are 0 everywhere are the bins left out)
     ctx->err = "gx_coverage_rank_gram: the rank rows' zero bins are not the bins left out";
     return GX_ERR_DEVICE;
   }
   if (n_samples) *n_samples = (int)S;
-  if (n_bins) *n_bins = n;
+  if (n_bins) *n_bins = b.n;
   if (n_zero) *n_zero = nz;
-  if (sum) std::copy(s1.begin(), s1.end(), sum);
-  if (gram)
-    for (size_t i = 0; i < S; i++) std::copy(g1.begin() + i * S, g1.begin() + (i + 1) * S, gram + i * (size_t)cap);
+  stat_give_sums(s1, g1, sum, gram, (size_t)cap);
   return GX_OK;
 }
 
@@ -1410,70 +1286,33 @@ int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros
 int gx_coverage_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, int skip_zeros, uint64_t* n_ranked, gx_u128* sum, gx_u128* gram,
                                uint64_t* n_distinct) {
   if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)RK_MAX_S || !sum || !gram) return GX_ERR_ORDER;
-  const size_t S = (size_t)n_samples, G = (size_t)n_ctx;
-  // 1. every context's tables, and with skip_zeros its all-zero bins
-  std::vector<std::vector<uint64_t>> v(G * S), c(G * S);
-  std::vector<gx_rank_table> tabs(G * S);
-  uint64_t nzAll = 0;
-  std::vector<size_t> room(S, 0);
-  for (size_t g = 0; g < G; g++) {
-    std::vector<const void*> rows;
-    u64 n = 0;
-    if (int rc = rank_cov_rows(ctxs[g], rows, &n)) return rc;
-    if (rows.size() != S) {
-      ctxs[g]->err = "gx_coverage_spearman_group: a context has another number of samples";
-      return GX_ERR_ORDER;
-    }
-    if (skip_zeros) {
-      u64 nz = 0;
-      if (int rc = rank_nzero_pass(ctxs[g], rows, n, &nz)) return rc;
-      nzAll += nz;
-    }
-    for (size_t i = 0; i < S; i++) {
-      const size_t k = g * S + i;
-      if (int rc = rank_distinct_pass(ctxs[g], rows[i], n, 0, v[k], c[k])) return rc;
-      tabs[k] = gx_rank_table{v[k].data(), c[k].data(), v[k].size()};
-      room[i] += v[k].size();
-    }
+  const size_t S = (size_t)n_samples;
+  // 1. every context's rows, then the rank tables over all contexts (with skip_zeros without the all-zero bins)
+  std::vector<RankGroup> groups;
+  for (int g = 0; g < n_ctx; g++) {
+    BinRows b;
+    if (int rc = rank_cov_rows(ctxs[g], b)) return rc;
+    if (b.rows.size() != S) return stat_refuse(ctxs[g], "gx_coverage_spearman_group: a context has another number of samples");
+    groups.push_back(RankGroup{ctxs[g], std::move(b.rows), b.n});
   }
-  // 2. the rank tables over all contexts
-  const size_t most = *std::max_element(room.begin(), room.end());
-  std::vector<std::vector<uint64_t>> lv(S), lr(S);
-  std::vector<uint64_t*> pv(S), pr(S);
-  for (size_t i = 0; i < S; i++) {
-    lv[i].resize(most);
-    lr[i].resize(most);
-    pv[i] = lv[i].data();
-    pr[i] = lr[i].data();
-  }
-  std::vector<size_t> nOut(S, 0);
-  uint64_t N = 0;
-  if (int rc = gx_rank_tables(n_ctx, n_samples, tabs.data(), nzAll, pv.data(), pr.data(), most, nOut.data(), &N)) {
-    for (size_t g = 0; g < G; g++) ctxs[g]->err = "the contexts' tables do not make rank tables (more than 2^41 bins?)";
-    return rc;
-  }
-  std::vector<gx_rank_lut> lut(S);
-  for (size_t i = 0; i < S; i++) lut[i] = gx_rank_lut{lv[i].data(), lr[i].data(), nOut[i]};
-  // 3. every context's rank rows and their sums, added with carries
-  std::vector<u128> st(S, 0), gt(S * S, 0);
+  RankTables t;
+  if (int rc = rank_make_tables(groups, 0, skip_zeros != 0, "the contexts' tables do not make rank tables (more than 2^41 bins?)", t)) return rc;
+  // 2. every context's rank rows and their sums, added with carries
+  Sums128 total(S);
   uint64_t nzSeen = 0;
-  for (size_t g = 0; g < G; g++) {
-    int s = 0;
+  for (int g = 0; g < n_ctx; g++) {
     uint64_t nz1 = 0;
-    if (int rc = gx_coverage_rank_gram(ctxs[g], lut.data(), skip_zeros, &s, nullptr, &nz1, sum, gram, n_samples)) return rc;
+    if (int rc = gx_coverage_rank_gram(ctxs[g], t.lut.data(), skip_zeros, nullptr, nullptr, &nz1, sum, gram, n_samples)) return rc;
     nzSeen += nz1;
-    for (size_t k = 0; k < S; k++) st[k] += ((u128)sum[k].hi << 64) | sum[k].lo;
-    for (size_t k = 0; k < S * S; k++) gt[k] += ((u128)gram[k].hi << 64) | gram[k].lo;
+    total.add(sum, gram);
   }
-  if (skip_zeros && nzSeen != nzAll) {
-    for (size_t g = 0; g < G; g++) ctxs[g]->err = "gx_coverage_spearman_group: the bins left out are not the all-zero bins counted";
+  if (skip_zeros && nzSeen != t.nZero) {
+    for (int g = 0; g < n_ctx; g++) ctxs[g]->err = "gx_coverage_spearman_group: the bins left out are not the all-zero bins counted";
     return GX_ERR_DEVICE;
   }
-  for (size_t k = 0; k < S; k++) sum[k] = gx_u128{(uint64_t)st[k], (uint64_t)(st[k] >> 64)};
-  for (size_t k = 0; k < S * S; k++) gram[k] = gx_u128{(uint64_t)gt[k], (uint64_t)(gt[k] >> 64)};
-  if (n_ranked) *n_ranked = N;
-  if (n_distinct)
-    for (size_t i = 0; i < S; i++) n_distinct[i] = nOut[i];
+  total.give(sum, gram);
+  if (n_ranked) *n_ranked = t.nRanked;
+  if (n_distinct) std::copy(t.nDistinct.begin(), t.nDistinct.end(), n_distinct);
   return GX_OK;
 }
 

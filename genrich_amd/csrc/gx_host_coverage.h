@@ -42,11 +42,7 @@ int cov_sample(gx_ctx* ctx, int isCtrl) {
   cs.rep = ctx->sample;
   cs.ctrl = isCtrl != 0;
   const size_t nBins = ctx->covOff[ctx->nChrom];
-  if (pooled(ctx, cs.bins, std::max<size_t>(nBins, 1) * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
+  POOLED(ctx, cs.bins, std::max<size_t>(nBins, 1) * 8);
   if (nBins) {
     phase_begin(ctx, isCtrl ? "c.cover" : "t.cover");   // (the zeroing, with -E regions the tight arrays, the pass)
     HIPCHECK(hipMemsetAsync(cs.bins.p, 0, nBins * 8, s));

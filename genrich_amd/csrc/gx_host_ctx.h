@@ -443,20 +443,18 @@ struct gx_ctx {
   DevBuf profDev;                 // ProfAnchor per anchor
   DevBuf profPartial;             // k_profile's workgroups' sums
   std::vector<ProfSample> prof;   // until gx_reset
-  // the samples' Gram sums (gx_coverage_gram / gx_gram_u64, gx_gram.h): nothing here exists before the first call
-  DevBuf gramRows;                // the row pointers for the device
-  DevBuf gramIn;                  // gx_gram_u64's copy of the caller's rows
+  // the statistics over the bins (gx_host_binstat.h) share two buffers; nothing here exists before the first call.  Sharing is
+  // safe because every pass that uses them drains the stream before it returns (each reads its results back): no pass is in
+  // flight when the next one stages rows or uploads pointers.
+  DevBuf statRows;                // the row pointers for the device: the 32 rows read, then the 32 rows written
+  DevBuf statIn;                  // the *_u64 hooks' copy of the caller's rows
+  // the samples' Gram sums (gx_coverage_gram / gx_gram_u64, gx_gram.h)
   DevBuf gramPartial, gramOut;    // k_gram's workgroups' sums, k_gram_sum's totals
   bool gramUsed = false;          // the kernels ran since the last gx_reset
-  // the samples' fingerprint histograms (gx_coverage_fingerprint / gx_fp_u64, gx_fingerprint.h): nothing here exists before the first call
-  DevBuf fpRows;                  // the row pointers for the device
-  DevBuf fpIn;                    // gx_fp_u64's copy of the caller's rows
+  // the samples' fingerprint histograms (gx_coverage_fingerprint / gx_fp_u64, gx_fingerprint.h)
   DevBuf fpOut;                   // count[S][FP_NC], sum[S][FP_NC]
   bool fpUsed = false;            // the kernel ran since the last gx_reset
-  // the samples' rank rows (gx_coverage_distinct / gx_coverage_rank_gram / gx_distinct_u64 / gx_rank_u64, gx_rank.h): nothing
-  // here exists before the first call
-  DevBuf rankRows;                // the row pointers for the device: the S rows read, then the S rows written
-  DevBuf rankIn;                  // gx_distinct_u64's / gx_rank_u64's copy of the caller's rows
+  // the samples' rank rows (gx_coverage_distinct / gx_coverage_rank_gram / gx_distinct_u64 / gx_rank_u64, gx_rank.h)
   DevBuf rankTab, rankCtl;        // k_rank_distinct's table (keys, then counts) and the control words (RKC_*)
   DevBuf rankPairs;               // k_rank_compact's (value, count) pairs
   DevBuf rankLut;                 // k_rank's tables: the samples' values, their rank2, the offsets
@@ -498,6 +496,17 @@ hipError_t pooled(gx_ctx* ctx, DevBuf& b, size_t bytes) {
 void recycle(gx_ctx* ctx, DevBuf& b) {
   if (b.p) ctx->pool.push_back(std::move(b));
 }
+
+// pooled() failed: the runtime's sticky error is cleared, the context says "Cannot allocate memory"
+int pool_failed(gx_ctx* ctx) {
+  (void)hipGetLastError();
+  ctx->err = "Cannot allocate memory";
+  return GX_ERR_MEM;
+}
+#define POOLED(ctx, buf, bytes)                                                          \
+  do {                                                                                   \
+    if (pooled(ctx, buf, bytes) != hipSuccess) return pool_failed(ctx);                  \
+  } while (0)
 
 // misc device words (u32 indices into ctx->misc)
 enum { M_TICKET = 0, M_NIV = 1, M_BHCOUNT = 5, M_ALLONE = 6, M_BHOVF = 7, M_GENOME = 10 /* u64 */, M_NMERGED = 15, M_PSTAR = 14, M_VQ = 12 /* two words: k_bh_small */,

@@ -13,21 +13,16 @@ int fp_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32 grid, 
   // (a workgroup's step is two values a lane; with S rows the launch stays at FP_GRID workgroups: what is resident together)
   if (!grid) grid = (u32)std::min<u64>((n + 2 * lanes - 1) / (2 * lanes), std::max<u32>(FP_GRID / S, 1u));
   const size_t outBytes = (size_t)2 * S * FP_NC * 8;
-  if (pooled(ctx, ctx->fpRows, FP_MAX_S * sizeof(void*)) != hipSuccess || pooled(ctx, ctx->fpOut, (size_t)2 * FP_MAX_S * FP_NC * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
+  POOLED(ctx, ctx->fpOut, (size_t)2 * FP_MAX_S * FP_NC * 8);
+  if (int rc = stat_upload_rows(ctx, rows)) return rc;
   hipStream_t s = ctx->stream;
-  HIPCHECK(hipMemcpyAsync(ctx->fpRows.p, rows.data(), S * sizeof(void*), hipMemcpyHostToDevice, s));
-  HIPCHECK(hipStreamSynchronize(s));   // (`rows` is the caller's)
   phase_begin(ctx, "fingerprint");
   HIPCHECK(hipMemsetAsync(ctx->fpOut.p, 0, outBytes, s));
   if (ctx->knob.fpAgg)
-    hipLaunchKernelGGL(k_fp_hist<true>, dim3(grid, S), dim3(lanes), 0, s, ctx->fpRows.as<const unsigned long long*>(), n,
+    hipLaunchKernelGGL(k_fp_hist<true>, dim3(grid, S), dim3(lanes), 0, s, ctx->statRows.as<const unsigned long long*>(), n,
                        ctx->fpOut.as<unsigned long long>());
   else
-    hipLaunchKernelGGL(k_fp_hist<false>, dim3(grid, S), dim3(lanes), 0, s, ctx->fpRows.as<const unsigned long long*>(), n,
+    hipLaunchKernelGGL(k_fp_hist<false>, dim3(grid, S), dim3(lanes), 0, s, ctx->statRows.as<const unsigned long long*>(), n,
                        ctx->fpOut.as<unsigned long long>());
   if (int rc__ = dbg_sync(ctx, "k_fp_hist")) return rc__;
   phase_end(ctx);

@@ -15,17 +15,12 @@ int gram_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32 grid
   const u32 lanes = GRAM_NW * 64;
   if (!grid) grid = (u32)std::min<u64>((n + lanes - 1) / lanes, GRAM_GRID);
   const size_t outWords = (size_t)nY * GRAM_ACCS * 2;
-  if (pooled(ctx, ctx->gramRows, GRAM_MAX_S * sizeof(void*)) != hipSuccess || pooled(ctx, ctx->gramPartial, outWords * grid * 8) != hipSuccess ||
-      pooled(ctx, ctx->gramOut, outWords * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
+  POOLED(ctx, ctx->gramPartial, outWords * grid * 8);
+  POOLED(ctx, ctx->gramOut, outWords * 8);
+  if (int rc = stat_upload_rows(ctx, rows)) return rc;
   hipStream_t s = ctx->stream;
-  HIPCHECK(hipMemcpyAsync(ctx->gramRows.p, rows.data(), S * sizeof(void*), hipMemcpyHostToDevice, s));
-  HIPCHECK(hipStreamSynchronize(s));   // (`rows` is the caller's)
   phase_begin(ctx, "gram");
-  hipLaunchKernelGGL(k_gram, dim3(grid, nY), dim3(lanes), 0, s, ctx->gramRows.as<const unsigned long long*>(), S, n, nT,
+  hipLaunchKernelGGL(k_gram, dim3(grid, nY), dim3(lanes), 0, s, ctx->statRows.as<const unsigned long long*>(), S, n, nT,
                      ctx->gramPartial.as<unsigned long long>());
   if (int rc__ = dbg_sync(ctx, "k_gram")) return rc__;
   hipLaunchKernelGGL(k_gram_sum, dim3(nY), dim3(256), 0, s, ctx->gramPartial.as<unsigned long long>(), grid, ctx->gramOut.as<unsigned long long>());

@@ -34,11 +34,9 @@ int prof_sample(gx_ctx* ctx, int isCtrl) {
   ps.ctrl = isCtrl != 0;
   if (pooled(ctx, ps.agg, (size_t)nb * 8) != hipSuccess || (ctx->profKeep && pooled(ctx, ps.cells, (size_t)nA * nb * 8) != hipSuccess) ||
       pooled(ctx, ctx->profPartial, (size_t)grid * nb * 8) != hipSuccess) {
-    (void)hipGetLastError();
     recycle(ctx, ps.agg);
     recycle(ctx, ps.cells);
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
+    return pool_failed(ctx);
   }
   phase_begin(ctx, isCtrl ? "c.profile" : "t.profile");   // (with -E regions the tight arrays, the pass, the column sums)
   CovIn in{};

@@ -1,5 +1,6 @@
 // gx_host_rank.h -- the host side of the samples' rank rows (gx_rank.h): a row's distinct values through the table that grows,
-// the count of the all-zero bins, the rank rows from the uploaded tables.  (a part of gx_api.hip's translation unit)
+// the count of the all-zero bins, the rank rows from the uploaded tables, the samples' rank tables over contexts.  (a part of
+// gx_api.hip's translation unit)
 #pragma once
 namespace {
 
@@ -33,11 +34,8 @@ int rank_distinct_pass(gx_ctx* ctx, const void* row, u64 n, u32 grid, std::vecto
   u32 ctl[RKC_WORDS];
   for (;;) {
     const size_t cap = (size_t)1 << capLog;
-    if (pooled(ctx, ctx->rankTab, cap * 12) != hipSuccess || pooled(ctx, ctx->rankCtl, RKC_WORDS * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->err = "Cannot allocate memory";
-      return GX_ERR_MEM;
-    }
+    POOLED(ctx, ctx->rankTab, cap * 12);
+    POOLED(ctx, ctx->rankCtl, RKC_WORDS * 4);
     RankTab T;
     T.keys = ctx->rankTab.as<unsigned long long>();
     T.counts = reinterpret_cast<u32*>(T.keys + cap);
@@ -60,11 +58,7 @@ int rank_distinct_pass(gx_ctx* ctx, const void* row, u64 n, u32 grid, std::vecto
       const u64 zeros = (u64)ctl[RKC_ZEROS] | ((u64)ctl[RKC_ZEROS + 1] << 32);
       std::vector<uint64_t> v(used), c(used);
       if (used) {
-        if (pooled(ctx, ctx->rankPairs, (size_t)used * 16) != hipSuccess) {
-          (void)hipGetLastError();
-          ctx->err = "Cannot allocate memory";
-          return GX_ERR_MEM;
-        }
+        POOLED(ctx, ctx->rankPairs, (size_t)used * 16);
         unsigned long long* dv = ctx->rankPairs.as<unsigned long long>();
         phase_begin(ctx, "rank_compact");
         hipLaunchKernelGGL(k_rank_compact, dim3((u32)std::min<size_t>((cap + 255) / 256, RK_GRID)), dim3(256), 0, s, T, dv, dv + used);
@@ -104,15 +98,10 @@ int rank_distinct_pass(gx_ctx* ctx, const void* row, u64 n, u32 grid, std::vecto
   }
 }
 
+// the row pointers for a kernel that counts into the control words, and those cleared
 int rank_upload_rows(gx_ctx* ctx, const std::vector<const void*>& in, const std::vector<const void*>& out) {
-  if (pooled(ctx, ctx->rankRows, 2 * RK_MAX_S * sizeof(void*)) != hipSuccess || pooled(ctx, ctx->rankCtl, RKC_WORDS * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
-  HIPCHECK(hipMemcpyAsync(ctx->rankRows.p, in.data(), in.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-  if (!out.empty())
-    HIPCHECK(hipMemcpyAsync(ctx->rankRows.as<const void*>() + RK_MAX_S, out.data(), out.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+  POOLED(ctx, ctx->rankCtl, RKC_WORDS * 4);
+  if (int rc = stat_upload_rows(ctx, in, out, false)) return rc;
   HIPCHECK(hipMemsetAsync(ctx->rankCtl.p, 0, RKC_WORDS * 4, ctx->stream));
   HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the vectors are the caller's)
   return GX_OK;
@@ -126,7 +115,7 @@ int rank_nzero_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u6
   if (int rc = rank_upload_rows(ctx, rows, {})) return rc;
   phase_begin(ctx, "rank_nzero");
   hipLaunchKernelGGL(k_rank_nzero, dim3((u32)std::min<u64>((n + 255) / 256, RK_GRID)), dim3(256), 0, ctx->stream,
-                     ctx->rankRows.as<const unsigned long long*>(), (u32)rows.size(), n, ctx->rankCtl.as<u32>());
+                     ctx->statRows.as<const unsigned long long*>(), (u32)rows.size(), n, ctx->rankCtl.as<u32>());
   if (int rc__ = dbg_sync(ctx, "k_rank_nzero")) return rc__;
   phase_end(ctx);
   HIPCHECK(hipGetLastError());
@@ -160,11 +149,8 @@ int rank_rows_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32
     total += room[i];
   }
   const size_t head = RK_MAX_S + 2;   // the offsets, in 8-byte words (even: the tables stay 16-byte aligned)
-  if (pooled(ctx, ctx->rankOut, (size_t)S * pitch * 8) != hipSuccess || pooled(ctx, ctx->rankLut, (head + 2 * total) * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
+  POOLED(ctx, ctx->rankOut, (size_t)S * pitch * 8);
+  POOLED(ctx, ctx->rankLut, (head + 2 * total) * 8);
   std::vector<uint64_t> staged(head + 2 * total, 0);
   if (probe) std::fill(staged.begin() + head, staged.end(), (uint64_t)RK_EMPTY);
   size_t at = 0;
@@ -192,8 +178,8 @@ int rank_rows_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32
   if (!grid) grid = (u32)std::min<u64>((n + 255) / 256, RK_GRID);
   const unsigned long long* lutp = ctx->rankLut.as<unsigned long long>();
   phase_begin(ctx, "rank");
-  hipLaunchKernelGGL(probe ? k_rank<true> : k_rank<false>, dim3(grid), dim3(256), 0, s, ctx->rankRows.as<const unsigned long long*>(),
-                     ctx->rankRows.as<unsigned long long*>() + RK_MAX_S, S, n, lutp + head, lutp + head + total,
+  hipLaunchKernelGGL(probe ? k_rank<true> : k_rank<false>, dim3(grid), dim3(256), 0, s, ctx->statRows.as<const unsigned long long*>(),
+                     ctx->statRows.as<unsigned long long*>() + STAT_MAX_S, S, n, lutp + head, lutp + head + total,
                      reinterpret_cast<const u64*>(lutp), skip ? 1 : 0, ctx->rankCtl.as<u32>());
   if (int rc__ = dbg_sync(ctx, "k_rank")) return rc__;
   phase_end(ctx);
@@ -209,23 +195,10 @@ int rank_rows_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32
   return GX_OK;
 }
 
-// gx_coverage_gram's order rules, and the closed samples' bins as device rows
-int rank_cov_rows(gx_ctx* ctx, std::vector<const void*>& rows, u64* n) {
-  if (!ctx || !ctx->covW || ctx->cov.empty() || ctx->phase == 1 || ctx->phase == 3) return GX_ERR_ORDER;
-  const size_t S = ctx->cov.size();
-  if (S > RK_MAX_S) {
-    ctx->err = "more than 32 samples for the rank correlation";
-    return GX_ERR_ORDER;
-  }
-  if (ctx->covDirty)
-    if (int rc = cov_layout(ctx)) return rc;
-  *n = ctx->covOff[ctx->nChrom];
-  if (*n > ((u64)1 << 30)) {
-    ctx->err = "more than 2^30 bins in a context for the rank correlation";
-    return GX_ERR_ORDER;
-  }
-  rows.resize(S);
-  for (size_t i = 0; i < S; i++) rows[i] = ctx->cov[i].bins.p;   // (each the start of an allocation: aligned)
+// the closed samples' bins as device rows (stat_cov_rows), within what a rank fits
+int rank_cov_rows(gx_ctx* ctx, BinRows& b) {
+  if (int rc = stat_cov_rows(ctx, "the rank correlation", b)) return rc;
+  if (b.n > ((u64)1 << 30)) return stat_refuse(ctx, "more than 2^30 bins in a context for the rank correlation");
   return GX_OK;
 }
 
@@ -253,34 +226,61 @@ int rank_give_table(gx_ctx* ctx, const char* who, const std::vector<uint64_t>& v
   return GX_OK;
 }
 
-// the caller's rows (host, row after row) on the device, 16 bytes apart at least: an odd n is padded by one value no lane reads
-int rank_stage_rows(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, std::vector<const void*>& dev) {
-  dev.assign((size_t)n_rows, nullptr);
-  if (!n) return GX_OK;
-  const size_t pitch = (n + 1) & ~(size_t)1;
-  std::vector<uint64_t> staged((size_t)n_rows * pitch, 0);
-  for (int r = 0; r < n_rows; r++) std::copy(rows + (size_t)r * n, rows + (size_t)(r + 1) * n, staged.begin() + (size_t)r * pitch);
-  HIPCHECK(hipSetDevice(ctx->device));
-  if (pooled(ctx, ctx->rankIn, staged.size() * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "Cannot allocate memory";
-    return GX_ERR_MEM;
-  }
-  HIPCHECK(hipMemcpyAsync(ctx->rankIn.p, staged.data(), staged.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (`staged` is this call's)
-  for (int r = 0; r < n_rows; r++) dev[r] = ctx->rankIn.as<uint64_t>() + (size_t)r * pitch;
-  return GX_OK;
-}
+// the samples' rank tables over the rows of one or more contexts, and the storage behind them
+struct RankGroup {
+  gx_ctx* ctx;
+  std::vector<const void*> rows;   // S device rows (16-byte aligned) of n values each
+  u64 n;
+};
+struct RankTables {
+  std::vector<std::vector<uint64_t>> value, rank2;   // per sample, what lut[] points to
+  std::vector<gx_rank_lut> lut;
+  std::vector<size_t> nDistinct;                     // the entries of each sample's table
+  u64 nZero = 0, nRanked = 0;                        // the all-zero bins left out (skip), the bins ranked
+};
 
-// the hooks' domain (gx_distinct_u64 / gx_rank_u64): nullptr when the rows are inside it
-const char* rank_u64_domain(const uint64_t* rows, int n_rows, size_t n, unsigned grid) {
-  if (n_rows < 1 || n_rows > (int)RK_MAX_S) return "the number of rows is outside [1, 32]";
-  if (n > ((size_t)1 << 24)) return "more than 2^24 values a row";
-  if (n && !rows) return "no rows";
-  if (grid > RK_MAX_GRID) return "a grid of more than 65535 workgroups";
-  for (size_t k = 0; k < (size_t)n_rows * n; k++)
-    if (rows[k] >> 51) return "a value of 2^51 or more";
-  return nullptr;
+// per group the count of the all-zero bins (skip) and a distinct pass per row, then gx_rank_tables over all groups; `why`: what
+// every group's context says when the tables do not merge
+int rank_make_tables(const std::vector<RankGroup>& groups, u32 grid, bool skip, const char* why, RankTables& t) {
+  const size_t G = groups.size(), S = groups[0].rows.size();
+  std::vector<std::vector<uint64_t>> v(G * S), c(G * S);
+  std::vector<gx_rank_table> tabs(G * S);
+  std::vector<size_t> room(S, 0);
+  t.nZero = 0;
+  for (size_t g = 0; g < G; g++) {
+    const RankGroup& gr = groups[g];
+    if (skip) {
+      u64 nz = 0;
+      if (int rc = rank_nzero_pass(gr.ctx, gr.rows, gr.n, &nz)) return rc;
+      t.nZero += nz;
+    }
+    for (size_t i = 0; i < S; i++) {
+      const size_t k = g * S + i;
+      if (int rc = rank_distinct_pass(gr.ctx, gr.rows[i], gr.n, grid, v[k], c[k])) return rc;
+      tabs[k] = gx_rank_table{v[k].data(), c[k].data(), v[k].size()};
+      room[i] += v[k].size();
+    }
+  }
+  const size_t most = *std::max_element(room.begin(), room.end());
+  t.value.resize(S);
+  t.rank2.resize(S);
+  std::vector<uint64_t*> pv(S), pr(S);
+  for (size_t i = 0; i < S; i++) {
+    t.value[i].resize(most);
+    t.rank2[i].resize(most);
+    pv[i] = t.value[i].data();
+    pr[i] = t.rank2[i].data();
+  }
+  t.nDistinct.assign(S, 0);
+  uint64_t N = 0;
+  if (int rc = gx_rank_tables((int)G, (int)S, tabs.data(), t.nZero, pv.data(), pr.data(), most, t.nDistinct.data(), &N)) {
+    for (const RankGroup& gr : groups) gr.ctx->err = why;
+    return rc;
+  }
+  t.nRanked = N;
+  t.lut.resize(S);
+  for (size_t i = 0; i < S; i++) t.lut[i] = gx_rank_lut{pv[i], pr[i], t.nDistinct[i]};
+  return GX_OK;
 }
 
 }  // namespace

@@ -2614,6 +2614,40 @@ void writeRegionCounts(State& S, const std::vector<std::string>& tFiles, const s
   }
 }
 
+// the samples closed on the first context, as the outputs per sample name them: t<rep> for a treatment, c<rep> for a control
+// that was read; from the coverage's samples, or the profile's (the same samples in the same order)
+struct ClosedSamples {
+  std::vector<std::string> labels;
+  std::vector<const char*> names;   // the labels, for the library (good while `labels` is not copied or grown)
+  std::vector<int> reps, ctrls;
+  int n() const { return (int)labels.size(); }
+};
+ClosedSamples closedSamples(State& S, bool profile = false) {
+  gx_ctx* g0 = S.devs.ctx[0];
+  int nS = 0;
+  check(S, profile ? gx_profile_samples(g0, &nS) : gx_coverage_samples(g0, &nS), g0);
+  ClosedSamples L;
+  L.labels.reserve((size_t)nS);   // (no label moves after `names` points at it)
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    check(S, profile ? gx_get_profile(g0, i, &rep, &ctrl, nullptr, nullptr, 0, 0) : gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
+    L.labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
+    L.names.push_back(L.labels.back().c_str());
+    L.reps.push_back(rep);
+    L.ctrls.push_back(ctrl);
+  }
+  return L;
+}
+
+// the smallest finite entry above the diagonal of an nS x nS matrix: its row and column, (-1, -1) when there is none
+std::pair<int, int> leastAlike(const std::vector<double>& r, int nS) {
+  int li = -1, lj = -1;
+  for (int i = 0; i < nS; i++)
+    for (int j = i + 1; j < nS; j++)
+      if (r[(size_t)i * nS + j] == r[(size_t)i * nS + j] && (li < 0 || r[(size_t)i * nS + j] < r[(size_t)li * nS + lj])) { li = i; lj = j; }
+  return {li, lj};
+}
+
 // --coverage PREFIX: each sample's pileup in bins, one bedGraph file per sample -- PREFIX.t<rep>.bedgraph for a treatment,
 // PREFIX.c<rep>.bedgraph for a control that was read (.gz behind it with -z); with -v the mean of each track
 void writeCoverage(State& S, const std::vector<const char*>& names) {
@@ -2626,11 +2660,11 @@ void writeCoverage(State& S, const std::vector<const char*>& names) {
     if (g != S.devs.ctx[0] && n != nS) die("", "--coverage: the devices closed different numbers of samples");
     nS = n;
   }
+  const ClosedSamples L = closedSamples(S);
   std::vector<int64_t> sums;
   for (int i = 0; i < nS; i++) {
-    int rep = 0, ctrl = 0;
-    check(S, gx_get_coverage(S.devs.ctx[0], i, 0, &rep, &ctrl, nullptr, 0), S.devs.ctx[0]);
-    const std::string path = std::string(o.coveragePrefix) + (ctrl ? ".c" : ".t") + std::to_string(rep) + ".bedgraph" + (o.gzOut ? ".gz" : "");
+    const int rep = L.reps[i], ctrl = L.ctrls[i];
+    const std::string path = std::string(o.coveragePrefix) + "." + L.labels[i] + ".bedgraph" + (o.gzOut ? ".gz" : "");
     Out out = openWrite(path.c_str(), o.gzOut);
     check(S, gx_write_coverage_group(S.devs.ctx.data(), S.devs.owner.data(), i, names.data(), nChrom, o.coverageScale, out.f));
     closeOut(out);
@@ -2662,16 +2696,9 @@ void writeCoverage(State& S, const std::vector<const char*>& names) {
 void writeCorrelation(State& S) {
   const Opts& o = S.o;
   gx_ctx* g0 = S.devs.ctx[0];
-  int nS = 0;
-  check(S, gx_coverage_samples(g0, &nS), g0);
-  std::vector<std::string> labels;
-  for (int i = 0; i < nS; i++) {
-    int rep = 0, ctrl = 0;
-    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
-    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
-  }
-  std::vector<const char*> names;
-  for (const std::string& l : labels) names.push_back(l.c_str());
+  const ClosedSamples L = closedSamples(S);
+  const int nS = L.n();
+  const std::vector<const char*>& names = L.names;
   // one pass per context; the matrix is formatted, and with -v searched, from the added sums
   std::vector<gx_u128> sum((size_t)nS), gram((size_t)nS * nS);
   uint64_t bins = 0, zeros = 0;
@@ -2682,10 +2709,7 @@ void writeCorrelation(State& S) {
   if (!o.verbose) return;
   std::vector<double> r((size_t)nS * nS);
   check(S, gx_correlation_matrix(nS, bins, zeros, sum.data(), gram.data(), o.corrSkipZeros ? 1 : 0, r.data()), g0);
-  int li = -1, lj = -1;
-  for (int i = 0; i < nS; i++)
-    for (int j = i + 1; j < nS; j++)
-      if (r[(size_t)i * nS + j] == r[(size_t)i * nS + j] && (li < 0 || r[(size_t)i * nS + j] < r[(size_t)li * nS + lj])) { li = i; lj = j; }
+  const auto [li, lj] = leastAlike(r, nS);
   if (li >= 0)
     fprintf(stderr, "  Correlation: %llu bins, %llu all zero; smallest r %f (%s, %s)\n", (unsigned long long)bins, (unsigned long long)zeros,
             r[(size_t)li * nS + lj], names[li], names[lj]);
@@ -2698,16 +2722,9 @@ void writeCorrelation(State& S) {
 void writeSpearman(State& S) {
   const Opts& o = S.o;
   gx_ctx* g0 = S.devs.ctx[0];
-  int nS = 0;
-  check(S, gx_coverage_samples(g0, &nS), g0);
-  std::vector<std::string> labels;
-  for (int i = 0; i < nS; i++) {
-    int rep = 0, ctrl = 0;
-    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
-    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
-  }
-  std::vector<const char*> names;
-  for (const std::string& l : labels) names.push_back(l.c_str());
+  const ClosedSamples L = closedSamples(S);
+  const int nS = L.n();
+  const std::vector<const char*>& names = L.names;
   // every context's value tables, one ranking over all of them, one pass per context over its rank rows; the sums are added
   std::vector<gx_u128> sum((size_t)nS), gram((size_t)nS * nS);
   std::vector<uint64_t> distinct((size_t)nS);
@@ -2720,10 +2737,7 @@ void writeSpearman(State& S) {
   if (!o.verbose) return;
   std::vector<double> r((size_t)nS * nS);
   check(S, gx_correlation_matrix(nS, ranked, 0, sum.data(), gram.data(), 0, r.data()), g0);
-  int li = -1, lj = -1;
-  for (int i = 0; i < nS; i++)
-    for (int j = i + 1; j < nS; j++)
-      if (r[(size_t)i * nS + j] == r[(size_t)i * nS + j] && (li < 0 || r[(size_t)i * nS + j] < r[(size_t)li * nS + lj])) { li = i; lj = j; }
+  const auto [li, lj] = leastAlike(r, nS);
   const unsigned long long most = nS ? (unsigned long long)*std::max_element(distinct.begin(), distinct.end()) : 0ull;
   if (li >= 0)
     fprintf(stderr, "  Spearman: %llu bins ranked, at most %llu distinct values a sample; smallest rho %f (%s, %s)\n", (unsigned long long)ranked,
@@ -2739,23 +2753,13 @@ void writeSpearman(State& S) {
 void writeFingerprint(State& S) {
   const Opts& o = S.o;
   gx_ctx* g0 = S.devs.ctx[0];
-  int nS = 0;
-  check(S, gx_coverage_samples(g0, &nS), g0);
-  std::vector<std::string> labels;
-  std::vector<int> reps, ctrls;
-  for (int i = 0; i < nS; i++) {
-    int rep = 0, ctrl = 0;
-    check(S, gx_get_coverage(g0, i, 0, &rep, &ctrl, nullptr, 0), g0);
-    labels.push_back((ctrl ? "c" : "t") + std::to_string(rep));
-    reps.push_back(rep);
-    ctrls.push_back(ctrl);
-  }
-  std::vector<const char*> names;
-  for (const std::string& l : labels) names.push_back(l.c_str());
+  const ClosedSamples L = closedSamples(S);
+  const int nS = L.n();
+  const std::vector<const char*>& names = L.names;
   std::vector<int> ctrlOf((size_t)nS, -1);   // a treatment's control: the control sample of the same replicate
   for (int i = 0; i < nS; i++)
-    for (int j = 0; j < nS && !ctrls[i]; j++)
-      if (ctrls[j] && reps[j] == reps[i]) ctrlOf[i] = j;
+    for (int j = 0; j < nS && !L.ctrls[i]; j++)
+      if (L.ctrls[j] && L.reps[j] == L.reps[i]) ctrlOf[i] = j;
   std::vector<uint64_t> count((size_t)nS * GX_FP_NC), sum((size_t)nS * GX_FP_NC);
   check(S, gx_coverage_fingerprint_group(S.devs.ctx.data(), (int)S.devs.n(), nS, nullptr, count.data(), sum.data()), g0);
   Out out = openWrite(o.fingerprintFile, o.gzOut);
@@ -2828,16 +2832,17 @@ void writeProfile(State& S, const ProfilePlan& P, const std::vector<std::string>
     closeOut(out);
   }
   const uint32_t nb = (uint32_t)(2 * o.flank / o.profileBin);
+  const ClosedSamples L = closedSamples(S, true);
   std::vector<int64_t> agg(nb), one(nb);
   for (int i = 0; i < nS; i++) {
-    int rep = 0, ctrl = 0;
+    const int rep = L.reps[i], ctrl = L.ctrls[i];
     std::fill(agg.begin(), agg.end(), 0);
     for (gx_ctx* g : S.devs.ctx) {
-      check(S, gx_get_profile(g, i, &rep, &ctrl, one.data(), nullptr, 0, 0), g);
+      check(S, gx_get_profile(g, i, nullptr, nullptr, one.data(), nullptr, 0, 0), g);
       for (uint32_t j = 0; j < nb; j++) agg[j] += one[j];
     }
     if (o.profileMatrix) {
-      const std::string path = std::string(o.profilePrefix) + (ctrl ? ".c" : ".t") + std::to_string(rep) + ".matrix.tsv";
+      const std::string path = std::string(o.profilePrefix) + "." + L.labels[i] + ".matrix.tsv";
       Out out = openWrite(path.c_str(), o.gzOut);
       check(S, gx_write_profile_rows_group(S.devs.ctx.data(), (int)S.devs.n(), i, P.allNames.data(), P.regions.data(), P.rowNames.data(),
                                            P.anchors.data(), out.f));

@@ -98,6 +98,18 @@ def _join128(a):
     return out
 
 
+def _sums128(S):
+    """Zeroed gx_u128 (sum [S], gram [S, S]) for the library to fill; one sample's room at least."""
+    S = max(S, 1)
+    return np.zeros(S, dtype=U128_DTYPE), np.zeros((S, S), dtype=U128_DTYPE)
+
+
+def _u64_rows(rows):
+    """(contiguous uint64 array, its address or None when it is empty): a hook's rows argument."""
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    return r, (r.ctypes.data if r.size else None)
+
+
 def _split128(values, shape):
     out = np.zeros(shape, dtype=U128_DTYPE)
     flat = out.reshape(-1)
@@ -455,7 +467,7 @@ def coverage_spearman_group(ctxs, skip_zeros=False):
     lib = load_library()
     S = ctxs[0].coverage_samples()
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
-    s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+    s, g = _sums128(S)
     nd = np.zeros(max(S, 1), dtype=np.uint64)
     N = C.c_uint64(0)
     ctxs[0]._check(lib.gx_coverage_spearman_group(arr, len(ctxs), S, int(bool(skip_zeros)), C.byref(N), s.ctypes.data, g.ctypes.data,
@@ -861,7 +873,7 @@ class Genrich:
     def coverage_gram(self):
         """(n, n_zero, sum, gram) of the samples closed since the last reset: Python ints, sum an object array [S], gram [S, S]."""
         S = self.coverage_samples()
-        s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+        s, g = _sums128(S)
         ns, n, nz = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.gx_coverage_gram(self.ctx, C.byref(ns), C.byref(n), C.byref(nz), s.ctypes.data, g.ctypes.data, max(S, 1)))
         return n.value, nz.value, _join128(s[:ns.value]), _join128(g[:ns.value, :ns.value])
@@ -869,11 +881,11 @@ class Genrich:
     def gram_u64(self, rows, grid=0):
         """(n_zero, sum, gram) of the rows (uint64 [n_rows, n], every value < 2^51) by the same kernels (gx_gram_u64); grid = 0:
         the library's geometry, else that many workgroups along the bin axis."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r, ptr = _u64_rows(rows)
         n_rows, n = r.shape
-        s, g = np.zeros(max(n_rows, 1), dtype=U128_DTYPE), np.zeros((max(n_rows, 1), max(n_rows, 1)), dtype=U128_DTYPE)
+        s, g = _sums128(n_rows)
         nz = C.c_uint64(0)
-        self._check(self.lib.gx_gram_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), C.byref(nz), s.ctypes.data,
+        self._check(self.lib.gx_gram_u64(self.ctx, ptr, n_rows, n, int(grid), C.byref(nz), s.ctypes.data,
                                          g.ctypes.data))
         return nz.value, _join128(s[:n_rows]), _join128(g[:n_rows, :n_rows])
 
@@ -889,10 +901,10 @@ class Genrich:
     def fp_u64(self, rows, grid=0):
         """(count, sum), uint64 [n_rows, FP_NC], of the rows (uint64 [n_rows, n]) by the same kernel (gx_fp_u64); grid = 0: the
         library's geometry, else that many workgroups along the bin axis."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r, ptr = _u64_rows(rows)
         n_rows, n = r.shape
         c, t = np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64), np.zeros((max(n_rows, 1), FP_NC), dtype=np.uint64)
-        self._check(self.lib.gx_fp_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), c.ctypes.data, t.ctypes.data))
+        self._check(self.lib.gx_fp_u64(self.ctx, ptr, n_rows, n, int(grid), c.ctypes.data, t.ctypes.data))
         return c[:n_rows], t[:n_rows]
 
     # -- rank correlation of the samples' bins (include/genrich_amd.h, gx_coverage_distinct) -------------------------------
@@ -910,7 +922,7 @@ class Genrich:
         (gx_coverage_rank_gram): Python ints, sum an object array [S], gram [S, S]."""
         S = self.coverage_samples()
         arr, keep = _rank_structs(list(luts))
-        s, g = np.zeros(max(S, 1), dtype=U128_DTYPE), np.zeros((max(S, 1), max(S, 1)), dtype=U128_DTYPE)
+        s, g = _sums128(S)
         ns, n, nz = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
         if len(luts) != S:
             raise ValueError("one table per sample")
@@ -921,21 +933,21 @@ class Genrich:
     def distinct_u64(self, row, grid=0):
         """(values ascending, counts) of the row (uint64 [n], every value < 2^51) by the same kernels (gx_distinct_u64); grid = 0:
         the library's geometry, else that many workgroups."""
-        r = np.ascontiguousarray(row, dtype=np.uint64)
+        r, ptr = _u64_rows(row)
         n = C.c_size_t(0)
         v, c = np.zeros(max(r.size, 1), dtype=np.uint64), np.zeros(max(r.size, 1), dtype=np.uint64)
-        self._check(self.lib.gx_distinct_u64(self.ctx, r.ctypes.data if r.size else None, r.size, int(grid), v.ctypes.data, c.ctypes.data,
+        self._check(self.lib.gx_distinct_u64(self.ctx, ptr, r.size, int(grid), v.ctypes.data, c.ctypes.data,
                                              v.size, C.byref(n)))
         return v[:n.value], c[:n.value]
 
     def rank_u64(self, rows, grid=0, skip_zeros=False):
         """(rank2 uint64 [n_rows, n], n_zero) of the rows (uint64 [n_rows, n], every value < 2^51) ranked as the samples of one
         context (gx_rank_u64); grid = 0: the library's geometry."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        r, ptr = _u64_rows(rows)
         n_rows, n = r.shape
         out = np.zeros((n_rows, n), dtype=np.uint64)
         nz = C.c_uint64(0)
-        self._check(self.lib.gx_rank_u64(self.ctx, r.ctypes.data if r.size else None, n_rows, n, int(grid), int(bool(skip_zeros)),
+        self._check(self.lib.gx_rank_u64(self.ctx, ptr, n_rows, n, int(grid), int(bool(skip_zeros)),
                                          out.ctypes.data if out.size else None, C.byref(nz)))
         return out, nz.value
 

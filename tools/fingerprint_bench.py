@@ -18,61 +18,18 @@ from __future__ import annotations
 
 import argparse
 import json
-import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-def mmm(xs):
-    return dict(min=round(min(xs), 4), median=round(statistics.median(xs), 4), max=round(max(xs), 4), n=len(xs))
+from binstat_bench_common import Workload, mmm
 
 
 def run(frags, steps, warmup, sample_counts):
-    import torch
-
-    import bench
     import fingerprint_ref as R
-    from genrich_amd import synth
-    from genrich_amd.lib import GX_PATH_FINGERPRINT, Genrich, GxParams, minus_log10f
+    from genrich_amd.lib import GX_PATH_FINGERPRINT
 
-    cfg = dict(bench.CONFIGS[2])
-    lens = synth.HG38_LENS
-    (tv, _), = bench.build_workload(cfg, frags, lens)
-    d_tv = torch.from_numpy(tv.view(np.uint32).reshape(-1, 4).copy()).to(torch.device("cuda:0"))
-    torch.cuda.synchronize()
-    par = GxParams(minus_log10f(0.01), 0, 200.0, 0, 100, 0, 0)
-    W = 50
-
-    def make(beds=None):
-        gx = Genrich(par)
-        gx.set_chroms(lens, None, beds)
-        gx.set_keep_pileups(False)
-        gx.set_coverage_bins(W)
-        return gx
-
-    def close_sample(gx, n_events):
-        gx.sample_begin(0, None)
-        gx.push_events_device(d_tv.data_ptr(), n_events)
-        gx.sample_end()
-        gx.sample_no_control()
-        gx.pvalues()
-
-    def cover_ms(gx):
-        out = []
-        for i in range(warmup + 5):
-            gx.reset()
-            gx.set_phase_filter("cover")
-            close_sample(gx, d_tv.shape[0])
-            if i >= warmup:
-                out.append([ms for name, ms in gx.phase_times() if name == "t.cover"][-1])
-            gx.set_phase_timing(0)
-        return out
+    w = Workload(frags, warmup)
 
     def pass_ms(gx):
         gx.set_phase_filter("fingerprint")
@@ -83,28 +40,10 @@ def run(frags, steps, warmup, sample_counts):
         assert len(ms) == steps and gx.path_info() & GX_PATH_FINGERPRINT
         return n, ms
 
-    out = dict(config=2, desc=cfg["desc"], fragments=frags, bin_size=W, samples={})
-    # the yardstick: k_pack by the difference of two event-timed phases
-    beds = [[] for _ in lens]
-    beds[-1] = [lens[-1] - 1, lens[-1]]
-    gx = make(beds)
-    with_pack = cover_ms(gx)
-    n_iv = gx.interval_total(0)
-    gx.close()
-    gx = make()
-    without = cover_ms(gx)
-    pack_ms = statistics.median(with_pack) - statistics.median(without)
-    pack_bytes = 16 * n_iv
-    pack_ns_per_kb = pack_ms * 1e6 / (pack_bytes / 1e3)
-    out["k_pack"] = dict(cover_ms_with=mmm(with_pack), cover_ms_without=mmm(without), ms=round(pack_ms, 4), bytes=int(pack_bytes),
-                         ns_per_kb=round(pack_ns_per_kb, 4), tb_per_s=round(pack_bytes / (pack_ms * 1e-3) / 1e12, 3))
-    # S samples of one run: every one the same fragments but for its last r * 1000
-    gx.reset()
-    closed = 0
+    out = w.header()
+    gx, out["k_pack"], pack_ns_per_kb = w.k_pack()
     for S in sample_counts:
-        while closed < S:
-            close_sample(gx, d_tv.shape[0] - 1000 * closed)
-            closed += 1
+        w.close_up_to(gx, S)
         n, ms = pass_ms(gx)
         must_read = 8 * S * n
         med = statistics.median(ms)
@@ -120,7 +59,7 @@ def run(frags, steps, warmup, sample_counts):
             n1, count, total = gx.coverage_fingerprint()
             assert np.array_equal(count, c_agg) and np.array_equal(total, t_agg)
             res["variants_ms"] = dict(atomics_per_lane=mmm(ms), aggregated_in_the_wavefront=mmm(ms_agg))
-            rows = [np.concatenate([gx.coverage(i, c).sum120 for c in range(len(lens))]) for i in range(S)]
+            rows = w.rows(gx, S)
             assert n1 == len(rows[0])
             for i in range(S):
                 a = rows[i].astype(np.uint64)
