@@ -15,6 +15,7 @@
 #include "gx_host_gram.h"
 #include "gx_host_fingerprint.h"
 #include "gx_host_rank.h"
+#include "gx_host_complexity.h"
 
 
 // ================================ C ABI ==================================================
@@ -260,6 +261,8 @@ int gx_reset(gx_ctx* ctx) {
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
+  ctx->cpx.clear();     // (the buffers stay with the context)
+  ctx->cpxReady = ctx->cpxUsed = false;
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -842,7 +845,8 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
-           (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u);
+           (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
+           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u);
   return GX_OK;
 }
 
@@ -1322,6 +1326,97 @@ int gx_write_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const
   uint64_t N = 0;
   if (int rc = gx_coverage_spearman_group(ctxs, n_ctx, n_samples, skip_zeros, &N, s1.data(), g1.data(), nullptr)) return rc;
   return gx_format_correlation(out, n_samples, sample_names, N, 0, s1.data(), g1.data(), 0);
+}
+
+int gx_complexity(gx_ctx* ctx, int* n_samples) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (!ctx->countOn) return cpx_refuse(ctx, "gx_complexity needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase == 1 || ctx->phase == 3) return cpx_refuse(ctx, "gx_complexity: a sample is open");
+  if (ctx->kept.empty()) return cpx_refuse(ctx, "gx_complexity: no closed sample");
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->cpxReady = false;
+  if (int rc = complexity_kept(ctx)) return rc;
+  if (n_samples) *n_samples = (int)ctx->cpx.size();
+  return GX_OK;
+}
+
+int gx_get_complexity(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult, uint64_t* keys,
+                      size_t cap, size_t* n_classes) {
+  if (!ctx || !ctx->cpxReady || sample < 0 || (size_t)sample >= ctx->cpx.size()) return GX_ERR_ORDER;
+  const gx_ctx::CpxResult& r = ctx->cpx[sample];
+  if (rep) *rep = r.rep;
+  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
+  return cpx_give(r, n_obs, n_distinct, mult, keys, cap, n_classes);
+}
+
+int gx_complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, int cap_log, uint64_t* n_obs, uint64_t* n_distinct,
+                         uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes) {
+  if (!ctx || ctx->nChrom == 0 || (n && !ev) || cap_log < 0 || (cap && (!mult || !keys))) return GX_ERR_ORDER;
+  if (ctx->phase == 1 || ctx->phase == 3) return cpx_refuse(ctx, "gx_complexity_events: a sample is open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  gx_ctx::CpxResult r;
+  if (int rc = complexity_events(ctx, ev, n, grid, cap_log, r)) return rc;
+  return cpx_give(r, n_obs, n_distinct, mult, keys, cap, n_classes);
+}
+
+int gx_complexity_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint64_t n, size_t* least_capacity) {
+  if (lanes) *lanes = CPX_NT;
+  if (grid) *grid = (int)CPX_GRID;
+  if (lds_bound) *lds_bound = CPX_BOUND;
+  if (least_capacity) *least_capacity = n >> 31 ? 0 : (size_t)1 << cpx_least_cap_log(n);
+  return GX_OK;
+}
+
+int gx_complexity_last(gx_ctx* ctx, size_t* capacity) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (capacity) *capacity = ctx->cpxLastCapLog ? (size_t)1 << ctx->cpxLastCapLog : 0;
+  return GX_OK;
+}
+
+// (the two over contexts live here, not in gx_emit.cpp, like the fingerprint's: they read contexts)
+int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult,
+                        uint64_t* keys, size_t cap, size_t* n_classes) {
+  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
+  gx_ctx::CpxResult sum;
+  for (int g = 0; g < n_ctx; g++) {
+    gx_ctx* c = ctxs[g];
+    if (!c || !c->cpxReady || sample < 0 || (size_t)sample >= c->cpx.size() || c->cpx.size() != ctxs[0]->cpx.size()) return GX_ERR_ORDER;
+    if (g == 0) {
+      sum.rep = c->cpx[sample].rep;
+      sum.ctrl = c->cpx[sample].ctrl;
+    }
+    cpx_add(sum, c->cpx[sample]);
+  }
+  if (rep) *rep = sum.rep;
+  if (is_ctrl) *is_ctrl = sum.ctrl ? 1 : 0;
+  return cpx_give(sum, n_obs, n_distinct, mult, keys, cap, n_classes);
+}
+
+int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist) {
+  if (!ctxs || n_ctx < 1 || !metrics) return GX_ERR_ORDER;
+  int nS = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int n = 0;
+    if (int rc = gx_complexity(ctxs[g], &n)) return rc;
+    if (g && n != nS) return GX_ERR_ORDER;
+    nS = n;
+  }
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> N((size_t)nS), D((size_t)nS);
+  std::vector<std::vector<uint64_t>> mult((size_t)nS), keys((size_t)nS);
+  std::vector<const uint64_t*> pm((size_t)nS), pk((size_t)nS);
+  std::vector<size_t> np((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    size_t n = 0;
+    if (int rc = gx_complexity_group(ctxs, n_ctx, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n)) return rc;
+    mult[i].resize(n);
+    keys[i].resize(n);
+    if (int rc = gx_complexity_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], &N[i], &D[i], mult[i].data(), keys[i].data(), n, &np[i])) return rc;
+    pm[i] = mult[i].data();
+    pk[i] = keys[i].data();
+  }
+  if (int rc = gx_format_complexity(metrics, nS, rep.data(), ctrl.data(), N.data(), D.data(), pm.data(), pk.data(), np.data())) return rc;
+  return hist ? gx_format_complexity_hist(hist, nS, rep.data(), ctrl.data(), pm.data(), pk.data(), np.data()) : GX_OK;
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

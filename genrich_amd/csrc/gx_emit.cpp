@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation) and the fingerprint tables (--fingerprint).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint) and the library complexity tables (--complexity).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -548,6 +548,110 @@ int gx_format_fingerprint_metrics(FILE* out, int n_samples, const char* const* s
     for (double v : {m[s].zero_fraction, m[s].auc, m[s].gini, m[s].elbow_bins, m[s].elbow_gap, m[s].jsd_control}) put_fraction(out, v);
     fprintf(out, "\n");
   }
+  return GX_OK;
+}
+
+// --complexity's figures, from the integers alone: NaN where a definition divides by 0 or has no root
+namespace {
+// a / b, the correctly rounded double when both are below 2^53 (every count a device pass gives is); else through long double
+double cpx_ratio(uint64_t a, uint64_t b) {
+  if (!((a | b) >> 53)) return (double)a / (double)b;
+  return (double)((long double)a / (long double)b);
+}
+// the X with D / X = 1 - exp(-N / X) (Lander-Waterman), 0 < D < N: g(X) = -X expm1(-N / X) - D rises from g(D) < 0 to N - D
+long double cpx_library_size(uint64_t N, uint64_t D) {
+  const long double n = (long double)N, d = (long double)D;
+  auto g = [&](long double X) { return -X * expm1l(-n / X) - d; };
+  long double lo = d, hi = d;
+  do hi *= 2;
+  while (g(hi) < 0 && hi < 0x1p1000L);
+  for (int it = 0; it < 400; it++) {
+    const long double mid = lo + (hi - lo) / 2;
+    if (mid <= lo || mid >= hi) break;
+    if (g(mid) < 0) lo = mid;
+    else hi = mid;
+  }
+  return lo + (hi - lo) / 2;
+}
+bool cpx_pairs_ok(uint64_t N, uint64_t D, const uint64_t* mult, const uint64_t* keys, size_t n_pairs) {
+  if (n_pairs && (!mult || !keys)) return false;
+  u128_t sh = 0, smh = 0;
+  for (size_t i = 0; i < n_pairs; i++) {
+    if (!mult[i] || !keys[i] || (i && mult[i - 1] >= mult[i])) return false;
+    sh += keys[i];
+    smh += (u128_t)mult[i] * keys[i];
+    if (smh > N) return false;
+  }
+  return sh == D && smh == N;
+}
+void put_cpx(FILE* out, double v, const char* fmt) {
+  if (std::isnan(v)) fprintf(out, "\tNA");
+  else fprintf(out, fmt, v);
+}
+}  // namespace
+
+int gx_complexity_metrics(uint64_t n_obs, uint64_t n_distinct, const uint64_t* mult, const uint64_t* keys, size_t n_pairs, gx_cpx_metrics* out) {
+  if (!out || !cpx_pairs_ok(n_obs, n_distinct, mult, keys, n_pairs)) return GX_ERR_ORDER;
+  const uint64_t N = n_obs, D = n_distinct;
+  const double nan = std::nan("");
+  gx_cpx_metrics m{};
+  for (size_t i = 0; i < n_pairs; i++) {
+    if (mult[i] == 1) m.h1 = keys[i];
+    if (mult[i] == 2) m.h2 = keys[i];
+  }
+  m.nrf = N ? cpx_ratio(D, N) : nan;
+  m.pbc1 = D ? cpx_ratio(m.h1, D) : nan;
+  m.pbc2 = m.h2 ? cpx_ratio(m.h1, m.h2) : nan;
+  m.dup_fraction = N ? cpx_ratio(N - D, N) : nan;
+  m.library_size = (N && D < N) ? (double)roundl(cpx_library_size(N, D)) : nan;
+  for (int k = 1; k <= GX_CPX_CURVE; k++) {
+    const uint64_t n = (uint64_t)(((u128_t)N * (unsigned)k + GX_CPX_CURVE / 2) / GX_CPX_CURVE);   // round(k N / 20), halves up
+    long double E = 0;
+    for (size_t i = 0; i < n_pairs; i++) {
+      // the chance that none of a key's m observations is among the n drawn: prod_{i < m} (N - n - i) / (N - i), factor by
+      // factor until it is 0 (m > N - n) or too small to show in 1 - p (below 2^-80)
+      long double p = 1;
+      for (uint64_t j = 0; j < mult[i] && p >= 0x1p-80L; j++) p = j >= N - n ? 0.0L : p * ((long double)(N - n - j) / (long double)(N - j));
+      if (p < 0x1p-80L) p = 0;
+      E += (long double)keys[i] * (1 - p);
+    }
+    m.curve[k - 1] = (double)E;
+  }
+  *out = m;
+  return GX_OK;
+}
+
+// ... one row per sample, labelled t<rep> / c<rep>
+int gx_format_complexity(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_obs, const uint64_t* n_distinct,
+                         const uint64_t* const* mult, const uint64_t* const* keys, const size_t* n_pairs) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !n_obs || !n_distinct || !mult || !keys || !n_pairs) return GX_ERR_ORDER;
+  std::vector<gx_cpx_metrics> m((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (int rc = gx_complexity_metrics(n_obs[s], n_distinct[s], mult[s], keys[s], n_pairs[s], &m[s])) return rc;
+  fprintf(out, "sample\tN\tD\th1\th2\tNRF\tPBC1\tPBC2\tdup_fraction\tlibrary_size");
+  for (int k = 1; k <= GX_CPX_CURVE; k++) fprintf(out, "\tc%03d", k * 100 / GX_CPX_CURVE);
+  fprintf(out, "\n");
+  for (int s = 0; s < n_samples; s++) {
+    fprintf(out, "%c%d\t%llu\t%llu\t%llu\t%llu", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)n_obs[s], (unsigned long long)n_distinct[s],
+            (unsigned long long)m[s].h1, (unsigned long long)m[s].h2);
+    for (double v : {m[s].nrf, m[s].pbc1, m[s].pbc2, m[s].dup_fraction}) put_cpx(out, v, "\t%.6f");
+    put_cpx(out, m[s].library_size, "\t%.0f");
+    for (int k = 0; k < GX_CPX_CURVE; k++) put_cpx(out, m[s].curve[k], "\t%.3f");
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// ... and the sparse histogram: sample, multiplicity, keys
+int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* mult,
+                              const uint64_t* const* keys, const size_t* n_pairs) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !mult || !keys || !n_pairs) return GX_ERR_ORDER;
+  for (int s = 0; s < n_samples; s++)
+    if (n_pairs[s] && (!mult[s] || !keys[s])) return GX_ERR_ORDER;
+  fprintf(out, "sample\tmultiplicity\tkeys\n");
+  for (int s = 0; s < n_samples; s++)
+    for (size_t i = 0; i < n_pairs[s]; i++)
+      fprintf(out, "%c%d\t%llu\t%llu\n", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)mult[s][i], (unsigned long long)keys[s][i]);
   return GX_OK;
 }
 

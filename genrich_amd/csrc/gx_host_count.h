@@ -36,6 +36,43 @@ void drop_kept(gx_ctx* ctx) {
   ctx->countsReady = ctx->regionsReady = false;
 }
 
+// The staging the passes over the kept samples share (count_in_peaks, count_in_regions, the complexity pass): a sample's view of
+// the chromosome table, and its pieces cut into chunks of CNT_CHUNK events.
+// save: the chromosomes the sample's pileup took (null: every one)
+void stage_chroms(const gx_ctx* ctx, const std::vector<uint8_t>* save, CntChrom* ch) {
+  for (u32 c = 0; c < ctx->nChrom; c++) {
+    const DChrom& d = ctx->hChrom[c];
+    const bool act = !ctx->skip[c] && (!save || (*save)[c]) && ctx->owned[c] && d.tileBase != NULL_TILE;
+    ch[c] = CntChrom{act ? (u64)d.tileBase << TB : 0ull, d.len, act ? 1u : 0u};
+  }
+}
+size_t chunks_of(const std::vector<gx_ctx::Seg>& segs) {
+  size_t c = 0;
+  for (const gx_ctx::Seg& sg : segs) c += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
+  return c;
+}
+CntChunk* stage_chunks(const std::vector<gx_ctx::Seg>& segs, CntChunk* at) {
+  for (const gx_ctx::Seg& sg : segs) {
+    const size_t esz = sg.packed ? sizeof(gx_event8) : sizeof(gx_event);
+    for (size_t o = 0; o < sg.n; o += CNT_CHUNK)
+      *at++ = CntChunk{reinterpret_cast<const char*>(sg.p) + o * esz, (u32)std::min<size_t>(CNT_CHUNK, sg.n - o), sg.packed ? 1u : 0u};
+  }
+  return at;
+}
+// chunk0[k] = the first chunk of kept sample k (chunk0[nS] = all of them)
+std::vector<size_t> kept_chunk_offsets(const gx_ctx* ctx) {
+  std::vector<size_t> chunk0(ctx->kept.size() + 1, 0);
+  for (size_t k = 0; k < ctx->kept.size(); k++) chunk0[k + 1] = chunk0[k] + chunks_of(ctx->kept[k].segs);
+  return chunk0;
+}
+// ch[nS * nChrom], ck[chunk0[nS]]
+void stage_kept(const gx_ctx* ctx, const std::vector<size_t>& chunk0, CntChrom* ch, CntChunk* ck) {
+  for (size_t k = 0; k < ctx->kept.size(); k++) {
+    stage_chroms(ctx, &ctx->kept[k].save, ch + k * ctx->nChrom);
+    stage_chunks(ctx->kept[k].segs, ck + chunk0[k]);
+  }
+}
+
 int count_in_peaks(gx_ctx* ctx) {
   hipStream_t s = ctx->stream;
   const u32 nS = (u32)ctx->kept.size(), nChrom = ctx->nChrom;
@@ -46,12 +83,7 @@ int count_in_peaks(gx_ctx* ctx) {
   }
   const gx_peak* hp = static_cast<const gx_peak*>(ctx->hPeaks.p);
   // staging: the peaks in tile space (+ the sentinel), each sample's chromosome table, each sample's chunks
-  std::vector<size_t> chunk0(nS + 1, 0);
-  for (u32 k = 0; k < nS; k++) {
-    size_t c = 0;
-    for (const gx_ctx::Seg& sg : ctx->kept[k].segs) c += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
-    chunk0[k + 1] = chunk0[k] + c;
-  }
+  const std::vector<size_t> chunk0 = kept_chunk_offsets(ctx);
   const size_t pkBytes = (nPk + 1) * sizeof(CntPeak), chBytes = (size_t)nS * nChrom * sizeof(CntChrom),
                ckBytes = chunk0[nS] * sizeof(CntChunk);
   const size_t total = pkBytes + chBytes + ckBytes;
@@ -71,20 +103,7 @@ int count_in_peaks(gx_ctx* ctx) {
   pk[nPk] = CntPeak{~0ull, ~0ull};
   CntChrom* ch = reinterpret_cast<CntChrom*>(st + pkBytes);
   CntChunk* ck = reinterpret_cast<CntChunk*>(st + pkBytes + chBytes);
-  for (u32 k = 0; k < nS; k++) {
-    const gx_ctx::KeptSample& ks = ctx->kept[k];
-    for (u32 c = 0; c < nChrom; c++) {
-      const DChrom& d = ctx->hChrom[c];
-      const bool act = !ctx->skip[c] && ks.save[c] && ctx->owned[c] && d.tileBase != NULL_TILE;
-      ch[(size_t)k * nChrom + c] = CntChrom{act ? (u64)d.tileBase << TB : 0ull, d.len, act ? 1u : 0u};
-    }
-    CntChunk* at = ck + chunk0[k];
-    for (const gx_ctx::Seg& sg : ks.segs) {
-      const size_t esz = sg.packed ? sizeof(gx_event8) : sizeof(gx_event);
-      for (size_t o = 0; o < sg.n; o += CNT_CHUNK)
-        *at++ = CntChunk{reinterpret_cast<const char*>(sg.p) + o * esz, (u32)std::min<size_t>(CNT_CHUNK, sg.n - o), sg.packed ? 1u : 0u};
-    }
-  }
+  stage_kept(ctx, chunk0, ch, ck);
   phase_begin(ctx, "count");
   HIPCHECK(hipMemcpyAsync(ctx->cntIn.p, st, total, hipMemcpyHostToDevice, s));
   const CntPeak* dPk = ctx->cntIn.as<CntPeak>();

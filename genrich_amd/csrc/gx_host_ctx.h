@@ -32,6 +32,7 @@
 #include "gx_gram.h"
 #include "gx_fingerprint.h"
 #include "gx_rank.h"
+#include "gx_complexity.h"
 
 using namespace gx;
 
@@ -461,6 +462,20 @@ struct gx_ctx {
   DevBuf rankOut;                 // the rank rows k_gram reads
   bool rankUsed = false;          // k_rank ran since the last gx_reset
   u32 rankLastCapLog = 0, rankLastGrown = 0;   // the last k_rank_distinct pass: log2 of the capacity it ended with, how often it grew (gx_rank_last)
+  // library complexity of the kept samples' intervals (gx_complexity / gx_complexity_events, gx_complexity.h); nothing here
+  // exists before the first call
+  struct CpxResult {
+    int rep = 0;
+    bool ctrl = false;
+    u64 N = 0, D = 0;               // observations, distinct keys
+    std::vector<uint64_t> mult, keys;   // h, sparse: keys[i] keys were seen mult[i] times (mult ascending)
+  };
+  DevBuf cpxTab, cpxCtl, cpxBig;  // the table (reused sample after sample), the control words + k_cpx_hist's histogram, its list
+  DevBuf cpxIn, cpxEv;            // the staged chromosome views and chunk lists; gx_complexity_events' copy of the caller's events
+  std::vector<CpxResult> cpx;     // the last gx_complexity, per kept sample (until gx_reset)
+  bool cpxReady = false;
+  bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
+  u32 cpxLastCapLog = 0;          // log2 of the capacity the last pass used (gx_complexity_last)
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

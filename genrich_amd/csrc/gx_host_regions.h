@@ -32,12 +32,7 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
   ctx->regSamples = nS;
   if (!nS) return GX_OK;
   // staging: A, B (room for n + a sentinel each), the regions' ranks, each sample's chromosome table, each sample's chunks
-  std::vector<size_t> chunk0(nS + 1, 0);
-  for (u32 k = 0; k < nS; k++) {
-    size_t c = 0;
-    for (const gx_ctx::Seg& sg : ctx->kept[k].segs) c += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
-    chunk0[k + 1] = chunk0[k] + c;
-  }
+  const std::vector<size_t> chunk0 = kept_chunk_offsets(ctx);
   const size_t abBytes = (n + 1) * 8, rkBytes = ((n + 1) & ~(size_t)1) * 4, chBytes = (size_t)nS * nChrom * sizeof(CntChrom),
                ckBytes = chunk0[nS] * sizeof(CntChunk);
   const size_t total = 2 * abBytes + 2 * rkBytes + chBytes + ckBytes;
@@ -69,20 +64,7 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
   hA[m] = hB[m] = ~0ull;
   CntChrom* ch = reinterpret_cast<CntChrom*>(st + 2 * abBytes + 2 * rkBytes);
   CntChunk* ck = reinterpret_cast<CntChunk*>(st + 2 * abBytes + 2 * rkBytes + chBytes);
-  for (u32 k = 0; k < nS; k++) {
-    const gx_ctx::KeptSample& ks = ctx->kept[k];
-    for (u32 c = 0; c < nChrom; c++) {
-      const DChrom& d = ctx->hChrom[c];
-      const bool act = !ctx->skip[c] && ks.save[c] && ctx->owned[c] && d.tileBase != NULL_TILE;
-      ch[(size_t)k * nChrom + c] = CntChrom{act ? (u64)d.tileBase << TB : 0ull, d.len, act ? 1u : 0u};
-    }
-    CntChunk* at = ck + chunk0[k];
-    for (const gx_ctx::Seg& sg : ks.segs) {
-      const size_t esz = sg.packed ? sizeof(gx_event8) : sizeof(gx_event);
-      for (size_t o = 0; o < sg.n; o += CNT_CHUNK)
-        *at++ = CntChunk{reinterpret_cast<const char*>(sg.p) + o * esz, (u32)std::min<size_t>(CNT_CHUNK, sg.n - o), sg.packed ? 1u : 0u};
-    }
-  }
+  stage_kept(ctx, chunk0, ch, ck);
   const char* din = ctx->regIn.as<char>();
   const u64* dA = reinterpret_cast<const u64*>(din);
   const u64* dB = reinterpret_cast<const u64*>(din + abBytes);

@@ -161,6 +161,8 @@ struct Opts {
   const char* spearmanFile = nullptr;      // --spearman FILE: the samples' Spearman matrix from the coverage bins
   const char* fingerprintFile = nullptr;   // --fingerprint FILE: each sample's Lorenz curve from the coverage bins
   const char* fingerprintMetricsFile = nullptr;   // --fingerprint-metrics FILE: ... and its figures
+  const char* complexityFile = nullptr;    // --complexity FILE: each sample's library complexity from its kept intervals
+  const char* complexityHistFile = nullptr;   // --complexity-hist FILE: ... and its duplication histogram
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2778,6 +2780,52 @@ void writeFingerprint(State& S) {
             m[i].zero_fraction, m[i].auc, m[i].gini, m[i].elbow_bins, m[i].elbow_gap, m[i].jsd_control);
 }
 
+// --complexity FILE [--complexity-hist FILE]: each sample's intervals (its -b lines) as observations of (chromosome, start, end)
+// keys, counted on the device (one pass per context and sample, added): N, D, the duplication histogram and the figures made
+// of it (NRF, PBC1, PBC2, the duplicate fraction, the estimated library size, the complexity curve), one row per sample labelled
+// t<rep> / c<rep>; with -v the main figures on stderr too
+void writeComplexity(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n();
+  int nS = 0;
+  for (gx_ctx* g : S.devs.ctx) {   // (before a file is opened: a context's refusal carries its own text)
+    int n = 0;
+    check(S, gx_complexity(g, &n), g);
+    if (g != g0 && n != nS) die("", "--complexity: the devices kept different numbers of samples");
+    nS = n;
+  }
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> N((size_t)nS), D((size_t)nS);
+  std::vector<std::vector<uint64_t>> mult((size_t)nS), keys((size_t)nS);
+  std::vector<const uint64_t*> pm((size_t)nS), pk((size_t)nS);
+  std::vector<size_t> np((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    check(S, gx_complexity_group(ctxs, nCtx, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &np[i]), g0);
+    mult[i].resize(np[i]);
+    keys[i].resize(np[i]);
+    check(S, gx_complexity_group(ctxs, nCtx, i, &rep[i], &ctrl[i], &N[i], &D[i], mult[i].data(), keys[i].data(), np[i], nullptr), g0);
+    pm[i] = mult[i].data();
+    pk[i] = keys[i].data();
+  }
+  Out out = openWrite(o.complexityFile, o.gzOut);
+  check(S, gx_format_complexity(out.f, nS, rep.data(), ctrl.data(), N.data(), D.data(), pm.data(), pk.data(), np.data()), g0);
+  closeOut(out);
+  if (o.complexityHistFile) {
+    Out hist = openWrite(o.complexityHistFile, o.gzOut);
+    check(S, gx_format_complexity_hist(hist.f, nS, rep.data(), ctrl.data(), pm.data(), pk.data(), np.data()), g0);
+    closeOut(hist);
+  }
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++) {
+    gx_cpx_metrics m;
+    check(S, gx_complexity_metrics(N[i], D[i], pm[i], pk[i], np[i], &m), g0);
+    fprintf(stderr, "  Library complexity, %s file #%d: %llu intervals, %llu distinct (NRF %f, PBC1 %f, PBC2 %f, estimated library size %.0f)\n",
+            ctrl[i] ? "control" : "experimental", rep[i], (unsigned long long)N[i], (unsigned long long)D[i], m.nrf, m.pbc1, m.pbc2, m.library_size);
+  }
+}
+
 // --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
@@ -2881,6 +2929,10 @@ void usage() {
           "  --fingerprint FILE [--fingerprint-metrics FILE]   each sample's fingerprint (Lorenz curve) over its bins of --bin-size N (50)\n"
           "                  bases: a TSV of cumulative bins and signal per value class; the metrics file has the zero fraction, area,\n"
           "                  Gini, elbow and the divergence from the replicate's control per sample\n"
+          "  --complexity FILE [--complexity-hist FILE]   each sample's library complexity from its intervals (the -b lines) as\n"
+          "                  (chromosome, start, end) keys: N, distinct, NRF, PBC1, PBC2, duplicate fraction, estimated library size and\n"
+          "                  the expected distinct keys at 5 %% .. 100 %% of the depth, a TSV labelled t<rep> / c<rep>; the histogram\n"
+          "                  file has the number of keys seen m times per sample and m\n"
           "  --profile BED --profile-out PREFIX [--flank N] [--profile-bin N] [--profile-at tss|center] [--profile-matrix]\n"
           "                  each sample's pileup around the BED's sites, N (2000) bases to either side in bins of N (10) bases,\n"
           "                  oriented by column 6: PREFIX.profile.tsv, the mean per base and site at every offset; a site is the\n"
@@ -2919,6 +2971,8 @@ int main(int argc, char** argv) {
                                      {"fingerprint", required_argument, nullptr, 1018},
                                      {"fingerprint-metrics", required_argument, nullptr, 1019},
                                      {"spearman", required_argument, nullptr, 1020},
+                                     {"complexity", required_argument, nullptr, 1021},
+                                     {"complexity-hist", required_argument, nullptr, 1022},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -2987,6 +3041,8 @@ int main(int argc, char** argv) {
       case 1017: o.corrSkipZeros = true; break;
       case 1018: o.fingerprintFile = optarg; break;
       case 1019: o.fingerprintMetricsFile = optarg; break;
+      case 1021: o.complexityFile = optarg; break;
+      case 1022: o.complexityHistFile = optarg; break;
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -3021,6 +3077,9 @@ int main(int argc, char** argv) {
   if (o.corrSkipZeros && !o.correlationFile && !o.spearmanFile) die("", "--corr-skip-zeros needs --correlation FILE or --spearman FILE");
   if (o.fingerprintFile && (o.peaksOnly || o.eventsOnly)) die("", "--fingerprint needs the pileups of this run (not with -P or --events-only)");
   if (o.fingerprintMetricsFile && !o.fingerprintFile) die("", "--fingerprint-metrics needs --fingerprint FILE");
+  // (the complexity counts the events the library keeps: none with -P or --events-only; -X is fine)
+  if (o.complexityFile && (o.peaksOnly || o.eventsOnly)) die("", "--complexity needs the intervals of this run (not with -P or --events-only)");
+  if (o.complexityHistFile && !o.complexityFile) die("", "--complexity-hist needs --complexity FILE");
   if (o.correlationFile || o.fingerprintFile || o.spearmanFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
     auto split = [](const char* list) {
       std::vector<std::string> out;
@@ -3128,7 +3187,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.regionsBed) check(S, gx_set_count_in_peaks(g, 1), g);
+      if (o.countsFile || o.regionsBed || o.complexityFile) check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -3303,6 +3362,7 @@ int main(int argc, char** argv) {
   if (o.correlationFile) writeCorrelation(S);
   if (o.spearmanFile) writeSpearman(S);
   if (o.fingerprintFile) writeFingerprint(S);
+  if (o.complexityFile) writeComplexity(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);

@@ -128,6 +128,19 @@ FP_METRICS_DTYPE = np.dtype([(k, "<f8") for k in ("zero_fraction", "auc", "gini"
 
 
 GX_PATH_SPEARMAN = 4194304      # gx_path_info bit 22: k_rank ran (gx_coverage_rank_gram, gx_rank_u64)
+GX_PATH_COMPLEXITY = 8388608    # gx_path_info bit 23: k_cpx_insert ran (gx_complexity, gx_complexity_events)
+CPX_CURVE = 20                  # GX_CPX_CURVE: the points of the complexity curve (5 % steps of the depth)
+CPX_METRICS_DTYPE = np.dtype([("h1", "<u8"), ("h2", "<u8")] + [(k, "<f8") for k in ("nrf", "pbc1", "pbc2", "dup_fraction", "library_size")]
+                             + [("curve", "<f8", (CPX_CURVE,))])   # gx_cpx_metrics
+
+
+class Complexity(NamedTuple):
+    """One sample's library complexity (gx_get_complexity): N observations, D distinct keys, pairs = [(m, h[m])] ascending."""
+    n_obs: int
+    n_distinct: int
+    pairs: list
+    rep: int
+    is_ctrl: bool
 
 
 class RankTable(C.Structure):
@@ -252,6 +265,19 @@ _SIGS = {
     "gx_rank_u64": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)],
     "gx_rank_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "gx_rank_last": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "gx_complexity": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_complexity": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
+                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_complexity_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
+                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_complexity_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_size_t)],
+    "gx_complexity_last": [C.c_void_p, C.POINTER(C.c_size_t)],
+    "gx_complexity_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                            C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_complexity_metrics": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "gx_format_complexity": [C.c_void_p, C.c_int] + [C.c_void_p] * 7,
+    "gx_format_complexity_hist": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,
+    "gx_write_complexity_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -481,6 +507,93 @@ def spearman_text(ctxs, sample_names, skip_zeros=False) -> bytes:
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
     names = _c_names(list(sample_names))
     return _to_tmpfile(lambda f: lib.gx_write_spearman_group(arr, len(ctxs), len(sample_names), names, int(bool(skip_zeros)), f))
+
+
+def complexity_geometry(n=0):
+    """(lanes, grid, lds_bound, least_capacity) of the complexity pass as the library was built (gx_complexity_geometry): the lanes
+    of a workgroup of k_cpx_insert, its most workgroups with grid = 0, the multiplicity from which k_cpx_hist lists a key instead
+    of counting it in LDS, and the least table capacity for a sample of n events."""
+    lib = load_library()
+    lanes, grid, bound, cap = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_size_t(0)
+    lib.gx_complexity_geometry(C.byref(lanes), C.byref(grid), C.byref(bound), int(n), C.byref(cap))
+    return lanes.value, grid.value, bound.value, cap.value
+
+
+def _cpx_pairs(pairs):
+    m = np.ascontiguousarray([p[0] for p in pairs], dtype=np.uint64)
+    k = np.ascontiguousarray([p[1] for p in pairs], dtype=np.uint64)
+    return m, k
+
+
+def complexity_metrics(n_obs, n_distinct, pairs):
+    """gx_complexity_metrics as one CPX_METRICS_DTYPE record; pairs: [(m, h[m])] ascending; host-only."""
+    lib = load_library()
+    m, k = _cpx_pairs(pairs)
+    out = np.zeros(1, dtype=CPX_METRICS_DTYPE)
+    rc = lib.gx_complexity_metrics(int(n_obs), int(n_distinct), m.ctypes.data if m.size else None, k.ctypes.data if k.size else None, m.size,
+                                   out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_complexity_metrics: {rc}")
+    return out[0]
+
+
+def _cpx_samples(samples):
+    """samples: [(rep, is_ctrl, N, D, pairs)] -> the arrays gx_format_complexity* take (and what keeps them alive)."""
+    S = len(samples)
+    rep = np.ascontiguousarray([s[0] for s in samples], dtype=np.int32)
+    ctrl = np.ascontiguousarray([int(bool(s[1])) for s in samples], dtype=np.int32)
+    N = np.ascontiguousarray([s[2] for s in samples], dtype=np.uint64)
+    D = np.ascontiguousarray([s[3] for s in samples], dtype=np.uint64)
+    cols = [_cpx_pairs(s[4]) for s in samples]
+    pm = (C.c_void_p * max(S, 1))(*[c[0].ctypes.data if c[0].size else None for c in cols])
+    pk = (C.c_void_p * max(S, 1))(*[c[1].ctypes.data if c[1].size else None for c in cols])
+    npairs = (C.c_size_t * max(S, 1))(*[c[0].size for c in cols])
+    return S, rep, ctrl, N, D, pm, pk, npairs, cols
+
+
+def format_complexity(samples) -> bytes:
+    """--complexity's table (gx_format_complexity); samples: [(rep, is_ctrl, N, D, pairs)]; host-only, needs no GPU."""
+    lib = load_library()
+    S, rep, ctrl, N, D, pm, pk, npairs, keep = _cpx_samples(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_complexity(f, S, rep.ctypes.data, ctrl.ctypes.data, N.ctypes.data, D.ctypes.data, pm, pk, npairs))
+
+
+def format_complexity_hist(samples) -> bytes:
+    """--complexity-hist's table (gx_format_complexity_hist); samples as for format_complexity."""
+    lib = load_library()
+    S, rep, ctrl, N, D, pm, pk, npairs, keep = _cpx_samples(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_complexity_hist(f, S, rep.ctypes.data, ctrl.ctypes.data, pm, pk, npairs))
+
+
+def complexity_group(ctxs, sample):
+    """Complexity of one sample added over the contexts of a run (gx_complexity_group); every context has run complexity()."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    n = C.c_size_t(0)
+    ctxs[0]._check(lib.gx_complexity_group(arr, len(ctxs), int(sample), None, None, None, None, None, None, 0, C.byref(n)))
+    m, k = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint64)
+    rep, ctrl, N, D = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+    ctxs[0]._check(lib.gx_complexity_group(arr, len(ctxs), int(sample), C.byref(rep), C.byref(ctrl), C.byref(N), C.byref(D), m.ctypes.data,
+                                           k.ctypes.data, n.value, C.byref(n)))
+    return Complexity(N.value, D.value, [(int(a), int(b)) for a, b in zip(m[:n.value], k[:n.value])], rep.value, bool(ctrl.value))
+
+
+def complexity_text(ctxs, with_hist=True):
+    """(--complexity's table, --complexity-hist's) over the contexts of a run (gx_write_complexity_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    hist = []
+
+    def both(f):
+        if not with_hist:
+            return lib.gx_write_complexity_group(arr, len(ctxs), f, None)
+        hist.append(_to_tmpfile(lambda h: lib.gx_write_complexity_group(arr, len(ctxs), f, h)))
+        return 0
+    try:
+        met = _to_tmpfile(both)
+    except RuntimeError as e:
+        raise RuntimeError(f"{e} [{'; '.join(lib.gx_last_error(c.ctx).decode() for c in ctxs)}]") from None
+    return met, (hist[0] if hist else None)
 
 
 def fp_geometry():
@@ -780,7 +893,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -888,6 +1001,41 @@ class Genrich:
         self._check(self.lib.gx_gram_u64(self.ctx, ptr, n_rows, n, int(grid), C.byref(nz), s.ctypes.data,
                                          g.ctypes.data))
         return nz.value, _join128(s[:n_rows]), _join128(g[:n_rows, :n_rows])
+
+    # -- library complexity of the samples' intervals (include/genrich_amd.h, gx_complexity) -----------------------------
+    def complexity(self):
+        """N, D and the duplication histogram of every sample closed so far (gx_complexity); needs set_count_in_peaks(True), no
+        peaks.  Returns the number of samples."""
+        n = C.c_int(0)
+        self._check(self.lib.gx_complexity(self.ctx, C.byref(n)))
+        return n.value
+
+    def get_complexity(self, sample):
+        """Complexity(n_obs, n_distinct, pairs, rep, is_ctrl) of one sample of the last complexity()."""
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_get_complexity(self.ctx, int(sample), None, None, None, None, None, None, 0, C.byref(n)))
+        m, k = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint64)
+        rep, ctrl, N, D = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_get_complexity(self.ctx, int(sample), C.byref(rep), C.byref(ctrl), C.byref(N), C.byref(D), m.ctypes.data,
+                                               k.ctypes.data, n.value, C.byref(n)))
+        return Complexity(N.value, D.value, [(int(a), int(b)) for a, b in zip(m[:n.value], k[:n.value])], rep.value, bool(ctrl.value))
+
+    def complexity_events(self, events, grid=0, cap_log=0):
+        """(N, D, pairs) of host events (EVENT_DTYPE) taken as one sample over this context's chromosome table, by the same kernels
+        (gx_complexity_events); grid = 0 / cap_log = 0: the library's geometry and capacity."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+        N, D, n = C.c_uint64(0), C.c_uint64(0), C.c_size_t(0)
+        cap = int(ev.size) + 1   # (at most one class per event)
+        m, k = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+        self._check(self.lib.gx_complexity_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, int(grid), int(cap_log), C.byref(N),
+                                                  C.byref(D), m.ctypes.data, k.ctypes.data, cap, C.byref(n)))
+        return N.value, D.value, [(int(a), int(b)) for a, b in zip(m[:n.value], k[:n.value])]
+
+    def complexity_last(self):
+        """The table capacity the last complexity pass of this context used (gx_complexity_last; 0: none yet)."""
+        c = C.c_size_t(0)
+        self._check(self.lib.gx_complexity_last(self.ctx, C.byref(c)))
+        return c.value
 
     # -- fingerprint of the samples' bins (include/genrich_amd.h, gx_coverage_fingerprint) -------------------------------
     def coverage_fingerprint(self):

@@ -468,6 +468,54 @@ int gx_rank_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigne
 int gx_rank_geometry(int* lanes, int* grid, int* cache_entries, size_t* first_capacity, size_t* load_limit);
 int gx_rank_last(gx_ctx* ctx, size_t* capacity, int* n_grown);
 
+/* ---- library complexity of each sample's intervals (no Genrich counterpart: NRF, PBC1, PBC2, Picard's estimated library size
+ *      and preseq's c_curve, which otherwise want the whole BAM sorted into a bedpe, or another reading of it) ----
+ * A sample = every gx_sample_end of the run in call order, as for gx_count_in_peaks.  Its intervals are exactly those
+ * gx_count_in_peaks counts, i.e. its -b lines: count valid (1-6, 8 or 10), chromosome known, not skipped (-e), in the
+ * sample's save mask and owned by this context, start < the chromosome's length, the end clamped to that length; empty
+ * intervals are included, and so are intervals that end before they start, as they are.  Each interval is ONE observation,
+ * whatever its -s weight.  Its key is the triple (chrom, start, clamped end); `count` is not part of it.  Two ends that differ
+ * but clamp to the same length are the same key; the same coordinates on two chromosomes are two keys.  Per sample, all
+ * exact uint64:
+ *     N    = observations          D = distinct keys          h[m] = the number of keys seen exactly m times
+ * so that sum h[m] = D and sum m h[m] = N.  h is reported sparse: (m, h[m]) pairs with h[m] > 0, ascending in m.  A key lives
+ * on one chromosome and a chromosome on one context, so the contexts' N, D and h simply add (gx_complexity_group does).  The
+ * result is the same for every launch geometry, table capacity, push mode and number of GPUs: integer adds only.
+ * In -j ATAC mode a fragment contributes its two cut-site intervals, and the figures are over cut sites, not fragments.  After
+ * -r the figures describe what -r left (its duplicates never reach the library).  Events carry no strand: none in the key.
+ * Limits, each refused with GX_ERR_ORDER and a text before anything is allocated or launched: the device's key is 64 bits,
+ * 32 of them the start in the context's tile space (every chromosome's length rounded up to a tile, added), so that space
+ * must not exceed 2^32 - 1 bases (hg38: 3.1 * 10^9); a sample of 2^31 events or more on one context.
+ *
+ * gx_complexity: the pass (k_cpx_insert, k_cpx_hist: gx_complexity.h) over every sample closed so far (*n_samples of them): per
+ *   sample a table of at least 2 n slots for its n events, sized once and reused for the next sample.  It needs
+ *   gx_set_count_in_peaks on, at least one closed sample and none open, else GX_ERR_ORDER with a text; it needs no gx_pvalues
+ *   and no gx_find_peaks, and may be called again: the same answer.  The results of gx_count_in_peaks / gx_count_in_regions
+ *   stay readable.  gx_reset drops the result.  A failed allocation: GX_ERR_MEM.  A bounded loop of the kernels that ran out
+ *   (it cannot, with a table at most half full): GX_ERR_DEVICE with a text, never a hang.  Nothing of it is allocated or
+ *   launched before the first call.
+ * gx_get_complexity: the last pass's result for one sample (0 .. n_samples-1): its replicate, whether it is a control, N, D,
+ *   min(cap, n_classes) pairs in mult[] / keys[] and *n_classes.  Any pointer may be NULL (mult and keys when cap is 0).
+ * gx_complexity_events: the same two kernels over n events in host memory (copied to the device by the call), all treated as
+ *   ONE sample whose save mask lists every chromosome of the context's table (-e and gx_set_owned hold as for a sample).
+ *   grid = 0 and cap_log = 0: the library's choices; else that many workgroups (at most 65535) for either kernel and a table of
+ *   2^cap_log slots; 2^cap_log < 2 n (or cap_log > 32): GX_ERR_ORDER before anything is launched.  No sample open.  For tests
+ *   and measurements; it leaves gx_get_complexity's result alone.
+ * gx_complexity_geometry: what the edge cases depend on: the lanes of a workgroup of k_cpx_insert, its most workgroups with
+ *   grid = 0, the bound below which k_cpx_hist counts a multiplicity in LDS (at or above it the key goes to a list), and the
+ *   least capacity for n events (0: n >= 2^31).  Any pointer may be NULL.  gx_complexity_last: the capacity the last pass used.
+ * gx_complexity_group: sample `sample` of every context's last gx_complexity, added; the outputs as gx_get_complexity's.  A
+ *   context without a result, or contexts that differ in their samples: GX_ERR_ORDER. */
+int gx_complexity(gx_ctx* ctx, int* n_samples);
+int gx_get_complexity(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult,
+                      uint64_t* keys, size_t cap, size_t* n_classes);
+int gx_complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, int cap_log, uint64_t* n_obs,
+                         uint64_t* n_distinct, uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes);
+int gx_complexity_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint64_t n, size_t* least_capacity);
+int gx_complexity_last(gx_ctx* ctx, size_t* capacity);
+int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct,
+                        uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -621,6 +669,38 @@ int gx_format_fingerprint_metrics(FILE* out, int n_samples, const char* const* s
 int gx_coverage_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum);
 int gx_write_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, const int* ctrl_of,
                                FILE* curve, FILE* metrics);
+/* --complexity (no Genrich counterpart).  The first three: host only, no context.  A sample's histogram is n_pairs pairs
+ * (mult[i], keys[i]), mult strictly ascending and >= 1, keys >= 1, with sum keys = D and sum mult keys = N (else GX_ERR_ORDER).
+ * gx_complexity_metrics, with h1 = h[1] and h2 = h[2]:
+ *     nrf = D / N        pbc1 = h1 / D        pbc2 = h1 / h2        dup_fraction = (N - D) / N
+ *   each ONE division of two integers (the correctly rounded double while both are below 2^53), NaN where the divisor is 0;
+ *     library_size = the X with D / X = 1 - exp(-N / X) (Lander-Waterman: what Picard prints), by bisection with expm1 in long
+ *   double, rounded to an integer; NaN when D == N or N == 0;
+ *     curve[k - 1], k = 1 .. GX_CPX_CURVE = 20: with n = floor((k N + 10) / 20), i.e. round(0.05 k N) with halves up, the expected
+ *   number of distinct keys among n of the N observations drawn without replacement,
+ *     E_n = sum_m h[m] (1 - prod_{i=0}^{m-1} (N - n - i) / (N - i)),
+ *   the product taken factor by factor in long double and stopped once it is 0 or below 2^-80 (then 1 - p is 1); E_N = D exactly,
+ *   and every point is 0 when N == 0.
+ * gx_format_complexity: a TSV, header "sample N D h1 h2 NRF PBC1 PBC2 dup_fraction library_size c005 c010 ... c100", one row
+ *   per sample labelled t<rep> / c<rep>: the integers, the four ratios as %.6f, the library size as an integer, the curve's
+ *   points as %.3f; a figure that is not defined prints as NA.
+ * gx_format_complexity_hist: header "sample multiplicity keys", one row per sample and pair.
+ * A missing pointer or n_samples < 1: GX_ERR_ORDER, nothing written.
+ * gx_write_complexity_group (gx_api.hip: it reads contexts): gx_complexity on every context, gx_complexity_group per sample,
+ *   then the figures to `metrics` and, unless NULL, the histogram to `hist`. */
+#define GX_CPX_CURVE 20
+typedef struct {
+  uint64_t h1, h2;
+  double nrf, pbc1, pbc2, dup_fraction, library_size;
+  double curve[GX_CPX_CURVE];
+} gx_cpx_metrics;
+int gx_complexity_metrics(uint64_t n_obs, uint64_t n_distinct, const uint64_t* mult, const uint64_t* keys, size_t n_pairs,
+                          gx_cpx_metrics* out);
+int gx_format_complexity(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_obs,
+                         const uint64_t* n_distinct, const uint64_t* const* mult, const uint64_t* const* keys, const size_t* n_pairs);
+int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* mult,
+                              const uint64_t* const* keys, const size_t* n_pairs);
+int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -714,6 +794,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_GRAM 1048576u /* bit 20: k_gram / k_gram_sum ran since the last gx_reset (gx_coverage_gram, gx_gram_u64) */
 #define GX_PATH_FINGERPRINT 2097152u /* bit 21: k_fp_hist ran since the last gx_reset (gx_coverage_fingerprint, gx_fp_u64) */
 #define GX_PATH_SPEARMAN 4194304u /* bit 22: k_rank ran since the last gx_reset (gx_coverage_rank_gram, gx_rank_u64) */
+#define GX_PATH_COMPLEXITY 8388608u /* bit 23: k_cpx_insert ran since the last gx_reset (gx_complexity, gx_complexity_events) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
