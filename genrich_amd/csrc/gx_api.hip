@@ -16,6 +16,7 @@
 #include "gx_host_fingerprint.h"
 #include "gx_host_rank.h"
 #include "gx_host_complexity.h"
+#include "gx_host_subsample.h"
 
 
 // ================================ C ABI ==================================================
@@ -117,6 +118,8 @@ int gx_create(gx_ctx** out, const gx_params* par) {
 
 void gx_destroy(gx_ctx* ctx) {
   if (!ctx) return;
+  if (ctx->satChild) gx_destroy(ctx->satChild);   // (gx_saturation's child context)
+  ctx->satChild = nullptr;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) {
@@ -141,6 +144,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
                   const int32_t* bed_len) {
   if (!ctx || n <= 0 || !len) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
+  if (ctx->satChild) sat_drop(ctx);   // (its table is the old one)
   ctx->nChrom = (u32)n;
   ctx->len.assign(len, len + n);
   ctx->skip.assign(n, 0);
@@ -223,6 +227,7 @@ int gx_set_keep_pileups(gx_ctx* ctx, int keep) {
 int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   if (!ctx || !owned || ctx->nChrom == 0) return GX_ERR_ORDER;
   if (ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;  // the tile space changes: between runs only
+  if (ctx->satChild) sat_drop(ctx);   // (its mask is the old one)
   ctx->owned.assign(owned, owned + ctx->nChrom);
   ctx->covDirty = true;
   ctx->profDirty = true;
@@ -263,6 +268,7 @@ int gx_reset(gx_ctx* ctx) {
   ctx->rankUsed = false;
   ctx->cpx.clear();     // (the buffers stay with the context)
   ctx->cpxReady = ctx->cpxUsed = false;
+  if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
@@ -846,7 +852,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
-           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u);
+           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u);
   return GX_OK;
 }
 
@@ -1417,6 +1423,87 @@ int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FIL
   }
   if (int rc = gx_format_complexity(metrics, nS, rep.data(), ctrl.data(), N.data(), D.data(), pm.data(), pk.data(), np.data())) return rc;
   return hist ? gx_format_complexity_hist(hist, nS, rep.data(), ctrl.data(), pm.data(), pk.data(), np.data()) : GX_OK;
+}
+
+uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index) { return subsample_draw(subsample_key(seed, sample), index); }
+
+int gx_subsample_geometry(int* lanes, int* grid, uint32_t* block_events) {
+  if (lanes) *lanes = SUB_NT;
+  if (grid) *grid = (int)SUB_GRID;
+  if (block_events) *block_events = SUB_BLOCK;
+  return GX_OK;
+}
+
+int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold, unsigned grid,
+                        gx_event* out, size_t cap, size_t* n_out) {
+  if (!ctx || (n && !ev) || (cap && !out)) return GX_ERR_ORDER;
+  if (ctx->phase == 1 || ctx->phase == 3) return sub_refuse(ctx, "gx_subsample_events: a sample is open");
+  if (threshold > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
+  if (grid > SUB_MAX_GRID) return sub_refuse(ctx, "subsample: more than 65535 workgroups");
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<gx_ctx::Seg> segs;
+  if (n) {
+    const size_t bytes = n * (packed ? sizeof(gx_event8) : sizeof(gx_event));
+    POOLED(ctx, ctx->subEv, bytes);
+    HIPCHECK(hipMemcpyAsync(ctx->subEv.p, ev, bytes, hipMemcpyHostToDevice, ctx->stream));
+    segs.push_back({ctx->subEv.as<gx_event>(), n, nullptr, packed != 0});
+  }
+  const CntChunk* dCk = nullptr;
+  const u64* dFirst = nullptr;
+  u32 nCk = 0;
+  u64 nEv = 0, nKept = 0;
+  if (int rc = sub_stage(ctx, segs, &dCk, &dFirst, &nCk, &nEv)) return rc;
+  if (int rc = sub_pass(ctx, dCk, dFirst, nCk, nEv, subsample_key(seed, sample), threshold, grid, ctx->subOut, &nKept)) return rc;
+  return sub_give(ctx, ctx->subOut, nKept, out, cap, n_out);
+}
+
+int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_out) {
+  if (!ctx || (cap && !out)) return GX_ERR_ORDER;
+  if (!ctx->countOn) return sub_refuse(ctx, "gx_subsample_kept needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase == 1 || ctx->phase == 3) return sub_refuse(ctx, "gx_subsample_kept: a sample is open");
+  if (sample < 0 || (size_t)sample >= ctx->kept.size()) return sub_refuse(ctx, "gx_subsample_kept: no such sample");
+  if (threshold > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
+  HIPCHECK(hipSetDevice(ctx->device));
+  u64 n = 0, nKept = 0;
+  if (int rc = sub_kept(ctx, (size_t)sample, seed, threshold, &n, &nKept)) return rc;
+  return sub_give(ctx, ctx->subBufs[sample], nKept, out, cap, n_out);
+}
+
+int gx_saturation(gx_ctx* ctx, const uint64_t* threshold, int n_points, uint64_t seed, unsigned flags, gx_sat_point* out) {
+  if (!ctx || !threshold || n_points < 1 || !out || (flags & ~GX_SAT_CONTROLS)) return GX_ERR_ORDER;
+  if (!ctx->countOn) return sub_refuse(ctx, "gx_saturation needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase != 0 || !ctx->peaksReady) return sub_refuse(ctx, "gx_saturation comes after gx_find_peaks, with no sample open");
+  if (ctx->world > 1 || ctx->forceColl) return sub_refuse(ctx, "gx_saturation: one context only (the re-call on several needs collectives between their children)");
+  for (int j = 0; j < n_points; j++)
+    if (threshold[j] > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = sat_child(ctx)) return rc;
+  std::vector<gx_sat_point> pts((size_t)n_points);
+  std::vector<std::vector<gx_peak>> peaks((size_t)n_points);
+  for (int j = 0; j < n_points; j++)
+    if (int rc = sat_point(ctx, threshold[j], seed, flags, pts[j], peaks[j])) return rc;
+  std::copy(pts.begin(), pts.end(), out);
+  ctx->satPts = std::move(pts);
+  ctx->satPeaks = std::move(peaks);
+  return GX_OK;
+}
+
+int gx_get_saturation_peaks(gx_ctx* ctx, int point, gx_peak* out, size_t cap) {
+  if (!ctx || point < 0 || (size_t)point >= ctx->satPeaks.size() || (cap && !out)) return GX_ERR_ORDER;
+  const size_t n = std::min(cap, ctx->satPeaks[point].size());
+  if (n) memcpy(out, ctx->satPeaks[point].data(), n * sizeof(gx_peak));
+  return GX_OK;
+}
+
+// (here, not in gx_emit.cpp, like the other writers over contexts: it reads one)
+int gx_write_saturation(gx_ctx* ctx, FILE* out) {
+  if (!ctx || !out || ctx->satPts.empty() || !ctx->peaksReady) return GX_ERR_ORDER;
+  const size_t nP = ctx->satPts.size();
+  const gx_peak* full = static_cast<const gx_peak*>(ctx->hPeaks.p);
+  std::vector<uint64_t> rec(nP, 0), sub(nP, 0), bp(nP, 0);
+  for (size_t j = 0; j < nP; j++)
+    if (int rc = gx_saturation_overlap(full, ctx->nHostPeaks, ctx->satPeaks[j].data(), ctx->satPeaks[j].size(), &rec[j], &sub[j], &bp[j])) return rc;
+  return gx_format_saturation(out, (int)nP, ctx->satPts.data(), rec.data(), sub.data(), bp.data(), ctx->nHostPeaks, ctx->peakBP);
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint) and the library complexity tables (--complexity).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -652,6 +652,62 @@ int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const in
   for (int s = 0; s < n_samples; s++)
     for (size_t i = 0; i < n_pairs[s]; i++)
       fprintf(out, "%c%d\t%llu\t%llu\n", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)mult[s][i], (unsigned long long)keys[s][i]);
+  return GX_OK;
+}
+
+// --saturation: two peak lists in gx_get_peaks order, one merge walk (the --counts predicate: s < pe && ps < e)
+int gx_saturation_overlap(const gx_peak* full, size_t n_full, const gx_peak* sub, size_t n_sub, uint64_t* full_recovered,
+                          uint64_t* sub_in_full, uint64_t* shared_bp) {
+  if ((n_full && !full) || (n_sub && !sub)) return GX_ERR_ORDER;
+  uint64_t rec = 0, in = 0, bp = 0;
+  size_t i = 0, j = 0, lastI = (size_t)-1, lastJ = (size_t)-1;
+  while (i < n_full && j < n_sub) {
+    const gx_peak &F = full[i], &S = sub[j];
+    if (F.chrom != S.chrom) {
+      (F.chrom < S.chrom ? i : j)++;
+    } else if (F.end <= S.start) {
+      i++;
+    } else if (S.end <= F.start) {
+      j++;
+    } else {
+      if (i != lastI) rec++;
+      if (j != lastJ) in++;
+      lastI = i;
+      lastJ = j;
+      bp += std::min(F.end, S.end) - std::max(F.start, S.start);
+      if (F.end <= S.end) i++;   // (whichever ends first cannot touch what follows in the other list)
+      else j++;
+    }
+  }
+  if (full_recovered) *full_recovered = rec;
+  if (sub_in_full) *sub_in_full = in;
+  if (shared_bp) *shared_bp = bp;
+  return GX_OK;
+}
+
+int gx_saturation_thresholds(int n_points, uint64_t* threshold) {
+  if (n_points < 1 || n_points > 100 || !threshold) return GX_ERR_ORDER;
+  for (int j = 1; j <= n_points; j++) threshold[j - 1] = ((uint64_t)j << 32) / (uint64_t)n_points;
+  return GX_OK;
+}
+
+// ... one row per point, under a comment line with the run's own peaks
+int gx_format_saturation(FILE* out, int n_points, const gx_sat_point* points, const uint64_t* full_recovered, const uint64_t* sub_in_full,
+                         const uint64_t* shared_bp, uint64_t n_full, uint64_t full_bp) {
+  if (!out || n_points < 1 || !points || !full_recovered || !sub_in_full || !shared_bp) return GX_ERR_ORDER;
+  fprintf(out, "# run: %llu peaks, %llu bp\n", (unsigned long long)n_full, (unsigned long long)full_bp);
+  fprintf(out, "fraction\tthreshold\tkept\tpeaks\tpeak_bp\trecovered\trecovered_share\tin_run\tshared_bp\tstatus\n");
+  for (int j = 0; j < n_points; j++) {
+    const gx_sat_point& p = points[j];
+    fprintf(out, "%.6f\t%llu\t%llu\t%llu\t%llu\t%llu", (double)p.threshold / 4294967296.0, (unsigned long long)p.threshold,
+            (unsigned long long)p.n_kept, (unsigned long long)p.n_peaks, (unsigned long long)p.peak_bp, (unsigned long long)full_recovered[j]);
+    if (n_full) fprintf(out, "\t%.6f", (double)full_recovered[j] / (double)n_full);
+    else fprintf(out, "\tNA");
+    fprintf(out, "\t%llu\t%llu", (unsigned long long)sub_in_full[j], (unsigned long long)shared_bp[j]);
+    if (p.status == GX_OK) fprintf(out, "\tok\n");
+    else if (p.status == GX_ERR_EXPT) fprintf(out, "\tno_fragments\n");
+    else fprintf(out, "\t%d\n", (int)p.status);
+  }
   return GX_OK;
 }
 

@@ -33,6 +33,7 @@
 #include "gx_fingerprint.h"
 #include "gx_rank.h"
 #include "gx_complexity.h"
+#include "gx_subsample.h"
 
 using namespace gx;
 
@@ -476,6 +477,15 @@ struct gx_ctx {
   bool cpxReady = false;
   bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
   u32 cpxLastCapLog = 0;          // log2 of the capacity the last pass used (gx_complexity_last)
+  // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
+  // nothing here exists before the first call
+  DevBuf subIn, subCnt, subOff;   // the staged chunk list, k_sub_count's counts per block, k_sub_scan's offsets
+  DevBuf subEv, subOut;           // gx_subsample_events' copy of the caller's events and its output
+  std::vector<DevBuf> subBufs;    // kept sample k's subsample: the child reads it in place until its gx_sample_end
+  bool subUsed = false;           // k_sub_write ran since the last gx_reset
+  gx_ctx* satChild = nullptr;     // the context gx_saturation re-calls the peaks on (until gx_reset / gx_destroy)
+  std::vector<gx_sat_point> satPts;             // the last gx_saturation, per point (until gx_reset)
+  std::vector<std::vector<gx_peak>> satPeaks;   // ... and its peaks
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

@@ -421,4 +421,20 @@ GX_HD inline float fisher_combine(double sum, int df, bool* risky) {
   return pval_round(fisher_double(sum, df), risky);
 }
 
+// The subsample's draw (gx_subsample.h, gx_subsample_draw): event `index` of kept sample `sample` gets the upper 32 bits of
+// splitmix64's finalizer over seed ^ (golden ratio * (sample + 1)), plus the index.  It is kept at threshold T (0 .. 2^32) iff
+// draw < T; the draw does not depend on T, so the subsamples of one seed are nested.
+GX_HD __forceinline__ uint64_t subsample_key(uint64_t seed, uint32_t sample) {
+  return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)((uint64_t)sample + 1));
+}
+GX_HD __forceinline__ uint32_t subsample_draw(uint64_t key, uint64_t index) {
+  uint64_t x = key + index;
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return (uint32_t)(x >> 32);
+}
+
 }  // namespace gx

@@ -33,6 +33,8 @@
 #include <getopt.h>
 #include <zlib.h>
 
+#include <cctype>
+#include <cerrno>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
@@ -163,6 +165,12 @@ struct Opts {
   const char* fingerprintMetricsFile = nullptr;   // --fingerprint-metrics FILE: ... and its figures
   const char* complexityFile = nullptr;    // --complexity FILE: each sample's library complexity from its kept intervals
   const char* complexityHistFile = nullptr;   // --complexity-hist FILE: ... and its duplication histogram
+  const char* saturationFile = nullptr;    // --saturation FILE: the peaks called once more on nested subsamples of the run's intervals
+  int saturationSteps = 10;                // --saturation-steps N: the points of the curve, T_j = (j << 32) / N
+  bool saturationStepsOpt = false;
+  uint64_t saturationSeed = 1;             // --saturation-seed S
+  bool saturationSeedOpt = false;
+  bool saturationControls = false;         // --saturation-controls: the controls are subsampled too
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -2826,6 +2834,45 @@ void writeComplexity(State& S) {
   }
 }
 
+// --saturation FILE [--saturation-steps N] [--saturation-seed S] [--saturation-controls]: the run's kept intervals subsampled
+// on the device at N nested thresholds and the peaks called once more at each (gx_saturation), one row per point with what it
+// recovers of the run's own peaks; with -v each point on stderr, the smallest fraction that recovers 90 % of the run's peaks
+// and the ratio of the last two points' peak counts as the slope of the curve
+void writeSaturation(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g = S.devs.ctx[0];
+  const int N = o.saturationSteps;
+  std::vector<uint64_t> thr((size_t)N);
+  check(S, gx_saturation_thresholds(N, thr.data()), g);
+  std::vector<gx_sat_point> pts((size_t)N);
+  check(S, gx_saturation(g, thr.data(), N, o.saturationSeed, o.saturationControls ? GX_SAT_CONTROLS : 0u, pts.data()), g);   // (before the file is opened)
+  Out out = openWrite(o.saturationFile, o.gzOut);
+  check(S, gx_write_saturation(g, out.f), g);
+  closeOut(out);
+  if (!o.verbose) return;
+  size_t nFull = 0;
+  check(S, gx_peak_count(g, &nFull), g);
+  std::vector<gx_peak> full(nFull), sub;
+  if (nFull) check(S, gx_get_peaks(g, full.data(), nFull), g);
+  double reach = -1.0;
+  for (int j = 0; j < N; j++) {
+    sub.resize((size_t)pts[j].n_peaks);
+    if (!sub.empty()) check(S, gx_get_saturation_peaks(g, j, sub.data(), sub.size()), g);
+    uint64_t rec = 0, in = 0, bp = 0;
+    check(S, gx_saturation_overlap(full.data(), nFull, sub.data(), sub.size(), &rec, &in, &bp), g);
+    const double frac = (double)thr[j] / 4294967296.0;
+    fprintf(stderr, "  Saturation, %f of the intervals (%llu): %llu peaks (%llubp), %llu of the run's %zu recovered%s\n", frac,
+            (unsigned long long)pts[j].n_kept, (unsigned long long)pts[j].n_peaks, (unsigned long long)pts[j].peak_bp, (unsigned long long)rec,
+            nFull, pts[j].status ? " -- no analyzable fragments" : "");
+    if (reach < 0 && nFull && rec * 10 >= (uint64_t)nFull * 9) reach = frac;
+  }
+  if (reach >= 0) fprintf(stderr, "  Saturation: %f of the intervals recover 90 %% of the run's peaks\n", reach);
+  else fprintf(stderr, "  Saturation: no point recovers 90 %% of the run's peaks\n");
+  if (N >= 2 && pts[N - 2].n_peaks)
+    fprintf(stderr, "  Saturation: the last step added intervals by %f and peaks by %f\n", (double)thr[N - 1] / (double)thr[N - 2],
+            (double)pts[N - 1].n_peaks / (double)pts[N - 2].n_peaks);
+}
+
 // --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
@@ -2933,6 +2980,11 @@ void usage() {
           "                  (chromosome, start, end) keys: N, distinct, NRF, PBC1, PBC2, duplicate fraction, estimated library size and\n"
           "                  the expected distinct keys at 5 %% .. 100 %% of the depth, a TSV labelled t<rep> / c<rep>; the histogram\n"
           "                  file has the number of keys seen m times per sample and m\n"
+          "  --saturation FILE [--saturation-steps N] [--saturation-seed S] [--saturation-controls]   the peaks called once more on\n"
+          "                  N (10, at most 100) nested subsamples of the run's intervals, j / N of them for j = 1 .. N drawn with seed S\n"
+          "                  (1): a TSV with one row per point -- fraction, threshold, intervals kept, peaks, peak bp, the run's peaks\n"
+          "                  recovered and their share, the point's peaks that touch one of the run's, shared bp, status; the controls\n"
+          "                  stay whole unless --saturation-controls; one device; not with -X, -P or --events-only\n"
           "  --profile BED --profile-out PREFIX [--flank N] [--profile-bin N] [--profile-at tss|center] [--profile-matrix]\n"
           "                  each sample's pileup around the BED's sites, N (2000) bases to either side in bins of N (10) bases,\n"
           "                  oriented by column 6: PREFIX.profile.tsv, the mean per base and site at every offset; a site is the\n"
@@ -2973,6 +3025,10 @@ int main(int argc, char** argv) {
                                      {"spearman", required_argument, nullptr, 1020},
                                      {"complexity", required_argument, nullptr, 1021},
                                      {"complexity-hist", required_argument, nullptr, 1022},
+                                     {"saturation", required_argument, nullptr, 1023},
+                                     {"saturation-steps", required_argument, nullptr, 1024},
+                                     {"saturation-seed", required_argument, nullptr, 1025},
+                                     {"saturation-controls", no_argument, nullptr, 1026},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -3043,6 +3099,17 @@ int main(int argc, char** argv) {
       case 1019: o.fingerprintMetricsFile = optarg; break;
       case 1021: o.complexityFile = optarg; break;
       case 1022: o.complexityHistFile = optarg; break;
+      case 1023: o.saturationFile = optarg; break;
+      case 1024: o.saturationSteps = getInt(optarg); o.saturationStepsOpt = true; break;
+      case 1025: {
+        char* end;
+        errno = 0;
+        o.saturationSeed = strtoull(optarg, &end, 10);
+        if (!isdigit((unsigned char)optarg[0]) || *end != '\0' || errno == ERANGE) die(optarg, ": --saturation-seed takes an integer in [0, 2^64 - 1]");
+        o.saturationSeedOpt = true;
+        break;
+      }
+      case 1026: o.saturationControls = true; break;
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -3080,6 +3147,14 @@ int main(int argc, char** argv) {
   // (the complexity counts the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.complexityFile && (o.peaksOnly || o.eventsOnly)) die("", "--complexity needs the intervals of this run (not with -P or --events-only)");
   if (o.complexityHistFile && !o.complexityFile) die("", "--complexity-hist needs --complexity FILE");
+  // (the curve is made of this run's peaks and of the events the library keeps: none with -X, -P or --events-only)
+  if (o.saturationFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly))
+    die("", "--saturation needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
+  if ((o.saturationStepsOpt || o.saturationSeedOpt || o.saturationControls) && !o.saturationFile)
+    die("", "--saturation-steps, --saturation-seed and --saturation-controls need --saturation FILE");
+  if (o.saturationFile && (o.saturationSteps < 1 || o.saturationSteps > 100)) die("", "--saturation-steps must be in [1, 100]");
+  // (the re-call on several contexts needs the collectives between their child contexts)
+  if (o.saturationFile && o.devices.size() > 1) die("", "--saturation takes one device (not with --devices of more than one)");
   if (o.correlationFile || o.fingerprintFile || o.spearmanFile) {   // (a sample per -t file and per -c file that is not "null": known before anything is read or written)
     auto split = [](const char* list) {
       std::vector<std::string> out;
@@ -3187,7 +3262,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.regionsBed || o.complexityFile) check(S, gx_set_count_in_peaks(g, 1), g);
+      if (o.countsFile || o.regionsBed || o.complexityFile || o.saturationFile) check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -3363,6 +3438,7 @@ int main(int argc, char** argv) {
   if (o.spearmanFile) writeSpearman(S);
   if (o.fingerprintFile) writeFingerprint(S);
   if (o.complexityFile) writeComplexity(S);
+  if (o.saturationFile) writeSaturation(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {
     Out log = openWrite(o.logFile, o.gzOut);

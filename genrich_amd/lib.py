@@ -134,6 +134,13 @@ CPX_METRICS_DTYPE = np.dtype([("h1", "<u8"), ("h2", "<u8")] + [(k, "<f8") for k 
                              + [("curve", "<f8", (CPX_CURVE,))])   # gx_cpx_metrics
 
 
+GX_PATH_SATURATION = 16777216   # gx_path_info bit 24: k_sub_write ran (gx_subsample_events, gx_subsample_kept, gx_saturation)
+GX_SAT_CONTROLS = 1             # gx_saturation: the controls are subsampled at the point's threshold too
+GX_ERR_EXPT = -3                # a point of gx_saturation whose subsample left no analyzable fragment
+SAT_POINT_DTYPE = np.dtype([("threshold", "<u8"), ("n_total", "<u8"), ("n_kept", "<u8"), ("n_peaks", "<u8"), ("peak_bp", "<u8"),
+                            ("genome_len", "<u8"), ("status", "<i4"), ("_pad", "<i4")])   # gx_sat_point
+
+
 class Complexity(NamedTuple):
     """One sample's library complexity (gx_get_complexity): N observations, D distinct keys, pairs = [(m, h[m])] ascending."""
     n_obs: int
@@ -278,6 +285,16 @@ _SIGS = {
     "gx_format_complexity": [C.c_void_p, C.c_int] + [C.c_void_p] * 7,
     "gx_format_complexity_hist": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,
     "gx_write_complexity_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_subsample_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint, C.c_void_p, C.c_size_t,
+                            C.POINTER(C.c_size_t)],
+    "gx_subsample_kept": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_subsample_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)],
+    "gx_saturation": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint, C.c_void_p],
+    "gx_get_saturation_peaks": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
+    "gx_saturation_thresholds": [C.c_int, C.c_void_p],
+    "gx_saturation_overlap": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "gx_format_saturation": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64],
+    "gx_write_saturation": [C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -305,6 +322,7 @@ def load_library(path: str = os.environ.get("GENRICH_AMD_LIB", LIB_PATH)):
     lib.gx_filter_saturation.restype = C.c_longlong
     lib.gx_filter_saturation.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     lib.gx_fp_class.restype, lib.gx_fp_class.argtypes = C.c_uint32, [C.c_uint64]
+    lib.gx_subsample_draw.restype, lib.gx_subsample_draw.argtypes = C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint64]
     lib.gx_fp_class_lo.restype, lib.gx_fp_class_lo.argtypes = C.c_uint64, [C.c_uint32]
     lib.gx_fp_class_hi.restype, lib.gx_fp_class_hi.argtypes = C.c_uint64, [C.c_uint32]
     _lib = lib
@@ -594,6 +612,47 @@ def complexity_text(ctxs, with_hist=True):
     except RuntimeError as e:
         raise RuntimeError(f"{e} [{'; '.join(lib.gx_last_error(c.ctx).decode() for c in ctxs)}]") from None
     return met, (hist[0] if hist else None)
+
+
+def subsample_draw(seed, sample, index):
+    """The 32-bit draw of event `index` of kept sample `sample` (gx_subsample_draw); host-only, needs no GPU."""
+    return int(load_library().gx_subsample_draw(int(seed), int(sample), int(index)))
+
+
+def subsample_geometry():
+    """(lanes, grid, block_events) of the subsample pass as the library was built (gx_subsample_geometry)."""
+    lanes, grid, block = C.c_int(0), C.c_int(0), C.c_uint32(0)
+    load_library().gx_subsample_geometry(C.byref(lanes), C.byref(grid), C.byref(block))
+    return lanes.value, grid.value, block.value
+
+
+def saturation_thresholds(n_points):
+    """--saturation's thresholds for n_points steps (gx_saturation_thresholds): [(j << 32) // n_points]; host-only."""
+    out = np.zeros(max(int(n_points), 1), dtype=np.uint64)
+    rc = load_library().gx_saturation_thresholds(int(n_points), out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_saturation_thresholds: {rc}")
+    return [int(t) for t in out]
+
+
+def saturation_overlap(full, sub):
+    """(full_recovered, sub_in_full, shared_bp) of two peak lists in get_peaks() order (gx_saturation_overlap); host-only."""
+    f, s = np.ascontiguousarray(full, dtype=PEAK_DTYPE), np.ascontiguousarray(sub, dtype=PEAK_DTYPE)
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = load_library().gx_saturation_overlap(f.ctypes.data if f.size else None, f.size, s.ctypes.data if s.size else None, s.size,
+                                              C.byref(a), C.byref(b), C.byref(c))
+    if rc:
+        raise RuntimeError(f"gx_saturation_overlap: {rc}")
+    return a.value, b.value, c.value
+
+
+def format_saturation(points, full_recovered, sub_in_full, shared_bp, n_full, full_bp) -> bytes:
+    """--saturation's table (gx_format_saturation); points: SAT_POINT_DTYPE records; host-only, needs no GPU."""
+    lib = load_library()
+    pts = np.ascontiguousarray(points, dtype=SAT_POINT_DTYPE)
+    cols = [np.ascontiguousarray(c, dtype=np.uint64) for c in (full_recovered, sub_in_full, shared_bp)]
+    return _to_tmpfile(lambda f: lib.gx_format_saturation(f, len(pts), pts.ctypes.data, cols[0].ctypes.data, cols[1].ctypes.data,
+                                                          cols[2].ctypes.data, int(n_full), int(full_bp)))
 
 
 def fp_geometry():
@@ -893,7 +952,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -1036,6 +1095,45 @@ class Genrich:
         c = C.c_size_t(0)
         self._check(self.lib.gx_complexity_last(self.ctx, C.byref(c)))
         return c.value
+
+    # -- subsamples of the kept samples and the peak saturation curve (include/genrich_amd.h, gx_saturation) ----------------
+    def subsample_events(self, events, seed, sample, threshold, grid=0, packed=False):
+        """The events (EVENT_DTYPE; packed: EVENT8 records as pack_events gives them) kept at `threshold` as sample `sample`, by
+        the subsample kernels (gx_subsample_events): always EVENT_DTYPE, in order."""
+        ev = np.ascontiguousarray(events)
+        out = np.zeros(max(int(ev.size), 1), dtype=EVENT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_subsample_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, int(bool(packed)), int(seed), int(sample),
+                                                 int(threshold), int(grid), out.ctypes.data, ev.size, C.byref(n)))
+        return out[:n.value]
+
+    def subsample_kept(self, sample, seed, threshold):
+        """Kept sample `sample`'s events kept at `threshold` (gx_subsample_kept), in kept order."""
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_subsample_kept(self.ctx, int(sample), int(seed), int(threshold), None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=EVENT_DTYPE)
+        self._check(self.lib.gx_subsample_kept(self.ctx, int(sample), int(seed), int(threshold), out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
+
+    def saturation(self, thresholds, seed=1, flags=0):
+        """The peaks called once more per threshold on nested subsamples of the kept samples (gx_saturation), after find_peaks():
+        SAT_POINT_DTYPE records, one per threshold."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.uint64)
+        out = np.zeros(len(thr), dtype=SAT_POINT_DTYPE)
+        self._check(self.lib.gx_saturation(self.ctx, thr.ctypes.data, len(thr), int(seed), int(flags), out.ctypes.data))
+        self._sat_peaks = [int(p) for p in out["n_peaks"]]
+        return out
+
+    def saturation_peaks(self, point):
+        """The peaks of one point of the last saturation() (gx_get_saturation_peaks), PEAK_DTYPE."""
+        n = self._sat_peaks[point]
+        out = np.zeros(n, dtype=PEAK_DTYPE)
+        self._check(self.lib.gx_get_saturation_peaks(self.ctx, int(point), out.ctypes.data if n else None, n))
+        return out
+
+    def saturation_text(self) -> bytes:
+        """--saturation's table of the last saturation() against this run's peaks (gx_write_saturation)."""
+        return _to_tmpfile(lambda f: self.lib.gx_write_saturation(self.ctx, f))
 
     # -- fingerprint of the samples' bins (include/genrich_amd.h, gx_coverage_fingerprint) -------------------------------
     def coverage_fingerprint(self):

@@ -516,6 +516,55 @@ int gx_complexity_last(gx_ctx* ctx, size_t* capacity);
 int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct,
                         uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes);
 
+/* ---- peak saturation: the peaks called once more on nested subsamples of the run's own intervals (no Genrich counterpart:
+ *      what a loop over `samtools view -s` and the caller answers -- would more reads have found more peaks?) ----
+ * A sample = every gx_sample_end of the run in call order, as for gx_count_in_peaks; sample k's events are taken in their kept
+ * order: the pushes as they came, minus the int16 rule's drops (the order gx_count_in_peaks and gx_complexity walk).  Event i
+ * of sample k gets a 32-bit draw,
+ *     x = seed ^ (0x9E3779B97F4A7C15 * (uint64)(k + 1));  x += i;
+ *     x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31;     draw = (uint32)(x >> 32)
+ * and is kept at threshold T (0 .. 2^32; more: GX_ERR_ORDER) iff draw < T: T = 2^32 keeps every event, T = 0 none, and since the
+ * draw does not depend on T the subsamples of one seed are nested -- an event kept at 30 % is kept at 40 %.  The draw is keyed
+ * on the position, not on the coordinates: copies of one interval are drawn independently, as reads are.  EVERY event is
+ * drawn, also one on a skipped, un-saved or un-owned chromosome: i counts them all, and whoever reads the subsample applies
+ * its own chromosome table, as the first run did.
+ *
+ * gx_subsample_draw: the draw; host only, no context.
+ * gx_subsample_events: the kernels (k_sub_count, k_sub_scan, k_sub_write: gx_subsample.h) over n events in host memory (copied
+ *   to the device by the call), gx_event or -- packed != 0 -- gx_event8, as sample `sample`: min(cap, kept) events into out[],
+ *   always 16-byte gx_event, in their order, and *n_out = kept.  grid = 0: the library's choice, else that many workgroups (at
+ *   most 65535); the output is the same bytes for every grid.  No sample open.  For tests and measurements.
+ * gx_subsample_kept: the same over kept sample `sample` (0 .. n_samples-1) of a context with gx_set_count_in_peaks on.
+ * gx_subsample_geometry: the lanes of a workgroup, the most workgroups with grid = 0, and the events per block (the unit the
+ *   kept events are counted, scanned and written by).  Any pointer may be NULL.
+ * gx_saturation: after gx_find_peaks, with gx_set_count_in_peaks on, no sample open and one context (no collectives), else
+ *   GX_ERR_ORDER with a text.  For each threshold in the order given, the whole run once more on an internal child context
+ *   (same device, gx_params, chromosome table, -e skips, -E coordinates, gx_set_owned mask, gx_expect_fractional and
+ *   gx_set_knob values; counting, coverage, profiles off; created by the first call, gone with gx_reset / gx_destroy): per
+ *   replicate the treatment's subsample with the sample's save mask, then its control WHOLE, read in place -- with
+ *   GX_SAT_CONTROLS subsampled at the same threshold -- or gx_sample_no_control, then gx_pvalues; then gx_find_peaks.  out[j]:
+ *   the threshold, the events of ALL the subsampled samples (n_total) and those kept (n_kept; both whole also at a point whose
+ *   re-call ends early), the point's peaks, their bases,
+ *   the genome length and a status.  A point whose re-call ends with GX_ERR_EXPT (the subsample left no analyzable fragment)
+ *   is a result: status GX_ERR_EXPT, no peaks; every other failure fails the call, with the child's text.  The run's own
+ *   peaks, counts and complexity results stay as they are; calling again gives the same.  Each kept sample takes a device
+ *   buffer of its size for its subsample, from the context's pool.  A caller's device buffers must stay valid as for
+ *   gx_count_in_peaks.
+ * gx_get_saturation_peaks: min(cap, n_peaks) peaks of point `point` of the last gx_saturation (gx_get_peaks order).
+ * gx_saturation_thresholds: the command line's points, T_j = (j << 32) / n for j = 1 .. n (the last is 2^32: the whole sample);
+ *   n in 1 .. 100, else GX_ERR_ORDER; host only. */
+typedef struct { uint64_t threshold, n_total, n_kept;   /* events of the subsampled samples: all, and those kept */
+                 uint64_t n_peaks, peak_bp, genome_len; int32_t status; } gx_sat_point;
+#define GX_SAT_CONTROLS 1u
+uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index);
+int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold,
+                        unsigned grid, gx_event* out, size_t cap, size_t* n_out);
+int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_out);
+int gx_subsample_geometry(int* lanes, int* grid, uint32_t* block_events);
+int gx_saturation(gx_ctx* ctx, const uint64_t* threshold, int n_points, uint64_t seed, unsigned flags, gx_sat_point* out);
+int gx_get_saturation_peaks(gx_ctx* ctx, int point, gx_peak* out, size_t cap);
+int gx_saturation_thresholds(int n_points, uint64_t* threshold);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -701,6 +750,22 @@ int gx_format_complexity(FILE* out, int n_samples, const int* rep, const int* is
 int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* mult,
                               const uint64_t* const* keys, const size_t* n_pairs);
 int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist);
+/* --saturation (no Genrich counterpart).  The first two: host only, no context.
+ * gx_saturation_overlap: two peak lists in gx_get_peaks order (by chromosome, then start; no overlaps inside a list), in one
+ *   merge walk, with gx_count_in_peaks' predicate (s < pe && ps < e on one chromosome): *full_recovered = the peaks of `full`
+ *   touched by at least one peak of `sub`, *sub_in_full = the peaks of `sub` touched by at least one of `full`, *shared_bp =
+ *   the bases both lists cover.  Any out pointer may be NULL.
+ * gx_format_saturation: a comment line "# run: <n_full> peaks, <full_bp> bp", then a TSV, header "fraction threshold kept peaks
+ *   peak_bp recovered recovered_share in_run shared_bp status", one row per point: the threshold over 2^32 as %.6f, the threshold, the intervals kept, the point's peaks and
+ *   their bases, the run's peaks it recovers and the same over n_full as %.6f (NA when the run has none), the point's peaks
+ *   that touch one of the run's, the shared bases, and "ok" or, for GX_ERR_EXPT, "no_fragments" (another status: its number).
+ *   A missing pointer or n_points < 1: GX_ERR_ORDER, nothing written.
+ * gx_write_saturation (gx_api.hip: it reads a context): the last gx_saturation against the run's own peaks. */
+int gx_saturation_overlap(const gx_peak* full, size_t n_full, const gx_peak* sub, size_t n_sub, uint64_t* full_recovered,
+                          uint64_t* sub_in_full, uint64_t* shared_bp);
+int gx_format_saturation(FILE* out, int n_points, const gx_sat_point* points, const uint64_t* full_recovered,
+                         const uint64_t* sub_in_full, const uint64_t* shared_bp, uint64_t n_full, uint64_t full_bp);
+int gx_write_saturation(gx_ctx* ctx, FILE* out);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -795,6 +860,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_FINGERPRINT 2097152u /* bit 21: k_fp_hist ran since the last gx_reset (gx_coverage_fingerprint, gx_fp_u64) */
 #define GX_PATH_SPEARMAN 4194304u /* bit 22: k_rank ran since the last gx_reset (gx_coverage_rank_gram, gx_rank_u64) */
 #define GX_PATH_COMPLEXITY 8388608u /* bit 23: k_cpx_insert ran since the last gx_reset (gx_complexity, gx_complexity_events) */
+#define GX_PATH_SATURATION 16777216u /* bit 24: k_sub_write ran since the last gx_reset (gx_subsample_events, gx_subsample_kept, gx_saturation) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
