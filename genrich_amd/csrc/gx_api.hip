@@ -874,14 +874,7 @@ int gx_count_in_peaks(gx_ctx* ctx, int* n_samples) {
 int gx_get_peak_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
                        int64_t* in_peaks120) {
   if (!ctx || !ctx->countsReady || sample < 0 || (size_t)sample >= ctx->kept.size() || (cap && !count120)) return GX_ERR_ORDER;
-  const int64_t* r = static_cast<const int64_t*>(ctx->cntHost.p) + (size_t)sample * (ctx->cntPk + 2);
-  if (rep) *rep = ctx->kept[sample].rep;
-  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
-  const size_t n = std::min<size_t>(cap, ctx->cntPk);
-  if (n) memcpy(count120, r, n * sizeof(int64_t));
-  if (total120) *total120 = r[ctx->cntPk];
-  if (in_peaks120) *in_peaks120 = r[ctx->cntPk + 1];
-  return GX_OK;
+  return give_counts(ctx, ctx->cntHost, ctx->cntPk, sample, rep, is_ctrl, count120, cap, total120, in_peaks120);
 }
 
 int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_samples) {
@@ -902,14 +895,7 @@ int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_
 int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
                          int64_t* in_regions120) {
   if (!ctx || !ctx->regionsReady || sample < 0 || (u32)sample >= ctx->regSamples || (cap && !count120)) return GX_ERR_ORDER;
-  const int64_t* r = static_cast<const int64_t*>(ctx->regHost.p) + (size_t)sample * (ctx->regN + 2);
-  if (rep) *rep = ctx->kept[sample].rep;
-  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
-  const size_t n = std::min<size_t>(cap, ctx->regN);
-  if (n) memcpy(count120, r, n * sizeof(int64_t));
-  if (total120) *total120 = r[ctx->regN];
-  if (in_regions120) *in_regions120 = r[ctx->regN + 1];
-  return GX_OK;
+  return give_counts(ctx, ctx->regHost, ctx->regN, sample, rep, is_ctrl, count120, cap, total120, in_regions120);
 }
 
 int gx_set_coverage_bins(gx_ctx* ctx, uint32_t bin_size) {
@@ -1083,7 +1069,7 @@ int gx_coverage_gram(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint64_t* n_
   if (int rc = stat_cov_rows(ctx, "the correlation", b)) return rc;
   if (int rc = stat_cap(ctx, "gx_coverage_gram", sum || gram, cap, b.rows.size())) return rc;
   if ((u128)ctx->covW * (u128)b.G > ((u128)1 << 64))
-    return stat_refuse(ctx, "bin size times genome length above 2^64: the correlation's sums could overflow");
+    return refuse(ctx, "bin size times genome length above 2^64: the correlation's sums could overflow");
   HIPCHECK(hipSetDevice(ctx->device));
   u64 nz = 0;
   std::vector<gx_u128> s1, g1;
@@ -1146,7 +1132,7 @@ int gx_coverage_fingerprint(gx_ctx* ctx, int* n_samples, uint64_t* n_bins, uint6
   BinRows b;
   if (int rc = stat_cov_rows(ctx, "the fingerprint", b)) return rc;
   if (int rc = stat_cap(ctx, "gx_coverage_fingerprint", count || sum, cap, b.rows.size())) return rc;
-  if (b.G >= ((u64)1 << 33)) return stat_refuse(ctx, "a genome of 2^33 bases or more: the fingerprint's sums could overflow");
+  if (b.G >= ((u64)1 << 33)) return refuse(ctx, "a genome of 2^33 bases or more: the fingerprint's sums could overflow");
   HIPCHECK(hipSetDevice(ctx->device));
   std::vector<uint64_t> c1, s1;
   if (int rc = fp_pass(ctx, b.rows, b.n, 0, c1, s1)) return rc;
@@ -1163,7 +1149,7 @@ int gx_fp_u64(gx_ctx* ctx, const uint64_t* rows, int n_rows, size_t n, unsigned 
   for (int r = 0; r < n_rows; r++) {
     u128 t = 0;
     for (size_t k = 0; k < n; k++) t += rows[(size_t)r * n + k];
-    if (t >> 64) return stat_refuse(ctx, "gx_fp_u64: a row's total of 2^64 or more");
+    if (t >> 64) return refuse(ctx, "gx_fp_u64: a row's total of 2^64 or more");
   }
   std::vector<const void*> dev;
   if (int rc = stat_stage_rows(ctx, rows, n_rows, n, dev)) return rc;
@@ -1274,7 +1260,7 @@ int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros
   if (int rc = rank_cov_rows(ctx, b)) return rc;
   const size_t S = b.rows.size();
   if (!tables || !rank_lut_ok(tables, S))
-    return stat_refuse(ctx, "gx_coverage_rank_gram: a table is not ascending, holds the value 2^64 - 1, or a rank is outside [1, 2^42)");
+    return refuse(ctx, "gx_coverage_rank_gram: a table is not ascending, holds the value 2^64 - 1, or a rank is outside [1, 2^42)");
   if (int rc = stat_cap(ctx, "gx_coverage_rank_gram", sum || gram, cap, S)) return rc;
   std::vector<const void*> ranks;
   u64 nz = 0, nzGram = 0;
@@ -1302,7 +1288,7 @@ int gx_coverage_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, in
   for (int g = 0; g < n_ctx; g++) {
     BinRows b;
     if (int rc = rank_cov_rows(ctxs[g], b)) return rc;
-    if (b.rows.size() != S) return stat_refuse(ctxs[g], "gx_coverage_spearman_group: a context has another number of samples");
+    if (b.rows.size() != S) return refuse(ctxs[g], "gx_coverage_spearman_group: a context has another number of samples");
     groups.push_back(RankGroup{ctxs[g], std::move(b.rows), b.n});
   }
   RankTables t;
@@ -1336,9 +1322,9 @@ int gx_write_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const
 
 int gx_complexity(gx_ctx* ctx, int* n_samples) {
   if (!ctx) return GX_ERR_ORDER;
-  if (!ctx->countOn) return cpx_refuse(ctx, "gx_complexity needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase == 1 || ctx->phase == 3) return cpx_refuse(ctx, "gx_complexity: a sample is open");
-  if (ctx->kept.empty()) return cpx_refuse(ctx, "gx_complexity: no closed sample");
+  if (!ctx->countOn) return refuse(ctx, "gx_complexity needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_complexity: a sample is open");
+  if (ctx->kept.empty()) return refuse(ctx, "gx_complexity: no closed sample");
   HIPCHECK(hipSetDevice(ctx->device));
   ctx->cpxReady = false;
   if (int rc = complexity_kept(ctx)) return rc;
@@ -1358,7 +1344,7 @@ int gx_get_complexity(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t*
 int gx_complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, int cap_log, uint64_t* n_obs, uint64_t* n_distinct,
                          uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes) {
   if (!ctx || ctx->nChrom == 0 || (n && !ev) || cap_log < 0 || (cap && (!mult || !keys))) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return cpx_refuse(ctx, "gx_complexity_events: a sample is open");
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_complexity_events: a sample is open");
   HIPCHECK(hipSetDevice(ctx->device));
   gx_ctx::CpxResult r;
   if (int rc = complexity_events(ctx, ev, n, grid, cap_log, r)) return rc;
@@ -1437,9 +1423,9 @@ int gx_subsample_geometry(int* lanes, int* grid, uint32_t* block_events) {
 int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold, unsigned grid,
                         gx_event* out, size_t cap, size_t* n_out) {
   if (!ctx || (n && !ev) || (cap && !out)) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return sub_refuse(ctx, "gx_subsample_events: a sample is open");
-  if (threshold > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
-  if (grid > SUB_MAX_GRID) return sub_refuse(ctx, "subsample: more than 65535 workgroups");
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_subsample_events: a sample is open");
+  if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
+  if (grid > SUB_MAX_GRID) return refuse(ctx, "subsample: more than 65535 workgroups");
   HIPCHECK(hipSetDevice(ctx->device));
   std::vector<gx_ctx::Seg> segs;
   if (n) {
@@ -1459,10 +1445,10 @@ int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint6
 
 int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_out) {
   if (!ctx || (cap && !out)) return GX_ERR_ORDER;
-  if (!ctx->countOn) return sub_refuse(ctx, "gx_subsample_kept needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase == 1 || ctx->phase == 3) return sub_refuse(ctx, "gx_subsample_kept: a sample is open");
-  if (sample < 0 || (size_t)sample >= ctx->kept.size()) return sub_refuse(ctx, "gx_subsample_kept: no such sample");
-  if (threshold > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
+  if (!ctx->countOn) return refuse(ctx, "gx_subsample_kept needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_subsample_kept: a sample is open");
+  if (sample < 0 || (size_t)sample >= ctx->kept.size()) return refuse(ctx, "gx_subsample_kept: no such sample");
+  if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
   HIPCHECK(hipSetDevice(ctx->device));
   u64 n = 0, nKept = 0;
   if (int rc = sub_kept(ctx, (size_t)sample, seed, threshold, &n, &nKept)) return rc;
@@ -1471,11 +1457,11 @@ int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold
 
 int gx_saturation(gx_ctx* ctx, const uint64_t* threshold, int n_points, uint64_t seed, unsigned flags, gx_sat_point* out) {
   if (!ctx || !threshold || n_points < 1 || !out || (flags & ~GX_SAT_CONTROLS)) return GX_ERR_ORDER;
-  if (!ctx->countOn) return sub_refuse(ctx, "gx_saturation needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase != 0 || !ctx->peaksReady) return sub_refuse(ctx, "gx_saturation comes after gx_find_peaks, with no sample open");
-  if (ctx->world > 1 || ctx->forceColl) return sub_refuse(ctx, "gx_saturation: one context only (the re-call on several needs collectives between their children)");
+  if (!ctx->countOn) return refuse(ctx, "gx_saturation needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase != 0 || !ctx->peaksReady) return refuse(ctx, "gx_saturation comes after gx_find_peaks, with no sample open");
+  if (ctx->world > 1 || ctx->forceColl) return refuse(ctx, "gx_saturation: one context only (the re-call on several needs collectives between their children)");
   for (int j = 0; j < n_points; j++)
-    if (threshold[j] > ((u64)1 << 32)) return sub_refuse(ctx, "subsample: a threshold above 2^32");
+    if (threshold[j] > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
   HIPCHECK(hipSetDevice(ctx->device));
   if (int rc = sat_child(ctx)) return rc;
   std::vector<gx_sat_point> pts((size_t)n_points);

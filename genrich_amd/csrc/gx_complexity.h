@@ -2,21 +2,21 @@
 // bedpe and an awk line, Picard's EstimateLibraryComplexity or preseq's c_curve take from another reading of the BAM).
 // (a part of gx_api.hip's translation unit)
 //
-// A sample's intervals are k_cnt_count's (gx_count.h): the same two event forms, the same rules.  Each is ONE observation of the
-// key (chromosome, start, clamped end); wanted are N = observations, D = distinct keys and h[m] = keys seen exactly m times.
+// A sample's intervals are gx_kept.h's (kept_interval).  Each is ONE observation of the key (chromosome, start, clamped end);
+// wanted are N = observations, D = distinct keys and h[m] = keys seen exactly m times.
 //
-// The key is 64 bits: (g + 1) << 32 | end, g = the start in the context's tile space (CntChrom::base + start, as the counts
-// take it: g names the chromosome and the start at once), end = the clamped end as it is -- an interval that ends before it
-// starts keeps its end.  The host refuses the pass unless the tile space is below 2^32 - 1 bases, so g + 1 fits 32 bits and is
-// never 0: the packing is injective and no key equals CPX_EMPTY = 0, which a plain memset makes.
+// The key is 64 bits: (g + 1) << 32 | end, g = the interval's start in tile space (it names the chromosome and the start at
+// once), end = its clamped end on the chromosome -- an interval that ends before it starts keeps its end.  The host refuses
+// the pass unless the tile space is below 2^32 - 1 bases, so g + 1 fits 32 bits and is never 0: the packing is injective and
+// no key equals CPX_EMPTY = 0, which a plain memset makes.
 //
 // 1. k_cpx_insert: the events -> an open-addressing table of 16-byte slots {key, count, 0} in global memory, a power of two of
 //    at least 2 n slots for a sample of n events, sized once (there is no growth path).  A slot is claimed with a 64-bit
 //    compare-and-swap on its key and counted with a 32-bit atomic add on the word next to it: key and count share a 16-byte
 //    slot, hence a cache line, so an insert touches one line where two arrays would touch two.  Nearly every key of a
 //    library is distinct: an LDS cache in front of the table (k_rank_distinct's) would hold singletons only, and there is none.
-//    CNT_ITEMS events per lane are loaded and hashed and their home slots read before the first claim, so that many table
-//    lines are in flight per lane.
+//    The pass is kept_walk's: CNT_ITEMS events per lane are loaded, then hashed and their home slots read (its stage in
+//    between) before the first claim, so that many table lines are in flight per lane.
 //    The probe loop is bounded by the capacity, not by the table's sparseness: a key that meets mask + 1 slots of other keys
 //    raises CPXC_STATUS (the host: GX_ERR_DEVICE) and is dropped; all lanes then stop early.
 // 2. k_cpx_hist: one pass over the slots, 16 bytes a load.  D and h[1] (nearly all keys) are counted by ballot, one add per
@@ -26,13 +26,13 @@
 //    raises CPXC_STATUS too.  The host sorts and run-length encodes the list.
 // Every add is an integer's: no result depends on the geometry, the capacity or the order of the races.
 #pragma once
-#include "gx_count.h"
+#include "gx_kept.h"
 #include "gx_rank.h"
 
 namespace gx {
 
 constexpr unsigned long long CPX_EMPTY = 0ull;
-constexpr int CPX_NT = 1024;                 // lanes of k_cpx_insert's workgroup (CNT_NT's reasons)
+constexpr int CPX_NT = CNT_NT;               // lanes of k_cpx_insert's workgroup: kept_walk's
 constexpr int CPX_HIST_NT = 256;             // ... and of k_cpx_hist's
 constexpr u32 CPX_BOUND = 4096;              // multiplicities below it are counted in LDS (16 KiB), the others listed
 constexpr u32 CPX_GRID = 512;                // most workgroups of k_cpx_insert unless the caller says so: two per CU, all its wavefronts
@@ -84,60 +84,28 @@ __device__ __forceinline__ void cpx_insert(const CpxTab& T, unsigned long long k
 }
 
 __global__ __launch_bounds__(CPX_NT) void k_cpx_insert(CpxArgs a) {
-  __shared__ unsigned long long red[CPX_NT / 64];
-  unsigned long long nObs = 0;
-  for (u32 c = blockIdx.x; c < a.nChunks; c += gridDim.x) {
-    const CntChunk ch = a.chunks[c];
-    for (u32 b = 0; b < ch.n; b += CPX_NT * CNT_ITEMS) {
-      unsigned long long key[CNT_ITEMS];
-      u32 hs[CNT_ITEMS];
+  __shared__ long long red[CPX_NT / 64];
+  long long nObs = 0;
+  unsigned long long key[CNT_ITEMS], k0[CNT_ITEMS];
+  u32 hs[CNT_ITEMS];
+  kept_walk(
+      a.chunks, a.nChunks, a.chroms, a.nChrom,
+      [&](const KeptIv(&iv)[CNT_ITEMS]) {
 #pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        const u32 i = b + (u32)j * CPX_NT + threadIdx.x;
-        key[j] = CPX_EMPTY;
-        hs[j] = 0;
-        if (i >= ch.n) continue;
-        u32 chrom, s, e, cnt;
-        if (ch.packed) {   // (k_cnt_count's decoding of both forms)
-          const uint2 v = static_cast<const uint2*>(ch.p)[i];
-          s = v.x;
-          e = v.x + (v.y & 0xFFFFu);
-          cnt = (0xA8654321u >> (4u * ((v.y >> 16) & 7u))) & 15u;
-          chrom = v.y >> 19;
-        } else {
-          const uint4 v = static_cast<const uint4*>(ch.p)[i];
-          chrom = v.x;
-          s = v.y;
-          e = v.z;
-          cnt = v.w;
+        for (int j = 0; j < CNT_ITEMS; j++) {
+          key[j] = iv[j].w ? ((iv[j].s + 1) << 32) | (iv[j].e - iv[j].base) : CPX_EMPTY;
+          hs[j] = iv[j].w ? rk_hash(key[j]) & a.T.mask : 0u;
         }
-        const bool cntOk = cnt <= 10u && ((0x57Eu >> cnt) & 1u);
-        if (!cntOk || chrom >= a.nChrom) continue;
-        const CntChrom cc = a.chroms[chrom];
-        if (!cc.active || s >= cc.len) continue;
-        key[j] = ((cc.base + s + 1) << 32) | (unsigned long long)(e > cc.len ? cc.len : e);
-        hs[j] = rk_hash(key[j]) & a.T.mask;
-      }
-      unsigned long long k0[CNT_ITEMS];
 #pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++)   // the home slots of all of them: CNT_ITEMS table lines in flight per lane
-        k0[j] = key[j] == CPX_EMPTY ? CPX_EMPTY : __hip_atomic_load(&a.T.slot[hs[j]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        if (key[j] == CPX_EMPTY) continue;
+        for (int j = 0; j < CNT_ITEMS; j++)   // the home slots of all of them: CNT_ITEMS table lines in flight per lane
+          k0[j] = key[j] == CPX_EMPTY ? CPX_EMPTY : __hip_atomic_load(&a.T.slot[hs[j]].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      },
+      [&](const KeptIv&, int j) {
         nObs++;
         cpx_insert(a.T, key[j], hs[j], k0[j]);
-      }
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) nObs += __shfl_xor(nObs, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nObs;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0;
-    for (int k = 0; k < CPX_NT / 64; k++) t += red[k];
-    if (t) atomicAdd(&a.T.ctl[CPXC_N], t);
-  }
+      });
+  nObs = kept_block_sum(nObs, red);
+  if (threadIdx.x == 0 && nObs) atomicAdd(&a.T.ctl[CPXC_N], (unsigned long long)nObs);
 }
 
 // hist[m] += the keys seen m times, 1 <= m < CPX_BOUND; big[0 .. ctl[CPXC_NBIG]) = the other keys' multiplicities (in no

@@ -3,27 +3,22 @@
 // gx_find_peaks left, for FRiP and a per-peak count matrix.
 // (a part of gx_api.hip's translation unit)
 //
-// Coordinates are the context's tile space: chromosome c's position x is tileBase(c) * TILE + x (gx_host_build.h layout_tiles),
-// so the peaks of all chromosomes form ONE sorted list of disjoint intervals and an interval never meets a peak of another
-// chromosome.  Per interval [s, e): k0 = the first peak with end > s, k1 = the first with start >= e; it overlaps peaks k0 .. k1-1
-// (s < pe && ps < e), i.e. some peak iff k0 < k1.  The tile index (k_cnt_index) gives a start for both searches, so an interval
-// costs one index load and one peak load unless it reaches past the end of peak k0.
+// The intervals, the two event forms, the pass over the chunks and the LDS window are gx_kept.h's.  Coordinates are the
+// context's tile space (gx_kept.h), so the peaks of all chromosomes form ONE sorted list of disjoint intervals and an interval
+// never meets a peak of another chromosome.  Per interval [s, e): k0 = the first peak with end > s, k1 = the first with
+// start >= e; it overlaps peaks k0 .. k1-1 (s < pe && ps < e), i.e. some peak iff k0 < k1.  The tile index (k_cnt_index) gives a
+// start for both searches, so an interval costs one index load and one peak load unless it reaches past the end of peak k0.
 // Counts go into a difference array over peak index (+w at k0, -w at k1) kept in LDS per workgroup (int32: a workgroup sees at
 // most CNT_WG_CHUNKS chunks, 120 * CNT_WG_CHUNKS * CNT_CHUNK < 2^31); one global add per (workgroup, non-zero entry); a scan
 // (k_cnt_scan) turns the sums into counts.  More peaks than one LDS window holds: one launch per window.  All sums are integers
 // (1/120 units): no result depends on the order of the adds.
 #pragma once
+#include "gx_kept.h"
 
 namespace gx {
 
 struct CntPeak { u64 s, e; };                        // [start, end) in tile space; entry nPk is a sentinel (both ~0)
-struct CntChrom { u64 base; u32 len; u32 active; };  // one sample's view of a chromosome (active: its events entered the pileup)
-struct CntChunk { const void* p; u32 n; u32 packed; };  // up to CNT_CHUNK events of one sample (gx_event, or gx_event8 when packed)
 
-constexpr int CNT_NT = 1024;
-constexpr int CNT_ITEMS = 4;                  // events in flight per thread
-constexpr u32 CNT_CHUNK = 1u << 16;
-constexpr u32 CNT_WG_CHUNKS = 272;            // 120 * 272 * 2^16 < 2^31
 constexpr u32 CNT_LDS_MAX = 36864;            // counters per window (144 KiB of the CU's 160)
 
 // idx0[t] = first peak with e > t * TILE, idx1[t] = first peak with s >= t * TILE (t = 0 .. nTiles)
@@ -62,86 +57,30 @@ struct CntArgs {
 __global__ __launch_bounds__(CNT_NT) void k_cnt_count(CntArgs a) {
   extern __shared__ int cntLds[];
   __shared__ long long red[2][CNT_NT / 64];
-  for (u32 i = threadIdx.x; i < a.wn; i += CNT_NT) cntLds[i] = 0;
-  __syncthreads();
+  kept_window_clear(cntLds, a.wn);
   long long tot = 0, inp = 0;
-  for (u32 c = blockIdx.x; c < a.nChunks; c += gridDim.x) {
-    const CntChunk ch = a.chunks[c];
-    for (u32 b = 0; b < ch.n; b += CNT_NT * CNT_ITEMS) {
-      u64 gs[CNT_ITEMS], ge[CNT_ITEMS];
-      int w[CNT_ITEMS];
-#pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        const u32 i = b + (u32)j * CNT_NT + threadIdx.x;
-        w[j] = 0;
-        gs[j] = ge[j] = 0;
-        if (i >= ch.n) continue;
-        u32 chrom, s, e, cnt;
-        if (ch.packed) {
-          const uint2 v = static_cast<const uint2*>(ch.p)[i];
-          s = v.x;
-          e = v.x + (v.y & 0xFFFFu);
-          cnt = (0xA8654321u >> (4u * ((v.y >> 16) & 7u))) & 15u;
-          chrom = v.y >> 19;
-        } else {
-          const uint4 v = static_cast<const uint4*>(ch.p)[i];
-          chrom = v.x;
-          s = v.y;
-          e = v.z;
-          cnt = v.w;
-        }
-        // what convert_event (gx_sort.h) lets into the pileup, empty intervals included (saveInterval prints them, 2586-2588)
-        const bool cntOk = cnt <= 10u && ((0x57Eu >> cnt) & 1u);
-        if (!cntOk || chrom >= a.nChrom) continue;
-        const CntChrom cc = a.chroms[chrom];
-        if (!cc.active || s >= cc.len) continue;
-        w[j] = (int)(120u / cnt);
-        gs[j] = cc.base + s;
-        ge[j] = cc.base + (e > cc.len ? cc.len : e);  // 2536-2544
-      }
-#pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        if (!w[j]) continue;
-        tot += w[j];
-        u32 k0 = a.idx0[gs[j] >> TB];
-        CntPeak P = a.pk[k0];
-        while (P.e <= gs[j]) P = a.pk[++k0];   // (the sentinel ends every scan)
-        if (P.s >= ge[j]) continue;
-        inp += w[j];
-        u32 k1 = k0 + 1;
-        if (ge[j] > P.e) {
-          k1 = max(k1, a.idx1[ge[j] >> TB]);
-          while (a.pk[k1].s < ge[j]) k1++;
-        }
-        if (k0 - a.w0 < a.wn) atomicAdd(&cntLds[k0 - a.w0], w[j]);
-        if (k1 - a.w0 < a.wn) atomicAdd(&cntLds[k1 - a.w0], -w[j]);
-      }
+  kept_walk(a.chunks, a.nChunks, a.chroms, a.nChrom, [&](const KeptIv& v, int) {
+    tot += v.w;
+    u32 k0 = a.idx0[v.s >> TB];
+    CntPeak P = a.pk[k0];
+    while (P.e <= v.s) P = a.pk[++k0];   // (the sentinel ends every scan)
+    if (P.s >= v.e) return;
+    inp += v.w;
+    u32 k1 = k0 + 1;
+    if (v.e > P.e) {
+      k1 = max(k1, a.idx1[v.e >> TB]);
+      while (a.pk[k1].s < v.e) k1++;
     }
-  }
-  __syncthreads();
-  for (u32 i = threadIdx.x; i < a.wn; i += CNT_NT) {
-    const int v = cntLds[i];
-    if (v) atomicAdd(a.diff + a.w0 + i, (unsigned long long)(long long)v);
-  }
+    if (k0 - a.w0 < a.wn) atomicAdd(&cntLds[k0 - a.w0], v.w);
+    if (k1 - a.w0 < a.wn) atomicAdd(&cntLds[k1 - a.w0], -v.w);
+  });
+  kept_window_flush(cntLds, a.w0, a.wn, a.diff);
   if (!a.tot) return;
-  for (int o = 32; o > 0; o >>= 1) {
-    tot += __shfl_xor(tot, o);
-    inp += __shfl_xor(inp, o);
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][wv] = tot;
-    red[1][wv] = inp;
-  }
-  __syncthreads();
+  tot = kept_block_sum(tot, red[0]);
+  inp = kept_block_sum(inp, red[1]);
   if (threadIdx.x == 0) {
-    long long t = 0, p = 0;
-    for (int k = 0; k < CNT_NT / 64; k++) {
-      t += red[0][k];
-      p += red[1][k];
-    }
-    if (t) atomicAdd(a.tot, (unsigned long long)t);
-    if (p) atomicAdd(a.tot + 1, (unsigned long long)p);
+    if (tot) atomicAdd(a.tot, (unsigned long long)tot);
+    if (inp) atomicAdd(a.tot + 1, (unsigned long long)inp);
   }
 }
 

@@ -33,15 +33,9 @@ int stat_cov_rows(gx_ctx* ctx, const char* what, BinRows& b) {
   return GX_OK;
 }
 
-// a refusal with its sentence
-int stat_refuse(gx_ctx* ctx, const std::string& why) {
-  ctx->err = why;
-  return GX_ERR_ORDER;
-}
-
 // an entry's arrays of cap samples a side take S samples
 int stat_cap(gx_ctx* ctx, const char* entry, bool wanted, int cap, size_t S) {
-  if (wanted && (cap < 0 || (size_t)cap < S)) return stat_refuse(ctx, std::string(entry) + ": cap is smaller than the number of samples");
+  if (wanted && (cap < 0 || (size_t)cap < S)) return refuse(ctx, std::string(entry) + ": cap is smaller than the number of samples");
   return GX_OK;
 }
 
@@ -55,7 +49,7 @@ int stat_u64_domain(gx_ctx* ctx, const char* entry, const uint64_t* rows, int n_
   else if (grid > 65535) why = ": a grid of more than 65535 workgroups";
   for (size_t k = 0; !why && values && k < (size_t)n_rows * n; k++)
     if (rows[k] >> 51) why = ": a value of 2^51 or more";
-  return why ? stat_refuse(ctx, std::string(entry) + why) : GX_OK;
+  return why ? refuse(ctx, std::string(entry) + why) : GX_OK;
 }
 
 // the caller's rows (host, row after row) on the device, 16 bytes apart at least: an odd n is padded by one value no lane reads

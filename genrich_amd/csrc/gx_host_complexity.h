@@ -11,15 +11,10 @@ int cpx_least_cap_log(u64 n) {
   return lg;
 }
 
-int cpx_refuse(gx_ctx* ctx, const char* why) {
-  ctx->err = why;
-  return GX_ERR_ORDER;
-}
-
 // what every pass checks before it allocates or launches anything: the key's 32 bits hold every start in tile space
 int cpx_domain(gx_ctx* ctx) {
   if (((u64)ctx->nTiles << TB) > CPX_MAX_SPACE)
-    return cpx_refuse(ctx, "library complexity: a genome of more than 2^32 - 1 bases in tile space does not fit the 64-bit key");
+    return refuse(ctx, "library complexity: a genome of more than 2^32 - 1 bases in tile space does not fit the 64-bit key");
   return GX_OK;
 }
 
@@ -27,11 +22,11 @@ int cpx_domain(gx_ctx* ctx) {
 // (multiplicity, keys) pairs, ascending.  grid = 0 / capLog = 0: the library's choices.
 int cpx_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, u64 n, u32 grid, int capLog, gx_ctx::CpxResult& r) {
   r = gx_ctx::CpxResult{};
-  if (n >> 31) return cpx_refuse(ctx, "library complexity: a sample of 2^31 events or more");
+  if (n >> 31) return refuse(ctx, "library complexity: a sample of 2^31 events or more");
   const int least = cpx_least_cap_log(n);
   if (!capLog) capLog = least;
-  if (capLog < least || capLog > 32) return cpx_refuse(ctx, "library complexity: a table of fewer than 2 n slots (or more than 2^32)");
-  if (grid > CPX_MAX_GRID) return cpx_refuse(ctx, "library complexity: more than 65535 workgroups");
+  if (capLog < least || capLog > 32) return refuse(ctx, "library complexity: a table of fewer than 2 n slots (or more than 2^32)");
+  if (grid > CPX_MAX_GRID) return refuse(ctx, "library complexity: more than 65535 workgroups");
   if (!n) return GX_OK;
   hipStream_t s = ctx->stream;
   const u64 cap = (u64)1 << capLog;
@@ -104,27 +99,22 @@ int cpx_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, u64
   return GX_OK;
 }
 
-// every kept sample, through the staging the counts share (gx_host_count.h stage_kept)
+// every kept sample, through the staging the passes share (gx_host_count.h kept_stage)
 int complexity_kept(gx_ctx* ctx) {
   const u32 nS = (u32)ctx->kept.size(), nChrom = ctx->nChrom;
   if (int rc = cpx_domain(ctx)) return rc;
-  const std::vector<size_t> chunk0 = kept_chunk_offsets(ctx);
   std::vector<u64> nEv(nS, 0);
   for (u32 k = 0; k < nS; k++) {
     for (const gx_ctx::Seg& sg : ctx->kept[k].segs) nEv[k] += sg.n;
-    if (nEv[k] >> 31) return cpx_refuse(ctx, "library complexity: a sample of 2^31 events or more");
+    if (nEv[k] >> 31) return refuse(ctx, "library complexity: a sample of 2^31 events or more");
   }
-  const size_t chBytes = (size_t)nS * nChrom * sizeof(CntChrom), ckBytes = chunk0[nS] * sizeof(CntChunk);
-  std::vector<char> st(chBytes + ckBytes + 16);
-  stage_kept(ctx, chunk0, reinterpret_cast<CntChrom*>(st.data()), reinterpret_cast<CntChunk*>(st.data() + chBytes));
-  POOLED(ctx, ctx->cpxIn, st.size());
-  HIPCHECK(hipMemcpyAsync(ctx->cpxIn.p, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the staging is this call's)
-  const CntChrom* dCh = ctx->cpxIn.as<CntChrom>();
-  const CntChunk* dCk = reinterpret_cast<const CntChunk*>(ctx->cpxIn.as<char>() + chBytes);
+  KeptIn in;
+  if (int rc = kept_stage(ctx, kept_views(ctx), 0, true, false, in)) return rc;
+  if (int rc = kept_send(ctx, in)) return rc;
+  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (a sample without events launches nothing: the staging area is free again)
   std::vector<gx_ctx::CpxResult> res(nS);
   for (u32 k = 0; k < nS; k++) {
-    if (int rc = cpx_pass(ctx, dCk + chunk0[k], (u32)(chunk0[k + 1] - chunk0[k]), dCh + (size_t)k * nChrom, nEv[k], 0, 0, res[k])) return rc;
+    if (int rc = cpx_pass(ctx, in.dCk + in.chunk0[k], (u32)(in.chunk0[k + 1] - in.chunk0[k]), in.dCh + (size_t)k * nChrom, nEv[k], 0, 0, res[k])) return rc;
     res[k].rep = ctx->kept[k].rep;
     res[k].ctrl = ctx->kept[k].ctrl;
   }
@@ -137,23 +127,20 @@ int complexity_kept(gx_ctx* ctx) {
 int complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, u32 grid, int capLog, gx_ctx::CpxResult& r) {
   if (int rc = cpx_domain(ctx)) return rc;
   // (the refusals that depend on n alone come before the upload: nothing is allocated for a call that is refused)
-  if ((u64)n >> 31) return cpx_refuse(ctx, "library complexity: a sample of 2^31 events or more");
-  if (capLog && (capLog < cpx_least_cap_log(n) || capLog > 32)) return cpx_refuse(ctx, "library complexity: a table of fewer than 2 n slots (or more than 2^32)");
-  if (grid > CPX_MAX_GRID) return cpx_refuse(ctx, "library complexity: more than 65535 workgroups");
+  if ((u64)n >> 31) return refuse(ctx, "library complexity: a sample of 2^31 events or more");
+  if (capLog && (capLog < cpx_least_cap_log(n) || capLog > 32)) return refuse(ctx, "library complexity: a table of fewer than 2 n slots (or more than 2^32)");
+  if (grid > CPX_MAX_GRID) return refuse(ctx, "library complexity: more than 65535 workgroups");
   std::vector<gx_ctx::Seg> segs;
   if (n) {
     POOLED(ctx, ctx->cpxEv, n * sizeof(gx_event));
     HIPCHECK(hipMemcpyAsync(ctx->cpxEv.p, ev, n * sizeof(gx_event), hipMemcpyHostToDevice, ctx->stream));
     segs.push_back({ctx->cpxEv.as<gx_event>(), n, nullptr, false});
   }
-  const size_t nCk = chunks_of(segs), chBytes = (size_t)ctx->nChrom * sizeof(CntChrom);
-  std::vector<char> st(chBytes + nCk * sizeof(CntChunk) + 16);
-  stage_chroms(ctx, nullptr, reinterpret_cast<CntChrom*>(st.data()));
-  stage_chunks(segs, reinterpret_cast<CntChunk*>(st.data() + chBytes));
-  POOLED(ctx, ctx->cpxIn, st.size());
-  HIPCHECK(hipMemcpyAsync(ctx->cpxIn.p, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the staging is this call's, the events the caller's)
-  return cpx_pass(ctx, reinterpret_cast<const CntChunk*>(ctx->cpxIn.as<char>() + chBytes), (u32)nCk, ctx->cpxIn.as<CntChrom>(), n, grid, capLog, r);
+  KeptIn in;
+  if (int rc = kept_stage(ctx, {KeptView{&segs, nullptr}}, 0, true, false, in)) return rc;
+  if (int rc = kept_send(ctx, in)) return rc;
+  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the events are the caller's; no events launch nothing)
+  return cpx_pass(ctx, in.dCk, (u32)in.chunk0[1], in.dCh, n, grid, capLog, r);
 }
 
 // a result to the caller: min(cap, classes) pairs

@@ -1,4 +1,6 @@
-// gx_host_count.h -- the host side of gx_count_in_peaks (gx_count.h): which events each sample keeps, and the one count pass.
+// gx_host_count.h -- the kept samples on the host: which events each sample keeps (keep_sample), what every pass over them
+// stages for the device (kept_stage; the passes: count_in_peaks here, gx_host_regions.h, gx_host_complexity.h,
+// gx_host_subsample.h), and the host side of gx_count_in_peaks (gx_count.h).
 // (a part of gx_api.hip's translation unit)
 #pragma once
 namespace {
@@ -36,41 +38,90 @@ void drop_kept(gx_ctx* ctx) {
   ctx->countsReady = ctx->regionsReady = false;
 }
 
-// The staging the passes over the kept samples share (count_in_peaks, count_in_regions, the complexity pass): a sample's view of
-// the chromosome table, and its pieces cut into chunks of CNT_CHUNK events.
-// save: the chromosomes the sample's pileup took (null: every one)
-void stage_chroms(const gx_ctx* ctx, const std::vector<uint8_t>* save, CntChrom* ch) {
-  for (u32 c = 0; c < ctx->nChrom; c++) {
-    const DChrom& d = ctx->hChrom[c];
-    const bool act = !ctx->skip[c] && (!save || (*save)[c]) && ctx->owned[c] && d.tileBase != NULL_TILE;
-    ch[c] = CntChrom{act ? (u64)d.tileBase << TB : 0ull, d.len, act ? 1u : 0u};
+// What a pass over kept events stages for the device (gx_kept.h), in ONE pinned area and ONE device buffer (ctx->keptStage,
+// ctx->keptIn) that all the passes share -- each drains the stream before it returns:
+//   front   the pass's own inputs, `front` bytes it fills itself between kept_stage and kept_send
+//   dCh     [views][nChrom]  on request: each view's CntChrom table
+//   dCk     [chunk0[views]]  each view's pieces cut into chunks of CNT_CHUNK events; view v's from chunk0[v] on
+//   dFirst  [chunk0[views]]  on request: the view's events before each of its chunks
+// A view is a sample's pieces and the chromosomes its pileup took (null: every one).
+struct KeptView { const std::vector<gx_ctx::Seg>* segs; const std::vector<uint8_t>* save; };
+struct KeptIn {
+  char* front = nullptr;          // on the host
+  const char* dFront = nullptr;   // ... and on the device, like the rest
+  const CntChrom* dCh = nullptr;
+  const CntChunk* dCk = nullptr;
+  const u64* dFirst = nullptr;
+  std::vector<size_t> chunk0;
+  size_t bytes = 0;
+};
+std::vector<KeptView> kept_views(const gx_ctx* ctx) {
+  std::vector<KeptView> v;
+  for (const gx_ctx::KeptSample& k : ctx->kept) v.push_back({&k.segs, &k.save});
+  return v;
+}
+int kept_stage(gx_ctx* ctx, const std::vector<KeptView>& views, size_t front, bool wantChroms, bool wantFirst, KeptIn& in) {
+  const u32 nChrom = ctx->nChrom;
+  in.chunk0.assign(views.size() + 1, 0);
+  for (size_t v = 0; v < views.size(); v++) {
+    size_t c = 0;
+    for (const gx_ctx::Seg& sg : *views[v].segs) c += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
+    in.chunk0[v + 1] = in.chunk0[v] + c;
   }
-}
-size_t chunks_of(const std::vector<gx_ctx::Seg>& segs) {
-  size_t c = 0;
-  for (const gx_ctx::Seg& sg : segs) c += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
-  return c;
-}
-CntChunk* stage_chunks(const std::vector<gx_ctx::Seg>& segs, CntChunk* at) {
-  for (const gx_ctx::Seg& sg : segs) {
-    const size_t esz = sg.packed ? sizeof(gx_event8) : sizeof(gx_event);
-    for (size_t o = 0; o < sg.n; o += CNT_CHUNK)
-      *at++ = CntChunk{reinterpret_cast<const char*>(sg.p) + o * esz, (u32)std::min<size_t>(CNT_CHUNK, sg.n - o), sg.packed ? 1u : 0u};
+  const size_t nCk = in.chunk0.back(), chAt = (front + 15) & ~(size_t)15, ckAt = chAt + (wantChroms ? views.size() * nChrom * sizeof(CntChrom) : 0),
+               firstAt = ckAt + nCk * sizeof(CntChunk);
+  in.bytes = firstAt + (wantFirst ? nCk * 8 : 0);
+  HIPCHECK(ctx->keptStage.ensure(in.bytes));
+  POOLED(ctx, ctx->keptIn, in.bytes);
+  in.front = static_cast<char*>(ctx->keptStage.p);
+  CntChrom* ch = reinterpret_cast<CntChrom*>(in.front + chAt);
+  CntChunk* ck = reinterpret_cast<CntChunk*>(in.front + ckAt);
+  u64* first = reinterpret_cast<u64*>(in.front + firstAt);
+  for (const KeptView& view : views) {
+    for (u32 c = 0; wantChroms && c < nChrom; c++) {
+      const DChrom& d = ctx->hChrom[c];
+      const bool act = !ctx->skip[c] && (!view.save || (*view.save)[c]) && ctx->owned[c] && d.tileBase != NULL_TILE;
+      *ch++ = CntChrom{act ? (u64)d.tileBase << TB : 0ull, d.len, act ? 1u : 0u};
+    }
+    u64 run = 0;
+    for (const gx_ctx::Seg& sg : *view.segs) {
+      const size_t esz = sg.packed ? sizeof(gx_event8) : sizeof(gx_event);
+      for (size_t o = 0; o < sg.n; o += CNT_CHUNK) {
+        *ck = CntChunk{reinterpret_cast<const char*>(sg.p) + o * esz, (u32)std::min<size_t>(CNT_CHUNK, sg.n - o), sg.packed ? 1u : 0u};
+        if (wantFirst) *first++ = run;
+        run += (ck++)->n;
+      }
+    }
   }
-  return at;
+  in.dFront = ctx->keptIn.as<char>();
+  in.dCh = wantChroms ? reinterpret_cast<const CntChrom*>(in.dFront + chAt) : nullptr;
+  in.dCk = reinterpret_cast<const CntChunk*>(in.dFront + ckAt);
+  in.dFirst = wantFirst ? reinterpret_cast<const u64*>(in.dFront + firstAt) : nullptr;
+  return GX_OK;
 }
-// chunk0[k] = the first chunk of kept sample k (chunk0[nS] = all of them)
-std::vector<size_t> kept_chunk_offsets(const gx_ctx* ctx) {
-  std::vector<size_t> chunk0(ctx->kept.size() + 1, 0);
-  for (size_t k = 0; k < ctx->kept.size(); k++) chunk0[k + 1] = chunk0[k] + chunks_of(ctx->kept[k].segs);
-  return chunk0;
+// the pass's one copy of its inputs
+int kept_send(gx_ctx* ctx, const KeptIn& in) {
+  HIPCHECK(hipMemcpyAsync(ctx->keptIn.p, ctx->keptStage.p, in.bytes, hipMemcpyHostToDevice, ctx->stream));
+  return GX_OK;
 }
-// ch[nS * nChrom], ck[chunk0[nS]]
-void stage_kept(const gx_ctx* ctx, const std::vector<size_t>& chunk0, CntChrom* ch, CntChunk* ck) {
-  for (size_t k = 0; k < ctx->kept.size(); k++) {
-    stage_chroms(ctx, &ctx->kept[k].save, ch + k * ctx->nChrom);
-    stage_chunks(ctx->kept[k].segs, ck + chunk0[k]);
-  }
+
+// the grid of a launch with an LDS window of wn counters over nCk chunks (k_cnt_count, k_reg_count<true>): two workgroups per
+// CU when the window leaves room for them; enough workgroups that none sees more than CNT_WG_CHUNKS chunks
+u32 kept_window_grid(const gx_ctx* ctx, u32 wn, u32 nCk) {
+  const u32 grid = (u32)ctx->numCU * (wn * 4 <= 64 * 1024 ? 2u : 1u);
+  return std::max(std::min(grid, nCk), (nCk + CNT_WG_CHUNKS - 1) / CNT_WG_CHUNKS);
+}
+
+// a sample's counted row {count[n], total, in} to the caller (gx_get_peak_counts, gx_get_region_counts): min(cap, n) counts
+int give_counts(const gx_ctx* ctx, const PinnedBuf& host, size_t n, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap,
+                int64_t* total120, int64_t* in120) {
+  const int64_t* r = static_cast<const int64_t*>(host.p) + (size_t)sample * (n + 2);
+  if (rep) *rep = ctx->kept[sample].rep;
+  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
+  if (const size_t k = std::min(cap, n)) memcpy(count120, r, k * sizeof(int64_t));
+  if (total120) *total120 = r[n];
+  if (in120) *in120 = r[n + 1];
+  return GX_OK;
 }
 
 int count_in_peaks(gx_ctx* ctx) {
@@ -82,15 +133,11 @@ int count_in_peaks(gx_ctx* ctx) {
     return GX_ERR_MEM;
   }
   const gx_peak* hp = static_cast<const gx_peak*>(ctx->hPeaks.p);
-  // staging: the peaks in tile space (+ the sentinel), each sample's chromosome table, each sample's chunks
-  const std::vector<size_t> chunk0 = kept_chunk_offsets(ctx);
-  const size_t pkBytes = (nPk + 1) * sizeof(CntPeak), chBytes = (size_t)nS * nChrom * sizeof(CntChrom),
-               ckBytes = chunk0[nS] * sizeof(CntChunk);
-  const size_t total = pkBytes + chBytes + ckBytes;
-  HIPCHECK(ctx->cntStage.ensure(total));
-  HIPCHECK(ctx->cntIn.ensure(total));
-  char* st = static_cast<char*>(ctx->cntStage.p);
-  CntPeak* pk = reinterpret_cast<CntPeak*>(st);
+  // staging: the peaks in tile space (+ the sentinel) in front of the kept samples' views and chunks
+  KeptIn in;
+  if (int rc = kept_stage(ctx, kept_views(ctx), (nPk + 1) * sizeof(CntPeak), true, false, in)) return rc;
+  const std::vector<size_t>& chunk0 = in.chunk0;
+  CntPeak* pk = reinterpret_cast<CntPeak*>(in.front);
   for (size_t k = 0; k < nPk; k++) {
     const gx_peak& p = hp[k];
     if (p.chrom >= nChrom || ctx->hChrom[p.chrom].tileBase == NULL_TILE) {
@@ -101,14 +148,11 @@ int count_in_peaks(gx_ctx* ctx) {
     pk[k] = CntPeak{base + p.start, base + p.end};
   }
   pk[nPk] = CntPeak{~0ull, ~0ull};
-  CntChrom* ch = reinterpret_cast<CntChrom*>(st + pkBytes);
-  CntChunk* ck = reinterpret_cast<CntChunk*>(st + pkBytes + chBytes);
-  stage_kept(ctx, chunk0, ch, ck);
   phase_begin(ctx, "count");
-  HIPCHECK(hipMemcpyAsync(ctx->cntIn.p, st, total, hipMemcpyHostToDevice, s));
-  const CntPeak* dPk = ctx->cntIn.as<CntPeak>();
-  const CntChrom* dCh = reinterpret_cast<const CntChrom*>(ctx->cntIn.as<char>() + pkBytes);
-  const CntChunk* dCk = reinterpret_cast<const CntChunk*>(ctx->cntIn.as<char>() + pkBytes + chBytes);
+  if (int rc = kept_send(ctx, in)) return rc;
+  const CntPeak* dPk = reinterpret_cast<const CntPeak*>(in.dFront);
+  const CntChrom* dCh = in.dCh;
+  const CntChunk* dCk = in.dCk;
   // tile index, difference arrays, results ({counts, total, in_peaks} per sample)
   const u32 nIdx = ctx->nTiles + 1;
   HIPCHECK(ctx->cntIdx.ensure((size_t)nIdx * 8));
@@ -145,10 +189,7 @@ int count_in_peaks(gx_ctx* ctx) {
       a.wn = (u32)std::min<size_t>(CNT_LDS_MAX, nDiff - a.w0);
       a.diff = ctx->cntDiff.as<unsigned long long>() + (size_t)k * nDiff;
       a.tot = wdw == 0 ? ctx->cntRes.as<unsigned long long>() + (size_t)k * stride + nPk : nullptr;
-      // two workgroups per CU when the window leaves room for them; enough workgroups that none sees more than CNT_WG_CHUNKS chunks
-      u32 grid = (u32)ctx->numCU * (a.wn * 4 <= 64 * 1024 ? 2u : 1u);
-      grid = std::max(std::min(grid, nCk), (nCk + CNT_WG_CHUNKS - 1) / CNT_WG_CHUNKS);
-      hipLaunchKernelGGL(k_cnt_count, dim3(grid), dim3(CNT_NT), (size_t)a.wn * 4, s, a);
+      hipLaunchKernelGGL(k_cnt_count, dim3(kept_window_grid(ctx, a.wn, nCk)), dim3(CNT_NT), (size_t)a.wn * 4, s, a);
       if (int rc__ = dbg_sync(ctx, "k_cnt_count")) return rc__;
     }
   }

@@ -408,17 +408,21 @@ struct gx_ctx {
   bool peaksReady = false;        // gx_find_peaks has called the peaks of the samples kept so far
   bool countsReady = false;       // ... and gx_count_in_peaks has counted them
   std::vector<KeptSample> kept;
+  // what a pass over kept events reads besides them (gx_host_count.h kept_stage): its staging area and the device's copy.  One
+  // pair serves all the passes: each drains the stream before it returns.
+  PinnedBuf keptStage;
+  DevBuf keptIn;
   u32 cntPk = 0;                  // peaks of the last count
-  DevBuf cntIn, cntIdx, cntDiff, cntRes;
-  PinnedBuf cntStage, cntHost;
+  DevBuf cntIdx, cntDiff, cntRes;
+  PinnedBuf cntHost;
   bool cntLdsSet = false;
   // counting in regions (gx_count_in_regions, gx_regions.h): the same kept samples, result buffers of its own
   bool regionsReady = false;      // gx_count_in_regions has counted: regSamples samples in regN regions
   size_t regN = 0;
   u32 regSamples = 0;
   u32 regInvCap = 1u << 14;       // REG_INV_CAP, or more after a pass that met more inverted intervals
-  DevBuf regIn, regIdx, regHist, regSums, regRes, regInv;
-  PinnedBuf regStage, regHost;
+  DevBuf regIdx, regHist, regSums, regRes, regInv;
+  PinnedBuf regHost;
   bool regLdsSet = false;
   // binned coverage (gx_set_coverage_bins, gx_coverage.h): every closed sample's pileup summed over bins of covW bases
   struct CovSample {
@@ -472,14 +476,14 @@ struct gx_ctx {
     std::vector<uint64_t> mult, keys;   // h, sparse: keys[i] keys were seen mult[i] times (mult ascending)
   };
   DevBuf cpxTab, cpxCtl, cpxBig;  // the table (reused sample after sample), the control words + k_cpx_hist's histogram, its list
-  DevBuf cpxIn, cpxEv;            // the staged chromosome views and chunk lists; gx_complexity_events' copy of the caller's events
+  DevBuf cpxEv;                   // gx_complexity_events' copy of the caller's events
   std::vector<CpxResult> cpx;     // the last gx_complexity, per kept sample (until gx_reset)
   bool cpxReady = false;
   bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
   u32 cpxLastCapLog = 0;          // log2 of the capacity the last pass used (gx_complexity_last)
   // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
   // nothing here exists before the first call
-  DevBuf subIn, subCnt, subOff;   // the staged chunk list, k_sub_count's counts per block, k_sub_scan's offsets
+  DevBuf subCnt, subOff;          // k_sub_count's counts per block, k_sub_scan's offsets
   DevBuf subEv, subOut;           // gx_subsample_events' copy of the caller's events and its output
   std::vector<DevBuf> subBufs;    // kept sample k's subsample: the child reads it in place until its gx_sample_end
   bool subUsed = false;           // k_sub_write ran since the last gx_reset
@@ -527,6 +531,11 @@ int pool_failed(gx_ctx* ctx) {
   (void)hipGetLastError();
   ctx->err = "Cannot allocate memory";
   return GX_ERR_MEM;
+}
+// a call that is refused with its sentence
+int refuse(gx_ctx* ctx, std::string why) {
+  ctx->err = std::move(why);
+  return GX_ERR_ORDER;
 }
 #define POOLED(ctx, buf, bytes)                                                          \
   do {                                                                                   \

@@ -198,7 +198,7 @@ int rank_rows_pass(gx_ctx* ctx, const std::vector<const void*>& rows, u64 n, u32
 // the closed samples' bins as device rows (stat_cov_rows), within what a rank fits
 int rank_cov_rows(gx_ctx* ctx, BinRows& b) {
   if (int rc = stat_cov_rows(ctx, "the rank correlation", b)) return rc;
-  if (b.n > ((u64)1 << 30)) return stat_refuse(ctx, "more than 2^30 bins in a context for the rank correlation");
+  if (b.n > ((u64)1 << 30)) return refuse(ctx, "more than 2^30 bins in a context for the rank correlation");
   return GX_OK;
 }
 

@@ -31,14 +31,12 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
   ctx->regN = n;
   ctx->regSamples = nS;
   if (!nS) return GX_OK;
-  // staging: A, B (room for n + a sentinel each), the regions' ranks, each sample's chromosome table, each sample's chunks
-  const std::vector<size_t> chunk0 = kept_chunk_offsets(ctx);
-  const size_t abBytes = (n + 1) * 8, rkBytes = ((n + 1) & ~(size_t)1) * 4, chBytes = (size_t)nS * nChrom * sizeof(CntChrom),
-               ckBytes = chunk0[nS] * sizeof(CntChunk);
-  const size_t total = 2 * abBytes + 2 * rkBytes + chBytes + ckBytes;
-  HIPCHECK(ctx->regStage.ensure(total));
-  HIPCHECK(ctx->regIn.ensure(total));
-  char* st = static_cast<char*>(ctx->regStage.p);
+  // staging: A, B (room for n + a sentinel each) and the regions' ranks in front of the kept samples' views and chunks
+  const size_t abBytes = (n + 1) * 8, rkBytes = ((n + 1) & ~(size_t)1) * 4;
+  KeptIn in;
+  if (int rc = kept_stage(ctx, kept_views(ctx), 2 * abBytes + 2 * rkBytes, true, false, in)) return rc;
+  const std::vector<size_t>& chunk0 = in.chunk0;
+  char* st = in.front;
   u64* hA = reinterpret_cast<u64*>(st);
   u64* hB = reinterpret_cast<u64*>(st + abBytes);
   u32* hRa = reinterpret_cast<u32*>(st + 2 * abBytes);
@@ -62,16 +60,13 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
   if (!sortedA) rank_regions(hA, m, hRa, n);
   if (!sortedB) rank_regions(hB, m, hRb, n);
   hA[m] = hB[m] = ~0ull;
-  CntChrom* ch = reinterpret_cast<CntChrom*>(st + 2 * abBytes + 2 * rkBytes);
-  CntChunk* ck = reinterpret_cast<CntChunk*>(st + 2 * abBytes + 2 * rkBytes + chBytes);
-  stage_kept(ctx, chunk0, ch, ck);
-  const char* din = ctx->regIn.as<char>();
+  const char* din = in.dFront;
   const u64* dA = reinterpret_cast<const u64*>(din);
   const u64* dB = reinterpret_cast<const u64*>(din + abBytes);
   const u32* dRa = reinterpret_cast<const u32*>(din + 2 * abBytes);
   const u32* dRb = reinterpret_cast<const u32*>(din + 2 * abBytes + rkBytes);
-  const CntChrom* dCh = reinterpret_cast<const CntChrom*>(din + 2 * abBytes + 2 * rkBytes);
-  const CntChunk* dCk = reinterpret_cast<const CntChunk*>(din + 2 * abBytes + 2 * rkBytes + chBytes);
+  const CntChrom* dCh = in.dCh;
+  const CntChunk* dCk = in.dCk;
   // tile index, histograms, tile sums of the scans, results, the inverted intervals' list (+ its counter)
   const u32 nIdx = ctx->nTiles + 1;
   const size_t seg = (size_t)m + 1, nH = 2 * seg;
@@ -91,7 +86,7 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
     ctx->regLdsSet = true;
   }
   phase_begin(ctx, "regions");
-  HIPCHECK(hipMemcpyAsync(ctx->regIn.p, st, total, hipMemcpyHostToDevice, s));
+  if (int rc = kept_send(ctx, in)) return rc;
   hipLaunchKernelGGL(k_reg_index, dim3(std::max(1u, std::min((nIdx + 255) / 256, (u32)(8 * ctx->numCU)))), dim3(256), 0, s, dA, dB, m, nIdx,
                      idx);
   if (int rc__ = dbg_sync(ctx, "k_reg_index")) return rc__;
@@ -133,10 +128,7 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
         a.w0 = wdw * CNT_LDS_MAX;
         a.wn = (u32)std::min<size_t>(CNT_LDS_MAX, nH - a.w0);
         a.tot = wdw == 0 ? tot : nullptr;
-        // as k_cnt_count: two workgroups per CU when the window leaves room, none with more than CNT_WG_CHUNKS chunks
-        u32 grid = (u32)ctx->numCU * (a.wn * 4 <= 64 * 1024 ? 2u : 1u);
-        grid = std::max(std::min(grid, nCk), (nCk + CNT_WG_CHUNKS - 1) / CNT_WG_CHUNKS);
-        hipLaunchKernelGGL(k_reg_count<true>, dim3(grid), dim3(CNT_NT), (size_t)a.wn * 4, s, a);
+        hipLaunchKernelGGL(k_reg_count<true>, dim3(kept_window_grid(ctx, a.wn, nCk)), dim3(CNT_NT), (size_t)a.wn * 4, s, a);
         if (int rc__ = dbg_sync(ctx, "k_reg_count<lds>")) return rc__;
       }
     }
@@ -154,7 +146,7 @@ int count_in_regions(gx_ctx* ctx, const gx_region* reg, size_t n) {
     }
     HIPCHECK(hipGetLastError());
     phase_end(ctx);
-    u32* hNInv = reinterpret_cast<u32*>(static_cast<char*>(ctx->regStage.p));   // (the staging area has been sent)
+    u32* hNInv = reinterpret_cast<u32*>(st);   // (the staging area has been sent: its front, A's 8 bytes at least, is free)
     HIPCHECK(hipMemcpyAsync(ctx->regHost.p, ctx->regRes.p, (size_t)nS * stride * 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(hNInv, dNInv, 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));

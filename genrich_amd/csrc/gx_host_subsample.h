@@ -4,33 +4,25 @@
 #pragma once
 namespace {
 
-int sub_refuse(gx_ctx* ctx, const char* why) {
-  ctx->err = why;
-  return GX_ERR_ORDER;
-}
-
-// one sample's pieces -> its chunk list and the events before each chunk, on the device (ctx->subIn); *n = its events
+// one sample's pieces -> its chunk list and the events before each chunk, on the device (gx_host_count.h kept_stage); *n =
+// its events
 int sub_stage(gx_ctx* ctx, const std::vector<gx_ctx::Seg>& segs, const CntChunk** dCk, const u64** dFirst, u32* nCk, u64* n) {
-  const size_t nc = chunks_of(segs);
-  *nCk = (u32)nc;
+  *nCk = 0;
   *n = 0;
-  for (const gx_ctx::Seg& sg : segs) *n += sg.n;
-  if (nc > 0xFFFFFFFFull / SUB_BPC) return sub_refuse(ctx, "subsample: a sample of 2^32 events or more");
-  if (!nc) return GX_OK;
-  std::vector<char> st(nc * (sizeof(CntChunk) + 8));
-  CntChunk* ck = reinterpret_cast<CntChunk*>(st.data());
-  u64* first = reinterpret_cast<u64*>(st.data() + nc * sizeof(CntChunk));
-  stage_chunks(segs, ck);
-  u64 run = 0;
-  for (size_t c = 0; c < nc; c++) {
-    first[c] = run;
-    run += ck[c].n;
+  size_t nc = 0;
+  for (const gx_ctx::Seg& sg : segs) {
+    *n += sg.n;
+    nc += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
   }
-  POOLED(ctx, ctx->subIn, st.size());
-  HIPCHECK(hipMemcpyAsync(ctx->subIn.p, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the staging is this call's)
-  *dCk = ctx->subIn.as<CntChunk>();
-  *dFirst = reinterpret_cast<const u64*>(ctx->subIn.as<char>() + nc * sizeof(CntChunk));
+  if (nc > 0xFFFFFFFFull / SUB_BPC) return refuse(ctx, "subsample: a sample of 2^32 events or more");
+  *nCk = (u32)nc;
+  if (!nc) return GX_OK;
+  KeptIn in;
+  if (int rc = kept_stage(ctx, {KeptView{&segs, nullptr}}, 0, false, true, in)) return rc;
+  if (int rc = kept_send(ctx, in)) return rc;
+  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the pieces may be this call's)
+  *dCk = in.dCk;
+  *dFirst = in.dFirst;
   return GX_OK;
 }
 
@@ -173,7 +165,7 @@ int sat_point(gx_ctx* ctx, u64 T, u64 seed, unsigned flags, gx_sat_point& pt, st
   }
   int rc = gx_reset(ch);
   for (int r = 0; !rc && r < ctx->sample; r++) {
-    if (kt[r] < 0) return sub_refuse(ctx, "saturation: a replicate whose treatment was not kept");
+    if (kt[r] < 0) return refuse(ctx, "saturation: a replicate whose treatment was not kept");
     rc = gx_sample_begin(ch, 0, ctx->kept[kt[r]].save.data());
     if (!rc && nk[kt[r]]) rc = gx_push_events_device(ch, ctx->subBufs[kt[r]].as<gx_event>(), (size_t)nk[kt[r]]);
     if (!rc) rc = gx_sample_end(ch, nullptr, nullptr, nullptr);

@@ -1,8 +1,8 @@
 // gx_regions.h -- each kept sample's intervals counted in a caller's region set (gx_count_in_regions).  The regions may overlap,
 // nest, repeat and come in any order, so gx_count.h's difference array over a sorted, disjoint list does not apply.
-// (a part of gx_api.hip's translation unit; the events, CntChunk and CntChrom are gx_count.h's)
+// (a part of gx_api.hip's translation unit; the intervals and the pass over them are gx_kept.h's)
 //
-// Coordinates are the context's tile space, as in gx_count.h; a region's end is clamped to its chromosome's length, so it never
+// Coordinates are the context's tile space (gx_kept.h); a region's end is clamped to its chromosome's length, so it never
 // reaches the next chromosome's tiles.  The m regions that can count anything ("live": a chromosome this context works on, start
 // below its length) give A = their sorted starts and B = their sorted ends.  Per interval [s, e) with s <= e:
 //   a = #{A < e}, b = #{B <= s}.  A region that ends at or before s starts before e, so the b regions are among the a, and the
@@ -11,14 +11,16 @@
 //   count[k] = W{b <= j} - W{a <= i} = PB[j] - PA[i],
 // PA / PB the inclusive prefix sums of two histograms HA[a] += w, HB[b] += w.  An interval with a == b overlaps nothing and adds
 // the same amount to both terms of every region: it is left out.  Ties need no care: equal starts are all < e or none is.
-// An inverted interval (e < s; convert_event lets them in) breaks "the b regions are among the a": those go to a short list and
+// An inverted interval (e < s; gx_kept.h lets them in) breaks "the b regions are among the a": those go to a short list and
 // are tested against every region directly (k_reg_inverted) after the gather.
 // The histograms of one sample are one array H of 2 (m + 1) entries (HA, then HB).  While H fits REG_WIN_MAX LDS windows of
-// CNT_LDS_MAX entries -- one -- it is kept in LDS as in k_cnt_count (int32 per workgroup, the same bound; a launch per window).
+// CNT_LDS_MAX entries -- one -- it is kept in LDS (gx_kept.h's window, as in k_cnt_count; a launch per window).
 // A larger H takes 64-bit global atomics in ONE launch: only the intervals that overlap a region add anything, the adds spread
 // over H as the regions spread over the genome, and a second pass over the events costs more than they do (DESIGN.md section 4,
 // "Counting in regions": measured).  All sums are integers: no result depends on the order of the adds.
 #pragma once
+#include "gx_kept.h"
+#include "gx_count.h"   // (CNT_LDS_MAX, k_cnt_scan)
 
 namespace gx {
 
@@ -82,114 +84,46 @@ template <bool LDS>
 __global__ __launch_bounds__(CNT_NT) void k_reg_count(RegArgs a) {
   extern __shared__ int regLds[];
   __shared__ long long red[2][CNT_NT / 64];
-  if (LDS) {
-    for (u32 i = threadIdx.x; i < a.wn; i += CNT_NT) regLds[i] = 0;
-    __syncthreads();
-  }
+  if (LDS) kept_window_clear(regLds, a.wn);
   long long tot = 0, inr = 0;
-  for (u32 c = blockIdx.x; c < a.nChunks; c += gridDim.x) {
-    const CntChunk ch = a.chunks[c];
-    for (u32 b = 0; b < ch.n; b += CNT_NT * CNT_ITEMS) {
-      u64 gs[CNT_ITEMS], ge[CNT_ITEMS];
-      int w[CNT_ITEMS];
-#pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        const u32 i = b + (u32)j * CNT_NT + threadIdx.x;
-        w[j] = 0;
-        gs[j] = ge[j] = 0;
-        if (i >= ch.n) continue;
-        u32 chrom, s, e, cnt;
-        if (ch.packed) {
-          const uint2 v = static_cast<const uint2*>(ch.p)[i];
-          s = v.x;
-          e = v.x + (v.y & 0xFFFFu);
-          cnt = (0xA8654321u >> (4u * ((v.y >> 16) & 7u))) & 15u;
-          chrom = v.y >> 19;
-        } else {
-          const uint4 v = static_cast<const uint4*>(ch.p)[i];
-          chrom = v.x;
-          s = v.y;
-          e = v.z;
-          cnt = v.w;
-        }
-        // the intervals of k_cnt_count (gx_count.h): what convert_event lets into the pileup, end clamped
-        const bool cntOk = cnt <= 10u && ((0x57Eu >> cnt) & 1u);
-        if (!cntOk || chrom >= a.nChrom) continue;
-        const CntChrom cc = a.chroms[chrom];
-        if (!cc.active || s >= cc.len) continue;
-        w[j] = (int)(120u / cnt);
-        gs[j] = cc.base + s;
-        ge[j] = cc.base + (e > cc.len ? cc.len : e);
+  kept_walk(a.chunks, a.nChunks, a.chroms, a.nChrom, [&](const KeptIv& v, int) {
+    tot += v.w;
+    if (v.e < v.s) {   // inverted: k_reg_inverted
+      if (a.tot) {
+        const u32 at = atomicAdd(a.nInv, 1u);
+        if (at < a.invCap) a.inv[at] = RegInv{v.s, v.e, (u32)v.w, a.sample};
       }
-#pragma unroll
-      for (int j = 0; j < CNT_ITEMS; j++) {
-        if (!w[j]) continue;
-        tot += w[j];
-        if (ge[j] < gs[j]) {   // inverted: k_reg_inverted
-          if (a.tot) {
-            const u32 at = atomicAdd(a.nInv, 1u);
-            if (at < a.invCap) a.inv[at] = RegInv{gs[j], ge[j], (u32)w[j], a.sample};
-          }
-          continue;
-        }
-        const u32 ts = (u32)(gs[j] >> TB), te = (u32)(ge[j] >> TB);
-        const uint4 is = a.idx[ts];
-        uint2 ie = make_uint2(is.x, is.y);
-        if (te != ts) ie = *reinterpret_cast<const uint2*>(a.idx + te);
-        const u32 x = reg_rank_lt(a.A, ie.x, ie.y, ge[j]);
-        u32 y = reg_rank_le(a.B, is.z, is.w, gs[j]);
-        if (x == y) continue;
-        inr += w[j];
-        y += a.m + 1;
-        if (LDS) {
-          if (x - a.w0 < a.wn) atomicAdd(&regLds[x - a.w0], w[j]);
-          if (y - a.w0 < a.wn) atomicAdd(&regLds[y - a.w0], w[j]);
-        } else {
-          atomicAdd(a.hist + x, (unsigned long long)w[j]);
-          atomicAdd(a.hist + y, (unsigned long long)w[j]);
-        }
-      }
+      return;
     }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (u32 i = threadIdx.x; i < a.wn; i += CNT_NT) {
-      const int v = regLds[i];
-      if (v) atomicAdd(a.hist + a.w0 + i, (unsigned long long)(long long)v);
+    const u32 ts = (u32)(v.s >> TB), te = (u32)(v.e >> TB);
+    const uint4 is = a.idx[ts];
+    uint2 ie = make_uint2(is.x, is.y);
+    if (te != ts) ie = *reinterpret_cast<const uint2*>(a.idx + te);
+    const u32 x = reg_rank_lt(a.A, ie.x, ie.y, v.e);
+    u32 y = reg_rank_le(a.B, is.z, is.w, v.s);
+    if (x == y) return;
+    inr += v.w;
+    y += a.m + 1;
+    if (LDS) {
+      if (x - a.w0 < a.wn) atomicAdd(&regLds[x - a.w0], v.w);
+      if (y - a.w0 < a.wn) atomicAdd(&regLds[y - a.w0], v.w);
+    } else {
+      atomicAdd(a.hist + x, (unsigned long long)v.w);
+      atomicAdd(a.hist + y, (unsigned long long)v.w);
     }
-  }
+  });
+  if (LDS) kept_window_flush(regLds, a.w0, a.wn, a.hist);
   if (!a.tot) return;
-  for (int o = 32; o > 0; o >>= 1) {
-    tot += __shfl_xor(tot, o);
-    inr += __shfl_xor(inr, o);
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[0][wv] = tot;
-    red[1][wv] = inr;
-  }
-  __syncthreads();
+  tot = kept_block_sum(tot, red[0]);
+  inr = kept_block_sum(inr, red[1]);
   if (threadIdx.x == 0) {
-    long long t = 0, p = 0;
-    for (int k = 0; k < CNT_NT / 64; k++) {
-      t += red[0][k];
-      p += red[1][k];
-    }
-    if (t) atomicAdd(a.tot, (unsigned long long)t);
-    if (p) atomicAdd(a.tot + 1, (unsigned long long)p);
+    if (tot) atomicAdd(a.tot, (unsigned long long)tot);
+    if (inr) atomicAdd(a.tot + 1, (unsigned long long)inr);
   }
 }
 
 // The prefix sums of H's segments (2 per sample, seg entries apart, the first m entries of each), by tiles of REG_SCAN_TILE:
 // the tiles' sums (k_reg_tile_sums), their prefix sums per segment (k_cnt_scan), the scan inside each tile (k_reg_tile_scan).
-__device__ __forceinline__ long long reg_block_sum(long long v, long long* sh) {   // sh[CNT_NT / 64]
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long t = 0;
-  for (int k = 0; k < CNT_NT / 64; k++) t += sh[k];
-  return t;
-}
 
 // sums[seg * (nT + 1) + tile]; grid (nT, segments)
 __global__ __launch_bounds__(CNT_NT) void k_reg_tile_sums(const long long* __restrict__ H, u32 m, size_t seg, u32 nT,
@@ -201,7 +135,7 @@ __global__ __launch_bounds__(CNT_NT) void k_reg_tile_sums(const long long* __res
 #pragma unroll
   for (int j = 0; j < REG_SCAN_ITEMS; j++)
     if (k0 + j < m) v += h[k0 + j];
-  v = reg_block_sum(v, sh);
+  v = kept_block_sum(v, sh);
   if (threadIdx.x == 0) sums[(size_t)blockIdx.y * (nT + 1) + blockIdx.x] = v;
 }
 

@@ -3,7 +3,7 @@
 // subsamples of the BAM.
 // (a part of gx_api.hip's translation unit)
 //
-// A sample's events are k_cnt_count's (gx_count.h): the same chunk list, the same two event forms.  Event i of the sample
+// A sample's events are gx_kept.h's: the same chunk list, the same two event forms (kept_event).  Event i of the sample
 // (its position in the chunk list's order, i.e. the kept order) is kept iff subsample_draw(key, i) < T (gx_math.h); the
 // output is the kept events as 16-byte gx_event, in that order.  Every event is drawn, whatever its chromosome or count: the
 // consumer applies its own rules, as the first run did.
@@ -21,7 +21,7 @@
 // lane are 32 registers of data.  As compiled k_sub_write takes 66 VGPRs, i.e. seven wavefronts per SIMD, not eight (forcing
 // eight spills two registers; k_sub_count takes 26).  A block of 2,048 events keeps the scan at 24,415 counts for 50 M events.
 #pragma once
-#include "gx_count.h"
+#include "gx_kept.h"
 #include "gx_math.h"
 
 namespace gx {
@@ -114,13 +114,7 @@ __global__ __launch_bounds__(SUB_NT) void k_sub_write(SubArgs a) {
       const u32 i = b0 + (u32)j * SUB_NT + threadIdx.x;
       const bool k = i < ch.n && (u64)subsample_draw(a.key, i0 + (u32)j * SUB_NT + threadIdx.x) < a.T;
       ev[j] = make_uint4(0, 0, 0, 0);
-      if (k) {   // (only the kept ones are read: a line is fetched once any of its events is)
-        if (ch.packed) {   // (k_cnt_count's decoding)
-          const uint2 v = static_cast<const uint2*>(ch.p)[i];
-          ev[j] = make_uint4(v.y >> 19, v.x, v.x + (v.y & 0xFFFFu), (0xA8654321u >> (4u * ((v.y >> 16) & 7u))) & 15u);
-        } else
-          ev[j] = static_cast<const uint4*>(ch.p)[i];
-      }
+      if (k) ev[j] = kept_event(ch, i);   // (only the kept ones are read: a line is fetched once any of its events is)
       keep[j] = __ballot(k);
       if (lane == 0) cnt[j * SUB_NW + wv] = (u32)__popcll(keep[j]);
     }
