@@ -479,8 +479,7 @@ int gx_dups_first(gx_ctx* ctx, const gx_dup_key* keys, const uint8_t* multi, siz
   if (!n) return GX_OK;
   HIPCHECK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  u32 cap = 1024;
-  while ((size_t)cap < 2 * n) cap <<= 1;   // (<= 2^31: no wrap)
+  const u32 cap = dup_capacity(n);
   DevBuf dKeys, dMulti, dOwner, dTab;
   HIPCHECK(dKeys.ensure(n * 16));
   HIPCHECK(dMulti.ensure(n + 16));
@@ -497,6 +496,15 @@ int gx_dups_first(gx_ctx* ctx, const gx_dup_key* keys, const uint8_t* multi, siz
   HIPCHECK(hipMemcpyAsync(owner, dOwner.p, n * 4, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   HIPCHECK(hipGetLastError());
+  return GX_OK;
+}
+
+int gx_dups_geometry(const gx_dup_key* keys, size_t n, uint32_t* capacity, uint32_t* home) {
+  if (n > ((size_t)1 << 30) || (n && home && !keys)) return GX_ERR_ORDER;
+  const u32 cap = dup_capacity(n);
+  if (capacity) *capacity = cap;
+  if (home)
+    for (size_t i = 0; i < n; i++) home[i] = dup_hash(make_uint4(keys[i].w[0], keys[i].w[1], keys[i].w[2], keys[i].w[3])) & (cap - 1);
   return GX_OK;
 }
 

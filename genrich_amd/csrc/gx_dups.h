@@ -17,6 +17,14 @@ namespace gx {
 constexpr u32 DUP_EMPTY = 0xFFFFFFFFu;
 constexpr u32 DUP_CONTESTED = 0x80000000u;
 
+// the slots of the table for n records: the least power of two >= 2 n (at most half full: a free slot ends every probe), 1024
+// at least.  n <= 2^30, so <= 2^31: no wrap.  (gx_dups_first and gx_dups_geometry both ask here)
+inline u32 dup_capacity(size_t n) {
+  u32 cap = 1024;
+  while ((size_t)cap < 2 * n) cap <<= 1;
+  return cap;
+}
+
 struct DupTab {
   u32* rep;      // [cap] index of a record that holds the slot's key (DUP_EMPTY: free)
   u32* first;    // [cap] smallest index among the records with that key
@@ -24,7 +32,7 @@ struct DupTab {
   u32 mask;
 };
 
-__device__ __forceinline__ u32 dup_hash(const uint4 k) {
+__host__ __device__ __forceinline__ u32 dup_hash(const uint4 k) {   // (the host: gx_dups_geometry)
   u32 h = k.x * 0x9E3779B1u;
   h = (h ^ (h >> 15)) + k.y * 0x85EBCA6Bu;
   h = (h ^ (h >> 13)) + k.z * 0xC2B2AE35u;

@@ -771,6 +771,7 @@ struct DupDevice {
   std::vector<uint8_t> multi;
   std::vector<uint32_t> owner, readOf;   // per record: gx_dups_first's word; the set (or addition) it belongs to
   uint64_t nKeys = 0, nContested = 0, nByTable[4] = {0, 0, 0, 0};   // (by the key's tag: 1 proper pairs, 2 discordant, 3 singletons)
+  uint64_t nContBy[4] = {0, 0, 0, 0}, nContAdds = 0;   // the contested records by tag; of the singleton table's, the additions apart
   void clear() { keys.clear(); multi.clear(); owner.clear(); readOf.clear(); }
   void push(uint32_t tag, uint32_t a, uint32_t b, uint32_t c, bool m, uint32_t read) {
     keys.push_back(gx_dup_key{{tag, a, b, c}});
@@ -800,13 +801,26 @@ void findDups(State& S, DupReads& D, Counts& C) {
     std::stable_sort(o.begin(), o.end(), [&](uint32_t a, uint32_t b) { return v[a].qual > v[b].qual; });
     return o;
   };
-  auto runDevice = [&]() {
+  auto runDevice = [&](size_t nAdds = 0) {   // (nAdds: the records that lead the batch and are additions, not sets)
     dev.owner.assign(dev.keys.size(), 0);
     if (!dev.keys.empty())
       check(S, gx_dups_first(S.devs.ctx[0], dev.keys.data(), dev.multi.data(), dev.keys.size(), dev.owner.data()), S.devs.ctx[0]);
     dev.nKeys += dev.keys.size();
     for (const gx_dup_key& k : dev.keys) dev.nByTable[k.w[0] & 3u]++;   // (per key: a batch need not hold one table's keys)
-    for (uint32_t w : dev.owner) dev.nContested += (w & DUP_CONTESTED) != 0;
+    for (size_t i = 0; i < dev.owner.size(); i++)
+      if (dev.owner[i] & DUP_CONTESTED) {
+        dev.nContested++;
+        if (i < nAdds) dev.nContAdds++;
+        else dev.nContBy[dev.keys[i].w[0] & 3u]++;
+      }
+  };
+  auto report = [&]() {
+    if (!dev.on || !getenv("GENRICH_DUPS_REPORT")) return;
+    fprintf(stderr, "[dups] device: %llu keys, %llu contested (resolved on the host); by table: %llu paired, %llu discordant, %llu single\n",
+            (unsigned long long)dev.nKeys, (unsigned long long)dev.nContested, (unsigned long long)dev.nByTable[1],
+            (unsigned long long)dev.nByTable[2], (unsigned long long)dev.nByTable[3]);
+    fprintf(stderr, "[dups] contested: %llu paired, %llu discordant, %llu single, %llu additions\n", (unsigned long long)dev.nContBy[1],
+            (unsigned long long)dev.nContBy[2], (unsigned long long)dev.nContBy[3], (unsigned long long)dev.nContAdds);
   };
 
   {  // properly paired sets (findDupsPr 3616)
@@ -862,10 +876,7 @@ void findDups(State& S, DupReads& D, Counts& C) {
     dev.clear();
   }
   if (!S.o.singleOpt) {
-    if (dev.on && getenv("GENRICH_DUPS_REPORT"))
-      fprintf(stderr, "[dups] device: %llu keys, %llu contested (resolved on the host); by table: %llu paired, %llu discordant, %llu single\n",
-            (unsigned long long)dev.nKeys, (unsigned long long)dev.nContested, (unsigned long long)dev.nByTable[1],
-            (unsigned long long)dev.nByTable[2], (unsigned long long)dev.nByTable[3]);
+    report();
     return;
   }
 
@@ -1006,7 +1017,7 @@ void findDups(State& S, DupReads& D, Counts& C) {
         for (auto& a : r.aln) dev.push(3u, (uint32_t)a.chrom, end5(a), a.strand, r.aln.size() > 1, nAdds + ord[q]);
       }
       firstRec[ord.size()] = (uint32_t)dev.keys.size();
-      runDevice();
+      runDevice(nAdds);
       // the contested keys among the additions enter the host's table, in their order (the first holder stays)
       for (uint32_t k = 0; k < nAdds; k++)
         if (dev.owner[k] & DUP_CONTESTED) tabSn.emplace(KeySn{snAdds[k].chrom, snAdds[k].pos, snAdds[k].strand}, snAdds[k].name);
@@ -1049,10 +1060,7 @@ void findDups(State& S, DupReads& D, Counts& C) {
     D.sn.shrink_to_fit();
     dev.clear();
   }
-  if (dev.on && getenv("GENRICH_DUPS_REPORT"))
-    fprintf(stderr, "[dups] device: %llu keys, %llu contested (resolved on the host); by table: %llu paired, %llu discordant, %llu single\n",
-            (unsigned long long)dev.nKeys, (unsigned long long)dev.nContested, (unsigned long long)dev.nByTable[1],
-            (unsigned long long)dev.nByTable[2], (unsigned long long)dev.nByTable[3]);
+  report();
   S.o = saved;
 }
 

@@ -201,6 +201,8 @@ _SIGS = {
     "gx_sample_no_control": [C.c_void_p, C.POINTER(C.c_float)],
     "gx_saturation_dropped": [C.c_void_p, C.POINTER(C.c_longlong)],
     "gx_window_net": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+    "gx_dups_first": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "gx_dups_geometry": [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p],
     "gx_pvalues": [C.c_void_p],
     "gx_find_peaks": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "gx_get_peaks": [C.c_void_p, C.c_void_p, C.c_size_t],
@@ -527,6 +529,28 @@ def spearman_text(ctxs, sample_names, skip_zeros=False) -> bytes:
     return _to_tmpfile(lambda f: lib.gx_write_spearman_group(arr, len(ctxs), len(sample_names), names, int(bool(skip_zeros)), f))
 
 
+DUP_CONTESTED = 0x80000000      # gx_dups_first's owner word, bit 31: a multi-alignment set holds the key
+
+
+def _dup_keys(keys):
+    k = np.ascontiguousarray(keys, dtype=np.uint32)
+    if k.ndim != 2 or k.shape[1] != 4:
+        raise ValueError("keys: a uint32 array [n, 4]")
+    return k
+
+
+def dups_geometry(keys):
+    """(capacity, home) of the -r table for these keys (uint32 [n, 4]) as the library was built (gx_dups_geometry): the slots
+    gx_dups_first uses for n records and the slot at which each key's probe starts; host-only, needs no GPU."""
+    k = _dup_keys(keys)
+    cap = C.c_uint32(0)
+    home = np.zeros(len(k), dtype=np.uint32)
+    rc = load_library().gx_dups_geometry(k.ctypes.data if len(k) else None, len(k), C.byref(cap), home.ctypes.data if len(k) else None)
+    if rc:
+        raise RuntimeError(f"gx_dups_geometry: {rc}")
+    return cap.value, home
+
+
 def complexity_geometry(n=0):
     """(lanes, grid, lds_bound, least_capacity) of the complexity pass as the library was built (gx_complexity_geometry): the lanes
     of a workgroup of k_cpx_insert, its most workgroups with grid = 0, the multiplicity from which k_cpx_hist lists a key instead
@@ -811,6 +835,18 @@ class Genrich:
         out = np.zeros(n, dtype=np.int64)
         self._check(self.lib.gx_window_net(self.ctx, chrom, pos0, n, out.ctypes.data))
         return out
+
+    def dups_first(self, keys, multi):
+        """The raw owner words (uint32 [n]) of gx_dups_first for keys (uint32 [n, 4]) and multi (uint8 [n]): the index of the
+        first record with record i's key, with DUP_CONTESTED set when a record with that key has multi != 0."""
+        k = _dup_keys(keys)
+        m = np.ascontiguousarray(multi, dtype=np.uint8)
+        if m.shape != (len(k),):
+            raise ValueError("multi: one flag per key")
+        owner = np.zeros(len(k), dtype=np.uint32)
+        self._check(self.lib.gx_dups_first(self.ctx, k.ctypes.data if len(k) else None, m.ctypes.data if len(k) else None, len(k),
+                                           owner.ctypes.data if len(k) else None))
+        return owner
 
     def set_keep_pileups(self, keep):
         """keep=False: the pileup floats of the p-value intervals (only the -f / -k emitters read them)

@@ -312,6 +312,12 @@ def write_sam_dups(path, names, lens, ev, seed, read_len=50, name_prefix="d", ba
             rl = min(read_len, lens[c1] - p1, lens[c2] - p2)
             recs.append((nm, 1 | 64 | (16 if r1rev else 0) | (32 if r2rev else 0), c1, p1, mapq, rl, c2, p2, 0, -1, quals(rl)))
             recs.append((nm, 1 | 128 | (16 if r2rev else 0) | (32 if r1rev else 0), c2, p2, mapq, rl, c1, p1, 0, -2, quals(rl)))
+    write_alignment_records(path, names, lens, recs, bam=bam, quirks=quirks, qrng=qrng)
+
+
+def write_alignment_records(path, names, lens, recs, bam=False, quirks=0.0, qrng=None):
+    """SAM text (or BAM when bam=True) of alignment records in file order: (qname, flag, chrom, pos0, mapq, read length,
+    RNEXT's chromosome or -1, pnext0, tlen, AS, base qualities as a uint8 array or None); quirks: write_sam_dups."""
     if not bam:
         with open(path, "w") as f:
             f.write("@HD\tVN:1.0\tSO:queryname\n")

@@ -183,9 +183,16 @@ int gx_window_net(gx_ctx* ctx, uint32_t chrom, uint32_t pos0, uint32_t n, long l
  * key was free), with bit 31 set when some record with that key belongs to a multi-alignment set: a set of one
  * alignment whose owner word has no bit 31 is a duplicate exactly when owner[i] != i, and of the set owner[i] belongs
  * to; everything that carries bit 31 is left to the caller, who walks those few sets in order as the reference does.
- * n < 2^31.  Uses the context's device and stream; independent of the sample state. */
+ * n <= 2^30 (the table has 2^k >= 2 n slots addressed by 32-bit indices); a larger n, or a NULL array with n > 0, is
+ * GX_ERR_ORDER before anything is allocated; n = 0 is GX_OK and leaves owner alone.  Uses the context's device and stream;
+ * independent of the sample state.
+ * gx_dups_geometry: what the table's edge cases depend on, host-only (no context, no device): *capacity = the slots
+ * gx_dups_first uses for n records -- the least power of two that is >= 2 n and >= 1024 -- and home[i] = the slot at which the
+ * probe of keys[i] starts in a table of that capacity (the kernels' own hash & (capacity - 1); a probe walks upwards from
+ * there and wraps at the end).  capacity or home may be NULL; n > 2^30: GX_ERR_ORDER. */
 typedef struct { uint32_t w[4]; } gx_dup_key;
 int gx_dups_first(gx_ctx* ctx, const gx_dup_key* keys, const uint8_t* multi, size_t n, uint32_t* owner);
+int gx_dups_geometry(const gx_dup_key* keys, size_t n, uint32_t* capacity, uint32_t* home);
 
 /* Treatment: == savePileupExpt (Genrich.c:2168-2295), returns fragLen.
  * Control : == savePileupCtrl (:2052-2161), returns lambda and factor.

@@ -251,6 +251,14 @@ def cases():
             name=nm, names=N2, args=extra + ["-a", "20"], mixed=dict(seed=21, bam=isbam, writer="dups"),
             reps=[dict(t=(N2, L2, mf(L2, 2500, 97)), c=(N2, L2, mf(L2, 2000, 98, uniform_only=True)))])
 
+    # -r on contested sets (tests/dups_cases.py): secondary alignments of the primary's AS on proper pairs, singletons and
+    # discordant pairs, on shared coordinates -- with unpaired alignments kept (-y), BAM input with -x, pairs only
+    for nm, extra, isbam in (("dups_contested_y", ["-r", "-y"], False), ("dups_contested_x_bam", ["-r", "-x"], True),
+                             ("dups_contested_pairs", ["-r"], False)):
+        yield dict(
+            name=nm, names=N2, args=extra + ["-a", "20"], mixed=dict(seed=41, bam=isbam, writer="contested"),
+            reps=[dict(t=(N2, L2, mf(L2, 1200, 151)), c=(N2, L2, mf(L2, 900, 152, uniform_only=True)))])
+
     # valid but unusual records: SAM lines without optional fields (QUAL keeps its line feed), records
     # without SEQ (the BAM reader takes l_seq = 0 at face value), soft clips -- with -r, where qualities count
     # (the BAM case keeps to proper pairs: on an unpaired reverse read without SEQ the reference's own
@@ -484,6 +492,9 @@ def write_input(path, names, lens, ev, mixed, seed_off, prefix):
     if mixed and mixed.get("writer") == "dups":
         synth.write_sam_dups(path, names, lens, ev, mixed["seed"] + seed_off, name_prefix=prefix, bam=mixed["bam"],
                              quirks=mixed.get("quirks", 0.0))
+    elif mixed and mixed.get("writer") == "contested":
+        import dups_cases
+        dups_cases.write_sam_contested(path, names, lens, ev, mixed["seed"] + seed_off, name_prefix=prefix, bam=mixed["bam"])
     elif mixed:
         synth.write_sam_mixed(path, names, lens, ev, mixed["seed"] + seed_off, name_prefix=prefix, bam=mixed["bam"])
     else:

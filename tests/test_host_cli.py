@@ -120,17 +120,16 @@ def test_cli_outputs_byte_identical(name):
         assert f"Peaks identified: {meta['ref_peaks'][0][0]} ({meta['ref_peaks'][0][1]}bp)" in res.stderr
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", ["dups_pairs", "dups_y", "dups_x_bam", "quirks_sam", "quirks_bam"])
-def test_cli_dups_on_the_device_match_the_reference_log(name):
-    """-r with the membership half of findDups on the device (gx_dups_first): the -R log, the -b event list and the
-    duplicate counts of the reference, and the report says the device path ran; the host-only path gives the same."""
+def _dups_by_both_routes(name):
+    """-r with the membership half of findDups on the device (gx_dups_first) and on the host's tables alone: the -R log, the -b
+    event list, the narrowPeak and the duplicate counts of the reference by either route, and the report says which one ran.
+    Returns the device run's stderr."""
     cases, mg = _cases()
     case = cases[name]
     meta, _, _, _ = G.load_case(name)
     tmp = meta["tmp_prefix"].rstrip("/")
     args = _write_inputs(case, mg, tmp)
-    got = {}
+    got, err = {}, {}
     for mode in ("device", "host"):
         out = os.path.join(tmp, "dup_" + mode)
         env = dict(os.environ, GENRICH_DUPS_REPORT="1")
@@ -146,9 +145,41 @@ def test_cli_dups_on_the_device_match_the_reference_log(name):
         if mode == "device":
             assert rep and all(int(l.split()[2]) > 0 for l in rep), res.stderr[-400:]
         else:
-            assert not rep
+            assert not rep and "[dups] contested:" not in res.stderr
         got[mode] = [l.strip() for l in res.stderr.splitlines() if "duplicates:" in l or "aln sets:" in l]
+        err[mode] = res.stderr
     assert got["device"] == got["host"] == meta["ref_dups"]   # the reference's counts, by either route
+    return err["device"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dups_pairs", "dups_y", "dups_x_bam", "quirks_sam", "quirks_bam"])
+def test_cli_dups_on_the_device_match_the_reference_log(name):
+    """-r with the membership half of findDups on the device (gx_dups_first): the -R log, the -b event list and the
+    duplicate counts of the reference, and the report says the device path ran; the host-only path gives the same."""
+    _dups_by_both_routes(name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dups_contested_pairs", "dups_contested_x_bam", "dups_contested_y"])
+def test_cli_contested_dups_on_the_device_match_the_reference_log(name):
+    """The same on the cases made of contested keys (tests/dups_cases.py): multi-alignment sets in all three tables whose keys
+    single-alignment sets share -- what the device cannot decide and findDups walks on tables of the contested keys alone.  The
+    report's second line counts the contested records by table (the additions: ends of kept pairs and discordant mates in the
+    singleton table); every count the case can produce must be there, in the treatment file and in the control."""
+    err = _dups_by_both_routes(name)
+    rep = [l for l in err.splitlines() if l.startswith("[dups] contested:")]
+    print("\n".join(l for l in err.splitlines() if l.startswith("[dups]")))
+    assert len(rep) == 2, err[-600:]
+    for l in rep:
+        w = l.replace(",", "").split()
+        assert w[3::2] == ["paired", "discordant", "single", "additions"], l
+        paired, discordant, single, additions = (int(v) for v in w[2::2])
+        assert paired > 0, l
+        if name == "dups_contested_pairs":
+            assert (discordant, single, additions) == (0, 0, 0), l      # (-r alone: proper pairs only)
+        else:
+            assert discordant > 0 and single > 0 and additions > 0, l
 
 
 def _p_runs():
