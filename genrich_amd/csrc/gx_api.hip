@@ -17,6 +17,7 @@
 #include "gx_host_rank.h"
 #include "gx_host_complexity.h"
 #include "gx_host_subsample.h"
+#include "gx_host_depth.h"
 
 
 // ================================ C ABI ==================================================
@@ -263,6 +264,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_kept(ctx);   // (the switch itself stays: gx_set_count_in_peaks)
   drop_coverage(ctx);   // (... and gx_set_coverage_bins')
   drop_profile(ctx);    // (... and gx_set_profile's)
+  drop_depth(ctx);      // (... and gx_set_depth_hist's)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
@@ -440,6 +442,8 @@ int gx_sample_end(gx_ctx* ctx, double* frag_len, float* lambda, float* factor) {
     return GX_ERR_ORDER;
   if (ctx->covW)
     if (int rc = cov_sample(ctx, ctx->phase == 4)) return rc;
+  if (ctx->depthOn)
+    if (int rc = depth_sample(ctx, ctx->phase == 4)) return rc;
   if (!ctx->profAnchors.empty())
     if (int rc = prof_sample(ctx, ctx->phase == 4)) return rc;
   if (ctx->countOn) keep_sample(ctx, ctx->phase == 4);
@@ -860,7 +864,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
-           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u);
+           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u);
   return GX_OK;
 }
 
@@ -963,6 +967,75 @@ int gx_get_coverage(gx_ctx* ctx, int sample, int chrom, int* rep, int* is_ctrl, 
   HIPCHECK(hipMemcpyAsync(sum120, c.bins.as<int64_t>() + ctx->covOff[chrom], n * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHECK(hipStreamSynchronize(ctx->stream));
   return GX_OK;
+}
+
+int gx_set_depth_hist(gx_ctx* ctx, int on) {
+  if (!ctx || ctx->nChrom == 0 || ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;   // idle, and the table is known
+  ctx->depthOn = on != 0;
+  drop_depth(ctx);
+  return GX_OK;
+}
+
+int gx_depth_samples(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !n_samples) return GX_ERR_ORDER;
+  *n_samples = (int)ctx->depth.size();
+  return GX_OK;
+}
+
+int gx_get_depth(gx_ctx* ctx, int sample, gx_depth_hist* out, uint64_t* bases, uint64_t* rsum, uint64_t* rsq, uint64_t* deep_v,
+                 uint64_t* deep_bases, size_t cap, size_t* n_deep) {
+  if (!ctx || ctx->phase == 1 || ctx->phase == 3 || sample < 0 || (size_t)sample >= ctx->depth.size()) return GX_ERR_ORDER;
+  return depth_give(ctx->depth[sample], out, bases, rsum, rsq, deep_v, deep_bases, cap, n_deep);
+}
+
+int gx_depth_group(gx_ctx* const* ctxs, int n_ctx, int sample, gx_depth_hist* out, uint64_t* bases, uint64_t* rsum, uint64_t* rsq,
+                   uint64_t* deep_v, uint64_t* deep_bases, size_t cap, size_t* n_deep) {
+  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
+  gx_ctx::DepthResult sum;
+  for (int g = 0; g < n_ctx; g++) {
+    gx_ctx* c = ctxs[g];
+    if (!c || c->phase == 1 || c->phase == 3 || sample < 0 || (size_t)sample >= c->depth.size() || c->depth.size() != ctxs[0]->depth.size())
+      return GX_ERR_ORDER;
+    if (g == 0) sum = c->depth[sample];
+    else depth_add(sum, c->depth[sample]);
+  }
+  return depth_give(sum, out, bases, rsum, rsq, deep_v, deep_bases, cap, n_deep);
+}
+
+int gx_depth_geometry(uint32_t* bound, int* lanes, int* grid, size_t* list_capacity) {
+  if (bound) *bound = DEPTH_BOUND;
+  if (lanes) *lanes = DEPTH_NW * 64;
+  if (grid) *grid = (int)DEPTH_GRID;
+  if (list_capacity) *list_capacity = DEPTH_LIST_CAP;
+  return GX_OK;
+}
+
+int gx_depth_last(gx_ctx* ctx, size_t* list_capacity, int* reruns) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (list_capacity) *list_capacity = ctx->depthLastCap;
+  if (reruns) *reruns = (int)ctx->depthLastReruns;
+  return GX_OK;
+}
+
+// (over contexts: here, not in gx_emit.cpp, like the complexity's -- it reads contexts)
+int gx_write_depth_group(gx_ctx* const* ctxs, int n_ctx, FILE* depth, FILE* metrics) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || (!depth && !metrics)) return GX_ERR_ORDER;
+  const size_t nS = ctxs[0]->depth.size();
+  if (!nS) return GX_ERR_ORDER;
+  std::vector<gx_depth_hist> hs(nS);
+  std::vector<std::vector<uint64_t>> arr(nS * 5);
+  for (size_t i = 0; i < nS; i++) {
+    size_t n = 0;
+    if (int rc = gx_depth_group(ctxs, n_ctx, (int)i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n)) return rc;
+    for (int k = 0; k < 3; k++) arr[i * 5 + k].assign(DEPTH_BOUND, 0);
+    for (int k = 3; k < 5; k++) arr[i * 5 + k].assign(std::max<size_t>(n, 1), 0);
+    if (int rc = gx_depth_group(ctxs, n_ctx, (int)i, &hs[i], arr[i * 5].data(), arr[i * 5 + 1].data(), arr[i * 5 + 2].data(), arr[i * 5 + 3].data(),
+                                arr[i * 5 + 4].data(), n, nullptr))
+      return rc;
+  }
+  if (depth)
+    if (int rc = gx_format_depth(depth, (int)nS, hs.data())) return rc;
+  return metrics ? gx_format_depth_metrics(metrics, (int)nS, hs.data()) : GX_OK;
 }
 
 int gx_set_profile(gx_ctx* ctx, const gx_anchor* anchors, size_t n, uint32_t flank, uint32_t bin_size, int keep_matrix) {

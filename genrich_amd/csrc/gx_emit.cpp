@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the depth distribution tables (--depth) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -53,6 +53,32 @@ U256 sub256(const U256& a, const U256& b) {   // a >= b
     const u128_t t = (u128_t)a.w[k] - b.w[k] - borrow;
     r.w[k] = (uint64_t)t;
     borrow = (uint64_t)(t >> 64) & 1;
+  }
+  return r;
+}
+U256 u256_of(u128_t a) {
+  U256 r;
+  r.w[0] = (uint64_t)a;
+  r.w[1] = (uint64_t)(a >> 64);
+  return r;
+}
+U256 add256(const U256& a, const U256& b) {   // (no sum here reaches 2^256)
+  U256 r;
+  uint64_t carry = 0;
+  for (int k = 0; k < 4; k++) {
+    const u128_t t = (u128_t)a.w[k] + b.w[k] + carry;
+    r.w[k] = (uint64_t)t;
+    carry = (uint64_t)(t >> 64);
+  }
+  return r;
+}
+U256 mul256_64(const U256& a, uint64_t b) {   // (the product stays below 2^256 for every caller)
+  U256 r;
+  uint64_t carry = 0;
+  for (int k = 0; k < 4; k++) {
+    const u128_t t = (u128_t)a.w[k] * b + carry;
+    r.w[k] = (uint64_t)t;
+    carry = (uint64_t)(t >> 64);
   }
   return r;
 }
@@ -652,6 +678,148 @@ int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const in
   for (int s = 0; s < n_samples; s++)
     for (size_t i = 0; i < n_pairs[s]; i++)
       fprintf(out, "%c%d\t%llu\t%llu\n", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)mult[s][i], (unsigned long long)keys[s][i]);
+  return GX_OK;
+}
+
+// --depth / --depth-metrics: the figures from the integers alone, every sum an exact big integer before anything is a double
+namespace {
+// what the formatters and the figures walk: (whole depth, bases) ascending, the depth-0 row first and always there (the bases at
+// pileup 0 and class 0's), deep entries grouped by v div 120; false: the histogram contradicts itself
+struct DepthRows {
+  std::vector<uint64_t> depth, bases;
+  uint64_t B = 0, covered = 0;
+};
+bool depth_rows(const gx_depth_hist& h, DepthRows& R) {
+  if (!h.bases || !h.rsum || !h.rsq || (h.n_deep && (!h.deep_v || !h.deep_bases)) || h.excluded > h.total) return false;
+  R.B = h.total - h.excluded;
+  u128_t covered = 0;
+  R.depth.assign(1, 0);
+  R.bases.assign(1, h.bases[0]);
+  covered += h.bases[0];
+  for (uint32_t d = 0; d < GX_DEPTH_BOUND; d++) {
+    if ((u128_t)h.rsum[d] > (u128_t)119 * h.bases[d] || (u128_t)h.rsq[d] > (u128_t)119 * h.rsum[d] || h.rsq[d] < h.rsum[d]) return false;
+    if (d == 0 && h.bases[0] && !h.rsum[0]) return false;   // (class 0 holds 0 < v < 120 only)
+    if (!d || !h.bases[d]) continue;
+    R.depth.push_back(d);
+    R.bases.push_back(h.bases[d]);
+    covered += h.bases[d];
+  }
+  for (size_t i = 0; i < h.n_deep; i++) {
+    if (h.deep_v[i] < (uint64_t)120 * GX_DEPTH_BOUND || !h.deep_bases[i] || (i && h.deep_v[i - 1] >= h.deep_v[i])) return false;
+    const uint64_t d = h.deep_v[i] / 120;
+    if (R.depth.back() == d) R.bases.back() += h.deep_bases[i];
+    else {
+      R.depth.push_back(d);
+      R.bases.push_back(h.deep_bases[i]);
+    }
+    covered += h.deep_bases[i];
+  }
+  if (covered + h.zero != (u128_t)R.B) return false;
+  R.covered = (uint64_t)covered;
+  R.bases[0] += h.zero;
+  if (R.covered && (!h.min_v || h.max_v < h.min_v)) return false;
+  return true;
+}
+void put_depth_value(FILE* out, uint64_t v) {   // a pileup in 1/120 units, as --coverage prints a value
+  if (v % 120 == 0) fprintf(out, "\t%llu", (unsigned long long)(v / 120));
+  else fprintf(out, "\t%.4f", (double)v / 120.0);
+}
+const unsigned DEPTH_GE[GX_DEPTH_NGE] = {1, 2, 5, 10, 20, 50, 100};
+}  // namespace
+
+int gx_depth_metrics(const gx_depth_hist* hist, gx_depth_metrics_t* out) {
+  DepthRows R;
+  if (!hist || !out || !depth_rows(*hist, R)) return GX_ERR_ORDER;
+  const gx_depth_hist& h = *hist;
+  gx_depth_metrics_t m{};
+  const double nan = std::nan("");
+  m.bases = R.B;
+  m.excluded = h.excluded;
+  m.covered = R.covered;
+  m.min_v = (h.zero || !R.covered) ? 0 : h.min_v;
+  m.max_v = R.covered ? h.max_v : 0;
+  // sum v and sum v^2 over the bases, exact
+  U256 sv, sv2;
+  for (uint32_t d = 0; d < GX_DEPTH_BOUND; d++) {
+    if (!h.bases[d]) continue;
+    sv = add256(sv, u256_of((u128_t)(120ull * d) * h.bases[d] + h.rsum[d]));
+    sv2 = add256(sv2, u256_of((u128_t)(14400ull * d * d) * h.bases[d]));
+    sv2 = add256(sv2, u256_of((u128_t)(240ull * d) * h.rsum[d] + h.rsq[d]));
+  }
+  for (size_t i = 0; i < h.n_deep; i++) {
+    sv = add256(sv, u256_of((u128_t)h.deep_v[i] * h.deep_bases[i]));
+    sv2 = add256(sv2, mul128((u128_t)h.deep_v[i] * h.deep_v[i], h.deep_bases[i]));
+  }
+  const u128_t sv128 = ((u128_t)sv.w[1] << 64) | sv.w[0];   // (sum v < 2^64 * 2^64: deep_v is checked against nothing above, so ...)
+  if (sv.w[2] | sv.w[3]) return GX_ERR_ORDER;              // (... a made-up list beyond it is refused)
+  if (R.B) {
+    const double nb = 120.0 * (double)R.B;
+    m.covered_fraction = (double)R.covered / (double)R.B;
+    m.mean = to_double(sv) / nb;
+    const U256 a = mul256_64(sv2, R.B), b = mul128(sv128, sv128);   // B sum v^2 >= (sum v)^2
+    if (sv2.w[3] || cmp256(a, b) < 0) return GX_ERR_ORDER;
+    m.sd = std::sqrt(to_double(sub256(a, b))) / nb;
+  } else {
+    m.mean = m.sd = nan;
+  }
+  // percentiles: the smallest whole depth d with 100 #(bases of depth <= d) >= q B
+  const unsigned q[5] = {25, 50, 75, 95, 99};
+  uint64_t* dst[5] = {&m.q25, &m.median, &m.q75, &m.p95, &m.p99};
+  u128_t below = 0;
+  int at = 0;
+  for (size_t i = 0; i < R.depth.size() && at < 5; i++) {
+    below += R.bases[i];
+    while (at < 5 && (u128_t)100 * below >= (u128_t)q[at] * R.B) *dst[at++] = R.depth[i];
+  }
+  for (int k = 0; k < GX_DEPTH_NGE; k++) {
+    u128_t n = 0;
+    for (size_t i = 0; i < R.depth.size(); i++)
+      if (R.depth[i] >= DEPTH_GE[k]) n += R.bases[i];
+    m.ge[k] = R.B ? (double)(uint64_t)n / (double)R.B : 0.0;
+  }
+  *out = m;
+  return GX_OK;
+}
+
+// --depth: one row per sample and non-empty whole depth
+int gx_format_depth(FILE* out, int n_samples, const gx_depth_hist* hist) {
+  if (!out || n_samples < 1 || !hist) return GX_ERR_ORDER;
+  std::vector<DepthRows> R((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (!depth_rows(hist[s], R[s])) return GX_ERR_ORDER;
+  fprintf(out, "#sample\tdepth\tbases\tbases_at_least\tfraction_at_least\n");
+  for (int s = 0; s < n_samples; s++) {
+    uint64_t atLeast = R[s].B;
+    for (size_t i = 0; i < R[s].depth.size(); i++) {
+      fprintf(out, "%c%d\t%llu\t%llu\t%llu\t%.6f\n", hist[s].is_ctrl ? 'c' : 't', (int)hist[s].rep, (unsigned long long)R[s].depth[i],
+              (unsigned long long)R[s].bases[i], (unsigned long long)atLeast, R[s].B ? (double)atLeast / (double)R[s].B : 0.0);
+      atLeast -= R[s].bases[i];
+    }
+  }
+  return GX_OK;
+}
+
+// --depth-metrics: one row per sample
+int gx_format_depth_metrics(FILE* out, int n_samples, const gx_depth_hist* hist) {
+  if (!out || n_samples < 1 || !hist) return GX_ERR_ORDER;
+  std::vector<gx_depth_metrics_t> m((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (int rc = gx_depth_metrics(&hist[s], &m[s])) return rc;
+  fprintf(out, "sample\tbases\texcluded\tcovered\tcovered_fraction\tmean\tsd\tmin\tq25\tmedian\tq75\tp95\tp99\tmax");
+  for (int k = 0; k < GX_DEPTH_NGE; k++) fprintf(out, "\tge%u", DEPTH_GE[k]);
+  fprintf(out, "\n");
+  for (int s = 0; s < n_samples; s++) {
+    fprintf(out, "%c%d\t%llu\t%llu\t%llu\t%.6f", hist[s].is_ctrl ? 'c' : 't', (int)hist[s].rep, (unsigned long long)m[s].bases,
+            (unsigned long long)m[s].excluded, (unsigned long long)m[s].covered, m[s].covered_fraction);
+    put_cpx(out, m[s].mean, "\t%.6f");
+    put_cpx(out, m[s].sd, "\t%.6f");
+    put_depth_value(out, m[s].min_v);
+    fprintf(out, "\t%llu\t%llu\t%llu\t%llu\t%llu", (unsigned long long)m[s].q25, (unsigned long long)m[s].median, (unsigned long long)m[s].q75,
+            (unsigned long long)m[s].p95, (unsigned long long)m[s].p99);
+    put_depth_value(out, m[s].max_v);
+    for (int k = 0; k < GX_DEPTH_NGE; k++) fprintf(out, "\t%.6f", m[s].ge[k]);
+    fprintf(out, "\n");
+  }
   return GX_OK;
 }
 

@@ -30,9 +30,25 @@ int cov_layout(gx_ctx* ctx) {
   return GX_OK;
 }
 
-// gx_sample_end, coverage on: the sample's pileup, where close_sample left it, summed into a bin array of its own.  Nothing
-// has stashed, merged or reused the loose slots yet; with -E regions the tight arrays are read (pack_pileup: what the control
-// merge needs there anyway -- no carry says V_MARK).
+// The closed sample's pileup as the passes over it read it (k_cov_bins, k_depth_hist), where close_sample left it.  Nothing has
+// stashed, merged or reused the loose slots yet; with -E regions the tight arrays are read (pack_pileup, which runs once per
+// pileup however many passes ask: what the control merge needs there anyway -- no carry says V_MARK).  chromBin stays the caller's.
+int cov_input(gx_ctx* ctx, Pileup& P, CovIn& in) {
+  in.tileIvOff = P.tileIvOff.as<u32>();
+  in.tileChrom = ctx->dTileChrom.as<u32>();
+  in.nChrom = ctx->nChrom;
+  if (ctx->hasBed) {
+    if (int rc = pack_pileup(ctx, P)) return rc;
+    in.end = P.ivEnd.as<u32>(); in.v = P.ivV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 0u;
+  } else if (P.inLoose) {   // (a control: scan_and_close has stashed it for its merge)
+    in.end = P.looseEnd.as<u32>(); in.v = P.looseV.as<int>(); in.meta = P.meta.as<TileMeta>(); in.loose = 1u;
+  } else {
+    in.end = ctx->looseEnd.as<u32>(); in.v = ctx->looseV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 1u;
+  }
+  return GX_OK;
+}
+
+// gx_sample_end, coverage on: the sample's pileup (cov_input) summed into a bin array of its own
 int cov_sample(gx_ctx* ctx, int isCtrl) {
   if (ctx->covDirty)
     if (int rc = cov_layout(ctx)) return rc;
@@ -47,18 +63,8 @@ int cov_sample(gx_ctx* ctx, int isCtrl) {
     phase_begin(ctx, isCtrl ? "c.cover" : "t.cover");   // (the zeroing, with -E regions the tight arrays, the pass)
     HIPCHECK(hipMemsetAsync(cs.bins.p, 0, nBins * 8, s));
     CovIn in{};
-    in.tileIvOff = P.tileIvOff.as<u32>();
-    in.tileChrom = ctx->dTileChrom.as<u32>();
+    if (int rc = cov_input(ctx, P, in)) return rc;
     in.chromBin = ctx->covChromBin.as<u32>();
-    in.nChrom = ctx->nChrom;
-    if (ctx->hasBed) {
-      if (int rc = pack_pileup(ctx, P)) return rc;
-      in.end = P.ivEnd.as<u32>(); in.v = P.ivV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 0u;
-    } else if (P.inLoose) {   // (a control: scan_and_close has stashed it for its merge)
-      in.end = P.looseEnd.as<u32>(); in.v = P.looseV.as<int>(); in.meta = P.meta.as<TileMeta>(); in.loose = 1u;
-    } else {
-      in.end = ctx->looseEnd.as<u32>(); in.v = ctx->looseV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 1u;
-    }
     const u32 nTiles = ctx->nTiles;
     hipLaunchKernelGGL(k_cov_bins, dim3(std::max(1u, std::min((nTiles + COV_NW - 1) / COV_NW, (u32)(8 * ctx->numCU)))), dim3(COV_NW * 64), 0, s,
                        in, nTiles, ctx->covW, cs.bins.as<unsigned long long>());

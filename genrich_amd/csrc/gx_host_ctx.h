@@ -34,6 +34,7 @@
 #include "gx_rank.h"
 #include "gx_complexity.h"
 #include "gx_subsample.h"
+#include "gx_depth.h"
 
 using namespace gx;
 
@@ -196,6 +197,9 @@ struct Knobs {
   int fpAgg = 0;          // GX_FP_AGG: k_fp_hist aggregates equal classes inside the wavefront before LDS (measurements; default: an atomic pair per lane)
   int rankCapLog = 0;     // GX_RANK_CAP_LOG: log2 of the first capacity of k_rank_distinct's table (default RK_CAP_LOG; tests: the growth path with a few thousand values)
   int rankLookup = 0;     // GX_RANK_LOOKUP: k_rank's lookup: 1 binary search in the sorted table, 2 probing a hashed one (measurements; default RK_LOOKUP)
+  int depthGrid = 0;      // GX_DEPTH_GRID: workgroups of k_depth_hist (0: one per DEPTH_NW tiles, at most DEPTH_GRID; tests: 1 makes one workgroup walk every tile)
+  int depthListCap = 0;   // GX_DEPTH_LIST_CAP: entries of k_depth_hist's deep list at first (0: DEPTH_LIST_CAP; tests: a tiny one forces the rerun)
+  int depthPriv = 0;      // GX_DEPTH_PRIV: k_depth_hist<true> sums the pieces of whole depth 1 .. 4 in registers, one LDS atomic per class and wavefront (measurements; default: an LDS atomic per piece)
   int roctx = 0;          // GX_ROCTX: a roctx range around every phase (rocprofv3 --marker-trace: kernel -> phase attribution)
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
@@ -242,6 +246,7 @@ const KnobDef KNOBS[] = {
     {"GX_FP_AGG", &Knobs::fpAgg, nullptr},
     {"GX_RANK_CAP_LOG", &Knobs::rankCapLog, nullptr},
     {"GX_RANK_LOOKUP", &Knobs::rankLookup, nullptr},
+    {"GX_DEPTH_GRID", &Knobs::depthGrid, nullptr}, {"GX_DEPTH_LIST_CAP", &Knobs::depthListCap, nullptr}, {"GX_DEPTH_PRIV", &Knobs::depthPriv, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
 };
 // a switch that is merely present counts as 1 (GX_NO_LOOSE= is "on", as it was with getenv() != nullptr), and so does a
@@ -481,6 +486,21 @@ struct gx_ctx {
   bool cpxReady = false;
   bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
   u32 cpxLastCapLog = 0;          // log2 of the capacity the last pass used (gx_complexity_last)
+  // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
+  struct DepthResult {
+    int rep = 0;
+    bool ctrl = false;
+    u64 total = 0, excluded = 0, zero = 0;   // bases of the chromosomes that count, those inside -E regions, those at pileup 0
+    u64 minV = 0, maxV = 0;                  // the smallest and the largest pileup above 0 (0: none)
+    std::vector<uint64_t> bases, rsum, rsq;  // [DEPTH_BOUND] per whole depth
+    std::vector<uint64_t> deepV, deepBases;  // the deep list: one entry per distinct v, ascending
+  };
+  bool depthOn = false;
+  std::vector<DepthResult> depth;   // until gx_reset
+  DevBuf depthOut, depthDeep;       // the control words + the three arrays; the deep list
+  bool depthUsed = false;           // k_depth_hist ran since the last gx_reset
+  size_t depthLastCap = 0;          // the last pass: the list capacity it ended with, how often it ran again (gx_depth_last)
+  u32 depthLastReruns = 0;
   // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
   // nothing here exists before the first call
   DevBuf subCnt, subOff;          // k_sub_count's counts per block, k_sub_scan's offsets

@@ -164,6 +164,8 @@ struct Opts {
   const char* fingerprintFile = nullptr;   // --fingerprint FILE: each sample's Lorenz curve from the coverage bins
   const char* fingerprintMetricsFile = nullptr;   // --fingerprint-metrics FILE: ... and its figures
   const char* complexityFile = nullptr;    // --complexity FILE: each sample's library complexity from its kept intervals
+  const char* depthFile = nullptr;         // --depth FILE: each sample's per-base depth distribution from its pileup
+  const char* depthMetricsFile = nullptr;  // --depth-metrics FILE: ... and the figures made of it
   const char* complexityHistFile = nullptr;   // --complexity-hist FILE: ... and its duplication histogram
   const char* saturationFile = nullptr;    // --saturation FILE: the peaks called once more on nested subsamples of the run's intervals
   int saturationSteps = 10;                // --saturation-steps N: the points of the curve, T_j = (j << 32) / N
@@ -2842,6 +2844,46 @@ void writeComplexity(State& S) {
   }
 }
 
+// --depth FILE / --depth-metrics FILE: the distribution of per-base depth of each sample's pileup, taken on the device when the
+// sample was closed (one pass per context, added): one row per sample and non-empty whole depth, and one row of figures per
+// sample (bases, covered, mean, sd, min, quartiles, percentiles, max, the fractions at 1x .. 100x), labelled t<rep> / c<rep>; with
+// -v the mean, the median and the share covered on stderr too
+void writeDepth(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n();
+  int nS = 0;
+  check(S, gx_depth_samples(g0, &nS), g0);
+  if (nS < 1) die("", "--depth: no sample was closed");
+  std::vector<gx_depth_hist> hs((size_t)nS);
+  std::vector<std::vector<uint64_t>> arr((size_t)nS * 5);
+  for (int i = 0; i < nS; i++) {   // (before a file is opened: a context's refusal carries its own text)
+    size_t n = 0;
+    check(S, gx_depth_group(ctxs, nCtx, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n), g0);
+    std::vector<uint64_t>* a = &arr[(size_t)i * 5];
+    for (int k = 0; k < 3; k++) a[k].assign(GX_DEPTH_BOUND, 0);
+    for (int k = 3; k < 5; k++) a[k].assign(std::max<size_t>(n, 1), 0);
+    check(S, gx_depth_group(ctxs, nCtx, i, &hs[i], a[0].data(), a[1].data(), a[2].data(), a[3].data(), a[4].data(), n, nullptr), g0);
+  }
+  std::vector<gx_depth_metrics_t> m((size_t)nS);
+  for (int i = 0; i < nS; i++) check(S, gx_depth_metrics(&hs[i], &m[i]), g0);
+  if (o.depthFile) {
+    Out out = openWrite(o.depthFile, o.gzOut);
+    check(S, gx_format_depth(out.f, nS, hs.data()), g0);
+    closeOut(out);
+  }
+  if (o.depthMetricsFile) {
+    Out out = openWrite(o.depthMetricsFile, o.gzOut);
+    check(S, gx_format_depth_metrics(out.f, nS, hs.data()), g0);
+    closeOut(out);
+  }
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++)
+    fprintf(stderr, "  Depth, %s file #%d: mean %f, median %llu, %f%% of %llu bp covered\n", hs[i].is_ctrl ? "control" : "experimental", (int)hs[i].rep,
+            m[i].mean, (unsigned long long)m[i].median, 100.0 * m[i].covered_fraction, (unsigned long long)m[i].bases);
+}
+
 // --saturation FILE [--saturation-steps N] [--saturation-seed S] [--saturation-controls]: the run's kept intervals subsampled
 // on the device at N nested thresholds and the peaks called once more at each (gx_saturation), one row per point with what it
 // recovers of the run's own peaks; with -v each point on stderr, the smallest fraction that recovers 90 % of the run's peaks
@@ -2988,6 +3030,10 @@ void usage() {
           "                  (chromosome, start, end) keys: N, distinct, NRF, PBC1, PBC2, duplicate fraction, estimated library size and\n"
           "                  the expected distinct keys at 5 %% .. 100 %% of the depth, a TSV labelled t<rep> / c<rep>; the histogram\n"
           "                  file has the number of keys seen m times per sample and m\n"
+          "  --depth FILE [--depth-metrics FILE]   each sample's distribution of per-base depth over every base of the genome outside\n"
+          "                  the -E regions: a TSV labelled t<rep> / c<rep> with the bases at each whole depth and at that depth or\n"
+          "                  more; the metrics file (it may stand alone) has the bases, the share covered, mean, sd, min, quartiles,\n"
+          "                  p95, p99, max and the shares at 1x, 2x, 5x, 10x, 20x, 50x, 100x per sample\n"
           "  --saturation FILE [--saturation-steps N] [--saturation-seed S] [--saturation-controls]   the peaks called once more on\n"
           "                  N (10, at most 100) nested subsamples of the run's intervals, j / N of them for j = 1 .. N drawn with seed S\n"
           "                  (1): a TSV with one row per point -- fraction, threshold, intervals kept, peaks, peak bp, the run's peaks\n"
@@ -3037,6 +3083,8 @@ int main(int argc, char** argv) {
                                      {"saturation-steps", required_argument, nullptr, 1024},
                                      {"saturation-seed", required_argument, nullptr, 1025},
                                      {"saturation-controls", no_argument, nullptr, 1026},
+                                     {"depth", required_argument, nullptr, 1027},
+                                     {"depth-metrics", required_argument, nullptr, 1028},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -3107,6 +3155,8 @@ int main(int argc, char** argv) {
       case 1019: o.fingerprintMetricsFile = optarg; break;
       case 1021: o.complexityFile = optarg; break;
       case 1022: o.complexityHistFile = optarg; break;
+      case 1027: o.depthFile = optarg; break;
+      case 1028: o.depthMetricsFile = optarg; break;
       case 1023: o.saturationFile = optarg; break;
       case 1024: o.saturationSteps = getInt(optarg); o.saturationStepsOpt = true; break;
       case 1025: {
@@ -3155,6 +3205,9 @@ int main(int argc, char** argv) {
   // (the complexity counts the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.complexityFile && (o.peaksOnly || o.eventsOnly)) die("", "--complexity needs the intervals of this run (not with -P or --events-only)");
   if (o.complexityHistFile && !o.complexityFile) die("", "--complexity-hist needs --complexity FILE");
+  // (the distribution is taken from the pileups this run builds: none with -P or --events-only; -X is fine)
+  if ((o.depthFile || o.depthMetricsFile) && (o.peaksOnly || o.eventsOnly))
+    die("", "--depth and --depth-metrics need the pileups of this run (not with -P or --events-only)");
   // (the curve is made of this run's peaks and of the events the library keeps: none with -X, -P or --events-only)
   if (o.saturationFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly))
     die("", "--saturation needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
@@ -3314,6 +3367,8 @@ int main(int argc, char** argv) {
   sendChroms(S);
   if (o.coveragePrefix || o.correlationFile || o.fingerprintFile || o.spearmanFile)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
+  if (o.depthFile || o.depthMetricsFile)
+    for (gx_ctx* g : S.devs.ctx) check(S, gx_set_depth_hist(g, 1), g);
   ProfilePlan profilePlan;
   if (o.profileBed) {
     profilePlan = planProfile(S);
@@ -3446,6 +3501,7 @@ int main(int argc, char** argv) {
   if (o.spearmanFile) writeSpearman(S);
   if (o.fingerprintFile) writeFingerprint(S);
   if (o.complexityFile) writeComplexity(S);
+  if (o.depthFile || o.depthMetricsFile) writeDepth(S);
   if (o.saturationFile) writeSaturation(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {

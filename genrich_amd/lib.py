@@ -141,6 +141,36 @@ SAT_POINT_DTYPE = np.dtype([("threshold", "<u8"), ("n_total", "<u8"), ("n_kept",
                             ("genome_len", "<u8"), ("status", "<i4"), ("_pad", "<i4")])   # gx_sat_point
 
 
+GX_PATH_DEPTH = 33554432        # gx_path_info bit 25: k_depth_hist ran (gx_set_depth_hist)
+DEPTH_BOUND = 2048              # GX_DEPTH_BOUND: whole depths below it are counted per class, the others listed with their exact pileup
+DEPTH_GE = (1, 2, 5, 10, 20, 50, 100)
+DEPTH_METRICS_DTYPE = np.dtype([(k, "<u8") for k in ("bases", "excluded", "covered", "min_v", "max_v", "q25", "median", "q75", "p95", "p99")]
+                               + [(k, "<f8") for k in ("covered_fraction", "mean", "sd")] + [("ge", "<f8", (len(DEPTH_GE),))])   # gx_depth_metrics_t
+
+
+class DepthHist(C.Structure):
+    """gx_depth_hist: the scalars of one sample's depth distribution and pointers to its arrays."""
+    _fields_ = [("rep", C.c_int32), ("is_ctrl", C.c_int32), ("total", C.c_uint64), ("excluded", C.c_uint64), ("zero", C.c_uint64),
+                ("min_v", C.c_uint64), ("max_v", C.c_uint64), ("bases", C.c_void_p), ("rsum", C.c_void_p), ("rsq", C.c_void_p),
+                ("deep_v", C.c_void_p), ("deep_bases", C.c_void_p), ("n_deep", C.c_size_t)]
+
+
+class Depth(NamedTuple):
+    """One sample's depth distribution (gx_get_depth): bases / rsum / rsq uint64[DEPTH_BOUND] per whole depth, deep = [(v, bases)]
+    ascending with the exact pileup v (1/120 units) of the bases at DEPTH_BOUND or deeper."""
+    rep: int
+    is_ctrl: bool
+    total: int
+    excluded: int
+    zero: int
+    min_v: int
+    max_v: int
+    bases: np.ndarray
+    rsum: np.ndarray
+    rsq: np.ndarray
+    deep: list
+
+
 class Complexity(NamedTuple):
     """One sample's library complexity (gx_get_complexity): N observations, D distinct keys, pairs = [(m, h[m])] ascending."""
     n_obs: int
@@ -287,6 +317,16 @@ _SIGS = {
     "gx_format_complexity": [C.c_void_p, C.c_int] + [C.c_void_p] * 7,
     "gx_format_complexity_hist": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,
     "gx_write_complexity_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_set_depth_hist": [C.c_void_p, C.c_int],
+    "gx_depth_samples": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_depth": [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_depth_group": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_depth_geometry": [C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)],
+    "gx_depth_last": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "gx_depth_metrics": [C.c_void_p, C.c_void_p],
+    "gx_format_depth": [C.c_void_p, C.c_int, C.c_void_p],
+    "gx_format_depth_metrics": [C.c_void_p, C.c_int, C.c_void_p],
+    "gx_write_depth_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_subsample_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint, C.c_void_p, C.c_size_t,
                             C.POINTER(C.c_size_t)],
     "gx_subsample_kept": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
@@ -636,6 +676,80 @@ def complexity_text(ctxs, with_hist=True):
     except RuntimeError as e:
         raise RuntimeError(f"{e} [{'; '.join(lib.gx_last_error(c.ctx).decode() for c in ctxs)}]") from None
     return met, (hist[0] if hist else None)
+
+
+def depth_geometry():
+    """(bound, lanes, grid, list_capacity) of the depth pass as the library was built (gx_depth_geometry): the whole depth from which
+    a piece is listed, the lanes of a workgroup of k_depth_hist, its most workgroups, the deep list's first capacity."""
+    lib = load_library()
+    bound, lanes, grid, cap = C.c_uint32(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    lib.gx_depth_geometry(C.byref(bound), C.byref(lanes), C.byref(grid), C.byref(cap))
+    return bound.value, lanes.value, grid.value, cap.value
+
+
+def _depth_fetch(call, check):
+    """Both read-backs (gx_get_depth / gx_depth_group): the size of the deep list first, then everything."""
+    n = C.c_size_t(0)
+    check(call(None, None, None, None, None, None, 0, C.byref(n)))
+    h = DepthHist()
+    arr = [np.zeros(DEPTH_BOUND, dtype=np.uint64) for _ in range(3)] + [np.zeros(max(n.value, 1), dtype=np.uint64) for _ in range(2)]
+    check(call(C.addressof(h), *[a.ctypes.data for a in arr], n.value, C.byref(n)))
+    return Depth(h.rep, bool(h.is_ctrl), h.total, h.excluded, h.zero, h.min_v, h.max_v, arr[0], arr[1], arr[2],
+                 [(int(v), int(b)) for v, b in zip(arr[3][:n.value], arr[4][:n.value])])
+
+
+def _depth_structs(samples):
+    """samples: [Depth] -> a gx_depth_hist array (and what keeps its arrays alive)."""
+    hs = (DepthHist * max(len(samples), 1))()
+    keep = []
+    for h, d in zip(hs, samples):
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (d.bases, d.rsum, d.rsq, [p[0] for p in d.deep], [p[1] for p in d.deep])]
+        keep.append(arr)
+        h.rep, h.is_ctrl, h.total, h.excluded, h.zero, h.min_v, h.max_v = d.rep, int(bool(d.is_ctrl)), d.total, d.excluded, d.zero, d.min_v, d.max_v
+        h.bases, h.rsum, h.rsq = (a.ctypes.data for a in arr[:3])
+        h.deep_v, h.deep_bases = (a.ctypes.data if a.size else None for a in arr[3:])
+        h.n_deep = len(d.deep)
+    return hs, keep
+
+
+def depth_metrics(sample):
+    """gx_depth_metrics of one Depth as one DEPTH_METRICS_DTYPE record; host-only, needs no GPU."""
+    lib = load_library()
+    hs, keep = _depth_structs([sample])
+    out = np.zeros(1, dtype=DEPTH_METRICS_DTYPE)
+    rc = lib.gx_depth_metrics(C.addressof(hs), out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_depth_metrics: {rc}")
+    return out[0]
+
+
+def format_depth(samples) -> bytes:
+    """--depth's table (gx_format_depth); samples: [Depth]; host-only, needs no GPU."""
+    lib = load_library()
+    hs, keep = _depth_structs(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_depth(f, len(samples), C.addressof(hs)))
+
+
+def format_depth_metrics(samples) -> bytes:
+    """--depth-metrics' table (gx_format_depth_metrics); samples: [Depth]; host-only, needs no GPU."""
+    lib = load_library()
+    hs, keep = _depth_structs(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_depth_metrics(f, len(samples), C.addressof(hs)))
+
+
+def depth_group(ctxs, sample):
+    """Depth of one sample added over the contexts of a run (gx_depth_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _depth_fetch(lambda *a: lib.gx_depth_group(arr, len(ctxs), int(sample), *a), ctxs[0]._check)
+
+
+def depth_text(ctxs):
+    """(--depth's table, --depth-metrics') over the contexts of a run (gx_write_depth_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return (_to_tmpfile(lambda f: lib.gx_write_depth_group(arr, len(ctxs), f, None)),
+            _to_tmpfile(lambda f: lib.gx_write_depth_group(arr, len(ctxs), None, f)))
 
 
 def subsample_draw(seed, sample, index):
@@ -988,7 +1102,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -1076,6 +1190,26 @@ class Genrich:
     def write_coverage(self, sample, names, path, scale=1.0):
         """--coverage's bedGraph (gx_write_coverage) of one sample of this context."""
         self._check(self.lib.gx_write_coverage_path(self.ctx, int(sample), self._names(names), len(names), float(scale), path.encode()))
+
+    # -- depth distribution of the samples' pileups (include/genrich_amd.h, gx_set_depth_hist) -------------------------------
+    def set_depth_hist(self, on=True):
+        """Take the per-base depth distribution of every closed sample's pileup; only while idle, after set_chroms."""
+        self._check(self.lib.gx_set_depth_hist(self.ctx, int(bool(on))))
+
+    def depth_samples(self):
+        n = C.c_int(0)
+        self._check(self.lib.gx_depth_samples(self.ctx, C.byref(n)))
+        return n.value
+
+    def depth(self, sample):
+        """Depth of one closed sample of this context (gx_get_depth)."""
+        return _depth_fetch(lambda *a: self.lib.gx_get_depth(self.ctx, int(sample), *a), self._check)
+
+    def depth_last(self):
+        """(list capacity, reruns) of the last depth pass of this context (gx_depth_last)."""
+        c, r = C.c_size_t(0), C.c_int(0)
+        self._check(self.lib.gx_depth_last(self.ctx, C.byref(c), C.byref(r)))
+        return c.value, r.value
 
     # -- correlation of the samples' bins (include/genrich_amd.h, gx_coverage_gram) --------------------------------------
     def coverage_gram(self):

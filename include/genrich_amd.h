@@ -20,6 +20,7 @@
  *   (counting on: gx_count_in_peaks -> gx_get_peak_counts / gx_write_counts)
  *   (coverage on, any time after a gx_sample_end: gx_get_coverage / gx_write_coverage)
  *   (profile on, any time after a gx_sample_end: gx_get_profile / gx_write_profile_group)
+ *   (depth on, any time after a gx_sample_end: gx_get_depth / gx_write_depth_group)
  *   (coverage on, between samples or after them: gx_coverage_gram / gx_write_correlation_group)
  *   (coverage on, between samples or after them: gx_coverage_fingerprint / gx_write_fingerprint_group)
  *   gx_destroy
@@ -523,6 +524,53 @@ int gx_complexity_last(gx_ctx* ctx, size_t* capacity);
 int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct,
                         uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes);
 
+/* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
+ *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
+ * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
+ * a chromosome COUNTS iff it has coverage bins (not -e skipped, owned, length > 0); one the replicate's treatment header does
+ * not list (save mask 0) has pileup 0 everywhere.  total = the lengths of the counting chromosomes, added; excluded = the size
+ * of the union of each counting chromosome's -E regions clipped to [0, len) (they may overlap, nest, lie past the end);
+ * B = total - excluded.  Every non-excluded base has a pileup v >= 0 in 1/120 units, exactly what gx_get_coverage integrates;
+ * its whole depth is d = v div 120, its remainder r = v mod 120 (non-zero only with -s weights).  With GX_DEPTH_BOUND = 2048,
+ * over the bases with v > 0, all exact uint64:
+ *     d < GX_DEPTH_BOUND:   bases[d]    rsum[d] = sum of r    rsq[d] = sum of r^2        (class 0 holds only 0 < v < 120)
+ *     d >= GX_DEPTH_BOUND:  the deep list, pairs (v, bases) with the exact v, sorted by v, one entry per distinct v
+ *     min_v / max_v:        the smallest and the largest v > 0 met (0: no covered base)
+ * covered = the bases with v > 0; zero = B - covered, taken by complement on the host (covered > B: GX_ERR_ARR, a lost or
+ * doubled contribution, not a result).  The result is the same for every launch geometry, list capacity, push mode, tile-stage
+ * path and number of contexts, whose results add (gx_depth_group: min_v / max_v combine, the deep lists merge): integers only.
+ *
+ * gx_set_depth_hist: on = 0: off (default).  Only while idle (after gx_create / gx_reset, before the first gx_sample_begin of a
+ *   run) and after gx_set_chroms, else GX_ERR_ORDER.  Survives gx_reset; gx_saturation's child context does not inherit it.
+ *   Independent of gx_set_coverage_bins and gx_set_count_in_peaks.  On, every gx_sample_end runs one more pass (k_depth_hist:
+ *   gx_depth.h) over the pileup it has just closed and keeps the integers on the host until gx_reset.  When the deep list runs
+ *   full the pass is run once more with a list of the counted size, while the pileup is still in place.
+ * gx_depth_samples: samples closed with the switch on since the last gx_reset.
+ * gx_get_depth: one sample (0 .. n_samples-1; no sample open, else GX_ERR_ORDER): *out's scalars; bases, rsum, rsq:
+ *   GX_DEPTH_BOUND entries each; min(cap, *n_deep) pairs in deep_v[] / deep_bases[].  Any pointer may be NULL (the deep arrays
+ *   when cap is 0); out's pointers are set to the arrays the caller passed, so that *out can go to the formatters as it is.
+ * gx_depth_group: the same for sample `sample` of every context, added.  Contexts that differ in their samples: GX_ERR_ORDER.
+ * gx_depth_geometry: what the edge cases depend on: the bound from which a piece is listed, the lanes of a workgroup, the most
+ *   workgroups unless GX_DEPTH_GRID says otherwise, the list's first capacity.  Any pointer may be NULL.
+ * gx_depth_last: the list capacity the last pass of this context ended with and how often it ran again (0 or 1). */
+#define GX_DEPTH_BOUND 2048
+typedef struct {
+  int32_t rep, is_ctrl;
+  uint64_t total, excluded, zero;
+  uint64_t min_v, max_v;
+  const uint64_t *bases, *rsum, *rsq;   /* [GX_DEPTH_BOUND] each */
+  const uint64_t *deep_v, *deep_bases;  /* [n_deep] */
+  size_t n_deep;
+} gx_depth_hist;
+int gx_set_depth_hist(gx_ctx* ctx, int on);
+int gx_depth_samples(gx_ctx* ctx, int* n_samples);
+int gx_get_depth(gx_ctx* ctx, int sample, gx_depth_hist* out, uint64_t* bases, uint64_t* rsum, uint64_t* rsq, uint64_t* deep_v,
+                 uint64_t* deep_bases, size_t cap, size_t* n_deep);
+int gx_depth_group(gx_ctx* const* ctxs, int n_ctx, int sample, gx_depth_hist* out, uint64_t* bases, uint64_t* rsum, uint64_t* rsq,
+                   uint64_t* deep_v, uint64_t* deep_bases, size_t cap, size_t* n_deep);
+int gx_depth_geometry(uint32_t* bound, int* lanes, int* grid, size_t* list_capacity);
+int gx_depth_last(gx_ctx* ctx, size_t* list_capacity, int* reruns);
+
 /* ---- peak saturation: the peaks called once more on nested subsamples of the run's own intervals (no Genrich counterpart:
  *      what a loop over `samtools view -s` and the caller answers -- would more reads have found more peaks?) ----
  * A sample = every gx_sample_end of the run in call order, as for gx_count_in_peaks; sample k's events are taken in their kept
@@ -757,6 +805,36 @@ int gx_format_complexity(FILE* out, int n_samples, const int* rep, const int* is
 int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* mult,
                               const uint64_t* const* keys, const size_t* n_pairs);
 int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist);
+/* --depth / --depth-metrics (no Genrich counterpart).  The first three: host only, no context.  A histogram that contradicts
+ * itself (a missing array, excluded > total, covered + zero != B, rsum[d] > 119 bases[d], a deep list that is not strictly
+ * ascending from 120 GX_DEPTH_BOUND, covered bases without min_v <= max_v): GX_ERR_ORDER, nothing written.
+ * gx_depth_metrics: from the integers, every sum an exact big integer before anything becomes a double:
+ *     sum v   = sum_d (120 d bases[d] + rsum[d]) + sum_deep v bases
+ *     sum v^2 = sum_d (14400 d^2 bases[d] + 240 d rsum[d] + rsq[d]) + sum_deep v^2 bases
+ *   bases = B, covered, covered_fraction = covered / B, mean = sum v / (120 B), sd = sqrt(B sum v^2 - (sum v)^2) / (120 B)
+ *   (population; mean and sd NaN when B = 0, every fraction 0 then); min_v / max_v: the exact smallest and largest pileup over
+ *   the B bases in 1/120 units (min_v 0 when a base is at 0); q25 .. p99: the smallest whole depth d with
+ *   100 #(bases of depth <= d) >= q B, in integers; ge[k]: the fraction of B at whole depth >= 1, 2, 5, 10, 20, 50, 100.
+ * gx_format_depth: a TSV, header "#sample depth bases bases_at_least fraction_at_least", per sample (labelled t<rep> / c<rep>)
+ *   one row per non-empty whole depth, ascending; the depth-0 row is always there and includes the bases at pileup 0; deep
+ *   entries are grouped by v div 120; fraction_at_least is %.6f of B, 0.000000 when B = 0.
+ * gx_format_depth_metrics: header "sample bases excluded covered covered_fraction mean sd min q25 median q75 p95 p99 max ge1 ge2
+ *   ge5 ge10 ge20 ge50 ge100", one row per sample; fractions, mean and sd as %.6f (NA when not defined), min and max as --coverage
+ *   prints a value (an integer when v divides by 120, else %.4f).
+ * gx_write_depth_group (gx_api.hip: it reads contexts): gx_depth_group per sample, then the distribution to `depth` and the
+ *   figures to `metrics`; either may be NULL, not both. */
+#define GX_DEPTH_NGE 7
+typedef struct {
+  uint64_t bases, excluded, covered;
+  uint64_t min_v, max_v;
+  uint64_t q25, median, q75, p95, p99;
+  double covered_fraction, mean, sd;
+  double ge[GX_DEPTH_NGE];
+} gx_depth_metrics_t;
+int gx_depth_metrics(const gx_depth_hist* hist, gx_depth_metrics_t* out);
+int gx_format_depth(FILE* out, int n_samples, const gx_depth_hist* hist);
+int gx_format_depth_metrics(FILE* out, int n_samples, const gx_depth_hist* hist);
+int gx_write_depth_group(gx_ctx* const* ctxs, int n_ctx, FILE* depth, FILE* metrics);
 /* --saturation (no Genrich counterpart).  The first two: host only, no context.
  * gx_saturation_overlap: two peak lists in gx_get_peaks order (by chromosome, then start; no overlaps inside a list), in one
  *   merge walk, with gx_count_in_peaks' predicate (s < pe && ps < e on one chromosome): *full_recovered = the peaks of `full`
@@ -868,6 +946,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_SPEARMAN 4194304u /* bit 22: k_rank ran since the last gx_reset (gx_coverage_rank_gram, gx_rank_u64) */
 #define GX_PATH_COMPLEXITY 8388608u /* bit 23: k_cpx_insert ran since the last gx_reset (gx_complexity, gx_complexity_events) */
 #define GX_PATH_SATURATION 16777216u /* bit 24: k_sub_write ran since the last gx_reset (gx_subsample_events, gx_subsample_kept, gx_saturation) */
+#define GX_PATH_DEPTH 33554432u /* bit 25: k_depth_hist ran since the last gx_reset (gx_set_depth_hist; a sample was closed with it on) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
