@@ -3,7 +3,10 @@ a table (gx_host_build.h SBT_INSTANCES), and a launch looks its instance up ther
 only when a sample asks for it.  The first launch's instances and the second launch over the first one's list run in
   test_hip_sbt_persistent.py: test_a_workgroup_runs_many_bins_in_a_row, test_a_bin_that_leaves_for_the_second_launch_between_ordinary_bins,
       test_fractional_pair_records_with_one_persistent_workgroup, test_excluded_regions_with_one_persistent_workgroup,
-  test_hip_paths.py: test_excluded_regions_on_the_fused_tile_stage_and_on_the_general_chain, the GX_NO_PAIRS cases.
+  test_hip_paths.py: test_excluded_regions_on_the_fused_tile_stage_and_on_the_general_chain, the GX_NO_PAIRS cases,
+  test_hip_tile_limits.py: constructed tiles at sbt_tile's and sbt_heavy's per-tile limits in the pair instance, the start / end
+      key instance, the fractional one, the -E one (ordinary tiles), with one persistent workgroup, and -- four cases -- in the dense
+      launch's two instances (test_tile_stage_in_the_dense_launch).
 What is left is the DENSE launch -- a sample whose average bin holds more keys than the key array: one launch takes every bin
 by rounds -- for plain data, -E regions and fractional pair records, each in the instance with the large scratch (TR = 448)
 and the small one (TR = 384; GX_SBT_TR chooses, as the measurements do).
