@@ -207,6 +207,90 @@ __device__ __forceinline__ u32 sbt_class_of(int w) {  // weight (> 0) -> class; 
   return c;
 }
 
+// What one tile's steps hand on to each other -- the running pileup, the intervals written, the last end -- with a step's
+// emit and the tile's epilogue: sbt_tile's and, side by side for two tiles, sbt_tile_x2's.
+template <bool FRAC>
+struct SbtRun {
+  const u32 pos0, negPos0, slot;   // (pos0 + p != 0  <=>  p != -pos0)
+  const int vsig;
+  int runBase;
+  u32 outCount = 0, lastEnd = 0;
+  u64 negM = 0, bigM;
+  __device__ __forceinline__ SbtRun(u32 pos0_, int carry, u32 slot_, int vsig_)
+      : pos0(pos0_), negPos0(0u - pos0_), slot(slot_), vsig(vsig_), runBase(carry), bigM(carry >= FRAG_FAST_MAXV ? ~0ull : 0ull) {}
+  // one step's 64 touched bases: p their offsets, d120 their differences, incS the inclusive scan of the differences
+  __device__ __forceinline__ void emit(const int lane, const SbtOut& out, bool fragTerms, long long& fhi, long long& flo, const u32 p, const int d120,
+                                       const int incS) {
+    const int after = runBase + incS;
+    const int before = after - d120;                          // the pileup of the interval that ends here (2244)
+    // nz = d120 != 0 && pos0 + p != 0 (2241: base 0 closes nothing), as a lane mask made of the compares'
+    // own scalar results: __ballot() of a composite condition sends it through a VGPR and back (two more VALU
+    // instructions per ballot, four ballots per step)
+    const u64 mask = __builtin_amdgcn_uicmp((u32)d120, 0u, 33 /* ne */) & __builtin_amdgcn_uicmp(p, negPos0, 33);
+    const bool nz = __builtin_amdgcn_inverse_ballot_w64(mask);
+    const u32 orank = __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
+    if (nz) {
+      const u32 o = slot + outCount + orank;
+      st_u32(out.to.looseEnd, o, pos0 + p);
+      st_u32(out.to.looseV, o, (u32)before);
+    }
+    if (vsig != 0x7FFFFFFF)  // wave-uniform
+      sig_flush_m(out.to.sigMask, slot + outCount, mask & __builtin_amdgcn_sicmp(before, vsig, 39 /* sge */), orank, mask);
+    // (a pileup below zero or at the table's end: one unsigned compare finds either, the rare step that has one says which)
+    if (__builtin_amdgcn_uicmp((u32)after, (u32)FRAG_FAST_MAXV, 35 /* uge */)) {  // wave-uniform
+      negM |= __ballot(after < 0);
+      bigM |= __ballot(after >= FRAG_FAST_MAXV);
+    }
+    runBase += __builtin_amdgcn_readlane(incS, 63);
+    if (FRAC && fragTerms && mask) {  // wave-uniform
+      // the interval that ends here starts at the end before it: the lane's, the steps', or -- the tile's first
+      // interval -- somewhere before the tile (k_scan_iv adds that one: it knows where)
+      const u64 below = mask & ((1ull << lane) - 1ull);
+      const int prevLane = below ? 63 - __builtin_clzll(below) : 0;
+      const u32 pp = (u32)__shfl((int)p, prevLane, 64);
+      if (nz && (below || outCount)) frag_term(pos0 + p - (below ? pos0 + pp : lastEnd), before, fhi, flo);
+    }
+    if (mask) {  // wave-uniform
+      outCount += (u32)__popcll(mask);
+      lastEnd = pos0 + (u32)__builtin_amdgcn_readlane((int)p, 63 - __builtin_clzll(mask));
+    }
+  }
+  // an active tile's epilogue: the closing interval of a chromosome's last tile, the tile's count and last end, what it reports, its
+  // unused slots (n: the tile's keys)
+  __device__ __forceinline__ void finish(const int lane, const SbtOut& out, u32 t, u32 n, u32 len, bool lastTile, u32& bad, bool fragTerms,
+                                         long long& fhi, long long& flo) {
+    const u32 total = outCount + (lastTile ? 1u : 0u);
+    if (lane == 0) {
+      if (lastTile) {  // closing interval [.., len): 2268-2273
+        const u32 o = slot + outCount;
+        out.to.looseEnd[o] = len;
+        out.to.looseV[o] = runBase;
+        if (runBase >= vsig) atomicOr((unsigned long long*)&out.to.sigMask[o >> 6], 1ull << (o & 63));
+        if (FRAC && fragTerms && outCount) frag_term(len - lastEnd, runBase, fhi, flo);  // (the tile's first interval: k_scan_iv)
+        lastEnd = len;
+      }
+      if (total) out.to.tileLastEnd[t] = lastEnd;
+    }
+    lastEnd = (u32)__builtin_amdgcn_readfirstlane((int)lastEnd);
+    if (negM) bad |= ST_NEG_PILE;
+    if (bigM && lane == 0) {  // rare
+      atomicOr(&out.to.tileDeep[t], 1u);
+      if (out.to.ctl) atomicOr(&out.to.ctl->bad, 1u);  // a pileup beyond (or close to the end of) the table p(V)
+    }
+    if (lane == 0) out.to.tileCount[t] = total;
+    // the unused slots of the tile: zero-length intervals behind its last one (a tile without intervals does not
+    // know where the previous one ended: k_scan_iv fills its slots)
+    // (round 6: also when the sweep's bits come later -- a sample whose lambda is not known yet, LooseCtl handed over all the same)
+    if (total && (vsig != 0x7FFFFFFF || out.to.ctl)) {  // wave-uniform
+      const u32 size = n + 1;
+      for (u32 j = total + lane; j < size; j += 64) {
+        st_u32(out.to.looseEnd, slot + j, lastEnd);
+        st_u32(out.to.looseV, slot + j, 0u);
+      }
+    }
+  }
+};
+
 // (lane: the caller's lane_id() -- a persistent workgroup hands it over afresh for every bin, so that what the passes derive from it
 // lives as long as a bin's tile loop and not as long as the kernel)
 template <bool FRAC, bool BED>
@@ -236,8 +320,6 @@ __device__ __forceinline__ void sbt_tile(const int lane, int* lds, const u32 TR_
     if (lane == 0) out.to.tileCount[t] = 0;
     return;
   }
-  constexpr bool active = true;
-  const u32 negPos0 = 0u - pos0;   // (pos0 + p != 0  <=>  p != -pos0)
   const bool lastTile = (flags & TM_LAST) != 0;
 #ifndef GX_SBT_KR
 #define GX_SBT_KR 2
@@ -270,9 +352,7 @@ __device__ __forceinline__ void sbt_tile(const int lane, int* lds, const u32 TR_
   const u32 T = (u32)__builtin_amdgcn_readlane(incC, 63);
   pre[lane] = exc | ((exc + (u32)c0) << 16);
   wave_lds_sync();
-  int runBase = carry;
-  u32 outCount = 0, lastEnd = 0;
-  u64 negM = 0, bigM = carry >= FRAG_FAST_MAXV ? ~0ull : 0ull;
+  SbtRun<FRAC> run(pos0, carry, slot, vsig);
   auto rankOf = [&](u32 key) -> u32 {
     const u32 off = offOf(key), wi = off >> 5;
     return (u32)pre16[wi] + (u32)__popc(occ[wi] & ((1u << (off & 31)) - 1u));
@@ -303,85 +383,120 @@ __device__ __forceinline__ void sbt_tile(const int lane, int* lds, const u32 TR_
       p = list[j];
       d120 = __hip_atomic_exchange(&cnt[j], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // read and clear
     };
-    // one step's 64 touched bases: p their offsets, d120 their differences, incS the inclusive scan of the differences
-    auto emit = [&](const u32 p, const int d120, const int incS) {
-      const int after = runBase + incS;
-      const int before = after - d120;                          // the pileup of the interval that ends here (2244)
-      // nz = d120 != 0 && pos0 + p != 0 (2241: base 0 closes nothing), as a lane mask made of the compares'
-      // own scalar results: __ballot() of a composite condition sends it through a VGPR and back (two more VALU
-      // instructions per ballot, four ballots per step)
-      const u64 mask = __builtin_amdgcn_uicmp((u32)d120, 0u, 33 /* ne */) & __builtin_amdgcn_uicmp(p, negPos0, 33);
-      const bool nz = __builtin_amdgcn_inverse_ballot_w64(mask);
-      const u32 orank = __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
-      if (nz) {
-        const u32 o = slot + outCount + orank;
-        st_u32(out.to.looseEnd, o, pos0 + p);
-        st_u32(out.to.looseV, o, (u32)before);
-      }
-      if (vsig != 0x7FFFFFFF)  // wave-uniform
-        sig_flush_m(out.to.sigMask, slot + outCount, mask & __builtin_amdgcn_sicmp(before, vsig, 39 /* sge */), orank, mask);
-      // (a pileup below zero or at the table's end: one unsigned compare finds either, the rare step that has one says which)
-      if (__builtin_amdgcn_uicmp((u32)after, (u32)FRAG_FAST_MAXV, 35 /* uge */)) {  // wave-uniform
-        negM |= __ballot(after < 0);
-        bigM |= __ballot(after >= FRAG_FAST_MAXV);
-      }
-      runBase += __builtin_amdgcn_readlane(incS, 63);
-      if (FRAC && fragTerms && mask) {  // wave-uniform
-        // the interval that ends here starts at the end before it: the lane's, the steps', or -- the tile's first
-        // interval -- somewhere before the tile (k_scan_iv adds that one: it knows where)
-        const u64 below = mask & ((1ull << lane) - 1ull);
-        const int prevLane = below ? 63 - __builtin_clzll(below) : 0;
-        const u32 pp = (u32)__shfl((int)p, prevLane, 64);
-        if (nz && (below || outCount)) frag_term(pos0 + p - (below ? pos0 + pp : lastEnd), before, fhi, flo);
-      }
-      if (mask) {  // wave-uniform
-        outCount += (u32)__popcll(mask);
-        lastEnd = pos0 + (u32)__builtin_amdgcn_readlane((int)p, 63 - __builtin_clzll(mask));
-      }
-    };
     for (u32 j0 = 0; j0 < nL; j0 += 64) {
       u32 p;
       int d120;
       loadEl(j0 + lane, p, d120);
-      emit(p, d120, dpp_scan_add(d120));
+      run.emit(lane, out, fragTerms, fhi, flo, p, d120, dpp_scan_add(d120));
     }
   }
   {
     const u32 z = sbt_zero();
     *reinterpret_cast<uint2*>(occ + 2 * lane) = make_uint2(z, z);
   }
-  u32 total = 0;
-  if (active) {  // wave-uniform
-    total = outCount + (lastTile ? 1u : 0u);
-    if (lane == 0) {
-      if (lastTile) {  // closing interval [.., len): 2268-2273
-        const u32 o = slot + outCount;
-        out.to.looseEnd[o] = len;
-        out.to.looseV[o] = runBase;
-        if (runBase >= vsig) atomicOr((unsigned long long*)&out.to.sigMask[o >> 6], 1ull << (o & 63));
-        if (FRAC && fragTerms && outCount) frag_term(len - lastEnd, runBase, fhi, flo);  // (the tile's first interval: k_scan_iv)
-        lastEnd = len;
-      }
-      if (total) out.to.tileLastEnd[t] = lastEnd;
-    }
-    lastEnd = (u32)__builtin_amdgcn_readfirstlane((int)lastEnd);
-    if (negM) bad |= ST_NEG_PILE;
-    if (bigM && lane == 0) {  // rare
-      atomicOr(&out.to.tileDeep[t], 1u);
-      if (out.to.ctl) atomicOr(&out.to.ctl->bad, 1u);  // a pileup beyond (or close to the end of) the table p(V)
-    }
+  run.finish(lane, out, t, n, len, lastTile, bad, fragTerms, fhi, flo);
+  wave_lds_sync();
+}
+
+// TWO ordinary tiles, one wavefront (round 18): the passes of sbt_tile for the adjacent tiles A = t and B = t + 1, written side
+// by side.  A wavefront's stream through one tile is a chain of dependent LDS round trips and DPP scans -- about half its cycles
+// wait --, and the CU's LDS allows no fifth wavefront per SIMD; two tiles are two independent chains in one stream, so each
+// round trip and each scan's latency is paid once per two tiles.  The tiles stay two tiles: their own bitmaps, ranks, steps,
+// outputs; only the program order interleaves them.  Both are active and hold at most GX_SBT_KR * 64 keys (sbt_bin pairs them
+// so), hence: every key in a register, one round, at most two steps, no loop over the LDS list.
+// GX_SBT_X2=0 (tools/build_variant.sh) builds the kernel without the pair path: the A/B.
+#ifndef GX_SBT_X2
+#define GX_SBT_X2 1
+#endif
+constexpr u32 SBT_X2_KEYS = GX_SBT_KR * 64;            // a paired tile's keys, hence its touched bases, at most
+// A's scratch is sbt_tile's own, B's lies where sbt_tile keeps the counters and offsets of ranks that a paired tile does not
+// have.  What must be zero on entry (bitmap, counters) lies in sbt_tile's counters -- zero between tiles, and zero again when the
+// pair is through (the counters by the exchange, the bitmap by the closing store); what is written before it is read (the offsets,
+// B's prefix counts) lies in sbt_tile's offsets.  B's dummy prefix entry is nobody's between tiles: the pair writes it.
+constexpr int SBT_X2_CNT = SBT_OCCW + SBT_PREW;                            // both: sbt_tile's counters begin here
+constexpr int SBT_X2_OCC_B = SBT_X2_CNT + (int)SBT_X2_KEYS;                // B's bitmap, behind A's counters
+constexpr int SBT_X2_CNT_B = SBT_X2_OCC_B + SBT_OCCW;                      // B's counters
+constexpr int SBT_X2_LIST = SBT_X2_CNT + SBT_TR;                           // A's offsets: sbt_tile's own
+constexpr int SBT_X2_LIST_B = SBT_X2_LIST + (int)SBT_X2_KEYS / 2;          // B's offsets
+constexpr int SBT_X2_PRE_B = SBT_X2_LIST_B + (int)SBT_X2_KEYS / 2;         // B's prefix counts
+constexpr bool SBT_X2_FITS = SBT_X2_CNT_B + (int)SBT_X2_KEYS <= SBT_X2_LIST && SBT_X2_PRE_B + SBT_PREW <= (int)sbt_tw(SBT_TR);
+static_assert(SBT_TR != 448 || GX_SBT_KR != 2 || SBT_X2_FITS, "the pair layout fits a wavefront's scratch: sbt_tw(SBT_TR)");
+static_assert(SBT_X2_OCC_B % 2 == 0, "a lane reads its two bitmap words as one 8-byte word");
+
+__device__ __forceinline__ void sbt_tile_x2(const int lane, int* lds, const uint16_t* __restrict__ klA, const u32 nA, const u32 nB, const u32 t,
+                                            const uint4 tfA, const uint4 tfB, const u32 slotA, const int vsig, const SbtOut& out, u32& bad) {
+  constexpr int KR = GX_SBT_KR;
+  u32* occA = reinterpret_cast<u32*>(lds);
+  u32* occB = reinterpret_cast<u32*>(lds + SBT_X2_OCC_B);
+  u32* preA = reinterpret_cast<u32*>(lds + SBT_OCCW);
+  u32* preB = reinterpret_cast<u32*>(lds + SBT_X2_PRE_B);
+  int* cntA = lds + SBT_X2_CNT;
+  int* cntB = lds + SBT_X2_CNT_B;
+  uint16_t* listA = reinterpret_cast<uint16_t*>(lds + SBT_X2_LIST);
+  uint16_t* listB = reinterpret_cast<uint16_t*>(lds + SBT_X2_LIST_B);
+  const uint16_t* __restrict__ klB = klA + nA;   // (adjacent tiles: adjacent lists)
+  u32 ka[KR], kb[KR];
+#pragma unroll
+  for (int q = 0; q < KR; q++) {
+    const u32 va = klA[lane + q * 64], vb = klB[lane + q * 64];  // (in bounds: the key array has 192 entries of slack)
+    ka[q] = (u32)lane + q * 64 < nA ? va : SBT_NOKEY;
+    kb[q] = (u32)lane + q * 64 < nB ? vb : SBT_NOKEY;
   }
-  if (lane == 0) out.to.tileCount[t] = total;
-  // the unused slots of the tile: zero-length intervals behind its last one (a tile without intervals does not
-  // know where the previous one ended: k_scan_iv fills its slots)
-  // (round 6: also when the sweep's bits come later -- a sample whose lambda is not known yet, LooseCtl handed over all the same)
-  if (total && (vsig != 0x7FFFFFFF || out.to.ctl)) {  // wave-uniform
-    const u32 size = n + 1;
-    for (u32 j = total + lane; j < size; j += 64) {
-      st_u32(out.to.looseEnd, slot + j, lastEnd);
-      st_u32(out.to.looseV, slot + j, 0u);
-    }
+  if (lane == 0) preB[TILE / 64] = ~0u;   // B's dummy prefix entry: its lanes without a key rank outside the tile, as A's do
+  // ---- A1: keys -> occupancy bitmaps (predicated, as sbt_tile's)
+  auto mark = [](u32* occ, u32 key) { const u32 off = key & (2 * TILE - 1); atomicOr(&occ[off >> 5], 1u << (off & 31)); };
+#pragma unroll
+  for (int q = 0; q < KR; q++) {
+    if (ka[q] != SBT_NOKEY) mark(occA, ka[q]);
+    if (kb[q] != SBT_NOKEY) mark(occB, kb[q]);
   }
+  wave_lds_sync();
+  // ---- B: touched bases before each bitmap word
+  const uint2 wa = *reinterpret_cast<const uint2*>(occA + 2 * lane), wb = *reinterpret_cast<const uint2*>(occB + 2 * lane);
+  const int ca0 = __popc(wa.x), ca = ca0 + __popc(wa.y), cb0 = __popc(wb.x), cb = cb0 + __popc(wb.y);
+  const int incA = dpp_scan_add(ca), incB = dpp_scan_add(cb);
+  const u32 excA = (u32)(incA - ca), excB = (u32)(incB - cb);
+  const u32 TA = (u32)__builtin_amdgcn_readlane(incA, 63), TB = (u32)__builtin_amdgcn_readlane(incB, 63);
+  preA[lane] = excA | ((excA + (u32)ca0) << 16);
+  preB[lane] = excB | ((excB + (u32)cb0) << 16);
+  wave_lds_sync();
+  // ---- A2: keys -> cnt[rank], list[rank] (one round: a rank is below SBT_X2_KEYS, or the dummy entry's)
+  auto put = [](const u32* occ, const u32* pre, int* cnt, uint16_t* list, u32 key) {
+    const u32 off = key & (2 * TILE - 1), wi = off >> 5;
+    const u32 r = (u32)reinterpret_cast<const uint16_t*>(pre)[wi] + (u32)__popc(occ[wi] & ((1u << (off & 31)) - 1u));
+    if (r < SBT_X2_KEYS) {
+      list[r] = (uint16_t)(key & (TILE - 1));
+      atomicAdd(&cnt[r], (key & 0x8000u) ? -GX_UNIT : GX_UNIT);
+    }
+  };
+#pragma unroll
+  for (int q = 0; q < KR; q++) {
+    put(occA, preA, cntA, listA, ka[q]);
+    put(occB, preB, cntB, listB, kb[q]);
+  }
+  wave_lds_sync();
+  // ---- C: the steps, A's and B's together.  A tile's step behind its last touched base reads zero counters: it emits nothing and
+  // reports what the lanes behind the last touched base of the step before report -- so the second step runs for both tiles when
+  // either has one, and the first one always (a tile without keys, T = 0, among them).
+  SbtRun<false> runA(tfA.x, (int)tfA.w, slotA, vsig), runB(tfB.x, (int)tfB.w, slotA + nA + 1u, vsig);
+  long long f0 = 0, f1 = 0;   // (fragLen's terms: fractional weights only)
+  auto step = [&](u32 j) {
+    const u32 pA = listA[j], pB = listB[j];
+    const int dA = __hip_atomic_exchange(&cntA[j], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // read and clear
+    const int dB = __hip_atomic_exchange(&cntB[j], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    const int sA = dpp_scan_add(dA), sB = dpp_scan_add(dB);
+    runA.emit(lane, out, false, f0, f1, pA, dA, sA);
+    runB.emit(lane, out, false, f0, f1, pB, dB, sB);
+  };
+  step((u32)lane);
+  if (max(TA, TB) > 64u) step(64u + (u32)lane);  // wave-uniform
+  {
+    const u32 z = sbt_zero();
+    *reinterpret_cast<uint2*>(occA + 2 * lane) = make_uint2(z, z);
+    *reinterpret_cast<uint2*>(occB + 2 * lane) = make_uint2(z, z);
+  }
+  runA.finish(lane, out, t, nA, tfA.y, (tfA.z & TM_LAST) != 0, bad, false, f0, f1);
+  runB.finish(lane, out, t + 1u, nB, tfB.y, (tfB.z & TM_LAST) != 0, bad, false, f0, f1);
   wave_lds_sync();
 }
 
@@ -566,6 +681,8 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
   constexpr u32 NSLOTS = (u32)KX * SBT_NW;
   constexpr bool OVERLAP = !BIG && GX_SBT_PREFETCH != 0;  // the next bin's prologue under this bin
   constexpr bool PF = PAIRS && OVERLAP;                   // ... down to its records, in registers of their own
+  // two ordinary tiles per wavefront (sbt_tile_x2): the plain first launch only
+  constexpr bool X2 = GX_SBT_X2 != 0 && SBT_X2_FITS && PAIRS && !BIG && !FRAC && !BED && TRC == SBT_TR;
   int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
   // how the LDS behind the tables is split: constants of the instance (runtime values cost the rounds launch 12 %: measured)
   static_assert(TRC % 64 == 0 && TRC >= 192 && TRC <= 448, "touched bases per round");
@@ -1036,11 +1153,22 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
     // the order in which the wavefronts draw the tiles (round 6): the ones with a peak -- one in twelve, several times an ordinary
     // tile's keys -- first, so that none of them is the last thing a wavefront starts while the others have run out of work
     // (tile stage 0.572 -> 0.556 ms at config 2).  L.heavy / L.nHeavy / L.nRounds are the second launch's: free here.
-    if (tid < (int)nT && !ovf) {
-      const u32 hA = L.hist[tid];
-      const u32 nk = (hA & 0xFFFFu) + (hA >> 16);
+    // Round 18: the array holds UNITS.  Two adjacent tiles, even-aligned in the bin, that are both active and both hold at most
+    // SBT_X2_KEYS keys are one entry (the even tile's index, bit 15 set: sbt_tile_x2); every other tile is its own, as before.
+    // The units fill the array from both ends -- nHeavy peaks in front, nRounds others at the back --; the draw loop skips the gap.
+    const u32 hA = tid < (int)nT && !ovf ? L.hist[tid] : 0u;
+    const u32 nk = (hA & 0xFFFFu) + (hA >> 16);
+    bool paired = false;
+    if constexpr (X2) {
+      const bool can = tid < (int)nT && segTileBase + (u32)tid < in.nTiles && (ti.z & TM_ACTIVE) && nk <= SBT_X2_KEYS;
+      // (tiles b and b ^ 1: two lanes of one wavefront.  Every lane shuffles, whatever its own answer: behind `can &&` the
+      // value shuffled is a constant 1 on every lane that gets there, and the compiler folds the shuffle away)
+      const int canN = __shfl_xor((int)can, 1, 64);
+      paired = can && canN != 0;
+    }
+    if (tid < (int)nT && !ovf && !(paired && (tid & 1))) {
       const u32 pos = nk > SBT_PEAK_KEYS ? atomicAdd(&L.nHeavy, 1u) : nT - 1u - atomicAdd(&L.nRounds, 1u);
-      L.heavy[pos] = (uint16_t)tid;
+      L.heavy[pos] = (uint16_t)((u32)tid | (paired ? 0x8000u : 0u));
     }
   }
   if (ovf) {
@@ -1058,12 +1186,30 @@ __device__ __forceinline__ void sbt_bin(const SbtIn& in, const SbtOut& out, u32*
   auto tiles = [&](u32 tileEnd, u32 keyBase) {
     // (from a counter, not dealt in turn: one tile in twelve carries a peak and costs several ordinary ones -- a static deal
     // measured 0.628 against 0.590 ms, the workgroup waits for the wavefront that drew three of them)
+    // (the first launch draws UNITS from the order array: nFront peaks in front, the others at the back)
+    u32 nFront = 0, gap = 0;   // (without pairs every tile is a unit: no gap)
+    if constexpr (X2) {
+      nFront = (u32)__builtin_amdgcn_readfirstlane((int)L.nHeavy);
+      gap = tileEnd - nFront - (u32)__builtin_amdgcn_readfirstlane((int)L.nRounds);
+      tileEnd -= gap;
+    }
     for (;;) {
       u32 b = 0;
       if (lane == 0) b = atomicAdd(&L.work, 1u);
       b = (u32)__builtin_amdgcn_readfirstlane((int)b);
       if (b >= tileEnd) break;
-      if constexpr (PAIRS && !BIG) b = (u32)__builtin_amdgcn_readfirstlane((int)L.heavy[b]);   // (peaks first)
+      if constexpr (PAIRS && !BIG) b = (u32)__builtin_amdgcn_readfirstlane((int)L.heavy[b < nFront ? b : b + gap]);   // (peaks first)
+      if constexpr (X2) {
+        if (b & 0x8000u) {  // wave-uniform: tiles b and b + 1, side by side
+          b &= 0x7FFFu;
+          const uint4 tfA = L.tinfo[b], tfB = L.tinfo[b + 1u];
+          const u32 sc = L.startC[b];
+          const u32 nA = (u32)__builtin_amdgcn_readfirstlane((int)tfA.z) >> 8, nB = (u32)__builtin_amdgcn_readfirstlane((int)tfB.z) >> 8;
+          sbt_tile_x2(lane, scr + (u32)__builtin_amdgcn_readfirstlane(wv) * tw, keysL + (sc - keyBase), nA, nB, segTileBase + b, tfA, tfB,
+                      segSlot + sc + b, vsig, out, bad);
+          continue;
+        }
+      }
       const u32 t = segTileBase + b;
       if (t >= in.nTiles) continue;
       const uint4 tf = L.tinfo[b];
