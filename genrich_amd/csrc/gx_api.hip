@@ -18,6 +18,7 @@
 #include "gx_host_complexity.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
+#include "gx_host_peaksig.h"
 
 
 // ================================ C ABI ==================================================
@@ -270,6 +271,7 @@ int gx_reset(gx_ctx* ctx) {
   ctx->rankUsed = false;
   ctx->cpx.clear();     // (the buffers stay with the context)
   ctx->cpxReady = ctx->cpxUsed = false;
+  ctx->psigReady = false;   // (gx_peak_signal's records go with the peaks; the buffers stay)
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
@@ -284,7 +286,7 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   HIPCHECK(hipSetDevice(ctx->device));
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
-    ctx->peaksReady = ctx->countsReady = false;
+    ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
     // (a further replicate: the previous one's loose slots, tile tables and p(V) table are about to be reused)
     for (size_t r = 0; r < ctx->reps.size(); r++)
       if (ctx->reps[r].loose || ctx->reps[r].pilesPending)
@@ -583,7 +585,7 @@ int gx_pvalues(gx_ctx* ctx) {
 int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* peak_bp) {
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
-  ctx->peaksReady = ctx->countsReady = false;
+  ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
   hipStream_t s = ctx->stream;
   u32* misc = ctx->misc.as<u32>();
   // One replicate without a control, -p, and the tile stage left the sweep's bits on the loose slots (LooseCtl): the
@@ -1400,6 +1402,96 @@ int gx_write_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const
   if (int rc = gx_coverage_spearman_group(ctxs, n_ctx, n_samples, skip_zeros, &N, s1.data(), g1.data(), nullptr)) return rc;
   return gx_format_correlation(out, n_samples, sample_names, N, 0, s1.data(), g1.data(), 0);
 }
+
+int gx_peak_signal(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !ctx->countOn || !ctx->peaksReady || ctx->phase != 0) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->psigReady = false;
+  if (int rc = peak_signal_kept(ctx)) return rc;
+  if (n_samples) *n_samples = (int)ctx->kept.size();
+  return GX_OK;
+}
+
+int gx_get_peak_signal(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* area120, int64_t* max120, uint32_t* summit, uint32_t* covered,
+                       int64_t* at_summit120, size_t cap) {
+  if (!ctx || !ctx->psigReady || sample < 0 || (size_t)sample >= ctx->kept.size()) return GX_ERR_ORDER;
+  if (rep) *rep = ctx->kept[sample].rep;
+  if (is_ctrl) *is_ctrl = ctx->kept[sample].ctrl ? 1 : 0;
+  psig_give(static_cast<const PsigRec*>(ctx->psigHost.p) + (size_t)sample * ctx->psigPk, ctx->psigPk, cap, area120, max120, summit, covered, at_summit120);
+  return GX_OK;
+}
+
+int gx_peak_signal_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_region* peaks, size_t n_peaks, const uint32_t* summit_off, unsigned grid,
+                          int64_t* area120, int64_t* max120, uint32_t* summit, uint32_t* covered, int64_t* at_summit120) {
+  if (!ctx || ctx->nChrom == 0 || (n && !ev) || (n_peaks && !peaks)) return GX_ERR_ORDER;
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_peak_signal_events: a sample is open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = peak_signal_events(ctx, ev, n, peaks, n_peaks, summit_off, grid)) return rc;
+  psig_give(static_cast<const PsigRec*>(ctx->psigEvHost.p), n_peaks, n_peaks, area120, max120, summit, covered, at_summit120);
+  return GX_OK;
+}
+
+int gx_peak_signal_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_t* slot_pad, uint64_t* max_events) {
+  if (lanes) *lanes = PSIG_NT;
+  if (grid) *grid = (int)PSIG_GRID;
+  if (step_bases) *step_bases = PSIG_STEP;
+  if (slot_pad) *slot_pad = PSIG_PAD;
+  if (max_events) *max_events = PSIG_MAX_EVENTS - 1;
+  return GX_OK;
+}
+
+// (here, not in gx_emit.cpp, like the other writers over contexts that run their pass themselves)
+int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out) {
+  if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
+  int nS = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int n = 0;
+    if (int rc = gx_peak_signal(ctxs[g], &n)) return rc;
+    if (g && n != nS) return GX_ERR_ORDER;
+    nS = n;
+  }
+  // the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group), their records following them
+  std::vector<gx_peak> pk;
+  std::vector<std::vector<int64_t>> area((size_t)nS), mx((size_t)nS), at((size_t)nS);
+  std::vector<std::vector<uint32_t>> sm((size_t)nS), cov((size_t)nS);
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  for (int g = 0; g < n_ctx; g++) {
+    size_t k = 0;
+    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
+    const size_t at0 = pk.size();
+    pk.resize(at0 + k);
+    if (k)
+      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
+    for (int i = 0; i < nS; i++) {
+      area[i].resize(at0 + k); mx[i].resize(at0 + k); at[i].resize(at0 + k); sm[i].resize(at0 + k); cov[i].resize(at0 + k);
+      if (int rc = gx_get_peak_signal(ctxs[g], i, &rep[i], &ctrl[i], area[i].data() + at0, mx[i].data() + at0, sm[i].data() + at0, cov[i].data() + at0,
+                                      at[i].data() + at0, k))
+        return rc;
+    }
+  }
+  std::vector<size_t> ord(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+  if (n_ctx > 1)
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
+  std::vector<gx_region> reg(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
+  std::vector<const int64_t*> pa((size_t)nS), pm((size_t)nS), pt((size_t)nS);
+  std::vector<const uint32_t*> ps((size_t)nS), pc((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    if (n_ctx > 1) {
+      std::vector<int64_t> a(ord.size()), m(ord.size()), t(ord.size());
+      std::vector<uint32_t> s(ord.size()), c(ord.size());
+      for (size_t j = 0; j < ord.size(); j++) {
+        a[j] = area[i][ord[j]]; m[j] = mx[i][ord[j]]; t[j] = at[i][ord[j]]; s[j] = sm[i][ord[j]]; c[j] = cov[i][ord[j]];
+      }
+      area[i].swap(a); mx[i].swap(m); at[i].swap(t); sm[i].swap(s); cov[i].swap(c);
+    }
+    pa[i] = area[i].data(); pm[i] = mx[i].data(); pt[i] = at[i].data(); ps[i] = sm[i].data(); pc[i] = cov[i].data();
+  }
+  return gx_format_peak_signal(out, names, reg.data(), reg.size(), nS, rep.data(), ctrl.data(), pa.data(), pm.data(), ps.data(), pc.data(), pt.data());
+}
+
+int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out) { return gx_write_peak_signal_group(&ctx, 1, names, out); }
 
 int gx_complexity(gx_ctx* ctx, int* n_samples) {
   if (!ctx) return GX_ERR_ORDER;

@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the depth distribution tables (--depth) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -228,6 +228,34 @@ int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* nam
 
 int gx_write_counts(gx_ctx* ctx, const char* const* names, int n_samples, const char* const* sample_names, FILE* out) {
   return gx_write_counts_group(&ctx, 1, names, n_samples, sample_names, out);
+}
+
+// --peak-signal (no Genrich counterpart): the rows of --counts -- chr, start, end, peak_N in the order given -- with five
+// columns per sample; host only, no context.  The figures in 1/120 units are printed as --counts prints a count.
+int gx_format_peak_signal(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, int n_samples, const int* rep,
+                          const int* is_ctrl, const int64_t* const* area120, const int64_t* const* max120, const uint32_t* const* summit,
+                          const uint32_t* const* covered, const int64_t* const* at_summit120) {
+  if (!out || n_samples < 0 || (n_peaks && (!peaks || !names))) return GX_ERR_ORDER;
+  if (n_samples && (!rep || !is_ctrl || !area120 || !max120 || !summit || !covered || !at_summit120)) return GX_ERR_ORDER;
+  for (int s = 0; n_peaks && s < n_samples; s++)
+    if (!area120[s] || !max120[s] || !summit[s] || !covered[s] || !at_summit120[s]) return GX_ERR_ORDER;
+  fprintf(out, "chr\tstart\tend\tname");
+  for (int s = 0; s < n_samples; s++)
+    for (const char* col : {"max", "summit", "area", "covered", "at_summit"}) fprintf(out, "\t%c%d.%s", is_ctrl[s] ? 'c' : 't', rep[s], col);
+  fprintf(out, "\n");
+  for (size_t i = 0; i < n_peaks; i++) {
+    const gx_region& k = peaks[i];
+    fprintf(out, "%s\t%ld\t%ld\tpeak_%d", names[k.chrom], (long)k.start, (long)k.end, (int)i);
+    for (int s = 0; s < n_samples; s++) {
+      put_count(out, (long long)max120[s][i]);
+      fprintf(out, "\t%u", summit[s][i]);
+      put_count(out, (long long)area120[s][i]);
+      fprintf(out, "\t%u", covered[s][i]);
+      put_count(out, (long long)at_summit120[s][i]);
+    }
+    fprintf(out, "\n");
+  }
+  return GX_OK;
 }
 
 // --region-counts: one row per region in the caller's order, the contexts' counts added (a region lies on one chromosome, which

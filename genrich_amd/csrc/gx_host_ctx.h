@@ -35,6 +35,7 @@
 #include "gx_complexity.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
+#include "gx_peaksig.h"
 
 using namespace gx;
 
@@ -501,6 +502,13 @@ struct gx_ctx {
   bool depthUsed = false;           // k_depth_hist ran since the last gx_reset
   size_t depthLastCap = 0;          // the last pass: the list capacity it ended with, how often it ran again (gx_depth_last)
   u32 depthLastReruns = 0;
+  // each kept sample's depth inside the called peaks (gx_peak_signal / gx_peak_signal_events, gx_peaksig.h); nothing here exists
+  // before the first call
+  DevBuf psigSpace, psigRes;      // the peak space (one, cleared for sample after sample) and the records [sample][peak]
+  DevBuf psigEv;                  // gx_peak_signal_events' copy of the caller's events
+  PinnedBuf psigHost, psigEvHost; // the last gx_peak_signal's records (until gx_reset); the last gx_peak_signal_events'
+  size_t psigPk = 0;              // peaks of the last gx_peak_signal
+  bool psigReady = false;
   // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
   // nothing here exists before the first call
   DevBuf subCnt, subOff;          // k_sub_count's counts per block, k_sub_scan's offsets

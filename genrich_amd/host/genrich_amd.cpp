@@ -150,6 +150,7 @@ struct Opts {
   const char *inFile = nullptr, *ctrlFile = nullptr, *outFile = nullptr, *logFile = nullptr, *pileFile = nullptr,
              *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
              *countsFile = nullptr,  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
+             *peakSignalFile = nullptr,  // --peak-signal: each sample's own depth inside the peaks: height, summit, area
              *regionsBed = nullptr, *regionCountsFile = nullptr,  // --count-regions BED --region-counts FILE: ... in given regions
              *coveragePrefix = nullptr,  // --coverage PREFIX: a binned bedGraph track per sample (no Genrich counterpart)
              *profileBed = nullptr, *profilePrefix = nullptr;  // --profile BED --profile-out PREFIX: signal around anchor sites
@@ -2552,6 +2553,38 @@ void writeCounts(State& S, const std::vector<std::string>& tFiles, const std::ve
   }
 }
 
+// --peak-signal FILE: every sample's own depth (its -b lines piled up, -E regions not masked) inside the peaks just called: one
+// row per narrowPeak line, five columns per sample (gx_write_peak_signal_group); with -v per sample the peaks in which it has no
+// depth at all and the peaks whose summit base is also the first base of its own maximum
+void writePeakSignal(State& S, const std::vector<std::string>& tFiles, const std::vector<std::string>& cFiles, const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  Out out = openWrite(o.peakSignalFile, o.gzOut);
+  check(S, gx_write_peak_signal_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), out.f), S.devs.ctx[0]);
+  closeOut(out);
+  if (!o.verbose) return;
+  const int nS = (int)sampleNamesOf(S, tFiles, cFiles).size();
+  for (int i = 0; i < nS; i++) {
+    size_t total = 0, empty = 0, shared = 0;
+    int rep = 0, ctrl = 0;
+    for (gx_ctx* g : S.devs.ctx) {
+      size_t k = 0;
+      check(S, gx_peak_count(g, &k), g);
+      std::vector<gx_peak> pk(k);
+      std::vector<int64_t> mx(k);
+      std::vector<uint32_t> sm(k);
+      if (k) check(S, gx_get_peaks(g, pk.data(), k), g);
+      check(S, gx_get_peak_signal(g, i, &rep, &ctrl, nullptr, mx.data(), sm.data(), nullptr, nullptr, k), g);
+      for (size_t j = 0; j < k; j++) {
+        empty += mx[j] == 0;
+        shared += sm[j] == pk[j].summit;
+      }
+      total += k;
+    }
+    fprintf(stderr, "  Signal in peaks, %s file #%d: no depth in %zu of %zu peaks, summit shared in %zu\n", ctrl ? "control" : "experimental", rep,
+            empty, total, shared);
+  }
+}
+
 // --count-regions BED --region-counts FILE: the same intervals counted in the BED's regions, which may overlap and come in any
 // order; exactly one output row per BED line, in the BED's order, so that the files of two runs line up.  The BED is read with
 // -E's rules (loadBED); a 4th column names the row, further columns are ignored (a narrowPeak file is valid input).
@@ -3015,6 +3048,7 @@ void usage() {
           "   -r -R -p -q -a -l -g -X -P -S -L -v -V)\n"
           "  --device N | --devices 0-7   GPU(s) to use;  --threads N   BGZF inflate threads\n"
           "  --counts FILE   each sample's intervals counted in the called peaks\n"
+          "  --peak-signal FILE   each sample's own depth inside the called peaks: max, summit, area, covered bases, depth at the summit\n"
           "  --count-regions BED --region-counts FILE   ... counted in the BED's regions, one row per BED line\n"
           "  --coverage PREFIX [--bin-size N] [--coverage-scale X]   each sample's pileup in bins of N bases (50):\n"
           "                  bedGraph PREFIX.t<rep>.bedgraph / PREFIX.c<rep>.bedgraph, values times X (1)\n"
@@ -3061,6 +3095,7 @@ int main(int argc, char** argv) {
                                      {"devices", required_argument, nullptr, 1003},
                                      {"threads", required_argument, nullptr, 1002},
                                      {"counts", required_argument, nullptr, 1004},
+                                     {"peak-signal", required_argument, nullptr, 1029},
                                      {"count-regions", required_argument, nullptr, 1005},
                                      {"region-counts", required_argument, nullptr, 1006},
                                      {"coverage", required_argument, nullptr, 1007},
@@ -3128,6 +3163,7 @@ int main(int argc, char** argv) {
       case 1001: o.device = getInt(optarg); break;
       case 1002: g_threads = getInt(optarg); break;
       case 1004: o.countsFile = optarg; break;
+      case 1029: o.peakSignalFile = optarg; break;
       case 1005: o.regionsBed = optarg; break;
       case 1006: o.regionCountsFile = optarg; break;
       case 1007: o.coveragePrefix = optarg; break;
@@ -3191,6 +3227,9 @@ int main(int argc, char** argv) {
   }
   // (the counts are counted in the peaks this run calls: nothing to count in with -P, -X or --events-only)
   if (o.countsFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly)) die("", "--counts needs the peaks of this run (not with -P or -X)");
+  // (the signal is taken in the peaks this run calls, from the events the library keeps: none with -X, -P or --events-only)
+  if (o.peakSignalFile && (o.peaksOnly || !o.peaksOpt || o.eventsOnly))
+    die("", "--peak-signal needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
   if ((o.regionsBed != nullptr) != (o.regionCountsFile != nullptr)) die("", "--count-regions BED and --region-counts FILE need each other");
   // (the regions count the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.regionsBed && (o.peaksOnly || o.eventsOnly)) die("", "--count-regions needs the intervals of this run (not with -P or --events-only)");
@@ -3323,7 +3362,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.regionsBed || o.complexityFile || o.saturationFile) check(S, gx_set_count_in_peaks(g, 1), g);
+      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile) check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -3495,6 +3534,7 @@ int main(int argc, char** argv) {
     if (o.verbose) fprintf(stderr, "Peaks identified: %d (%ldbp)\n", (int)nPeaks, (long)peakBP);
   }
   if (o.countsFile) writeCounts(S, tFiles, cFiles, names);
+  if (o.peakSignalFile) writePeakSignal(S, tFiles, cFiles, names);
   if (o.regionsBed) writeRegionCounts(S, tFiles, cFiles, names);
   if (o.coveragePrefix) writeCoverage(S, names);
   if (o.correlationFile) writeCorrelation(S);

@@ -62,6 +62,19 @@ class RegionCounts(NamedTuple):
     is_ctrl: bool
 
 
+class PeakSignal(NamedTuple):
+    """One sample's own depth inside the peaks (gx_get_peak_signal, gx_peak_signal_events), per peak: the area, the maximum
+    and the depth at the run's summit base in 1/120 units (int64); the first base (from the peak's start) at which the
+    maximum is reached and the bases with a depth above 0 (uint32)."""
+    area: np.ndarray
+    max: np.ndarray
+    summit: np.ndarray
+    covered: np.ndarray
+    at_summit: np.ndarray
+    rep: int
+    is_ctrl: bool
+
+
 GX_PATH_COVERAGE = 262144   # gx_path_info bit 18: the run summed its samples' pileups over bins (gx_set_coverage_bins)
 
 
@@ -260,6 +273,13 @@ _SIGS = {
     "gx_write_counts_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_counts_path": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_char_p],
+    "gx_peak_signal": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_peak_signal": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.c_void_p] * 5 + [C.c_size_t],
+    "gx_peak_signal_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint] + [C.c_void_p] * 5,
+    "gx_peak_signal_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+    "gx_format_peak_signal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 7,
+    "gx_write_peak_signal_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_write_peak_signal": [C.c_void_p, C.c_void_p, C.c_void_p],
     "gx_set_coverage_bins": [C.c_void_p, C.c_uint32],
     "gx_coverage_samples": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_coverage_bin_count": [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)],
@@ -589,6 +609,41 @@ def dups_geometry(keys):
     if rc:
         raise RuntimeError(f"gx_dups_geometry: {rc}")
     return cap.value, home
+
+
+def peak_signal_geometry():
+    """(lanes of a workgroup of k_psig_reduce, its most workgroups, bases a wavefront covers per step, the multiple a peak's
+    slots are padded to, the most events peak_signal_events takes) -- gx_peak_signal_geometry; needs no GPU."""
+    lib = load_library()
+    lanes, grid, step, pad, most = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    rc = lib.gx_peak_signal_geometry(C.byref(lanes), C.byref(grid), C.byref(step), C.byref(pad), C.byref(most))
+    if rc:
+        raise RuntimeError(f"gx_peak_signal_geometry: {rc}")
+    return lanes.value, grid.value, step.value, pad.value, most.value
+
+
+def _regions(regions):
+    reg = np.asarray(regions)
+    if reg.dtype != REGION_DTYPE:
+        rows = np.asarray(regions, dtype=np.int64).reshape(-1, 3)
+        reg = np.zeros(len(rows), dtype=REGION_DTYPE)
+        reg["chrom"], reg["start"], reg["end"] = rows[:, 0], rows[:, 1], rows[:, 2]
+    return np.ascontiguousarray(reg)
+
+
+def format_peak_signal(names, peaks, samples) -> bytes:
+    """--peak-signal's text (gx_format_peak_signal) of `samples` (PeakSignal each) in `peaks` (REGION_DTYPE, or rows of
+    (chrom, start, end)); host-only, needs no GPU."""
+    lib = load_library()
+    reg = _regions(peaks)
+    S = len(samples)
+    cols = [[np.ascontiguousarray(getattr(x, f), dtype=t) for x in samples]
+            for f, t in (("area", np.int64), ("max", np.int64), ("summit", np.uint32), ("covered", np.uint32), ("at_summit", np.int64))]
+    ptrs = [(C.c_void_p * max(S, 1))(*[a.ctypes.data for a in col]) for col in cols]
+    rep = (C.c_int * max(S, 1))(*[int(x.rep) for x in samples])
+    ctrl = (C.c_int * max(S, 1))(*[int(x.is_ctrl) for x in samples])
+    cn = _c_names(list(names))
+    return _to_tmpfile(lambda f: lib.gx_format_peak_signal(f, cn, reg.ctypes.data if reg.size else None, reg.size, S, rep, ctrl, *ptrs))
 
 
 def complexity_geometry(n=0):
@@ -1131,6 +1186,44 @@ class Genrich:
         """--counts' text (gx_write_counts) of this context."""
         self._check(self.lib.gx_write_counts_path(self.ctx, self._names(names), len(sample_names), self._names(sample_names),
                                                   path.encode()))
+
+    # -- each sample's signal inside the peaks (include/genrich_amd.h, gx_peak_signal) -----------------------------------
+    def peak_signal(self):
+        """Every kept sample's depth inside the peaks of the last find_peaks (gx_peak_signal); needs set_count_in_peaks(True).
+        Returns the number of samples."""
+        n = C.c_int(0)
+        self._check(self.lib.gx_peak_signal(self.ctx, C.byref(n)))
+        return n.value
+
+    def peak_signal_of(self, sample):
+        """PeakSignal of one sample of the last peak_signal()."""
+        k = self.n_peaks
+        a, m, t = (np.zeros(k, dtype=np.int64) for _ in range(3))
+        s, c = (np.zeros(k, dtype=np.uint32) for _ in range(2))
+        rep, ctrl = C.c_int(0), C.c_int(0)
+        self._check(self.lib.gx_get_peak_signal(self.ctx, int(sample), C.byref(rep), C.byref(ctrl), *[x.ctypes.data if k else None for x in (a, m, s, c, t)], k))
+        return PeakSignal(a, m, s, c, t, rep.value, bool(ctrl.value))
+
+    def peak_signal_events(self, events, peaks, summit_off=None, grid=0):
+        """PeakSignal of host events (EVENT_DTYPE) taken as one sample over this context's chromosome table, in the peaks given
+        (REGION_DTYPE or rows of (chrom, start, end): sorted, disjoint), by the same kernels (gx_peak_signal_events);
+        summit_off[k]: the base of peak k that at_summit reads (None: base 0); grid = 0: the library's geometry."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+        reg = _regions(peaks)
+        k = int(reg.size)
+        so = None if summit_off is None else np.ascontiguousarray(summit_off, dtype=np.uint32)
+        assert so is None or so.size == k
+        a, m, t = (np.zeros(k, dtype=np.int64) for _ in range(3))
+        s, c = (np.zeros(k, dtype=np.uint32) for _ in range(2))
+        self._check(self.lib.gx_peak_signal_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, reg.ctypes.data if k else None, k,
+                                                   so.ctypes.data if so is not None and k else None, int(grid),
+                                                   *[x.ctypes.data if k else None for x in (a, m, s, c, t)]))
+        return PeakSignal(a, m, s, c, t, 0, False)
+
+    def peak_signal_text(self, names) -> bytes:
+        """--peak-signal's text (gx_write_peak_signal) of this context; runs the pass."""
+        cn = self._names(names)
+        return _to_tmpfile(lambda f: self.lib.gx_write_peak_signal(self.ctx, cn, f))
 
     # -- counting in a given region set (include/genrich_amd.h, gx_count_in_regions) ----------------------------------
     def count_in_regions(self, regions):

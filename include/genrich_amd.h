@@ -285,6 +285,51 @@ int gx_count_in_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int* n_
 int gx_get_region_counts(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* count120, size_t cap, int64_t* total120,
                          int64_t* in_regions120);
 
+/* ---- each sample's own signal inside the called peaks: height, summit, area (no Genrich counterpart: the replicates'
+ *      p-values end in Fisher's sum, multPval Genrich.c:528-583, and the narrowPeak line does not say which replicate carries
+ *      a peak; the usual route is bedtools map / multiBigwigSummary over per-sample tracks made in another pass) ----
+ * The samples, their order, their intervals and their weights are exactly those of gx_count_in_peaks: every gx_sample_end of
+ * the run in call order; the sample's -b lines, the end clamped to the chromosome's length, after -r and the int16 rule's
+ * drops; weight 120 / count; nothing on -e, unsaved or un-owned chromosomes.  A sample's depth is the prefix sum of its
+ * difference array, as the pileup is: +w at s, -w at the clamped e.  An interval with e == s adds nothing; one with e < s
+ * (convert_event lets them in) adds -w over [e, s), as it does in the pileup.  -E regions are NOT masked: this is the depth of
+ * the sample's intervals, the one place where it differs from the `experimental` column of -k, which is 0 inside them.
+ * For sample i and peak k = [ps, pe) (gx_get_peaks order, narrowPeak coordinates), all exact signed int64 in 1/120 units
+ * (summit and covered: bases):
+ *     area120[k]      = the sum of depth(x) over x in [ps, pe)
+ *     max120[k]       = the largest depth(x) there             summit[k] = the smallest x - ps at which it is reached
+ *     covered[k]      = the bases of [ps, pe) with depth > 0
+ *     at_summit120[k] = depth(ps + gx_peak.summit), the run's own summit base
+ * No figure depends on the launch geometry, the order of the adds, the push mode (host, pinned, device, packed) or the number
+ * of contexts: integer adds only.  Domain: the pileup's own, a depth below 2^31 (1/120 units) at every base.
+ *
+ * gx_peak_signal: after gx_find_peaks, with gx_set_count_in_peaks on (else GX_ERR_ORDER); every kept sample (*n_samples of
+ *   them) through k_psig_scatter / k_psig_reduce (gx_peaksig.h) over ONE buffer of an int32 per peak base, cleared for every
+ *   sample, and one read-back; may be called again, with the same result; no peak or no sample is legal.  Under gx_set_owned a
+ *   context handles the peaks of the chromosomes it owns, as the count does.  The results of gx_count_in_peaks /
+ *   gx_count_in_regions stay readable; gx_reset drops this one.  A failed allocation: GX_ERR_MEM.  Its phase is "peaksig"
+ *   (gx_phase_times).  Nothing of it is allocated or launched before the first call.
+ * gx_get_peak_signal: the last pass's figures of one sample (0 .. n_samples-1): its replicate, whether it is a control and
+ *   min(cap, n_peaks) entries of each array.  Any pointer may be NULL.
+ * gx_peak_signal_events: the same two kernels over n events in host memory (copied to the device by the call), all ONE sample
+ *   whose save mask lists every chromosome of the context's table (after gx_set_chroms; -e and gx_set_owned hold as for a
+ *   sample), in n_peaks peaks the caller gives: sorted by (chrom, start), disjoint (end <= the next start), not empty, inside
+ *   their chromosomes, on chromosomes this context works on; summit_off[k] < end - start is the base at_summit120 reads (NULL:
+ *   base 0).  Anything else, n >= 2^31 / 120 (as many unit intervals on one base leave the domain) or grid > 65535:
+ *   GX_ERR_ORDER with a text before anything is allocated or launched.  grid = 0: the library's geometry, else that many
+ *   workgroups for either kernel.  Each output holds n_peaks entries (any may be NULL).  No sample open.  For tests and
+ *   measurements: constructed peaks that no small run calls; it leaves gx_get_peak_signal's result alone.
+ * gx_peak_signal_geometry: what the edge cases depend on, without a device: the lanes of a workgroup of k_psig_reduce (a
+ *   wavefront of 64 per peak), its most workgroups with grid = 0, the bases a wavefront covers per step, the multiple to which
+ *   a peak's slots are padded, and the most events gx_peak_signal_events takes.  Any pointer may be NULL. */
+int gx_peak_signal(gx_ctx* ctx, int* n_samples);
+int gx_get_peak_signal(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* area120, int64_t* max120, uint32_t* summit,
+                       uint32_t* covered, int64_t* at_summit120, size_t cap);
+int gx_peak_signal_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_region* peaks, size_t n_peaks,
+                          const uint32_t* summit_off, unsigned grid, int64_t* area120, int64_t* max120, uint32_t* summit,
+                          uint32_t* covered, int64_t* at_summit120);
+int gx_peak_signal_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_t* slot_pad, uint64_t* max_events);
+
 /* ---- binned coverage tracks per sample (no Genrich counterpart: -k, printPile Genrich.c:1697-1715, prints a replicate's pileups
  *      per run-length interval, the control's already scaled and floored; a track wants each sample's own pileup in bins) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_count_in_peaks: for replicate r its treatment, then its
@@ -700,6 +745,18 @@ int gx_write_region_counts(gx_ctx* ctx, const char* const* names, const gx_regio
                            size_t n, int n_samples, const char* const* sample_names, FILE* out);
 int gx_write_region_counts_path(gx_ctx* ctx, const char* const* names, const gx_region* regions, const char* const* region_names,
                                 size_t n, int n_samples, const char* const* sample_names, const char* path);
+/* --peak-signal (no Genrich counterpart).  gx_format_peak_signal: host only, no context.  A header "chr\tstart\tend\tname" and
+ * per sample the five columns <label>.max <label>.summit <label>.area <label>.covered <label>.at_summit, <label> = t<rep> or
+ * c<rep>; then one row per peak in the order given: names[chrom], start, end, peak_N with N = k, and the samples' figures --
+ * those in 1/120 units printed as --counts prints a count (n / 120 with %lld when n % 120 == 0, else %.2f), summit and covered
+ * as they are.  n_peaks == 0 and n_samples == 0 are legal.  gx_write_peak_signal_group: runs gx_peak_signal on every context,
+ * merges their peaks as gx_write_narrowpeak_group does (the same peak_N) and formats; contexts that differ in their samples:
+ * GX_ERR_ORDER.  gx_write_peak_signal: one context. */
+int gx_format_peak_signal(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, int n_samples,
+                          const int* rep, const int* is_ctrl, const int64_t* const* area120, const int64_t* const* max120,
+                          const uint32_t* const* summit, const uint32_t* const* covered, const int64_t* const* at_summit120);
+int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out);
+int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out);
 /* --coverage (no Genrich counterpart; printPile 1697 is what -k prints instead): bedGraph without a header line.
  * gx_format_coverage: host only, no context.  One chromosome's bins (n_bins = ceil(len / bin_size) sums in 1/120 units) as lines
  * "chrom\tstart\tend\tvalue\n" that tile [0, len) with no gap and no overlap, zero runs included.  Adjacent bins are merged
