@@ -16,6 +16,7 @@
 #include "gx_host_fingerprint.h"
 #include "gx_host_rank.h"
 #include "gx_host_complexity.h"
+#include "gx_host_ivstat.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
@@ -271,6 +272,8 @@ int gx_reset(gx_ctx* ctx) {
   ctx->rankUsed = false;
   ctx->cpx.clear();     // (the buffers stay with the context)
   ctx->cpxReady = ctx->cpxUsed = false;
+  ctx->ivs.clear();
+  ctx->ivsReady = ctx->ivsUsed = false;
   ctx->psigReady = false;   // (gx_peak_signal's records go with the peaks; the buffers stay)
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
@@ -866,7 +869,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
-           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u);
+           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u);
   return GX_OK;
 }
 
@@ -1582,6 +1585,122 @@ int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FIL
   }
   if (int rc = gx_format_complexity(metrics, nS, rep.data(), ctrl.data(), N.data(), D.data(), pm.data(), pk.data(), np.data())) return rc;
   return hist ? gx_format_complexity_hist(hist, nS, rep.data(), ctrl.data(), pm.data(), pk.data(), np.data()) : GX_OK;
+}
+
+int gx_interval_stats(gx_ctx* ctx, int* n_samples) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (!ctx->countOn) return refuse(ctx, "gx_interval_stats needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_interval_stats: a sample is open");
+  if (ctx->kept.empty()) return refuse(ctx, "gx_interval_stats: no closed sample");
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->ivsReady = false;
+  if (int rc = ivstat_kept(ctx)) return rc;
+  if (n_samples) *n_samples = (int)ctx->ivs.size();
+  return GX_OK;
+}
+
+int gx_get_interval_lengths(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120, size_t cap,
+                            size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted) {
+  if (!ctx || !ctx->ivsReady || sample < 0 || (size_t)sample >= ctx->ivs.size()) return GX_ERR_ORDER;
+  const gx_ctx::IvsResult& r = ctx->ivs[sample];
+  if (rep) *rep = r.rep;
+  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
+  return ivs_give(r, length, n, w120, cap, n_classes, n_inverted, w120_inverted, nullptr, nullptr, nullptr, 0);
+}
+
+int gx_get_chrom_stats(gx_ctx* ctx, int sample, uint64_t* cn, uint64_t* cw120, uint64_t* cbases120, size_t cap) {
+  if (!ctx || !ctx->ivsReady || sample < 0 || (size_t)sample >= ctx->ivs.size()) return GX_ERR_ORDER;
+  return ivs_give(ctx->ivs[sample], nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, cn, cw120, cbases120, cap);
+}
+
+int gx_interval_stats_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, size_t list_cap, uint64_t* length, uint64_t* n_iv,
+                             uint64_t* w120, size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn,
+                             uint64_t* cw120, uint64_t* cbases120, size_t chrom_cap) {
+  if (!ctx || ctx->nChrom == 0 || (n && !ev) || (cap && (!length || !n_iv || !w120)) || (chrom_cap && (!cn || !cw120 || !cbases120))) return GX_ERR_ORDER;
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_interval_stats_events: a sample is open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  gx_ctx::IvsResult r;
+  if (int rc = ivstat_events(ctx, ev, n, grid, list_cap, r)) return rc;
+  return ivs_give(r, length, n_iv, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
+}
+
+int gx_interval_stats_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint32_t* chrom_window, size_t* list_capacity) {
+  static_assert(IVS_BOUND == GX_IVS_BOUND, "the header's bound is the kernel's");
+  if (lanes) *lanes = CNT_NT;
+  if (grid) *grid = (int)IVS_GRID;
+  if (lds_bound) *lds_bound = IVS_BOUND;
+  if (chrom_window) *chrom_window = IVS_CHROM_WINDOW;
+  if (list_capacity) *list_capacity = IVS_LIST_CAP;
+  return GX_OK;
+}
+
+int gx_interval_stats_last(gx_ctx* ctx, size_t* list_capacity, int* reruns) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (list_capacity) *list_capacity = ctx->ivsLastCap;
+  if (reruns) *reruns = (int)ctx->ivsLastReruns;
+  return GX_OK;
+}
+
+// (the two over contexts live here, not in gx_emit.cpp, like the complexity's: they read contexts)
+int gx_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120,
+                            size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120,
+                            uint64_t* cbases120, size_t chrom_cap) {
+  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
+  gx_ctx::IvsResult sum;
+  for (int g = 0; g < n_ctx; g++) {
+    gx_ctx* c = ctxs[g];
+    if (!c || !c->ivsReady || sample < 0 || (size_t)sample >= c->ivs.size() || c->ivs.size() != ctxs[0]->ivs.size() ||
+        c->ivs[sample].cn.size() != ctxs[0]->ivs[sample].cn.size() || c->ivs[sample].rep != ctxs[0]->ivs[sample].rep ||
+        c->ivs[sample].ctrl != ctxs[0]->ivs[sample].ctrl)
+      return GX_ERR_ORDER;
+    if (g == 0) {
+      sum.rep = c->ivs[sample].rep;
+      sum.ctrl = c->ivs[sample].ctrl;
+    }
+    ivs_add(sum, c->ivs[sample]);
+  }
+  if (rep) *rep = sum.rep;
+  if (is_ctrl) *is_ctrl = sum.ctrl ? 1 : 0;
+  return ivs_give(sum, length, n, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
+}
+
+int gx_write_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_chrom, int cut_sites, const uint64_t* cuts,
+                                  int n_cuts, FILE* lengths, FILE* metrics, FILE* chroms) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || (!lengths && !metrics && !chroms) || (chroms && (!names || n_chrom != (int)ctxs[0]->nChrom))) return GX_ERR_ORDER;
+  int nS = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int n = 0;
+    if (int rc = gx_interval_stats(ctxs[g], &n)) return rc;
+    if (g && n != nS) return GX_ERR_ORDER;
+    nS = n;
+  }
+  const size_t nC = ctxs[0]->nChrom;
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> nInv((size_t)nS), wInv((size_t)nS);
+  std::vector<std::vector<uint64_t>> col((size_t)nS * 6);
+  std::vector<const uint64_t*> pl((size_t)nS), pn((size_t)nS), pw((size_t)nS), pcn((size_t)nS), pcw((size_t)nS), pcb((size_t)nS);
+  std::vector<size_t> np((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    size_t n = 0;
+    if (int rc = gx_interval_stats_group(ctxs, n_ctx, i, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, nullptr, nullptr, nullptr, nullptr, 0)) return rc;
+    std::vector<uint64_t>* a = &col[(size_t)i * 6];
+    for (int k = 0; k < 3; k++) a[k].assign(std::max<size_t>(n, 1), 0);
+    for (int k = 3; k < 6; k++) a[k].assign(nC, 0);
+    if (int rc = gx_interval_stats_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], a[0].data(), a[1].data(), a[2].data(), n, &np[i], &nInv[i], &wInv[i],
+                                         a[3].data(), a[4].data(), a[5].data(), nC))
+      return rc;
+    pl[i] = a[0].data(); pn[i] = a[1].data(); pw[i] = a[2].data(); pcn[i] = a[3].data(); pcw[i] = a[4].data(); pcb[i] = a[5].data();
+  }
+  if (lengths)
+    if (int rc = gx_format_lengths(lengths, nS, rep.data(), ctrl.data(), pl.data(), pn.data(), pw.data(), np.data(), nInv.data(), wInv.data(), cut_sites)) return rc;
+  if (metrics)
+    if (int rc = gx_format_lengths_metrics(metrics, nS, rep.data(), ctrl.data(), pl.data(), pn.data(), pw.data(), np.data(), cuts, n_cuts)) return rc;
+  if (chroms) {
+    std::vector<uint32_t> lens(nC);
+    for (size_t c = 0; c < nC; c++) lens[c] = ctxs[0]->hChrom[c].len;
+    if (int rc = gx_format_chrom_stats(chroms, names, lens.data(), (int)nC, nS, rep.data(), ctrl.data(), pcn.data(), pcw.data(), pcb.data())) return rc;
+  }
+  return GX_OK;
 }
 
 uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index) { return subsample_draw(subsample_key(seed, sample), index); }

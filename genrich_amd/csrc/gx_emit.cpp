@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the interval length and chromosome tables (--lengths, --chrom-stats), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -706,6 +706,173 @@ int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const in
   for (int s = 0; s < n_samples; s++)
     for (size_t i = 0; i < n_pairs[s]; i++)
       fprintf(out, "%c%d\t%llu\t%llu\n", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)mult[s][i], (unsigned long long)keys[s][i]);
+  return GX_OK;
+}
+
+// --lengths / --lengths-metrics / --chrom-stats: the figures from the integers alone
+namespace {
+// a sample's lengths as the device pass gives them: strictly ascending and below 2^32, every class with intervals whose weight
+// lies between 1/120 and 1 each; *W: the weight of all of them
+bool len_classes_ok(const uint64_t* length, const uint64_t* n, const uint64_t* w120, size_t n_classes, uint64_t* N, uint64_t* W) {
+  if (n_classes && (!length || !n || !w120)) return false;
+  u128_t sn = 0, sw = 0;
+  for (size_t i = 0; i < n_classes; i++) {
+    if ((length[i] >> 32) || (i && length[i - 1] >= length[i]) || !n[i] || w120[i] < n[i] || (u128_t)w120[i] > (u128_t)120 * n[i]) return false;
+    sn += n[i];
+    sw += w120[i];
+  }
+  if ((sn >> 64) || (sw >> 64)) return false;
+  *N = (uint64_t)sn;
+  *W = (uint64_t)sw;
+  return true;
+}
+bool len_cuts_ok(const uint64_t* cuts, int n_cuts) {
+  if (n_cuts < 0 || n_cuts > GX_LEN_MAX_CUTS || (n_cuts && !cuts)) return false;
+  for (int k = 0; k < n_cuts; k++)
+    if (!cuts[k] || (k && cuts[k - 1] >= cuts[k])) return false;
+  return true;
+}
+void put_w120(FILE* out, uint64_t w) {   // a weight in 1/120 units, as --counts prints one
+  if (w % 120 == 0) fprintf(out, "\t%llu", (unsigned long long)(w / 120));
+  else fprintf(out, "\t%.2f", (double)w / 120.0);
+}
+}  // namespace
+
+int gx_lengths_metrics(const uint64_t* length, const uint64_t* n, const uint64_t* w120, size_t n_classes, const uint64_t* cuts, int n_cuts,
+                       gx_len_metrics* out) {
+  uint64_t N = 0, W = 0;
+  if (!out || !len_cuts_ok(cuts, n_cuts) || !len_classes_ok(length, n, w120, n_classes, &N, &W)) return GX_ERR_ORDER;
+  gx_len_metrics m{};
+  const double nan = std::nan("");
+  m.n = N;
+  m.w120 = W;
+  m.n_shares = n_cuts + 1;
+  m.mean = m.sd = nan;
+  if (!n_classes) {
+    *out = m;
+    return GX_OK;
+  }
+  m.min = length[0];
+  m.max = length[n_classes - 1];
+  // sum w L (below 2^128: w < 2^64, L < 2^32, fewer than 2^32 classes) and sum w L^2, exact
+  u128_t swl = 0;
+  U256 swl2;
+  uint64_t best = 0;
+  for (size_t i = 0; i < n_classes; i++) {
+    swl += (u128_t)w120[i] * length[i];
+    swl2 = add256(swl2, mul128((u128_t)w120[i], (u128_t)length[i] * length[i]));
+    if (w120[i] > best) {   // (ascending: the smallest L of the greatest weight stays)
+      best = w120[i];
+      m.mode = length[i];
+    }
+  }
+  m.mean = to_double(u256_of(swl)) / (double)W;
+  const U256 a = mul256_64(swl2, W), b = mul128(swl, swl);   // W sum w L^2 >= (sum w L)^2
+  m.sd = cmp256(a, b) > 0 ? std::sqrt(to_double(sub256(a, b))) / (double)W : 0.0;
+  // percentiles: the smallest L whose cumulative weight times 100 is >= q W
+  const unsigned q[5] = {5, 25, 50, 75, 95};
+  uint64_t* dst[5] = {&m.p5, &m.q25, &m.median, &m.q75, &m.p95};
+  u128_t cum = 0;
+  int at = 0;
+  std::vector<u128_t> cls((size_t)n_cuts + 1, 0);
+  for (size_t i = 0; i < n_classes; i++) {
+    cum += w120[i];
+    while (at < 5 && (u128_t)100 * cum >= (u128_t)q[at] * W) *dst[at++] = length[i];
+    int k = 0;
+    while (k < n_cuts && length[i] >= cuts[k]) k++;   // class k: cuts[k - 1] <= L < cuts[k]
+    cls[(size_t)k] += w120[i];
+  }
+  for (int k = 0; k <= n_cuts; k++) m.share[k] = (double)(uint64_t)cls[(size_t)k] / (double)W;
+  *out = m;
+  return GX_OK;
+}
+
+// --lengths: one row per sample and occurring length, then the sample's inverted intervals, if any
+int gx_format_lengths(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* length, const uint64_t* const* n,
+                      const uint64_t* const* w120, const size_t* n_classes, const uint64_t* n_inverted, const uint64_t* w120_inverted, int cut_sites) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !length || !n || !w120 || !n_classes || !n_inverted || !w120_inverted) return GX_ERR_ORDER;
+  std::vector<uint64_t> W((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++) {
+    uint64_t N = 0;
+    if (!len_classes_ok(length[s], n[s], w120[s], n_classes[s], &N, &W[s])) return GX_ERR_ORDER;
+  }
+  if (cut_sites)
+    fprintf(out, "# an interval is a cut-site window of -j (ATAC mode), not a fragment: nearly all have one length; length = end (clamped to the chromosome) - start; weight = 1 / alignments\n");
+  else
+    fprintf(out, "# an interval is one of the sample's -b lines: a fragment, or an unpaired read as -y / -w extend it (with -j: cut-site windows instead); length = end (clamped to the chromosome) - start; weight = 1 / alignments\n");
+  fprintf(out, "sample\tlength\tintervals\tweight\tcum_weight_share\n");
+  for (int s = 0; s < n_samples; s++) {
+    uint64_t cum = 0;
+    for (size_t i = 0; i < n_classes[s]; i++) {
+      cum += w120[s][i];
+      fprintf(out, "%c%d\t%llu\t%llu", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)length[s][i], (unsigned long long)n[s][i]);
+      put_w120(out, w120[s][i]);
+      fprintf(out, "\t%.6f\n", (double)cum / (double)W[s]);
+    }
+    if (n_inverted[s]) {
+      fprintf(out, "%c%d\tinverted\t%llu", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)n_inverted[s]);
+      put_w120(out, w120_inverted[s]);
+      fprintf(out, "\tNA\n");
+    }
+  }
+  return GX_OK;
+}
+
+// --lengths-metrics: one row per sample
+int gx_format_lengths_metrics(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* length, const uint64_t* const* n,
+                              const uint64_t* const* w120, const size_t* n_classes, const uint64_t* cuts, int n_cuts) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !length || !n || !w120 || !n_classes) return GX_ERR_ORDER;
+  std::vector<gx_len_metrics> m((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (int rc = gx_lengths_metrics(length[s], n[s], w120[s], n_classes[s], cuts, n_cuts, &m[s])) return rc;
+  fprintf(out, "sample\tintervals\tweight\tmean\tsd\tmin\tp5\tq25\tmedian\tq75\tp95\tmax\tmode");
+  for (int k = 0; k <= n_cuts; k++) {
+    if (k == 0 && n_cuts) fprintf(out, "\tlt%llu", (unsigned long long)cuts[0]);
+    else if (k == 0) fprintf(out, "\tall");
+    else if (k == n_cuts) fprintf(out, "\tge%llu", (unsigned long long)cuts[k - 1]);
+    else fprintf(out, "\tge%llu_lt%llu", (unsigned long long)cuts[k - 1], (unsigned long long)cuts[k]);
+  }
+  fprintf(out, "\n");
+  for (int s = 0; s < n_samples; s++) {
+    fprintf(out, "%c%d\t%llu", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)m[s].n);
+    put_w120(out, m[s].w120);
+    put_cpx(out, m[s].mean, "\t%.6f");
+    put_cpx(out, m[s].sd, "\t%.6f");
+    for (uint64_t v : {m[s].min, m[s].p5, m[s].q25, m[s].median, m[s].q75, m[s].p95, m[s].max, m[s].mode}) fprintf(out, "\t%llu", (unsigned long long)v);
+    for (int k = 0; k <= n_cuts; k++) fprintf(out, "\t%.6f", m[s].n ? m[s].share[k] : 0.0);
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// --chrom-stats: one row per chromosome of the table, four columns per sample
+int gx_format_chrom_stats(FILE* out, const char* const* names, const uint32_t* lens, int n_chrom, int n_samples, const int* rep, const int* is_ctrl,
+                          const uint64_t* const* cn, const uint64_t* const* cw120, const uint64_t* const* cbases120) {
+  if (!out || !names || !lens || n_chrom < 1 || n_samples < 1 || !rep || !is_ctrl || !cn || !cw120 || !cbases120) return GX_ERR_ORDER;
+  std::vector<u128_t> W((size_t)n_samples, 0);
+  for (int s = 0; s < n_samples; s++) {
+    if (!cn[s] || !cw120[s] || !cbases120[s]) return GX_ERR_ORDER;
+    for (int c = 0; c < n_chrom; c++) W[s] += cw120[s][c];
+    if (W[s] >> 64) return GX_ERR_ORDER;
+  }
+  fprintf(out, "# intervals, weight and share count every interval of the sample on the chromosome; mean_depth = sum of weight x length / chromosome length; a chromosome skipped with -e never reaches the library: its row is zeros\n");
+  fprintf(out, "chrom\tlength");
+  for (int s = 0; s < n_samples; s++) {
+    char lab[32];
+    snprintf(lab, sizeof lab, "%c%d", is_ctrl[s] ? 'c' : 't', rep[s]);
+    fprintf(out, "\t%s.intervals\t%s.weight\t%s.share\t%s.mean_depth", lab, lab, lab, lab);
+  }
+  fprintf(out, "\n");
+  for (int c = 0; c < n_chrom; c++) {
+    fprintf(out, "%s\t%u", names[c], lens[c]);
+    for (int s = 0; s < n_samples; s++) {
+      fprintf(out, "\t%llu", (unsigned long long)cn[s][c]);
+      put_w120(out, cw120[s][c]);
+      fprintf(out, "\t%.6f\t%.6f", W[s] ? (double)cw120[s][c] / (double)(uint64_t)W[s] : 0.0,
+              lens[c] ? (double)cbases120[s][c] / (double)(120ull * lens[c]) : 0.0);
+    }
+    fprintf(out, "\n");
+  }
   return GX_OK;
 }
 

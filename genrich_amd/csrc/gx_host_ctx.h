@@ -33,6 +33,7 @@
 #include "gx_fingerprint.h"
 #include "gx_rank.h"
 #include "gx_complexity.h"
+#include "gx_ivstat.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
@@ -487,6 +488,22 @@ struct gx_ctx {
   bool cpxReady = false;
   bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
   u32 cpxLastCapLog = 0;          // log2 of the capacity the last pass used (gx_complexity_last)
+  // lengths and chromosome tallies of the kept samples' intervals (gx_interval_stats / gx_interval_stats_events, gx_ivstat.h);
+  // nothing here exists before the first call
+  struct IvsResult {
+    int rep = 0;
+    bool ctrl = false;
+    u64 nInv = 0, wInv = 0;                 // the intervals that end before they start, their weight
+    std::vector<uint64_t> len, n, w;        // sparse: n[i] intervals of length len[i] (ascending), their weight
+    std::vector<uint64_t> cn, cw, cb;       // [nChrom] intervals, weight, sum of w L
+  };
+  DevBuf ivsOut, ivsBig;          // the control words + the counters; the list of long lengths
+  DevBuf ivsEv;                   // gx_interval_stats_events' copy of the caller's events
+  std::vector<IvsResult> ivs;     // the last gx_interval_stats, per kept sample (until gx_reset)
+  bool ivsReady = false;
+  bool ivsUsed = false;           // k_ivstat ran since the last gx_reset
+  size_t ivsLastCap = 0;          // the last pass: the list capacity it ended with, how often it ran again (gx_interval_stats_last)
+  u32 ivsLastReruns = 0;
   // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
   struct DepthResult {
     int rep = 0;

@@ -167,6 +167,11 @@ struct Opts {
   const char* complexityFile = nullptr;    // --complexity FILE: each sample's library complexity from its kept intervals
   const char* depthFile = nullptr;         // --depth FILE: each sample's per-base depth distribution from its pileup
   const char* depthMetricsFile = nullptr;  // --depth-metrics FILE: ... and the figures made of it
+  const char* lengthsFile = nullptr;        // --lengths FILE: each sample's interval lengths from its kept intervals
+  const char* lengthsMetricsFile = nullptr; // --lengths-metrics FILE: ... and the figures made of them
+  const char* chromStatsFile = nullptr;     // --chrom-stats FILE: ... and its intervals per chromosome
+  std::vector<uint64_t> lengthsCuts{150, 300, 500};   // --lengths-cuts A,B,...: the class borders of the metrics' shares
+  bool lengthsCutsOpt = false;
   const char* complexityHistFile = nullptr;   // --complexity-hist FILE: ... and its duplication histogram
   const char* saturationFile = nullptr;    // --saturation FILE: the peaks called once more on nested subsamples of the run's intervals
   int saturationSteps = 10;                // --saturation-steps N: the points of the curve, T_j = (j << 32) / N
@@ -2877,6 +2882,76 @@ void writeComplexity(State& S) {
   }
 }
 
+// --lengths FILE / --lengths-metrics FILE / --chrom-stats FILE: each sample's intervals (its -b lines) by length and by
+// chromosome, counted on the device (one pass per context and sample, added): one row per sample and occurring length, one row
+// of figures per sample (mean, sd, quantiles, mode, the shares of the --lengths-cuts classes), one row per chromosome with each
+// sample's intervals, weight, share and mean depth; labelled t<rep> / c<rep>.  With -j the intervals are cut-site windows, not
+// fragments, and the header says so.  With -v the median and mode, the shares and the fullest chromosome on stderr too
+void writeIntervalStats(State& S, const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n();
+  const size_t nC = names.size();
+  int nS = 0;
+  for (gx_ctx* g : S.devs.ctx) {   // (before a file is opened: a context's refusal carries its own text)
+    int n = 0;
+    check(S, gx_interval_stats(g, &n), g);
+    if (g != g0 && n != nS) die("", "--lengths: the devices kept different numbers of samples");
+    nS = n;
+  }
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> nInv((size_t)nS), wInv((size_t)nS);
+  std::vector<std::vector<uint64_t>> col((size_t)nS * 6);
+  std::vector<const uint64_t*> pl((size_t)nS), pn((size_t)nS), pw((size_t)nS), pcn((size_t)nS), pcw((size_t)nS), pcb((size_t)nS);
+  std::vector<size_t> np((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    check(S, gx_interval_stats_group(ctxs, nCtx, i, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &np[i], nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, 0), g0);
+    std::vector<uint64_t>* a = &col[(size_t)i * 6];
+    for (int k = 0; k < 3; k++) a[k].assign(std::max<size_t>(np[i], 1), 0);
+    for (int k = 3; k < 6; k++) a[k].assign(nC, 0);
+    check(S, gx_interval_stats_group(ctxs, nCtx, i, &rep[i], &ctrl[i], a[0].data(), a[1].data(), a[2].data(), np[i], nullptr, &nInv[i], &wInv[i],
+                                     a[3].data(), a[4].data(), a[5].data(), nC), g0);
+    pl[i] = a[0].data(); pn[i] = a[1].data(); pw[i] = a[2].data(); pcn[i] = a[3].data(); pcw[i] = a[4].data(); pcb[i] = a[5].data();
+  }
+  const uint64_t* cuts = o.lengthsCuts.data();
+  const int nCuts = (int)o.lengthsCuts.size();
+  if (o.lengthsFile) {
+    Out out = openWrite(o.lengthsFile, o.gzOut);
+    check(S, gx_format_lengths(out.f, nS, rep.data(), ctrl.data(), pl.data(), pn.data(), pw.data(), np.data(), nInv.data(), wInv.data(),
+                               o.atacOpt ? 1 : 0), g0);
+    closeOut(out);
+  }
+  if (o.lengthsMetricsFile) {
+    Out out = openWrite(o.lengthsMetricsFile, o.gzOut);
+    check(S, gx_format_lengths_metrics(out.f, nS, rep.data(), ctrl.data(), pl.data(), pn.data(), pw.data(), np.data(), cuts, nCuts), g0);
+    closeOut(out);
+  }
+  if (o.chromStatsFile) {
+    std::vector<uint32_t> lens;
+    for (const Chrom& ch : S.chrom) lens.push_back(ch.len);
+    Out out = openWrite(o.chromStatsFile, o.gzOut);
+    check(S, gx_format_chrom_stats(out.f, names.data(), lens.data(), (int)nC, nS, rep.data(), ctrl.data(), pcn.data(), pcw.data(), pcb.data()), g0);
+    closeOut(out);
+  }
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++) {
+    gx_len_metrics m;
+    check(S, gx_lengths_metrics(pl[i], pn[i], pw[i], np[i], cuts, nCuts, &m), g0);
+    size_t top = 0;
+    unsigned __int128 W = 0;
+    for (size_t c = 0; c < nC; c++) {
+      W += pcw[i][c];
+      if (pcw[i][c] > pcw[i][top]) top = c;
+    }
+    fprintf(stderr, "  Interval lengths%s, %s file #%d: %llu intervals, median %llu, mode %llu; shares", o.atacOpt ? " (cut-site windows)" : "",
+            ctrl[i] ? "control" : "experimental", rep[i], (unsigned long long)m.n, (unsigned long long)m.median, (unsigned long long)m.mode);
+    for (int k = 0; k <= nCuts; k++) fprintf(stderr, " %f", m.n ? m.share[k] : 0.0);
+    fprintf(stderr, "; most on %s (%f)\n", nC ? names[top] : "-", W ? (double)pcw[i][top] / (double)W : 0.0);
+  }
+}
+
 // --depth FILE / --depth-metrics FILE: the distribution of per-base depth of each sample's pileup, taken on the device when the
 // sample was closed (one pass per context, added): one row per sample and non-empty whole depth, and one row of figures per
 // sample (bases, covered, mean, sd, min, quartiles, percentiles, max, the fractions at 1x .. 100x), labelled t<rep> / c<rep>; with
@@ -3064,6 +3139,13 @@ void usage() {
           "                  (chromosome, start, end) keys: N, distinct, NRF, PBC1, PBC2, duplicate fraction, estimated library size and\n"
           "                  the expected distinct keys at 5 %% .. 100 %% of the depth, a TSV labelled t<rep> / c<rep>; the histogram\n"
           "                  file has the number of keys seen m times per sample and m\n"
+          "  --lengths FILE [--lengths-metrics FILE] [--lengths-cuts A,B,...] [--chrom-stats FILE]   each sample's intervals (the -b\n"
+          "                  lines) by length: a TSV labelled t<rep> / c<rep> with the intervals, their weight and the cumulative share of\n"
+          "                  the weight at every length that occurs; the metrics file has the mean, sd, min, p5, quartiles, p95, max, mode\n"
+          "                  and the shares of weight below A, from A to B, ... (150,300,500; at most 8 ascending positive integers); the\n"
+          "                  chrom-stats file has one row per chromosome with each sample's intervals, weight, share and mean depth (a\n"
+          "                  chromosome skipped with -e: zeros); each of the three files may stand alone; with -j the intervals are\n"
+          "                  cut-site windows, nearly all of one length, not fragments; not with -P or --events-only\n"
           "  --depth FILE [--depth-metrics FILE]   each sample's distribution of per-base depth over every base of the genome outside\n"
           "                  the -E regions: a TSV labelled t<rep> / c<rep> with the bases at each whole depth and at that depth or\n"
           "                  more; the metrics file (it may stand alone) has the bases, the share covered, mean, sd, min, quartiles,\n"
@@ -3120,6 +3202,10 @@ int main(int argc, char** argv) {
                                      {"saturation-controls", no_argument, nullptr, 1026},
                                      {"depth", required_argument, nullptr, 1027},
                                      {"depth-metrics", required_argument, nullptr, 1028},
+                                     {"lengths", required_argument, nullptr, 1030},
+                                     {"lengths-metrics", required_argument, nullptr, 1031},
+                                     {"lengths-cuts", required_argument, nullptr, 1032},
+                                     {"chrom-stats", required_argument, nullptr, 1033},
                                      {nullptr, 0, nullptr, 0}};
   {  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
     const char* e = getenv("GENRICH_THREADS");
@@ -3193,6 +3279,26 @@ int main(int argc, char** argv) {
       case 1022: o.complexityHistFile = optarg; break;
       case 1027: o.depthFile = optarg; break;
       case 1028: o.depthMetricsFile = optarg; break;
+      case 1030: o.lengthsFile = optarg; break;
+      case 1031: o.lengthsMetricsFile = optarg; break;
+      case 1033: o.chromStatsFile = optarg; break;
+      case 1032: {  // --lengths-cuts A,B,...: at most 8 ascending positive integers
+        o.lengthsCuts.clear();
+        o.lengthsCutsOpt = true;
+        const char* t = optarg;
+        for (bool more = true; more;) {
+          char* end;
+          errno = 0;
+          const unsigned long long v = strtoull(t, &end, 10);
+          if (!isdigit((unsigned char)t[0]) || errno == ERANGE || v == 0 || v >> 32 || (*end != ',' && *end != '\0') ||
+              (!o.lengthsCuts.empty() && v <= o.lengthsCuts.back()) || o.lengthsCuts.size() == GX_LEN_MAX_CUTS)
+            die(optarg, ": --lengths-cuts takes at most 8 ascending positive integers, A,B,...");
+          o.lengthsCuts.push_back(v);
+          more = *end == ',';
+          t = end + 1;
+        }
+        break;
+      }
       case 1023: o.saturationFile = optarg; break;
       case 1024: o.saturationSteps = getInt(optarg); o.saturationStepsOpt = true; break;
       case 1025: {
@@ -3244,6 +3350,10 @@ int main(int argc, char** argv) {
   // (the complexity counts the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.complexityFile && (o.peaksOnly || o.eventsOnly)) die("", "--complexity needs the intervals of this run (not with -P or --events-only)");
   if (o.complexityHistFile && !o.complexityFile) die("", "--complexity-hist needs --complexity FILE");
+  // (the lengths and tallies count the events the library keeps: none with -P or --events-only; -X is fine)
+  if ((o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile) && (o.peaksOnly || o.eventsOnly))
+    die("", "--lengths, --lengths-metrics and --chrom-stats need the intervals of this run (not with -P or --events-only)");
+  if (o.lengthsCutsOpt && !o.lengthsMetricsFile) die("", "--lengths-cuts needs --lengths-metrics FILE");
   // (the distribution is taken from the pileups this run builds: none with -P or --events-only; -X is fine)
   if ((o.depthFile || o.depthMetricsFile) && (o.peaksOnly || o.eventsOnly))
     die("", "--depth and --depth-metrics need the pileups of this run (not with -P or --events-only)");
@@ -3362,7 +3472,8 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile) check(S, gx_set_count_in_peaks(g, 1), g);
+      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
+        check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
     S.gx = D.ctx[0];
@@ -3541,6 +3652,7 @@ int main(int argc, char** argv) {
   if (o.spearmanFile) writeSpearman(S);
   if (o.fingerprintFile) writeFingerprint(S);
   if (o.complexityFile) writeComplexity(S);
+  if (o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile) writeIntervalStats(S, names);
   if (o.depthFile || o.depthMetricsFile) writeDepth(S);
   if (o.saturationFile) writeSaturation(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);

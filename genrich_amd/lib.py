@@ -142,6 +142,11 @@ FP_METRICS_DTYPE = np.dtype([(k, "<f8") for k in ("zero_fraction", "auc", "gini"
 
 GX_PATH_SPEARMAN = 4194304      # gx_path_info bit 22: k_rank ran (gx_coverage_rank_gram, gx_rank_u64)
 GX_PATH_COMPLEXITY = 8388608    # gx_path_info bit 23: k_cpx_insert ran (gx_complexity, gx_complexity_events)
+GX_PATH_IVSTAT = 67108864       # gx_path_info bit 26: k_ivstat ran (gx_interval_stats, gx_interval_stats_events)
+LEN_MAX_CUTS = 8                # GX_LEN_MAX_CUTS: the most class borders gx_lengths_metrics takes
+LEN_METRICS_DTYPE = np.dtype([(f, "<u8") for f in ("n", "w120", "min", "max", "mode", "p5", "q25", "median", "q75", "p95")]
+                             + [("mean", "<f8"), ("sd", "<f8"), ("n_shares", "<i4"), ("_pad", "<i4"),
+                                ("share", "<f8", (LEN_MAX_CUTS + 1,))])   # gx_len_metrics
 CPX_CURVE = 20                  # GX_CPX_CURVE: the points of the complexity curve (5 % steps of the depth)
 CPX_METRICS_DTYPE = np.dtype([("h1", "<u8"), ("h2", "<u8")] + [(k, "<f8") for k in ("nrf", "pbc1", "pbc2", "dup_fraction", "library_size")]
                              + [("curve", "<f8", (CPX_CURVE,))])   # gx_cpx_metrics
@@ -182,6 +187,19 @@ class Depth(NamedTuple):
     rsum: np.ndarray
     rsq: np.ndarray
     deep: list
+
+
+class IntervalStats(NamedTuple):
+    """One sample's interval lengths and chromosome tallies (gx_get_interval_lengths, gx_get_chrom_stats): lengths = [(L, n, w120)]
+    ascending, the inverted intervals, and cn / cw120 / cbases120 per chromosome of the table."""
+    lengths: list
+    n_inverted: int
+    w120_inverted: int
+    cn: list
+    cw120: list
+    cbases120: list
+    rep: int = 0
+    is_ctrl: bool = False
 
 
 class Complexity(NamedTuple):
@@ -333,6 +351,21 @@ _SIGS = {
     "gx_complexity_last": [C.c_void_p, C.POINTER(C.c_size_t)],
     "gx_complexity_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_interval_stats": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_interval_lengths": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "gx_get_chrom_stats": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_interval_stats_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_interval_stats_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)],
+    "gx_interval_stats_last": [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "gx_interval_stats_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_lengths_metrics": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_format_lengths": [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int],
+    "gx_format_lengths_metrics": [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int],
+    "gx_format_chrom_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5,
+    "gx_write_interval_stats_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "gx_complexity_metrics": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     "gx_format_complexity": [C.c_void_p, C.c_int] + [C.c_void_p] * 7,
     "gx_format_complexity_hist": [C.c_void_p, C.c_int] + [C.c_void_p] * 5,
@@ -644,6 +677,74 @@ def format_peak_signal(names, peaks, samples) -> bytes:
     ctrl = (C.c_int * max(S, 1))(*[int(x.is_ctrl) for x in samples])
     cn = _c_names(list(names))
     return _to_tmpfile(lambda f: lib.gx_format_peak_signal(f, cn, reg.ctypes.data if reg.size else None, reg.size, S, rep, ctrl, *ptrs))
+
+
+def interval_stats_geometry():
+    """(lanes, grid, lds_bound, chrom_window, list_capacity) of the interval-length pass as the library was built
+    (gx_interval_stats_geometry): the lanes of a workgroup of k_ivstat, its most workgroups with grid = 0, the length from which
+    an interval goes to the list instead of an LDS counter, the chromosomes tallied in LDS, and the list's first capacity."""
+    lib = load_library()
+    lanes, grid, bound, win, cap = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    lib.gx_interval_stats_geometry(C.byref(lanes), C.byref(grid), C.byref(bound), C.byref(win), C.byref(cap))
+    return lanes.value, grid.value, bound.value, win.value, cap.value
+
+
+def _len_cols(lengths):
+    return tuple(np.ascontiguousarray([t[k] for t in lengths], dtype=np.uint64) for k in range(3))
+
+
+def lengths_metrics(lengths, cuts=(150, 300, 500)):
+    """gx_lengths_metrics as one LEN_METRICS_DTYPE record; lengths: [(L, n, w120)] ascending; host-only."""
+    lib = load_library()
+    L, n, w = _len_cols(lengths)
+    c = np.ascontiguousarray(list(cuts), dtype=np.uint64)
+    out = np.zeros(1, dtype=LEN_METRICS_DTYPE)
+    rc = lib.gx_lengths_metrics(L.ctypes.data if L.size else None, n.ctypes.data if L.size else None, w.ctypes.data if L.size else None, L.size,
+                                c.ctypes.data if c.size else None, c.size, out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_lengths_metrics: {rc}")
+    return out[0]
+
+
+def _ivs_result(call, n_chrom):
+    """An IntervalStats from call(rep, ctrl, length, n, w120, cap, n_classes, n_inv, w_inv, cn, cw, cb, chrom_cap), asked twice."""
+    n = C.c_size_t(0)
+    call(None, None, None, None, None, 0, C.byref(n), None, None, None, None, None, 0)
+    L, k, w = (np.zeros(max(n.value, 1), dtype=np.uint64) for _ in range(3))
+    cn, cw, cb = (np.zeros(max(n_chrom, 1), dtype=np.uint64) for _ in range(3))
+    rep, ctrl, ni, wi = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+    call(C.byref(rep), C.byref(ctrl), L.ctypes.data, k.ctypes.data, w.ctypes.data, n.value, C.byref(n), C.byref(ni), C.byref(wi), cn.ctypes.data,
+         cw.ctypes.data, cb.ctypes.data, n_chrom)
+    return IntervalStats([(int(a), int(b), int(c)) for a, b, c in zip(L[:n.value], k[:n.value], w[:n.value])], ni.value, wi.value,
+                         [int(x) for x in cn[:n_chrom]], [int(x) for x in cw[:n_chrom]], [int(x) for x in cb[:n_chrom]], rep.value, bool(ctrl.value))
+
+
+def interval_stats_group(ctxs, sample):
+    """IntervalStats of one sample added over the contexts of a run (gx_interval_stats_group); every context has run interval_stats()."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _ivs_result(lambda *a: ctxs[0]._check(lib.gx_interval_stats_group(arr, len(ctxs), int(sample), *a)), ctxs[0].n_chrom)
+
+
+def interval_stats_text(ctxs, names, cut_sites=False, cuts=(150, 300, 500)):
+    """(--lengths' table, --lengths-metrics', --chrom-stats') over the contexts of a run (gx_write_interval_stats_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    cn = _c_names(list(names))
+    c = np.ascontiguousarray(list(cuts), dtype=np.uint64)
+    out = []
+    try:
+        for k in range(3):
+            files = [None, None, None]
+
+            def one(f):
+                files[k] = f
+                return lib.gx_write_interval_stats_group(arr, len(ctxs), cn, len(names), int(bool(cut_sites)), c.ctypes.data if c.size else None,
+                                                         c.size, *files)
+            out.append(_to_tmpfile(one))
+    except RuntimeError as e:
+        raise RuntimeError(f"{e} [{'; '.join(lib.gx_last_error(x.ctx).decode() for x in ctxs)}]") from None
+    return tuple(out)
 
 
 def complexity_geometry(n=0):
@@ -1157,7 +1258,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -1358,6 +1459,42 @@ class Genrich:
         c = C.c_size_t(0)
         self._check(self.lib.gx_complexity_last(self.ctx, C.byref(c)))
         return c.value
+
+    # -- lengths and chromosome tallies of the samples' intervals (include/genrich_amd.h, gx_interval_stats) --------------
+    def interval_stats(self):
+        """The lengths and the chromosome tallies of every sample closed so far (gx_interval_stats); needs set_count_in_peaks(True),
+        no peaks.  Returns the number of samples."""
+        n = C.c_int(0)
+        self._check(self.lib.gx_interval_stats(self.ctx, C.byref(n)))
+        return n.value
+
+    def get_interval_stats(self, sample):
+        """IntervalStats of one sample of the last interval_stats() (gx_get_interval_lengths + gx_get_chrom_stats)."""
+        def call(rep, ctrl, L, n, w, cap, nc, ni, wi, cn, cw, cb, ccap):
+            self._check(self.lib.gx_get_interval_lengths(self.ctx, int(sample), rep, ctrl, L, n, w, cap, nc, ni, wi))
+            if ccap:
+                self._check(self.lib.gx_get_chrom_stats(self.ctx, int(sample), cn, cw, cb, ccap))
+        return _ivs_result(call, self.n_chrom)
+
+    def interval_stats_events(self, events, grid=0, list_cap=0):
+        """IntervalStats of host events (EVENT_DTYPE) taken as one sample over this context's chromosome table, by the same kernel
+        (gx_interval_stats_events); grid = 0 / list_cap = 0: the library's geometry and first list capacity."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+        cap = int(ev.size) + 1   # (at most one class per event)
+        L, k, w = (np.zeros(cap, dtype=np.uint64) for _ in range(3))
+        cn, cw, cb = (np.zeros(self.n_chrom, dtype=np.uint64) for _ in range(3))
+        n, ni, wi = C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_interval_stats_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, int(grid), int(list_cap), L.ctypes.data,
+                                                      k.ctypes.data, w.ctypes.data, cap, C.byref(n), C.byref(ni), C.byref(wi), cn.ctypes.data,
+                                                      cw.ctypes.data, cb.ctypes.data, self.n_chrom))
+        return IntervalStats([(int(a), int(b), int(c)) for a, b, c in zip(L[:n.value], k[:n.value], w[:n.value])], ni.value, wi.value,
+                             [int(x) for x in cn], [int(x) for x in cw], [int(x) for x in cb])
+
+    def interval_stats_last(self):
+        """(list capacity, reruns) of the last interval-length pass of this context (gx_interval_stats_last)."""
+        c, r = C.c_size_t(0), C.c_int(0)
+        self._check(self.lib.gx_interval_stats_last(self.ctx, C.byref(c), C.byref(r)))
+        return c.value, r.value
 
     # -- subsamples of the kept samples and the peak saturation curve (include/genrich_amd.h, gx_saturation) ----------------
     def subsample_events(self, events, seed, sample, threshold, grid=0, packed=False):

@@ -569,6 +569,62 @@ int gx_complexity_last(gx_ctx* ctx, size_t* capacity);
 int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct,
                         uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes);
 
+/* ---- lengths and per-chromosome tallies of each sample's intervals (no Genrich counterpart: the fragment-length distribution
+ *      of deepTools' bamPEFragmentSize or Picard's CollectInsertSizeMetrics, and `samtools idxstats`, which otherwise want
+ *      another reading of the BAM) ----
+ * A sample = every gx_sample_end of the run in call order, as for gx_count_in_peaks.  Its intervals are exactly those
+ * gx_count_in_peaks counts, i.e. its -b lines (the rule is gx_complexity's, above): count valid, chromosome known, not skipped
+ * (-e), in the sample's save mask and owned by this context, start < the chromosome's length, the end clamped to that length;
+ * empty intervals are included.  An interval whose clamped end lies below its start is INVERTED and has no length; every other
+ * has the length L = end - start >= 0.  Its weight is w = 120 / count, in 1/120 units.  Per sample, all exact uint64:
+ *     n[L], w120[L]             the intervals of length L and their summed weight, for every L that occurs
+ *     n_inverted, w120_inverted the inverted intervals: counted only here and in cn / cw120
+ *     cn[c], cw120[c]           the intervals on chromosome c of the table and their weight
+ *     cbases120[c]              sum of w L over the intervals on c that have a length: 120 x the bases they cover, with multiplicity
+ * so that sum n[L] + n_inverted = sum cn[c], the same for the weights, and sum w120[L] L = sum cbases120[c]: the host checks
+ * the three after every pass (GX_ERR_DEVICE with a text when one fails).  A chromosome lives on one context, so the contexts'
+ * results simply add (gx_interval_stats_group does).  The result is the same for every launch geometry, list capacity, push
+ * mode and number of GPUs: integer adds only.  A chromosome skipped with -e never reaches the library: its tallies are zeros.
+ * In -j ATAC mode the intervals are cut-site windows, two per fragment and nearly all of one length: the figures describe
+ * those windows, not fragments.
+ * Limits, each refused with GX_ERR_ORDER and a text before anything is allocated or launched: a sample of 2^31 events or
+ * more on one context; more than 65535 workgroups; a grid that lets a workgroup see more than 272 chunks of 65536 events
+ * (its LDS counters are 32 bits).
+ *
+ * gx_interval_stats: the pass (k_ivstat, gx_ivstat.h) over every sample closed so far (*n_samples of them).  It needs
+ *   gx_set_count_in_peaks on, at least one closed sample and none open, else GX_ERR_ORDER with a text; it needs no gx_pvalues
+ *   and no gx_find_peaks, and may be called again: the same answer.  The results of gx_count_in_peaks, gx_count_in_regions and
+ *   gx_complexity stay readable.  gx_reset drops the result.  A failed allocation: GX_ERR_MEM.  Lengths of GX_IVS_BOUND or
+ *   more go through a list in device memory; when it runs full the sample is run once more with a list of the counted size,
+ *   exactly once.  Nothing of it is allocated or launched before the first call.
+ * gx_get_interval_lengths: the last pass's result for one sample (0 .. n_samples-1): its replicate, whether it is a control,
+ *   min(cap, n_classes) entries in length[] / n[] / w120[] ascending in the length, *n_classes and the inverted ones.  Any
+ *   pointer may be NULL (the arrays when cap is 0).
+ * gx_get_chrom_stats: min(cap, chromosomes) entries per array, in table order.
+ * gx_interval_stats_events: the same kernel over n events in host memory (copied to the device by the call), all treated as ONE
+ *   sample whose save mask lists every chromosome of the context's table (-e and gx_set_owned hold as for a sample).  grid = 0
+ *   and list_cap = 0: the library's choices; else that many workgroups and a list of that many entries at first.  No sample
+ *   open.  For tests and measurements; it leaves the kept result alone.
+ * gx_interval_stats_geometry: what the edge cases depend on: the lanes of a workgroup, the most workgroups with grid = 0 (more
+ *   only when a sample has more than 272 chunks per workgroup), the length from which an interval goes to the list, the
+ *   chromosomes tallied in LDS (the others by global atomics), and the list's first capacity.  Any pointer may be NULL.
+ * gx_interval_stats_last: the list capacity the last pass ended with and how often it ran again (0 or 1).
+ * gx_interval_stats_group: sample `sample` of every context's last gx_interval_stats, added; the outputs as the two getters'.
+ *   A context without a result, or contexts that differ in their samples: GX_ERR_ORDER. */
+#define GX_IVS_BOUND 4096
+int gx_interval_stats(gx_ctx* ctx, int* n_samples);
+int gx_get_interval_lengths(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120, size_t cap,
+                            size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted);
+int gx_get_chrom_stats(gx_ctx* ctx, int sample, uint64_t* cn, uint64_t* cw120, uint64_t* cbases120, size_t cap);
+int gx_interval_stats_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, size_t list_cap, uint64_t* length, uint64_t* n_iv,
+                             uint64_t* w120, size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn,
+                             uint64_t* cw120, uint64_t* cbases120, size_t chrom_cap);
+int gx_interval_stats_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint32_t* chrom_window, size_t* list_capacity);
+int gx_interval_stats_last(gx_ctx* ctx, size_t* list_capacity, int* reruns);
+int gx_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120,
+                            size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120,
+                            uint64_t* cbases120, size_t chrom_cap);
+
 /* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
  *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
@@ -862,6 +918,44 @@ int gx_format_complexity(FILE* out, int n_samples, const int* rep, const int* is
 int gx_format_complexity_hist(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* mult,
                               const uint64_t* const* keys, const size_t* n_pairs);
 int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist);
+/* --lengths / --lengths-metrics / --chrom-stats (no Genrich counterpart).  The first four: host only, no context.  A sample's
+ * lengths are n_classes entries (length[i], n[i], w120[i]): length strictly ascending and below 2^32, n >= 1, n <= w120 <= 120 n
+ * (else GX_ERR_ORDER).  cuts: n_cuts <= GX_LEN_MAX_CUTS strictly ascending positive lengths.
+ * gx_lengths_metrics, every figure over WEIGHT (W = sum w120): n = sum n; mean = sum w L / W and sd = sqrt(W sum w L^2 -
+ *   (sum w L)^2) / W (population) from exact 128- / 256-bit sums, doubles only at the end, NaN for an empty sample; min, max;
+ *   mode = the smallest L of the greatest weight; p5, q25, median, q75, p95 = the smallest L whose cumulative weight times 100
+ *   is >= q W, in integers; share[k], k = 0 .. n_cuts: the share of W with cuts[k - 1] <= L < cuts[k] (150,300,500: the
+ *   nucleosome-free / mono- / di-nucleosome / longer reading of an ATAC library).  Inverted intervals take no part.
+ * gx_format_lengths: a comment line that says what an interval is (cut_sites != 0: the cut-site windows of -j), then a TSV, header
+ *   "sample length intervals weight cum_weight_share", one row per sample (t<rep> / c<rep>) and length; weight as --counts prints
+ *   a 1/120 value (an integer, else %.2f), the share as %.6f of the sample's W; then one row "inverted" per sample that has any
+ *   (share NA).
+ * gx_format_lengths_metrics: header "sample intervals weight mean sd min p5 q25 median q75 p95 max mode lt<A> ge<A>_lt<B> ...
+ *   ge<Z>", one row per sample; mean and sd %.6f (NA when empty), shares %.6f.
+ * gx_format_chrom_stats: a comment line, then header "chrom length" and per sample "<s>.intervals <s>.weight <s>.share
+ *   <s>.mean_depth"; one row per chromosome in table order; share = cw120 over the sample's whole weight, mean_depth =
+ *   cbases120 / (120 length), both %.6f (0 when the divisor is 0).  A chromosome skipped with -e: zeros.
+ * gx_write_interval_stats_group (gx_api.hip: it reads contexts): gx_interval_stats on every context, the group sums per
+ *   sample, then whichever of the three files is not NULL (at least one). */
+#define GX_LEN_MAX_CUTS 8
+typedef struct {
+  uint64_t n, w120;
+  uint64_t min, max, mode, p5, q25, median, q75, p95;
+  double mean, sd;
+  int n_shares;
+  double share[GX_LEN_MAX_CUTS + 1];
+} gx_len_metrics;
+int gx_lengths_metrics(const uint64_t* length, const uint64_t* n, const uint64_t* w120, size_t n_classes, const uint64_t* cuts, int n_cuts,
+                       gx_len_metrics* out);
+int gx_format_lengths(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* length, const uint64_t* const* n,
+                      const uint64_t* const* w120, const size_t* n_classes, const uint64_t* n_inverted, const uint64_t* w120_inverted,
+                      int cut_sites);
+int gx_format_lengths_metrics(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* const* length,
+                              const uint64_t* const* n, const uint64_t* const* w120, const size_t* n_classes, const uint64_t* cuts, int n_cuts);
+int gx_format_chrom_stats(FILE* out, const char* const* names, const uint32_t* lens, int n_chrom, int n_samples, const int* rep,
+                          const int* is_ctrl, const uint64_t* const* cn, const uint64_t* const* cw120, const uint64_t* const* cbases120);
+int gx_write_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_chrom, int cut_sites, const uint64_t* cuts,
+                                  int n_cuts, FILE* lengths, FILE* metrics, FILE* chroms);
 /* --depth / --depth-metrics (no Genrich counterpart).  The first three: host only, no context.  A histogram that contradicts
  * itself (a missing array, excluded > total, covered + zero != B, rsum[d] > 119 bases[d], a deep list that is not strictly
  * ascending from 120 GX_DEPTH_BOUND, covered bases without min_v <= max_v): GX_ERR_ORDER, nothing written.
@@ -1004,6 +1098,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_COMPLEXITY 8388608u /* bit 23: k_cpx_insert ran since the last gx_reset (gx_complexity, gx_complexity_events) */
 #define GX_PATH_SATURATION 16777216u /* bit 24: k_sub_write ran since the last gx_reset (gx_subsample_events, gx_subsample_kept, gx_saturation) */
 #define GX_PATH_DEPTH 33554432u /* bit 25: k_depth_hist ran since the last gx_reset (gx_set_depth_hist; a sample was closed with it on) */
+#define GX_PATH_IVSTAT 67108864u /* bit 26: k_ivstat ran since the last gx_reset (gx_interval_stats, gx_interval_stats_events) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
