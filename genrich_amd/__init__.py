@@ -13,3 +13,4 @@ from .lib import GX_PATH_GRAM, U128_DTYPE, correlation_matrix, format_correlatio
 from .lib import GX_PATH_FINGERPRINT, FP_NC, FP_METRICS_DTYPE, fp_geometry, fp_class, fp_class_lo, fp_class_hi  # noqa: F401
 from .lib import fingerprint_metrics, format_fingerprint, format_fingerprint_metrics  # noqa: F401
 from .lib import GX_PATH_IVSTAT, IntervalStats, interval_stats_geometry, interval_stats_group, interval_stats_text, lengths_metrics  # noqa: F401
+from .lib import GX_PATH_XCOR, TAG_DTYPE, Xcor, xcor_geometry, xcor_group, xcor_metrics, xcor_r, xcor_text, format_xcor, format_xcor_metrics  # noqa: F401

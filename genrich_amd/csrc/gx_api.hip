@@ -17,6 +17,7 @@
 #include "gx_host_rank.h"
 #include "gx_host_complexity.h"
 #include "gx_host_ivstat.h"
+#include "gx_host_xcor.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
@@ -138,6 +139,7 @@ void gx_destroy(gx_ctx* ctx) {
   if (ctx->sideEv) (void)hipEventDestroy(ctx->sideEv);
   for (hipEvent_t e : ctx->evPool) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->stageFree) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->xcStageFree) if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
 
@@ -164,6 +166,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
   }
   ctx->covDirty = true;
   ctx->profDirty = true;
+  ctx->xcDirty = ctx->xcOn;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -234,6 +237,7 @@ int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   ctx->owned.assign(owned, owned + ctx->nChrom);
   ctx->covDirty = true;
   ctx->profDirty = true;
+  ctx->xcDirty = ctx->xcOn;
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -267,6 +271,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_coverage(ctx);   // (... and gx_set_coverage_bins')
   drop_profile(ctx);    // (... and gx_set_profile's)
   drop_depth(ctx);      // (... and gx_set_depth_hist's)
+  drop_xcor(ctx);       // (... and gx_set_xcor's)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
@@ -321,6 +326,8 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   ctx->evChunkIdx = ctx->evChunkFill = ctx->evPoolUsed = 0;  // (the previous sample's uploads were consumed: gx_sample_end synchronised)
   ctx->satDone = false;
   ctx->satDropped = 0;
+  if (ctx->xcOn)
+    if (int rc = xc_begin(ctx)) return rc;
   return GX_OK;
 }
 
@@ -449,6 +456,8 @@ int gx_sample_end(gx_ctx* ctx, double* frag_len, float* lambda, float* factor) {
     if (int rc = cov_sample(ctx, ctx->phase == 4)) return rc;
   if (ctx->depthOn)
     if (int rc = depth_sample(ctx, ctx->phase == 4)) return rc;
+  if (ctx->xcOn)
+    if (int rc = xc_sample(ctx, ctx->phase == 4)) return rc;
   if (!ctx->profAnchors.empty())
     if (int rc = prof_sample(ctx, ctx->phase == 4)) return rc;
   if (ctx->countOn) keep_sample(ctx, ctx->phase == 4);
@@ -869,7 +878,8 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
-           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u);
+           (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u);
   return GX_OK;
 }
 
@@ -1700,6 +1710,110 @@ int gx_write_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, const char* co
     for (size_t c = 0; c < nC; c++) lens[c] = ctxs[0]->hChrom[c].len;
     if (int rc = gx_format_chrom_stats(chroms, names, lens.data(), (int)nC, nS, rep.data(), ctrl.data(), pcn.data(), pcw.data(), pcb.data())) return rc;
   }
+  return GX_OK;
+}
+
+int gx_set_xcor(gx_ctx* ctx, int lo, int hi) {
+  if (!ctx || ctx->nChrom == 0 || ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;   // idle, and the table is known
+  HIPCHECK(hipSetDevice(ctx->device));
+  drop_xcor(ctx);
+  if (hi < lo) {   // off: the vectors go
+    ctx->xcOn = ctx->xcDirty = false;
+    ctx->xcLo = 0;
+    ctx->xcHi = -1;
+    HIPCHECK(hipStreamSynchronize(ctx->stream));
+    ctx->xcPlus.release();
+    ctx->xcMinus.release();
+    return GX_OK;
+  }
+  const int oldLo = ctx->xcLo, oldHi = ctx->xcHi;
+  ctx->xcLo = lo;
+  ctx->xcHi = hi;
+  if (int rc = xc_layout(ctx)) {   // (a refused setting leaves the old one)
+    ctx->xcLo = oldLo;
+    ctx->xcHi = oldHi;
+    return rc;
+  }
+  ctx->xcOn = true;
+  return GX_OK;
+}
+
+int gx_push_tags(gx_ctx* ctx, const gx_tag* tags, size_t n) {
+  if (!ctx || !ctx->xcOn || (ctx->phase != 1 && ctx->phase != 3) || (n && !tags)) return GX_ERR_ORDER;
+  if (!n) return GX_OK;
+  HIPCHECK(hipSetDevice(ctx->device));
+  return xc_push(ctx, tags, n);
+}
+
+int gx_xcor_samples(gx_ctx* ctx, int* n_samples) {
+  if (!ctx || !n_samples) return GX_ERR_ORDER;
+  *n_samples = (int)ctx->xc.size();
+  return GX_OK;
+}
+
+int gx_get_xcor(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, int* lo,
+                int* hi, uint64_t* n11, size_t cap) {
+  if (!ctx || sample < 0 || (size_t)sample >= ctx->xc.size()) return GX_ERR_ORDER;
+  return xc_give(ctx->xc[sample], ctx->xcLo, ctx->xcHi, rep, is_ctrl, n_pos, n_plus, n_minus, rejected, lo, hi, n11, cap);
+}
+
+// (the two over contexts live here, not in gx_emit.cpp: they read contexts)
+int gx_xcor_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus,
+                  uint64_t* rejected, int* lo, int* hi, uint64_t* n11, size_t cap) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0]) return GX_ERR_ORDER;
+  gx_ctx::XcResult sum;
+  for (int g = 0; g < n_ctx; g++) {
+    gx_ctx* c = ctxs[g];
+    if (!c || sample < 0 || (size_t)sample >= c->xc.size() || c->xc.size() != ctxs[0]->xc.size() || c->xcLo != ctxs[0]->xcLo ||
+        c->xcHi != ctxs[0]->xcHi || c->xc[sample].rep != ctxs[0]->xc[sample].rep || c->xc[sample].ctrl != ctxs[0]->xc[sample].ctrl)
+      return GX_ERR_ORDER;
+    if (g == 0) {
+      sum.rep = c->xc[sample].rep;
+      sum.ctrl = c->xc[sample].ctrl;
+    }
+    xc_add(sum, c->xc[sample]);
+  }
+  return xc_give(sum, ctxs[0]->xcLo, ctxs[0]->xcHi, rep, is_ctrl, n_pos, n_plus, n_minus, rejected, lo, hi, n11, cap);
+}
+
+int gx_xcor_tags(gx_ctx* ctx, const uint32_t* lens, int n_chrom, const gx_tag* tags, size_t n, int lo, int hi, unsigned grid, uint32_t tile_words,
+                 uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, uint64_t* n11, size_t cap) {
+  if (!ctx || !lens || n_chrom < 1 || (n && !tags) || (cap && !n11)) return GX_ERR_ORDER;
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_xcor_tags: a sample is open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  gx_ctx::XcResult r;
+  if (int rc = xc_tags(ctx, lens, n_chrom, tags, n, lo, hi, grid, tile_words, r)) return rc;
+  return xc_give(r, lo, hi, nullptr, nullptr, n_pos, n_plus, n_minus, rejected, nullptr, nullptr, n11, cap);
+}
+
+int gx_xcor_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* pad_words_for_4096, uint64_t* flush_words) {
+  static_assert(XC_MAX_SHIFT == GX_XCOR_MAX_SHIFT && XC_MIN_TILE == GX_XCOR_MIN_TILE, "the header's limits are the kernel's");
+  if (lanes) *lanes = (int)XC_NT;
+  if (grid) *grid = (int)XC_GRID;
+  if (tile_words) *tile_words = XC_TILE;
+  if (pad_words_for_4096) *pad_words_for_4096 = xc_pad_words(-XC_MAX_SHIFT, XC_MAX_SHIFT);
+  if (flush_words) *flush_words = XC_FLUSH_WORDS;
+  return GX_OK;
+}
+
+int gx_write_xcor_group(gx_ctx* const* ctxs, int n_ctx, int read_len, FILE* curve, FILE* metrics) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || (!curve && !metrics)) return GX_ERR_ORDER;
+  const int nS = (int)ctxs[0]->xc.size();
+  if (nS < 1) return GX_ERR_ORDER;
+  int lo = 0, hi = -1;
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> N((size_t)nS), nP((size_t)nS), nM((size_t)nS), rej((size_t)nS);
+  std::vector<std::vector<uint64_t>> col((size_t)nS);
+  std::vector<const uint64_t*> pc((size_t)nS);
+  for (int i = 0; i < nS; i++) {
+    col[i].assign((size_t)(ctxs[0]->xcHi - ctxs[0]->xcLo + 1), 0);
+    if (int rc = gx_xcor_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], &N[i], &nP[i], &nM[i], &rej[i], &lo, &hi, col[i].data(), col[i].size())) return rc;
+    pc[i] = col[i].data();
+  }
+  if (curve)
+    if (int rc = gx_format_xcor(curve, nS, rep.data(), ctrl.data(), N.data(), nP.data(), nM.data(), rej.data(), lo, hi, pc.data())) return rc;
+  if (metrics)
+    if (int rc = gx_format_xcor_metrics(metrics, nS, rep.data(), ctrl.data(), N.data(), nP.data(), nM.data(), lo, hi, pc.data(), read_len)) return rc;
   return GX_OK;
 }
 

@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the interval length and chromosome tables (--lengths, --chrom-stats), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the interval length and chromosome tables (--lengths, --chrom-stats), the strand cross-correlation tables (--xcor), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -871,6 +871,126 @@ int gx_format_chrom_stats(FILE* out, const char* const* names, const uint32_t* l
       fprintf(out, "\t%.6f\t%.6f", W[s] ? (double)cw120[s][c] / (double)(uint64_t)W[s] : 0.0,
               lens[c] ? (double)cbases120[s][c] / (double)(120ull * lens[c]) : 0.0);
     }
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// --xcor / --xcor-metrics: the curve and the figures from the integers alone
+namespace {
+bool xcor_counts_ok(uint64_t N, uint64_t nP, uint64_t nM, int lo, int hi, const uint64_t* n11) {
+  if (lo < -GX_XCOR_MAX_SHIFT || hi > GX_XCOR_MAX_SHIFT || lo > hi || !n11 || nP > N || nM > N) return false;
+  for (int d = lo; d <= hi; d++)
+    if (n11[d - lo] > nP || n11[d - lo] > nM) return false;
+  return true;
+}
+// r(d) for every shift: the numerator N n11 - nP nM (a signed 128-bit integer: both products lie below 2^128) and the radicand
+// nP (N - nP) nM (N - nM) (256 bits) exact, each converted once (to_double), one square root, one division; NaN when the
+// radicand is 0
+void xcor_curve(uint64_t N, uint64_t nP, uint64_t nM, int lo, int hi, const uint64_t* n11, double* r) {
+  const U256 rad = mul128((u128_t)nP * (N - nP), (u128_t)nM * (N - nM));
+  const bool none = cmp256(rad, U256()) == 0;
+  const double den = none ? 0.0 : std::sqrt(to_double(rad));
+  const u128_t pm = (u128_t)nP * nM;
+  for (int d = lo; d <= hi; d++) {
+    if (none) {
+      r[d - lo] = std::nan("");
+      continue;
+    }
+    const u128_t a = (u128_t)N * n11[d - lo];
+    const double num = a >= pm ? to_double(u256_of(a - pm)) : -to_double(u256_of(pm - a));
+    r[d - lo] = num / den;
+  }
+}
+}  // namespace
+
+int gx_xcor_r(uint64_t n_pos, uint64_t n_plus, uint64_t n_minus, int lo, int hi, const uint64_t* n11, double* r) {
+  if (!r || !xcor_counts_ok(n_pos, n_plus, n_minus, lo, hi, n11)) return GX_ERR_ORDER;
+  xcor_curve(n_pos, n_plus, n_minus, lo, hi, n11, r);
+  return GX_OK;
+}
+
+int gx_xcor_metrics(uint64_t n_pos, uint64_t n_plus, uint64_t n_minus, int lo, int hi, const uint64_t* n11, int read_len, gx_xcor_metrics_t* out) {
+  if (!out || read_len < 0 || !xcor_counts_ok(n_pos, n_plus, n_minus, lo, hi, n11)) return GX_ERR_ORDER;
+  std::vector<double> r((size_t)(hi - lo + 1));
+  xcor_curve(n_pos, n_plus, n_minus, lo, hi, n11, r.data());
+  gx_xcor_metrics_t m{};
+  const double nan = std::nan("");
+  m.r_frag = m.r_min = m.r_phantom = m.nsc = m.rsc = nan;
+  const int ph = read_len - 1;
+  m.phantom_shift = read_len ? ph : 0;
+  m.has_phantom = read_len && ph >= lo && ph <= hi;
+  if (m.has_phantom) m.r_phantom = r[(size_t)(ph - lo)];
+  m.min_shift = lo;
+  if (!std::isnan(r[0])) {   // (the radicand does not depend on d: all of r is NaN or none of it)
+    m.r_min = r[0];
+    for (int d = lo; d <= hi; d++) {
+      const double v = r[(size_t)(d - lo)];
+      if (v < m.r_min) {   // (ascending: the smallest d of the least r stays)
+        m.r_min = v;
+        m.min_shift = d;
+      }
+      if (d < 1 || (read_len && d >= ph - 10 && d <= ph + 10)) continue;
+      if (!m.has_frag || v > m.r_frag) {
+        m.has_frag = 1;
+        m.r_frag = v;
+        m.frag_shift = d;
+      }
+    }
+  }
+  if (m.has_frag) {
+    m.fragment_length = m.frag_shift + 1;
+    if (m.r_min > 0.0) m.nsc = m.r_frag / m.r_min;
+    if (m.has_phantom && m.r_phantom - m.r_min > 0.0) m.rsc = (m.r_frag - m.r_min) / (m.r_phantom - m.r_min);
+  }
+  *out = m;
+  return GX_OK;
+}
+
+// --xcor: one row per sample and shift under the sample's line of totals
+int gx_format_xcor(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_pos, const uint64_t* n_plus,
+                   const uint64_t* n_minus, const uint64_t* rejected, int lo, int hi, const uint64_t* const* n11) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !n_pos || !n_plus || !n_minus || !rejected || !n11) return GX_ERR_ORDER;
+  for (int s = 0; s < n_samples; s++)
+    if (!xcor_counts_ok(n_pos[s], n_plus[s], n_minus[s], lo, hi, n11[s])) return GX_ERR_ORDER;
+  std::vector<double> r((size_t)(hi - lo + 1));
+  fprintf(out, "sample\tshift\tn11\tr\n");
+  for (int s = 0; s < n_samples; s++) {
+    const char k = is_ctrl[s] ? 'c' : 't';
+    fprintf(out, "# %c%d\tn_pos=%llu\tn_plus=%llu\tn_minus=%llu\trejected=%llu\n", k, rep[s], (unsigned long long)n_pos[s], (unsigned long long)n_plus[s],
+            (unsigned long long)n_minus[s], (unsigned long long)rejected[s]);
+    xcor_curve(n_pos[s], n_plus[s], n_minus[s], lo, hi, n11[s], r.data());
+    for (int d = lo; d <= hi; d++) {
+      fprintf(out, "%c%d\t%d\t%llu", k, rep[s], d, (unsigned long long)n11[s][d - lo]);
+      put_cpx(out, r[(size_t)(d - lo)], "\t%.6f");
+      fprintf(out, "\n");
+    }
+  }
+  return GX_OK;
+}
+
+// --xcor-metrics: one row per sample
+int gx_format_xcor_metrics(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_pos, const uint64_t* n_plus,
+                           const uint64_t* n_minus, int lo, int hi, const uint64_t* const* n11, int read_len) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !n_pos || !n_plus || !n_minus || !n11) return GX_ERR_ORDER;
+  std::vector<gx_xcor_metrics_t> m((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (int rc = gx_xcor_metrics(n_pos[s], n_plus[s], n_minus[s], lo, hi, n11[s], read_len, &m[s])) return rc;
+  fprintf(out, "sample\tn_pos\tn_plus\tn_minus\tfragment_length\tr_frag\tmin_shift\tr_min\tphantom_shift\tr_phantom\tNSC\tRSC\n");
+  for (int s = 0; s < n_samples; s++) {
+    fprintf(out, "%c%d\t%llu\t%llu\t%llu", is_ctrl[s] ? 'c' : 't', rep[s], (unsigned long long)n_pos[s], (unsigned long long)n_plus[s],
+            (unsigned long long)n_minus[s]);
+    if (m[s].has_frag) fprintf(out, "\t%d", m[s].fragment_length);
+    else fprintf(out, "\tNA");
+    put_cpx(out, m[s].r_frag, "\t%.6f");
+    if (std::isnan(m[s].r_min)) fprintf(out, "\tNA");
+    else fprintf(out, "\t%d", m[s].min_shift);
+    put_cpx(out, m[s].r_min, "\t%.6f");
+    if (read_len) fprintf(out, "\t%d", m[s].phantom_shift);
+    else fprintf(out, "\tNA");
+    put_cpx(out, m[s].r_phantom, "\t%.6f");
+    put_cpx(out, m[s].nsc, "\t%.6f");
+    put_cpx(out, m[s].rsc, "\t%.6f");
     fprintf(out, "\n");
   }
   return GX_OK;

@@ -34,6 +34,7 @@
 #include "gx_rank.h"
 #include "gx_complexity.h"
 #include "gx_ivstat.h"
+#include "gx_xcor.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
@@ -202,6 +203,8 @@ struct Knobs {
   int depthGrid = 0;      // GX_DEPTH_GRID: workgroups of k_depth_hist (0: one per DEPTH_NW tiles, at most DEPTH_GRID; tests: 1 makes one workgroup walk every tile)
   int depthListCap = 0;   // GX_DEPTH_LIST_CAP: entries of k_depth_hist's deep list at first (0: DEPTH_LIST_CAP; tests: a tiny one forces the rerun)
   int depthPriv = 0;      // GX_DEPTH_PRIV: k_depth_hist<true> sums the pieces of whole depth 1 .. 4 in registers, one LDS atomic per class and wavefront (measurements; default: an LDS atomic per piece)
+  int xcorGrid = 0;       // GX_XCOR_GRID: workgroups of k_xc_corr at gx_sample_end (0: one per tile, at most XC_GRID; tests: 1 makes one workgroup walk every tile)
+  int xcorTile = 0;       // GX_XCOR_TILE: plus words per tile of k_xc_corr at gx_sample_end (0: XC_TILE; tests: 64 puts many tile borders into a small genome)
   int roctx = 0;          // GX_ROCTX: a roctx range around every phase (rocprofv3 --marker-trace: kernel -> phase attribution)
   int fault = 0;          // GX_FAULT: fault injection for the tests of the device-side invariants.  1: the weight of the ends at
                           // chromosome 0's length is damaged behind level 1 of the sort (as if an end record had been lost)
@@ -249,6 +252,7 @@ const KnobDef KNOBS[] = {
     {"GX_RANK_CAP_LOG", &Knobs::rankCapLog, nullptr},
     {"GX_RANK_LOOKUP", &Knobs::rankLookup, nullptr},
     {"GX_DEPTH_GRID", &Knobs::depthGrid, nullptr}, {"GX_DEPTH_LIST_CAP", &Knobs::depthListCap, nullptr}, {"GX_DEPTH_PRIV", &Knobs::depthPriv, nullptr},
+    {"GX_XCOR_GRID", &Knobs::xcorGrid, nullptr}, {"GX_XCOR_TILE", &Knobs::xcorTile, nullptr},
     {"GX_ROCTX", &Knobs::roctx, nullptr},
 };
 // a switch that is merely present counts as 1 (GX_NO_LOOSE= is "on", as it was with getenv() != nullptr), and so does a
@@ -504,6 +508,25 @@ struct gx_ctx {
   bool ivsUsed = false;           // k_ivstat ran since the last gx_reset
   size_t ivsLastCap = 0;          // the last pass: the list capacity it ended with, how often it ran again (gx_interval_stats_last)
   u32 ivsLastReruns = 0;
+  // the strand cross-correlation of every closed sample's tags (gx_set_xcor / gx_push_tags, gx_xcor.h); nothing here exists
+  // before gx_set_xcor turns it on; the results live on the host
+  struct XcResult {
+    int rep = 0;
+    bool ctrl = false;
+    u64 N = 0, nP = 0, nM = 0, rejected = 0;   // bases of the chromosomes that take part, set bits per strand, tags that were refused
+    std::vector<uint64_t> n11;                 // [hi - lo + 1]
+  };
+  bool xcOn = false;
+  int xcLo = 0, xcHi = -1;
+  bool xcDirty = false;             // the table changed since the layout (gx_set_chroms / gx_set_owned)
+  std::vector<XcChrom> xcChrom;     // the layout, and who takes part in the open sample
+  u64 xcWords = 0;                  // words of one vector
+  DevBuf xcPlus, xcMinus, xcTab, xcOut, xcTags;   // the two vectors, the table, the control words + n11, gx_push_tags' device buffer
+  PinnedBuf xcStage[2];             // pinned staging of gx_push_tags (the caller's buffer is free on return)
+  hipEvent_t xcStageFree[2] = {nullptr, nullptr};
+  int xcStageNext = 0;
+  std::vector<XcResult> xc;         // until gx_reset
+  bool xcUsed = false;              // k_xc_set / k_xc_corr ran since the last gx_reset
   // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
   struct DepthResult {
     int rep = 0;

@@ -172,6 +172,13 @@ struct Opts {
   const char* chromStatsFile = nullptr;     // --chrom-stats FILE: ... and its intervals per chromosome
   std::vector<uint64_t> lengthsCuts{150, 300, 500};   // --lengths-cuts A,B,...: the class borders of the metrics' shares
   bool lengthsCutsOpt = false;
+  const char* xcorFile = nullptr;           // --xcor FILE: each sample's strand cross-correlation curve from its alignments' 5' ends
+  const char* xcorMetricsFile = nullptr;    // --xcor-metrics FILE: ... and the figures made of it (fragment length, NSC, RSC)
+  int xcorLo = -100, xcorHi = 600;          // --xcor-shifts LO,HI
+  bool xcorShiftsOpt = false;
+  int xcorReadLen = 0;                      // --xcor-read-length R: the phantom peak sits at R - 1 (0: not given)
+  bool xcorUnpaired = false;                // --xcor-unpaired: only unpaired alignments give tags
+  bool xcorOn() const { return xcorFile || xcorMetricsFile; }
   const char* complexityHistFile = nullptr;   // --complexity-hist FILE: ... and its duplication histogram
   const char* saturationFile = nullptr;    // --saturation FILE: the peaks called once more on nested subsamples of the run's intervals
   int saturationSteps = 10;                // --saturation-steps N: the points of the curve, T_j = (j << 32) / N
@@ -198,6 +205,7 @@ struct Devs {
   std::vector<gx_ctx*> ctx;
   std::vector<int> owner;                       // chromosome -> index into ctx
   std::vector<std::vector<gx_event>> buf;       // events on their way to each context
+  std::vector<std::vector<gx_tag>> tagBuf;      // --xcor: ... and tags
   // in-process collectives (callback mode)
   pthread_barrier_t bar;
   bool barInit = false;
@@ -279,6 +287,8 @@ struct State {
   std::unique_ptr<gxhost::Input> stdinIn;  // '-' can be opened once: its header pre-scan is replayed to the real pass
   bool sampleOpen = false;   // gx_sample_begin done for the file being read
   std::vector<gx_event> buf;
+  std::vector<gx_tag> tags;  // --xcor: the strand-tagged 5' ends on their way to the device
+  bool unpairedTags = false; // ... and some of them came from unpaired alignments
   Out bed;
   bool bedOpt = false;
   Out dups;               // -R: log of the reads removed as PCR duplicates
@@ -332,6 +342,20 @@ void flushEvents(State& S) {
   for (const gx_event& e : S.buf) D.buf[D.owner[e.chrom]].push_back(e);
   for (size_t g = 0; g < D.n(); g++)
     if (!D.buf[g].empty()) check(S, gx_push_events(D.ctx[g], D.buf[g].data(), D.buf[g].size()), D.ctx[g]);
+}
+
+// --xcor: the tags gathered so far go to the contexts that own their chromosomes (their order does not matter)
+void flushTags(State& S) {
+  Devs& D = S.devs;
+  if (S.tags.empty()) return;
+  if (D.n() == 1) check(S, gx_push_tags(S.gx, S.tags.data(), S.tags.size()));
+  else {
+    for (auto& b : D.tagBuf) b.clear();
+    for (const gx_tag& t : S.tags) D.tagBuf[D.owner[t.chrom]].push_back(t);
+    for (size_t g = 0; g < D.n(); g++)
+      if (!D.tagBuf[g].empty()) check(S, gx_push_tags(D.ctx[g], D.tagBuf[g].data(), D.tagBuf[g].size()), D.ctx[g]);
+  }
+  S.tags.clear();
 }
 
 void mergeBed(Chrom& c, const std::vector<BedRec>& xbed, bool verbose) {
@@ -402,6 +426,8 @@ struct Sink {
   std::string bed;                                      // -b lines
   std::vector<std::pair<std::string, bool>> warn;       // stderr lines in order; true: counts towards errCount
   std::vector<double> lenTerms;                         // C.totalLen += ... in order (a float sum: not associative)
+  std::vector<gx_tag> tags;                             // --xcor: strand-tagged 5' ends (any order)
+  bool unpairedTags = false;
 };
 thread_local Sink* t_sink = nullptr;
 
@@ -441,6 +467,24 @@ void pushEvent(State& S, const gx_event& e) {  // (state's side: the library tak
     if (S.gx && S.sampleOpen) flushEvents(S);
     if (!S.gx || S.sampleOpen) S.buf.clear();  // (--events-only: nothing to send them to; with -b the int16 decisions keep their own copy, hot.all)
   }
+}
+
+// --xcor: the 5' end of an alignment that becomes intervals, from its own coordinates (before -j / -y / -w / -x and
+// saveInterval's clamping change them, and whether or not the int16 replay drops the interval)
+void saveTag(State& S, int ci, bool plus, uint32_t pos, bool unpaired) {
+  const gx_tag t{(uint32_t)ci, pos, plus ? 1u : 0u};
+  if (t_sink) {
+    t_sink->tags.push_back(t);
+    t_sink->unpairedTags |= unpaired;
+    return;
+  }
+  S.tags.push_back(t);
+  S.unpairedTags |= unpaired;
+  if (S.tags.size() >= (1u << 20) && S.sampleOpen) flushTags(S);
+}
+// an unpaired alignment: forward (+, first base), reverse (-, last base; pos[1] is the exclusive end)
+void saveUnpairTag(State& S, int ci, const uint32_t* pos, bool strand) {
+  if (S.o.xcorOn()) saveTag(S, ci, strand, strand ? pos[0] : pos[1] - 1u, true);
 }
 
 // A loaded window's exact difference (1/120 units per base): from the device, which is sent what the host still holds first.
@@ -561,6 +605,10 @@ struct Counts {
 uint32_t saveFragment(State& S, const char* qname, const Aln& a, uint8_t count) {  // 2754-2774, 2728-2749
   uint32_t start = a.pos[0], end = a.pos[1];
   if (start > end) std::swap(start, end);
+  if (S.o.xcorOn() && !S.o.xcorUnpaired) {   // a proper pair: (+, its first base) and (-, its last base)
+    saveTag(S, a.chrom, true, start, false);
+    saveTag(S, a.chrom, false, end - 1u, false);
+  }
   if (!S.o.atacOpt) return saveInterval(S, a.chrom, start, end, qname, count);
   if (S.o.atacAdj) { start += 5; end += (uint32_t)-5; }
   if (start + S.o.atacLen3 >= (uint32_t)(int)(end - S.o.atacLen3))
@@ -571,6 +619,7 @@ uint32_t saveFragment(State& S, const char* qname, const Aln& a, uint8_t count) 
 
 void saveUnpair(State& S, const char* qname, Aln& a, uint8_t count) {  // 2689-2721
   const Opts& o = S.o;
+  saveUnpairTag(S, a.chrom, a.pos, a.strand);
   if (o.extendOpt) {
     if (a.strand) saveInterval(S, a.chrom, a.pos[0], (uint32_t)(a.pos[0] + o.extend), qname, count);
     else saveInterval(S, a.chrom, (int)(a.pos[1] - o.extend), a.pos[1], qname, count);
@@ -1293,6 +1342,7 @@ void finishFile(State& S, ReadSet& rs, Counts& C) {  // the tail of readSAM / pa
     } else
       avgLen = (int)(C.totalLen / C.pairedPr + 0.5);
     for (auto& u : rs.unpair) {
+      saveUnpairTag(S, u.chrom, u.pos, u.strand);
       if (!avgLen) saveInterval(S, u.chrom, u.pos[0], u.pos[1], u.name.c_str(), u.count);
       else if (u.strand) saveInterval(S, u.chrom, u.pos[0], (uint32_t)(u.pos[0] + avgLen), u.name.c_str(), u.count);
       else saveInterval(S, u.chrom, (int)(u.pos[1] - avgLen), u.pos[1], u.name.c_str(), u.count);
@@ -1743,6 +1793,11 @@ void mergeChunk(State& S, ReadSet& rs, Counts& C, Chunk& ch, int qualOffset) {
       if (S.gx && S.sampleOpen) flushEvents(S);
       if (!S.gx || S.sampleOpen) S.buf.clear();  // (--events-only: nothing to send them to; with -b the int16 decisions keep their own copy, hot.all)
     }
+  }
+  if (!ch.sink.tags.empty()) {
+    S.tags.insert(S.tags.end(), ch.sink.tags.begin(), ch.sink.tags.end());
+    S.unpairedTags |= ch.sink.unpairedTags;
+    if (S.tags.size() >= (1u << 20) && S.sampleOpen) flushTags(S);
   }
   addCounts(C, ch.C);
   for (double x : ch.sink.lenTerms) C.totalLen += x;
@@ -2952,6 +3007,53 @@ void writeIntervalStats(State& S, const std::vector<const char*>& names) {
   }
 }
 
+// --xcor FILE / --xcor-metrics FILE: the strand cross-correlation of each sample's 5' ends, counted on the device when the
+// sample was closed (one pass per context, added): the curve, one row per sample and shift with the exact pair count and r, and
+// one row of figures per sample (fragment length, NSC, RSC), labelled t<rep> / c<rep>.  With -v the figures on stderr too, and
+// for a library whose unpaired alignments gave tags, with no extension chosen, the length to extend them to
+void writeXcor(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* g0 = S.devs.ctx[0];
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n();
+  int nS = 0;
+  for (gx_ctx* g : S.devs.ctx) {
+    int n = 0;
+    check(S, gx_xcor_samples(g, &n), g);
+    if (g != g0 && n != nS) die("", "--xcor: the devices closed different numbers of samples");
+    nS = n;
+  }
+  Out curve, metrics;
+  if (o.xcorFile) curve = openWrite(o.xcorFile, o.gzOut);
+  if (o.xcorMetricsFile) metrics = openWrite(o.xcorMetricsFile, o.gzOut);
+  check(S, gx_write_xcor_group(ctxs, nCtx, o.xcorReadLen, o.xcorFile ? curve.f : nullptr, o.xcorMetricsFile ? metrics.f : nullptr), g0);
+  if (o.xcorFile) closeOut(curve);
+  if (o.xcorMetricsFile) closeOut(metrics);
+  if (!o.verbose) return;
+  std::vector<uint64_t> n11((size_t)(o.xcorHi - o.xcorLo + 1));
+  for (int i = 0; i < nS; i++) {
+    int rep = 0, ctrl = 0;
+    uint64_t N = 0, nP = 0, nM = 0;
+    check(S, gx_xcor_group(ctxs, nCtx, i, &rep, &ctrl, &N, &nP, &nM, nullptr, nullptr, nullptr, n11.data(), n11.size()), g0);
+    gx_xcor_metrics_t m;
+    check(S, gx_xcor_metrics(N, nP, nM, o.xcorLo, o.xcorHi, n11.data(), o.xcorReadLen, &m), g0);
+    fprintf(stderr, "  Strand cross-correlation, %s file #%d: fragment length ", ctrl ? "control" : "experimental", rep);
+    if (m.has_frag) fprintf(stderr, "%d", m.fragment_length);
+    else fprintf(stderr, "NA");
+    auto put = [](const char* name, double v) {
+      if (std::isnan(v)) fprintf(stderr, ", %s NA", name);
+      else fprintf(stderr, ", %s %f", name, v);
+    };
+    put("NSC", m.nsc);
+    put("RSC", m.rsc);
+    fprintf(stderr, "\n");
+    // (Genrich extends unpaired alignments to a given length with -w N, to the pairs' average with -x: a single-end library has
+    // no pairs, and this is the length either would want)
+    if (m.has_frag && !ctrl && S.unpairedTags && !o.extendOpt && !o.avgExtOpt)
+      fprintf(stderr, "  suggested -x %d (unpaired alignments extended to the estimated fragment length: -w %d)\n", m.fragment_length, m.fragment_length);
+  }
+}
+
 // --depth FILE / --depth-metrics FILE: the distribution of per-base depth of each sample's pileup, taken on the device when the
 // sample was closed (one pass per context, added): one row per sample and non-empty whole depth, and one row of figures per
 // sample (bases, covered, mean, sd, min, quartiles, percentiles, max, the fractions at 1x .. 100x), labelled t<rep> / c<rep>; with
@@ -3146,6 +3248,15 @@ void usage() {
           "                  chrom-stats file has one row per chromosome with each sample's intervals, weight, share and mean depth (a\n"
           "                  chromosome skipped with -e: zeros); each of the three files may stand alone; with -j the intervals are\n"
           "                  cut-site windows, nearly all of one length, not fragments; not with -P or --events-only\n"
+          "  --xcor FILE [--xcor-metrics FILE] [--xcor-shifts LO,HI] [--xcor-read-length R] [--xcor-unpaired]   each sample's strand\n"
+          "                  cross-correlation: a forward alignment tags its first base on the plus strand, a reverse one its last base\n"
+          "                  on the minus strand, a proper pair both ends of its fragment (--xcor-unpaired: unpaired alignments only);\n"
+          "                  positions, not reads, are counted (duplicates count once, -s weights not at all).  The curve is a TSV\n"
+          "                  labelled t<rep> / c<rep> with, per shift LO .. HI (-100,600; within -4096 .. 4096), the positions tagged on\n"
+          "                  the plus strand with a minus tag that far downstream and the correlation r; the metrics file (it may stand\n"
+          "                  alone) has the fragment length (1 + the shift >= 1 of the greatest r), NSC = r there over the least r, and\n"
+          "                  with the read length R the phantom peak at R - 1 (shifts within 10 of it are then no fragment peak) and\n"
+          "                  RSC; with -v and a library of unpaired alignments the length to extend them to; not with -P or --events-only\n"
           "  --depth FILE [--depth-metrics FILE]   each sample's distribution of per-base depth over every base of the genome outside\n"
           "                  the -E regions: a TSV labelled t<rep> / c<rep> with the bases at each whole depth and at that depth or\n"
           "                  more; the metrics file (it may stand alone) has the bases, the share covered, mean, sd, min, quartiles,\n"
@@ -3202,6 +3313,11 @@ int main(int argc, char** argv) {
                                      {"saturation-controls", no_argument, nullptr, 1026},
                                      {"depth", required_argument, nullptr, 1027},
                                      {"depth-metrics", required_argument, nullptr, 1028},
+                                     {"xcor", required_argument, nullptr, 1034},
+                                     {"xcor-metrics", required_argument, nullptr, 1035},
+                                     {"xcor-shifts", required_argument, nullptr, 1036},
+                                     {"xcor-read-length", required_argument, nullptr, 1037},
+                                     {"xcor-unpaired", no_argument, nullptr, 1038},
                                      {"lengths", required_argument, nullptr, 1030},
                                      {"lengths-metrics", required_argument, nullptr, 1031},
                                      {"lengths-cuts", required_argument, nullptr, 1032},
@@ -3279,6 +3395,31 @@ int main(int argc, char** argv) {
       case 1022: o.complexityHistFile = optarg; break;
       case 1027: o.depthFile = optarg; break;
       case 1028: o.depthMetricsFile = optarg; break;
+      case 1034: o.xcorFile = optarg; break;
+      case 1035: o.xcorMetricsFile = optarg; break;
+      case 1038: o.xcorUnpaired = true; break;
+      case 1036: {  // --xcor-shifts LO,HI: two integers, -4096 <= LO <= HI <= 4096
+        char *e1, *e2 = nullptr;
+        errno = 0;
+        const long lo = strtol(optarg, &e1, 10);
+        const long hi = (e1 != optarg && *e1 == ',') ? strtol(e1 + 1, &e2, 10) : 0;
+        if (e1 == optarg || *e1 != ',' || !e2 || e2 == e1 + 1 || *e2 != '\0' || isspace((unsigned char)optarg[0]) || isspace((unsigned char)e1[1]) ||
+            errno == ERANGE || lo < -GX_XCOR_MAX_SHIFT || hi > GX_XCOR_MAX_SHIFT || lo > hi)
+          die(optarg, ": --xcor-shifts takes two integers LO,HI with -4096 <= LO <= HI <= 4096");
+        o.xcorLo = (int)lo;
+        o.xcorHi = (int)hi;
+        o.xcorShiftsOpt = true;
+        break;
+      }
+      case 1037: {  // --xcor-read-length R: a positive integer
+        char* end;
+        errno = 0;
+        const long v = strtol(optarg, &end, 10);
+        if (!isdigit((unsigned char)optarg[0]) || *end != '\0' || errno == ERANGE || v < 1 || v > 1000000)
+          die(optarg, ": --xcor-read-length takes a positive integer (at most 1000000)");
+        o.xcorReadLen = (int)v;
+        break;
+      }
       case 1030: o.lengthsFile = optarg; break;
       case 1031: o.lengthsMetricsFile = optarg; break;
       case 1033: o.chromStatsFile = optarg; break;
@@ -3354,6 +3495,10 @@ int main(int argc, char** argv) {
   if ((o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile) && (o.peaksOnly || o.eventsOnly))
     die("", "--lengths, --lengths-metrics and --chrom-stats need the intervals of this run (not with -P or --events-only)");
   if (o.lengthsCutsOpt && !o.lengthsMetricsFile) die("", "--lengths-cuts needs --lengths-metrics FILE");
+  // (the tags are taken where this run's alignments become intervals: none with -P or --events-only; -X is fine)
+  if (o.xcorOn() && (o.peaksOnly || o.eventsOnly)) die("", "--xcor and --xcor-metrics need the alignments of this run (not with -P or --events-only)");
+  if ((o.xcorShiftsOpt || o.xcorReadLen || o.xcorUnpaired) && !o.xcorOn())
+    die("", "--xcor-shifts, --xcor-read-length and --xcor-unpaired need --xcor FILE or --xcor-metrics FILE");
   // (the distribution is taken from the pileups this run builds: none with -P or --events-only; -X is fine)
   if ((o.depthFile || o.depthMetricsFile) && (o.peaksOnly || o.eventsOnly))
     die("", "--depth and --depth-metrics need the pileups of this run (not with -P or --events-only)");
@@ -3479,6 +3624,7 @@ int main(int argc, char** argv) {
     S.gx = D.ctx[0];
     S.hot.on = getenv("GENRICH_NO_INT16") == nullptr;  // (saveInterval's int16 checks, read by read: HotWindows)
     D.buf.resize(D.n());
+    D.tagBuf.resize(D.n());
     if (D.n() > 1) {
       const int W = (int)D.n();
       bool distinct = true;
@@ -3519,6 +3665,8 @@ int main(int argc, char** argv) {
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_coverage_bins(g, (uint32_t)o.binSize), g);
   if (o.depthFile || o.depthMetricsFile)
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_depth_hist(g, 1), g);
+  if (o.xcorOn())
+    for (gx_ctx* g : S.devs.ctx) check(S, gx_set_xcor(g, o.xcorLo, o.xcorHi), g);
   ProfilePlan profilePlan;
   if (o.profileBed) {
     profilePlan = planProfile(S);
@@ -3543,6 +3691,7 @@ int main(int argc, char** argv) {
       S.sampleOpen = false;
       S.errCount = 0;
       S.buf.clear();
+      S.tags.clear();
       In file;
       const bool isStdin = !strcmp(filename, "-");
       In& in = isStdin ? openStdin(S) : file;
@@ -3571,6 +3720,7 @@ int main(int argc, char** argv) {
       openSample(S);  // a file without a single usable record still opens (and closes) its sample
       if (S.gx) flushEvents(S);
       S.buf.clear();
+      if (S.gx) flushTags(S);
       if (o.verbose) logCounts(S, C, bam);
       if (S.gx) {
         double fragLen = 0;
@@ -3654,6 +3804,7 @@ int main(int argc, char** argv) {
   if (o.complexityFile) writeComplexity(S);
   if (o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile) writeIntervalStats(S, names);
   if (o.depthFile || o.depthMetricsFile) writeDepth(S);
+  if (o.xcorOn()) writeXcor(S);
   if (o.saturationFile) writeSaturation(S);
   if (o.profileBed) writeProfile(S, profilePlan, tFiles, cFiles);
   if (o.logFile) {

@@ -143,6 +143,12 @@ FP_METRICS_DTYPE = np.dtype([(k, "<f8") for k in ("zero_fraction", "auc", "gini"
 GX_PATH_SPEARMAN = 4194304      # gx_path_info bit 22: k_rank ran (gx_coverage_rank_gram, gx_rank_u64)
 GX_PATH_COMPLEXITY = 8388608    # gx_path_info bit 23: k_cpx_insert ran (gx_complexity, gx_complexity_events)
 GX_PATH_IVSTAT = 67108864       # gx_path_info bit 26: k_ivstat ran (gx_interval_stats, gx_interval_stats_events)
+GX_PATH_XCOR = 134217728        # gx_path_info bit 27: k_xc_set / k_xc_corr ran (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags)
+TAG_DTYPE = np.dtype([("chrom", "<u4"), ("pos", "<u4"), ("strand", "<u4")])   # gx_tag; strand 1: +, 0: -
+XCOR_MAX_SHIFT = 4096           # GX_XCOR_MAX_SHIFT
+XCOR_MIN_TILE = 64              # GX_XCOR_MIN_TILE
+XCOR_METRICS_DTYPE = np.dtype([(k, "<i4") for k in ("has_frag", "frag_shift", "fragment_length", "min_shift", "has_phantom", "phantom_shift", "_pad")]
+                              + [("_pad2", "<i4")] + [(k, "<f8") for k in ("r_frag", "r_min", "r_phantom", "nsc", "rsc")])   # gx_xcor_metrics_t
 LEN_MAX_CUTS = 8                # GX_LEN_MAX_CUTS: the most class borders gx_lengths_metrics takes
 LEN_METRICS_DTYPE = np.dtype([(f, "<u8") for f in ("n", "w120", "min", "max", "mode", "p5", "q25", "median", "q75", "p95")]
                              + [("mean", "<f8"), ("sd", "<f8"), ("n_shares", "<i4"), ("_pad", "<i4"),
@@ -187,6 +193,19 @@ class Depth(NamedTuple):
     rsum: np.ndarray
     rsq: np.ndarray
     deep: list
+
+
+class Xcor(NamedTuple):
+    """One sample's strand cross-correlation counts (gx_get_xcor): N bases, set bits per strand, refused tags, n11[d - lo]."""
+    n_pos: int
+    n_plus: int
+    n_minus: int
+    rejected: int
+    lo: int
+    hi: int
+    n11: list
+    rep: int = 0
+    is_ctrl: bool = False
 
 
 class IntervalStats(NamedTuple):
@@ -351,6 +370,21 @@ _SIGS = {
     "gx_complexity_last": [C.c_void_p, C.POINTER(C.c_size_t)],
     "gx_complexity_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_set_xcor": [C.c_void_p, C.c_int, C.c_int],
+    "gx_push_tags": [C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_xcor_samples": [C.c_void_p, C.POINTER(C.c_int)],
+    "gx_get_xcor": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                                                                                  C.c_void_p, C.c_size_t],
+    "gx_xcor_group": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_uint64)] * 4
+                     + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t],
+    "gx_xcor_tags": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint, C.c_uint32] + [C.POINTER(C.c_uint64)] * 4
+                    + [C.c_void_p, C.c_size_t],
+    "gx_xcor_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+    "gx_xcor_metrics": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_xcor_r": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_format_xcor": [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
+    "gx_format_xcor_metrics": [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int],
+    "gx_write_xcor_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "gx_interval_stats": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_get_interval_lengths": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
@@ -677,6 +711,90 @@ def format_peak_signal(names, peaks, samples) -> bytes:
     ctrl = (C.c_int * max(S, 1))(*[int(x.is_ctrl) for x in samples])
     cn = _c_names(list(names))
     return _to_tmpfile(lambda f: lib.gx_format_peak_signal(f, cn, reg.ctypes.data if reg.size else None, reg.size, S, rep, ctrl, *ptrs))
+
+
+def xcor_geometry():
+    """(lanes, grid, tile_words, pad_words_for_4096, flush_words) of the cross-correlation pass as the library was built
+    (gx_xcor_geometry): the lanes of a workgroup of k_xc_corr, its most workgroups with grid = 0, the default plus words per tile
+    (the smallest a caller may ask for is XCOR_MIN_TILE), the zero words between chromosomes at the widest shifts, and the plus
+    words a workgroup walks at most before its 32-bit counters are added to the 64-bit ones."""
+    lib = load_library()
+    lanes, grid, tile, pad, flush = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    lib.gx_xcor_geometry(C.byref(lanes), C.byref(grid), C.byref(tile), C.byref(pad), C.byref(flush))
+    return lanes.value, grid.value, tile.value, pad.value, flush.value
+
+
+def xcor_r(n_pos, n_plus, n_minus, lo, hi, n11):
+    """r(d) for lo <= d <= hi as the library defines it (gx_xcor_r); NaN where undefined; host-only."""
+    lib = load_library()
+    a = np.ascontiguousarray(n11, dtype=np.uint64)
+    out = np.zeros(max(a.size, 1), dtype=np.float64)
+    rc = lib.gx_xcor_r(int(n_pos), int(n_plus), int(n_minus), int(lo), int(hi), a.ctypes.data if a.size == hi - lo + 1 else None, out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_xcor_r: {rc}")
+    return out[:a.size]
+
+
+def xcor_metrics(n_pos, n_plus, n_minus, lo, hi, n11, read_len=0):
+    """gx_xcor_metrics as one XCOR_METRICS_DTYPE record; read_len 0: not given; host-only."""
+    lib = load_library()
+    a = np.ascontiguousarray(n11, dtype=np.uint64)
+    out = np.zeros(1, dtype=XCOR_METRICS_DTYPE)
+    rc = lib.gx_xcor_metrics(int(n_pos), int(n_plus), int(n_minus), int(lo), int(hi), a.ctypes.data if a.size == hi - lo + 1 else None, int(read_len),
+                             out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_xcor_metrics: {rc}")
+    return out[0]
+
+
+def _xcor_cols(samples):
+    """The writers' arrays from [Xcor]: (n, rep, ctrl, N, nP, nM, rejected, rows kept alive, row pointers)."""
+    rep = np.ascontiguousarray([x.rep for x in samples], dtype=np.int32)
+    ctrl = np.ascontiguousarray([int(x.is_ctrl) for x in samples], dtype=np.int32)
+    cols = [np.ascontiguousarray([getattr(x, k) for x in samples], dtype=np.uint64) for k in ("n_pos", "n_plus", "n_minus", "rejected")]
+    rows = [np.ascontiguousarray(x.n11, dtype=np.uint64) for x in samples]
+    ptrs = (C.c_void_p * len(samples))(*[r.ctypes.data for r in rows])
+    return rep, ctrl, cols, rows, ptrs
+
+
+def format_xcor(samples) -> bytes:
+    """--xcor's table for [Xcor] with one range of shifts (gx_format_xcor); host-only."""
+    lib = load_library()
+    rep, ctrl, cols, rows, ptrs = _xcor_cols(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_xcor(f, len(samples), rep.ctypes.data, ctrl.ctypes.data, *[c.ctypes.data for c in cols],
+                                                    samples[0].lo, samples[0].hi, ptrs))
+
+
+def format_xcor_metrics(samples, read_len=0) -> bytes:
+    """--xcor-metrics' table for [Xcor] (gx_format_xcor_metrics); host-only."""
+    lib = load_library()
+    rep, ctrl, cols, rows, ptrs = _xcor_cols(samples)
+    return _to_tmpfile(lambda f: lib.gx_format_xcor_metrics(f, len(samples), rep.ctypes.data, ctrl.ctypes.data, *[c.ctypes.data for c in cols[:3]],
+                                                            samples[0].lo, samples[0].hi, ptrs, int(read_len)))
+
+
+def _xcor_result(call, n_shifts):
+    """An Xcor from call(rep, ctrl, N, nP, nM, rejected, lo, hi, n11, cap)."""
+    rep, ctrl, lo, hi = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    N, nP, nM, rej = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    n11 = np.zeros(max(n_shifts, 1), dtype=np.uint64)
+    call(C.byref(rep), C.byref(ctrl), C.byref(N), C.byref(nP), C.byref(nM), C.byref(rej), C.byref(lo), C.byref(hi), n11.ctypes.data, n_shifts)
+    return Xcor(N.value, nP.value, nM.value, rej.value, lo.value, hi.value, [int(x) for x in n11[:hi.value - lo.value + 1]], rep.value, bool(ctrl.value))
+
+
+def xcor_group(ctxs, sample):
+    """Xcor of one sample added over the contexts of a run (gx_xcor_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _xcor_result(lambda *a: ctxs[0]._check(lib.gx_xcor_group(arr, len(ctxs), int(sample), *a)), 2 * XCOR_MAX_SHIFT + 1)
+
+
+def xcor_text(ctxs, read_len=0):
+    """(--xcor's table, --xcor-metrics') over the contexts of a run (gx_write_xcor_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return (_to_tmpfile(lambda f: lib.gx_write_xcor_group(arr, len(ctxs), int(read_len), f, None)),
+            _to_tmpfile(lambda f: lib.gx_write_xcor_group(arr, len(ctxs), int(read_len), None, f)))
 
 
 def interval_stats_geometry():
@@ -1258,7 +1376,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran, 134217728 the cross-correlation kernels ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -1459,6 +1577,38 @@ class Genrich:
         c = C.c_size_t(0)
         self._check(self.lib.gx_complexity_last(self.ctx, C.byref(c)))
         return c.value
+
+    # -- strand cross-correlation of the samples' 5' ends (include/genrich_amd.h, gx_set_xcor) ------------------------------
+    def set_xcor(self, lo=-100, hi=600):
+        """Keep two strand bit vectors per open sample and count, at sample_end, the tag pairs at every shift lo .. hi (gx_set_xcor);
+        hi < lo: off.  Only while idle, after set_chroms."""
+        self._check(self.lib.gx_set_xcor(self.ctx, int(lo), int(hi)))
+
+    def push_tags(self, tags):
+        """Tags (TAG_DTYPE) of the open sample, any order, any split (gx_push_tags)."""
+        t = np.ascontiguousarray(tags, dtype=TAG_DTYPE)
+        self._check(self.lib.gx_push_tags(self.ctx, t.ctypes.data if t.size else None, t.size))
+
+    def xcor_samples(self):
+        n = C.c_int(0)
+        self._check(self.lib.gx_xcor_samples(self.ctx, C.byref(n)))
+        return n.value
+
+    def xcor(self, sample):
+        """Xcor of one closed sample of this context (gx_get_xcor)."""
+        return _xcor_result(lambda *a: self._check(self.lib.gx_get_xcor(self.ctx, int(sample), *a)), 2 * XCOR_MAX_SHIFT + 1)
+
+    def xcor_tags(self, lens, tags, lo=-100, hi=600, grid=0, tile_words=0):
+        """Xcor of host tags (TAG_DTYPE) over a chromosome table of their own, by the two kernels alone (gx_xcor_tags); grid = 0 /
+        tile_words = 0: the library's geometry."""
+        t = np.ascontiguousarray(tags, dtype=TAG_DTYPE)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = max(int(hi) - int(lo) + 1, 1)
+        n11 = np.zeros(n, dtype=np.uint64)
+        N, nP, nM, rej = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_xcor_tags(self.ctx, ln.ctypes.data, ln.size, t.ctypes.data if t.size else None, t.size, int(lo), int(hi), int(grid),
+                                          int(tile_words), C.byref(N), C.byref(nP), C.byref(nM), C.byref(rej), n11.ctypes.data, n))
+        return Xcor(N.value, nP.value, nM.value, rej.value, int(lo), int(hi), [int(x) for x in n11])
 
     # -- lengths and chromosome tallies of the samples' intervals (include/genrich_amd.h, gx_interval_stats) --------------
     def interval_stats(self):

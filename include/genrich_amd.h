@@ -625,6 +625,63 @@ int gx_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep
                             size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120,
                             uint64_t* cbases120, size_t chrom_cap);
 
+/* ---- strand cross-correlation of each sample's 5' ends (no Genrich counterpart: the curve and the three figures -- estimated
+ *      fragment length, NSC, RSC -- of phantompeakqualtools / SPP, MACS2 predictd or Q, which ENCODE asks of every ChIP-seq library
+ *      and which otherwise want another tool and another reading of the BAM; for a single-end library the fragment length is
+ *      also what -y's -x N should be) ----
+ * TAGS.  A tag is (chromosome, position, strand) of an alignment's 5' end, taken from the alignment's own coordinates: a forward
+ * alignment gives (+, first aligned base), a reverse one (-, last aligned base), a properly paired fragment both (+, its first
+ * base) and (-, its last base).  The caller makes them (the command line does, where an alignment becomes intervals, before -j /
+ * -y / -x / -w / -d / -D and the clamping change those) and pushes them beside the sample's events.  The library keeps two bit
+ * vectors per open sample, one per strand, one bit per base: a position tagged twice is tagged once, weights do not exist.  A tag
+ * on a chromosome that is skipped (-e), outside the sample's save mask or not owned by the context sets nothing; -E regions are
+ * not masked.  A tag whose chromosome lies beyond the table, whose position lies at or beyond the chromosome's length or whose
+ * strand is neither 0 nor 1 sets nothing and is counted in `rejected`.
+ * COUNTS, per sample, all exact uint64:
+ *     n_pos            N, the summed lengths of the chromosomes that take part (saved, not skipped, owned)
+ *     n_plus, n_minus  the set bits of the two vectors
+ *     n11[d - lo]      for every shift lo <= d <= hi: the positions (c, x) with plus_c[x] and minus_c[x + d], 0 <= x, x + d < len_c;
+ *                      pairs never cross a chromosome's border; d may be negative
+ * They are the same for every launch geometry, order and split of the tags and number of GPUs (a chromosome lives on one
+ * context: the contexts' counts add, gx_xcor_group).
+ * CURVE (host, gx_xcor_metrics):  r(d) = (N n11(d) - n_plus n_minus) / sqrt(n_plus (N - n_plus) n_minus (N - n_minus)), numerator
+ * and radicand exact (128 / 256 bits), each converted once; NaN ("NA") when the radicand is 0.  r uses the UNSHIFTED totals: a
+ * Pearson coefficient over the overlap of the two shifted windows differs from it by O(d / len).  This is the definition here.
+ * LAYOUT AND LIMITS.  Every chromosome starts on a 64-bit word; before and after each lie ceil(max(|lo|, |hi|) / 64) + 1 zero
+ * words, so a shifted window never reads another chromosome's bits.  Two vectors of (genome / 8) bytes per context: 2 x 388 MB
+ * for hg38.  Refused with GX_ERR_ORDER and a text: shifts outside -GX_XCOR_MAX_SHIFT <= lo <= hi <= GX_XCOR_MAX_SHIFT; a genome
+ * of 2^37 bases or more.  A failed allocation: GX_ERR_MEM.
+ *
+ * gx_set_xcor: on, with the shifts lo .. hi; hi < lo: off, the vectors are freed.  After gx_set_chroms, on an idle context before
+ *   its first sample (else GX_ERR_ORDER); the vectors are allocated here (and again when gx_set_chroms / gx_set_owned change the
+ *   table).  They are cleared at every gx_sample_begin, and gx_sample_end makes the pass (k_xc_corr, gx_xcor.h) and keeps the
+ *   sample's counts on the host.  gx_reset drops the results and keeps the setting.  Off: nothing is allocated, launched or recorded.
+ * gx_push_tags: n tags of the open sample, in any order and any split (k_xc_set: one 64-bit atomic OR per tag); the caller's
+ *   memory is free on return.  Without gx_set_xcor, or with no sample open: GX_ERR_ORDER.
+ * gx_xcor_samples / gx_get_xcor: the samples closed since gx_set_xcor / gx_reset, in call order; min(cap, hi - lo + 1) entries
+ *   of n11.  Any pointer may be NULL (n11 when cap is 0).
+ * gx_xcor_group: sample `sample` of every context, added.  Contexts that differ in their samples or shifts: GX_ERR_ORDER.
+ * gx_xcor_tags: the two kernels alone over n tags in host memory and a table of n_chrom lengths of its own, every chromosome
+ *   taking part: vectors of its own, released on return; the context's setting and results are left alone.  grid = 0 /
+ *   tile_words = 0: the library's choices; else that many workgroups (at most 65535) and plus words per tile (a multiple of
+ *   GX_XCOR_MIN_TILE from there to the default).  No sample open.  For tests and measurements.
+ * gx_xcor_geometry: the lanes of a workgroup of k_xc_corr, its most workgroups with grid = 0, the default words per tile, the
+ *   padding words of the widest setting, and the plus words a workgroup walks at most before it adds its 32-bit counters to the
+ *   64-bit ones (2^25: 2^25 words x 64 pairs < 2^32).  Any pointer may be NULL. */
+#define GX_XCOR_MAX_SHIFT 4096
+#define GX_XCOR_MIN_TILE 64
+typedef struct { uint32_t chrom; uint32_t pos; uint32_t strand; /* 1: +, 0: - */ } gx_tag;
+int gx_set_xcor(gx_ctx* ctx, int lo, int hi);
+int gx_push_tags(gx_ctx* ctx, const gx_tag* tags, size_t n);
+int gx_xcor_samples(gx_ctx* ctx, int* n_samples);
+int gx_get_xcor(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, int* lo,
+                int* hi, uint64_t* n11, size_t cap);
+int gx_xcor_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus,
+                  uint64_t* rejected, int* lo, int* hi, uint64_t* n11, size_t cap);
+int gx_xcor_tags(gx_ctx* ctx, const uint32_t* lens, int n_chrom, const gx_tag* tags, size_t n, int lo, int hi, unsigned grid, uint32_t tile_words,
+                 uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, uint64_t* n11, size_t cap);
+int gx_xcor_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* pad_words_for_4096, uint64_t* flush_words);
+
 /* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
  *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
@@ -956,6 +1013,35 @@ int gx_format_chrom_stats(FILE* out, const char* const* names, const uint32_t* l
                           const int* is_ctrl, const uint64_t* const* cn, const uint64_t* const* cw120, const uint64_t* const* cbases120);
 int gx_write_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_chrom, int cut_sites, const uint64_t* cuts,
                                   int n_cuts, FILE* lengths, FILE* metrics, FILE* chroms);
+/* --xcor / --xcor-metrics (no Genrich counterpart).  All but the last: host only, no context.  A sample's counts must be
+ * consistent (n_plus, n_minus <= n_pos, every n11 <= min(n_plus, n_minus), -GX_XCOR_MAX_SHIFT <= lo <= hi <= GX_XCOR_MAX_SHIFT),
+ * else GX_ERR_ORDER, nothing written.
+ * gx_xcor_metrics, read_len = R > 0 or 0 for none; the phantom shift is ph = R - 1:
+ *   frag_shift = the smallest d with the greatest r(d) among max(1, lo) <= d <= hi, without those with |d - ph| <= 10 when R is
+ *     given; fragment_length = frag_shift + 1; r_frag = r(frag_shift).  has_frag = 0 (and NaN) when no such d exists or r is NaN.
+ *   min_shift, r_min = the smallest d with the least r(d) over the whole range.
+ *   nsc = r_frag / r_min, NaN unless r_min > 0.  rsc = (r_frag - r_min) / (r(ph) - r_min), NaN without R, with ph outside
+ *     [lo, hi] or when the denominator is <= 0.  has_phantom: R given and ph inside the range (r_phantom = r(ph)).  No smoothing.
+ * gx_xcor_r: r(d) alone, hi - lo + 1 doubles.
+ * gx_format_xcor: header "sample shift n11 r", then per sample (t<rep> / c<rep>) a line "# <sample> n_pos=.. n_plus=.. n_minus=..
+ *   rejected=.." and one row per shift; r as %.6f, NA where undefined.
+ * gx_format_xcor_metrics: header "sample n_pos n_plus n_minus fragment_length r_frag min_shift r_min phantom_shift r_phantom NSC
+ *   RSC", one row per sample; doubles %.6f; NA where undefined.
+ * gx_write_xcor_group (gx_api.hip: it reads contexts): the group sums per sample, then whichever of the two files is not NULL. */
+typedef struct {
+  int has_frag, frag_shift, fragment_length;
+  int min_shift;
+  int has_phantom, phantom_shift;
+  int pad_;
+  double r_frag, r_min, r_phantom, nsc, rsc;
+} gx_xcor_metrics_t;
+int gx_xcor_metrics(uint64_t n_pos, uint64_t n_plus, uint64_t n_minus, int lo, int hi, const uint64_t* n11, int read_len, gx_xcor_metrics_t* out);
+int gx_xcor_r(uint64_t n_pos, uint64_t n_plus, uint64_t n_minus, int lo, int hi, const uint64_t* n11, double* r);   /* r[hi - lo + 1] */
+int gx_format_xcor(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_pos, const uint64_t* n_plus,
+                   const uint64_t* n_minus, const uint64_t* rejected, int lo, int hi, const uint64_t* const* n11);
+int gx_format_xcor_metrics(FILE* out, int n_samples, const int* rep, const int* is_ctrl, const uint64_t* n_pos, const uint64_t* n_plus,
+                           const uint64_t* n_minus, int lo, int hi, const uint64_t* const* n11, int read_len);
+int gx_write_xcor_group(gx_ctx* const* ctxs, int n_ctx, int read_len, FILE* curve, FILE* metrics);
 /* --depth / --depth-metrics (no Genrich counterpart).  The first three: host only, no context.  A histogram that contradicts
  * itself (a missing array, excluded > total, covered + zero != B, rsum[d] > 119 bases[d], a deep list that is not strictly
  * ascending from 120 GX_DEPTH_BOUND, covered bases without min_v <= max_v): GX_ERR_ORDER, nothing written.
@@ -1099,6 +1185,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_SATURATION 16777216u /* bit 24: k_sub_write ran since the last gx_reset (gx_subsample_events, gx_subsample_kept, gx_saturation) */
 #define GX_PATH_DEPTH 33554432u /* bit 25: k_depth_hist ran since the last gx_reset (gx_set_depth_hist; a sample was closed with it on) */
 #define GX_PATH_IVSTAT 67108864u /* bit 26: k_ivstat ran since the last gx_reset (gx_interval_stats, gx_interval_stats_events) */
+#define GX_PATH_XCOR 134217728u /* bit 27: k_xc_set / k_xc_corr ran since the last gx_reset (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
