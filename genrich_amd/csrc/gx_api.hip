@@ -7,6 +7,8 @@
 #include "gx_host_build.h"
 #include "gx_host_sweep.h"
 #include "gx_host_stats.h"
+#include "gx_sparse.h"
+#include "gx_host_kept.h"
 #include "gx_host_count.h"
 #include "gx_host_regions.h"
 #include "gx_host_coverage.h"
@@ -22,6 +24,68 @@
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
 
+namespace {
+
+// The entry checks the passes between samples repeat, with the function's name in their sentences.
+int guard_closed(gx_ctx* ctx, const char* fn) {
+  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, std::string(fn) + ": a sample is open");
+  return GX_OK;
+}
+// ... of the passes over the kept samples: counting on; with needSample, no sample open and at least one closed
+int guard_kept(gx_ctx* ctx, const char* fn, bool needSample) {
+  if (!ctx->countOn) return refuse(ctx, std::string(fn) + " needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (!needSample) return GX_OK;
+  if (int rc = guard_closed(ctx, fn)) return rc;
+  if (ctx->kept.empty()) return refuse(ctx, std::string(fn) + ": no closed sample");
+  return GX_OK;
+}
+
+// A sample's result summed over contexts (each works on chromosomes of its own): every context has its results
+// (ready(c)), as many as context 0 and compatible with them (same(c, c0, r, r0)); add(sum, r) adds one.
+template <class R, class Ready, class Same, class Add>
+int group_sum(gx_ctx* const* ctxs, int n_ctx, int sample, std::vector<R> gx_ctx::*results, Ready ready, Same same, Add add, R& sum) {
+  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
+  for (int g = 0; g < n_ctx; g++) {
+    const gx_ctx* c = ctxs[g];
+    if (!c || !ready(c) || sample < 0 || (size_t)sample >= (c->*results).size() || (c->*results).size() != (ctxs[0]->*results).size() ||
+        !same(c, ctxs[0], (c->*results)[sample], (ctxs[0]->*results)[sample]))
+      return GX_ERR_ORDER;
+    if (g == 0) sum = (c->*results)[sample];
+    else add(sum, (c->*results)[sample]);
+  }
+  return GX_OK;
+}
+template <class R>
+bool same_sample(const R& r, const R& r0) { return r.rep == r0.rep && r.ctrl == r0.ctrl; }
+constexpr auto any_goes = [](const auto&...) { return true; };
+
+int depth_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::DepthResult& sum) {
+  return group_sum(ctxs, n_ctx, sample, &gx_ctx::depth, [](const gx_ctx* c) { return c->phase != 1 && c->phase != 3; }, any_goes, depth_add, sum);
+}
+int cpx_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::CpxResult& sum) {
+  return group_sum(ctxs, n_ctx, sample, &gx_ctx::cpx, [](const gx_ctx* c) { return c->cpxReady; }, any_goes, cpx_add, sum);
+}
+int ivs_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::IvsResult& sum) {
+  return group_sum(ctxs, n_ctx, sample, &gx_ctx::ivs, [](const gx_ctx* c) { return c->ivsReady; },
+                   [](const gx_ctx*, const gx_ctx*, const auto& r, const auto& r0) { return r.cn.size() == r0.cn.size() && same_sample(r, r0); }, ivs_add, sum);
+}
+int xc_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::XcResult& sum) {
+  return group_sum(ctxs, n_ctx, sample, &gx_ctx::xc, any_goes,
+                   [](const gx_ctx* c, const gx_ctx* c0, const auto& r, const auto& r0) { return c->xcLo == c0->xcLo && c->xcHi == c0->xcHi && same_sample(r, r0); },
+                   xc_add, sum);
+}
+// The writers that run their pass themselves: on every context, which all report as many samples (*nS)
+int pass_on_all(gx_ctx* const* ctxs, int n_ctx, int (*pass)(gx_ctx*, int*), int* nS) {
+  for (int g = 0; g < n_ctx; g++) {
+    int n = 0;
+    if (int rc = pass(ctxs[g], &n)) return rc;
+    if (g && n != *nS) return GX_ERR_ORDER;
+    *nS = n;
+  }
+  return GX_OK;
+}
+
+}  // namespace
 
 // ================================ C ABI ==================================================
 
@@ -1005,15 +1069,8 @@ int gx_get_depth(gx_ctx* ctx, int sample, gx_depth_hist* out, uint64_t* bases, u
 
 int gx_depth_group(gx_ctx* const* ctxs, int n_ctx, int sample, gx_depth_hist* out, uint64_t* bases, uint64_t* rsum, uint64_t* rsq,
                    uint64_t* deep_v, uint64_t* deep_bases, size_t cap, size_t* n_deep) {
-  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
   gx_ctx::DepthResult sum;
-  for (int g = 0; g < n_ctx; g++) {
-    gx_ctx* c = ctxs[g];
-    if (!c || c->phase == 1 || c->phase == 3 || sample < 0 || (size_t)sample >= c->depth.size() || c->depth.size() != ctxs[0]->depth.size())
-      return GX_ERR_ORDER;
-    if (g == 0) sum = c->depth[sample];
-    else depth_add(sum, c->depth[sample]);
-  }
+  if (int rc = depth_sum(ctxs, n_ctx, sample, sum)) return rc;
   return depth_give(sum, out, bases, rsum, rsq, deep_v, deep_bases, cap, n_deep);
 }
 
@@ -1037,16 +1094,18 @@ int gx_write_depth_group(gx_ctx* const* ctxs, int n_ctx, FILE* depth, FILE* metr
   if (!ctxs || n_ctx < 1 || !ctxs[0] || (!depth && !metrics)) return GX_ERR_ORDER;
   const size_t nS = ctxs[0]->depth.size();
   if (!nS) return GX_ERR_ORDER;
+  std::vector<gx_ctx::DepthResult> sums(nS);
   std::vector<gx_depth_hist> hs(nS);
-  std::vector<std::vector<uint64_t>> arr(nS * 5);
-  for (size_t i = 0; i < nS; i++) {
-    size_t n = 0;
-    if (int rc = gx_depth_group(ctxs, n_ctx, (int)i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n)) return rc;
-    for (int k = 0; k < 3; k++) arr[i * 5 + k].assign(DEPTH_BOUND, 0);
-    for (int k = 3; k < 5; k++) arr[i * 5 + k].assign(std::max<size_t>(n, 1), 0);
-    if (int rc = gx_depth_group(ctxs, n_ctx, (int)i, &hs[i], arr[i * 5].data(), arr[i * 5 + 1].data(), arr[i * 5 + 2].data(), arr[i * 5 + 3].data(),
-                                arr[i * 5 + 4].data(), n, nullptr))
-      return rc;
+  for (size_t i = 0; i < nS; i++) {   // (the histograms point into the sums)
+    gx_ctx::DepthResult& r = sums[i];
+    if (int rc = depth_sum(ctxs, n_ctx, (int)i, r)) return rc;
+    (void)depth_give(r, &hs[i], nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+    hs[i].bases = r.bases.data();
+    hs[i].rsum = r.rsum.data();
+    hs[i].rsq = r.rsq.data();
+    hs[i].deep_v = r.deepV.data();
+    hs[i].deep_bases = r.deepBases.data();
+    hs[i].n_deep = r.deepV.size();
   }
   if (depth)
     if (int rc = gx_format_depth(depth, (int)nS, hs.data())) return rc;
@@ -1437,7 +1496,7 @@ int gx_get_peak_signal(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t*
 int gx_peak_signal_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_region* peaks, size_t n_peaks, const uint32_t* summit_off, unsigned grid,
                           int64_t* area120, int64_t* max120, uint32_t* summit, uint32_t* covered, int64_t* at_summit120) {
   if (!ctx || ctx->nChrom == 0 || (n && !ev) || (n_peaks && !peaks)) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_peak_signal_events: a sample is open");
+  if (int rc = guard_closed(ctx, "gx_peak_signal_events")) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   if (int rc = peak_signal_events(ctx, ev, n, peaks, n_peaks, summit_off, grid)) return rc;
   psig_give(static_cast<const PsigRec*>(ctx->psigEvHost.p), n_peaks, n_peaks, area120, max120, summit, covered, at_summit120);
@@ -1457,12 +1516,7 @@ int gx_peak_signal_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_
 int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out) {
   if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
   int nS = 0;
-  for (int g = 0; g < n_ctx; g++) {
-    int n = 0;
-    if (int rc = gx_peak_signal(ctxs[g], &n)) return rc;
-    if (g && n != nS) return GX_ERR_ORDER;
-    nS = n;
-  }
+  if (int rc = pass_on_all(ctxs, n_ctx, gx_peak_signal, &nS)) return rc;
   // the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group), their records following them
   std::vector<gx_peak> pk;
   std::vector<std::vector<int64_t>> area((size_t)nS), mx((size_t)nS), at((size_t)nS);
@@ -1508,9 +1562,7 @@ int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out) { ret
 
 int gx_complexity(gx_ctx* ctx, int* n_samples) {
   if (!ctx) return GX_ERR_ORDER;
-  if (!ctx->countOn) return refuse(ctx, "gx_complexity needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_complexity: a sample is open");
-  if (ctx->kept.empty()) return refuse(ctx, "gx_complexity: no closed sample");
+  if (int rc = guard_kept(ctx, "gx_complexity", true)) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   ctx->cpxReady = false;
   if (int rc = complexity_kept(ctx)) return rc;
@@ -1521,20 +1573,17 @@ int gx_complexity(gx_ctx* ctx, int* n_samples) {
 int gx_get_complexity(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult, uint64_t* keys,
                       size_t cap, size_t* n_classes) {
   if (!ctx || !ctx->cpxReady || sample < 0 || (size_t)sample >= ctx->cpx.size()) return GX_ERR_ORDER;
-  const gx_ctx::CpxResult& r = ctx->cpx[sample];
-  if (rep) *rep = r.rep;
-  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
-  return cpx_give(r, n_obs, n_distinct, mult, keys, cap, n_classes);
+  return cpx_give(ctx->cpx[sample], rep, is_ctrl, n_obs, n_distinct, mult, keys, cap, n_classes);
 }
 
 int gx_complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, int cap_log, uint64_t* n_obs, uint64_t* n_distinct,
                          uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes) {
   if (!ctx || ctx->nChrom == 0 || (n && !ev) || cap_log < 0 || (cap && (!mult || !keys))) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_complexity_events: a sample is open");
+  if (int rc = guard_closed(ctx, "gx_complexity_events")) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   gx_ctx::CpxResult r;
   if (int rc = complexity_events(ctx, ev, n, grid, cap_log, r)) return rc;
-  return cpx_give(r, n_obs, n_distinct, mult, keys, cap, n_classes);
+  return cpx_give(r, nullptr, nullptr, n_obs, n_distinct, mult, keys, cap, n_classes);
 }
 
 int gx_complexity_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint64_t n, size_t* least_capacity) {
@@ -1554,44 +1603,25 @@ int gx_complexity_last(gx_ctx* ctx, size_t* capacity) {
 // (the two over contexts live here, not in gx_emit.cpp, like the fingerprint's: they read contexts)
 int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult,
                         uint64_t* keys, size_t cap, size_t* n_classes) {
-  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
   gx_ctx::CpxResult sum;
-  for (int g = 0; g < n_ctx; g++) {
-    gx_ctx* c = ctxs[g];
-    if (!c || !c->cpxReady || sample < 0 || (size_t)sample >= c->cpx.size() || c->cpx.size() != ctxs[0]->cpx.size()) return GX_ERR_ORDER;
-    if (g == 0) {
-      sum.rep = c->cpx[sample].rep;
-      sum.ctrl = c->cpx[sample].ctrl;
-    }
-    cpx_add(sum, c->cpx[sample]);
-  }
-  if (rep) *rep = sum.rep;
-  if (is_ctrl) *is_ctrl = sum.ctrl ? 1 : 0;
-  return cpx_give(sum, n_obs, n_distinct, mult, keys, cap, n_classes);
+  if (int rc = cpx_sum(ctxs, n_ctx, sample, sum)) return rc;
+  return cpx_give(sum, rep, is_ctrl, n_obs, n_distinct, mult, keys, cap, n_classes);
 }
 
 int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FILE* hist) {
   if (!ctxs || n_ctx < 1 || !metrics) return GX_ERR_ORDER;
   int nS = 0;
-  for (int g = 0; g < n_ctx; g++) {
-    int n = 0;
-    if (int rc = gx_complexity(ctxs[g], &n)) return rc;
-    if (g && n != nS) return GX_ERR_ORDER;
-    nS = n;
-  }
-  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
-  std::vector<uint64_t> N((size_t)nS), D((size_t)nS);
-  std::vector<std::vector<uint64_t>> mult((size_t)nS), keys((size_t)nS);
-  std::vector<const uint64_t*> pm((size_t)nS), pk((size_t)nS);
-  std::vector<size_t> np((size_t)nS);
+  if (int rc = pass_on_all(ctxs, n_ctx, gx_complexity, &nS)) return rc;
+  std::vector<gx_ctx::CpxResult> sums((size_t)nS);   // (each sample summed once; the writers read the sums in place)
+  std::vector<int> rep, ctrl;
+  std::vector<uint64_t> N, D;
+  std::vector<const uint64_t*> pm, pk;
+  std::vector<size_t> np;
   for (int i = 0; i < nS; i++) {
-    size_t n = 0;
-    if (int rc = gx_complexity_group(ctxs, n_ctx, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n)) return rc;
-    mult[i].resize(n);
-    keys[i].resize(n);
-    if (int rc = gx_complexity_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], &N[i], &D[i], mult[i].data(), keys[i].data(), n, &np[i])) return rc;
-    pm[i] = mult[i].data();
-    pk[i] = keys[i].data();
+    const gx_ctx::CpxResult& r = sums[i];
+    if (int rc = cpx_sum(ctxs, n_ctx, i, sums[i])) return rc;
+    rep.push_back(r.rep); ctrl.push_back(r.ctrl); N.push_back(r.N); D.push_back(r.D);
+    pm.push_back(r.mult.data()); pk.push_back(r.keys.data()); np.push_back(r.mult.size());
   }
   if (int rc = gx_format_complexity(metrics, nS, rep.data(), ctrl.data(), N.data(), D.data(), pm.data(), pk.data(), np.data())) return rc;
   return hist ? gx_format_complexity_hist(hist, nS, rep.data(), ctrl.data(), pm.data(), pk.data(), np.data()) : GX_OK;
@@ -1599,9 +1629,7 @@ int gx_write_complexity_group(gx_ctx* const* ctxs, int n_ctx, FILE* metrics, FIL
 
 int gx_interval_stats(gx_ctx* ctx, int* n_samples) {
   if (!ctx) return GX_ERR_ORDER;
-  if (!ctx->countOn) return refuse(ctx, "gx_interval_stats needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_interval_stats: a sample is open");
-  if (ctx->kept.empty()) return refuse(ctx, "gx_interval_stats: no closed sample");
+  if (int rc = guard_kept(ctx, "gx_interval_stats", true)) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   ctx->ivsReady = false;
   if (int rc = ivstat_kept(ctx)) return rc;
@@ -1612,26 +1640,23 @@ int gx_interval_stats(gx_ctx* ctx, int* n_samples) {
 int gx_get_interval_lengths(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120, size_t cap,
                             size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted) {
   if (!ctx || !ctx->ivsReady || sample < 0 || (size_t)sample >= ctx->ivs.size()) return GX_ERR_ORDER;
-  const gx_ctx::IvsResult& r = ctx->ivs[sample];
-  if (rep) *rep = r.rep;
-  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
-  return ivs_give(r, length, n, w120, cap, n_classes, n_inverted, w120_inverted, nullptr, nullptr, nullptr, 0);
+  return ivs_give(ctx->ivs[sample], rep, is_ctrl, length, n, w120, cap, n_classes, n_inverted, w120_inverted, nullptr, nullptr, nullptr, 0);
 }
 
 int gx_get_chrom_stats(gx_ctx* ctx, int sample, uint64_t* cn, uint64_t* cw120, uint64_t* cbases120, size_t cap) {
   if (!ctx || !ctx->ivsReady || sample < 0 || (size_t)sample >= ctx->ivs.size()) return GX_ERR_ORDER;
-  return ivs_give(ctx->ivs[sample], nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, cn, cw120, cbases120, cap);
+  return ivs_give(ctx->ivs[sample], nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, cn, cw120, cbases120, cap);
 }
 
 int gx_interval_stats_events(gx_ctx* ctx, const gx_event* ev, size_t n, unsigned grid, size_t list_cap, uint64_t* length, uint64_t* n_iv,
                              uint64_t* w120, size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn,
                              uint64_t* cw120, uint64_t* cbases120, size_t chrom_cap) {
   if (!ctx || ctx->nChrom == 0 || (n && !ev) || (cap && (!length || !n_iv || !w120)) || (chrom_cap && (!cn || !cw120 || !cbases120))) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_interval_stats_events: a sample is open");
+  if (int rc = guard_closed(ctx, "gx_interval_stats_events")) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   gx_ctx::IvsResult r;
   if (int rc = ivstat_events(ctx, ev, n, grid, list_cap, r)) return rc;
-  return ivs_give(r, length, n_iv, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
+  return ivs_give(r, nullptr, nullptr, length, n_iv, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
 }
 
 int gx_interval_stats_geometry(int* lanes, int* grid, uint32_t* lds_bound, uint32_t* chrom_window, size_t* list_capacity) {
@@ -1655,51 +1680,28 @@ int gx_interval_stats_last(gx_ctx* ctx, size_t* list_capacity, int* reruns) {
 int gx_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120,
                             size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120,
                             uint64_t* cbases120, size_t chrom_cap) {
-  if (!ctxs || n_ctx < 1) return GX_ERR_ORDER;
   gx_ctx::IvsResult sum;
-  for (int g = 0; g < n_ctx; g++) {
-    gx_ctx* c = ctxs[g];
-    if (!c || !c->ivsReady || sample < 0 || (size_t)sample >= c->ivs.size() || c->ivs.size() != ctxs[0]->ivs.size() ||
-        c->ivs[sample].cn.size() != ctxs[0]->ivs[sample].cn.size() || c->ivs[sample].rep != ctxs[0]->ivs[sample].rep ||
-        c->ivs[sample].ctrl != ctxs[0]->ivs[sample].ctrl)
-      return GX_ERR_ORDER;
-    if (g == 0) {
-      sum.rep = c->ivs[sample].rep;
-      sum.ctrl = c->ivs[sample].ctrl;
-    }
-    ivs_add(sum, c->ivs[sample]);
-  }
-  if (rep) *rep = sum.rep;
-  if (is_ctrl) *is_ctrl = sum.ctrl ? 1 : 0;
-  return ivs_give(sum, length, n, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
+  if (int rc = ivs_sum(ctxs, n_ctx, sample, sum)) return rc;
+  return ivs_give(sum, rep, is_ctrl, length, n, w120, cap, n_classes, n_inverted, w120_inverted, cn, cw120, cbases120, chrom_cap);
 }
 
 int gx_write_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_chrom, int cut_sites, const uint64_t* cuts,
                                   int n_cuts, FILE* lengths, FILE* metrics, FILE* chroms) {
   if (!ctxs || n_ctx < 1 || !ctxs[0] || (!lengths && !metrics && !chroms) || (chroms && (!names || n_chrom != (int)ctxs[0]->nChrom))) return GX_ERR_ORDER;
   int nS = 0;
-  for (int g = 0; g < n_ctx; g++) {
-    int n = 0;
-    if (int rc = gx_interval_stats(ctxs[g], &n)) return rc;
-    if (g && n != nS) return GX_ERR_ORDER;
-    nS = n;
-  }
+  if (int rc = pass_on_all(ctxs, n_ctx, gx_interval_stats, &nS)) return rc;
   const size_t nC = ctxs[0]->nChrom;
-  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
-  std::vector<uint64_t> nInv((size_t)nS), wInv((size_t)nS);
-  std::vector<std::vector<uint64_t>> col((size_t)nS * 6);
-  std::vector<const uint64_t*> pl((size_t)nS), pn((size_t)nS), pw((size_t)nS), pcn((size_t)nS), pcw((size_t)nS), pcb((size_t)nS);
-  std::vector<size_t> np((size_t)nS);
+  std::vector<gx_ctx::IvsResult> sums((size_t)nS);   // (each sample summed once; the writers read the sums in place)
+  std::vector<int> rep, ctrl;
+  std::vector<uint64_t> nInv, wInv;
+  std::vector<const uint64_t*> pl, pn, pw, pcn, pcw, pcb;
+  std::vector<size_t> np;
   for (int i = 0; i < nS; i++) {
-    size_t n = 0;
-    if (int rc = gx_interval_stats_group(ctxs, n_ctx, i, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, nullptr, nullptr, nullptr, nullptr, 0)) return rc;
-    std::vector<uint64_t>* a = &col[(size_t)i * 6];
-    for (int k = 0; k < 3; k++) a[k].assign(std::max<size_t>(n, 1), 0);
-    for (int k = 3; k < 6; k++) a[k].assign(nC, 0);
-    if (int rc = gx_interval_stats_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], a[0].data(), a[1].data(), a[2].data(), n, &np[i], &nInv[i], &wInv[i],
-                                         a[3].data(), a[4].data(), a[5].data(), nC))
-      return rc;
-    pl[i] = a[0].data(); pn[i] = a[1].data(); pw[i] = a[2].data(); pcn[i] = a[3].data(); pcw[i] = a[4].data(); pcb[i] = a[5].data();
+    const gx_ctx::IvsResult& r = sums[i];
+    if (int rc = ivs_sum(ctxs, n_ctx, i, sums[i])) return rc;
+    rep.push_back(r.rep); ctrl.push_back(r.ctrl); nInv.push_back(r.nInv); wInv.push_back(r.wInv);
+    pl.push_back(r.len.data()); pn.push_back(r.n.data()); pw.push_back(r.w.data()); np.push_back(r.len.size());
+    pcn.push_back(r.cn.data()); pcw.push_back(r.cw.data()); pcb.push_back(r.cb.data());
   }
   if (lengths)
     if (int rc = gx_format_lengths(lengths, nS, rep.data(), ctrl.data(), pl.data(), pn.data(), pw.data(), np.data(), nInv.data(), wInv.data(), cut_sites)) return rc;
@@ -1760,26 +1762,15 @@ int gx_get_xcor(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos
 // (the two over contexts live here, not in gx_emit.cpp: they read contexts)
 int gx_xcor_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus,
                   uint64_t* rejected, int* lo, int* hi, uint64_t* n11, size_t cap) {
-  if (!ctxs || n_ctx < 1 || !ctxs[0]) return GX_ERR_ORDER;
   gx_ctx::XcResult sum;
-  for (int g = 0; g < n_ctx; g++) {
-    gx_ctx* c = ctxs[g];
-    if (!c || sample < 0 || (size_t)sample >= c->xc.size() || c->xc.size() != ctxs[0]->xc.size() || c->xcLo != ctxs[0]->xcLo ||
-        c->xcHi != ctxs[0]->xcHi || c->xc[sample].rep != ctxs[0]->xc[sample].rep || c->xc[sample].ctrl != ctxs[0]->xc[sample].ctrl)
-      return GX_ERR_ORDER;
-    if (g == 0) {
-      sum.rep = c->xc[sample].rep;
-      sum.ctrl = c->xc[sample].ctrl;
-    }
-    xc_add(sum, c->xc[sample]);
-  }
+  if (int rc = xc_sum(ctxs, n_ctx, sample, sum)) return rc;
   return xc_give(sum, ctxs[0]->xcLo, ctxs[0]->xcHi, rep, is_ctrl, n_pos, n_plus, n_minus, rejected, lo, hi, n11, cap);
 }
 
 int gx_xcor_tags(gx_ctx* ctx, const uint32_t* lens, int n_chrom, const gx_tag* tags, size_t n, int lo, int hi, unsigned grid, uint32_t tile_words,
                  uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, uint64_t* n11, size_t cap) {
   if (!ctx || !lens || n_chrom < 1 || (n && !tags) || (cap && !n11)) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_xcor_tags: a sample is open");
+  if (int rc = guard_closed(ctx, "gx_xcor_tags")) return rc;
   HIPCHECK(hipSetDevice(ctx->device));
   gx_ctx::XcResult r;
   if (int rc = xc_tags(ctx, lens, n_chrom, tags, n, lo, hi, grid, tile_words, r)) return rc;
@@ -1800,15 +1791,16 @@ int gx_write_xcor_group(gx_ctx* const* ctxs, int n_ctx, int read_len, FILE* curv
   if (!ctxs || n_ctx < 1 || !ctxs[0] || (!curve && !metrics)) return GX_ERR_ORDER;
   const int nS = (int)ctxs[0]->xc.size();
   if (nS < 1) return GX_ERR_ORDER;
-  int lo = 0, hi = -1;
-  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
-  std::vector<uint64_t> N((size_t)nS), nP((size_t)nS), nM((size_t)nS), rej((size_t)nS);
-  std::vector<std::vector<uint64_t>> col((size_t)nS);
-  std::vector<const uint64_t*> pc((size_t)nS);
+  const int lo = ctxs[0]->xcLo, hi = ctxs[0]->xcHi;
+  std::vector<gx_ctx::XcResult> sums((size_t)nS);   // (each sample summed once; the writers read the sums in place)
+  std::vector<int> rep, ctrl;
+  std::vector<uint64_t> N, nP, nM, rej;
+  std::vector<const uint64_t*> pc;
   for (int i = 0; i < nS; i++) {
-    col[i].assign((size_t)(ctxs[0]->xcHi - ctxs[0]->xcLo + 1), 0);
-    if (int rc = gx_xcor_group(ctxs, n_ctx, i, &rep[i], &ctrl[i], &N[i], &nP[i], &nM[i], &rej[i], &lo, &hi, col[i].data(), col[i].size())) return rc;
-    pc[i] = col[i].data();
+    const gx_ctx::XcResult& r = sums[i];
+    if (int rc = xc_sum(ctxs, n_ctx, i, sums[i])) return rc;
+    rep.push_back(r.rep); ctrl.push_back(r.ctrl); N.push_back(r.N); nP.push_back(r.nP); nM.push_back(r.nM); rej.push_back(r.rejected);
+    pc.push_back(r.n11.data());
   }
   if (curve)
     if (int rc = gx_format_xcor(curve, nS, rep.data(), ctrl.data(), N.data(), nP.data(), nM.data(), rej.data(), lo, hi, pc.data())) return rc;
@@ -1829,17 +1821,12 @@ int gx_subsample_geometry(int* lanes, int* grid, uint32_t* block_events) {
 int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold, unsigned grid,
                         gx_event* out, size_t cap, size_t* n_out) {
   if (!ctx || (n && !ev) || (cap && !out)) return GX_ERR_ORDER;
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_subsample_events: a sample is open");
+  if (int rc = guard_closed(ctx, "gx_subsample_events")) return rc;
   if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
   if (grid > SUB_MAX_GRID) return refuse(ctx, "subsample: more than 65535 workgroups");
   HIPCHECK(hipSetDevice(ctx->device));
   std::vector<gx_ctx::Seg> segs;
-  if (n) {
-    const size_t bytes = n * (packed ? sizeof(gx_event8) : sizeof(gx_event));
-    POOLED(ctx, ctx->subEv, bytes);
-    HIPCHECK(hipMemcpyAsync(ctx->subEv.p, ev, bytes, hipMemcpyHostToDevice, ctx->stream));
-    segs.push_back({ctx->subEv.as<gx_event>(), n, nullptr, packed != 0});
-  }
+  if (int rc = kept_upload(ctx, ev, n, packed != 0, segs)) return rc;
   const CntChunk* dCk = nullptr;
   const u64* dFirst = nullptr;
   u32 nCk = 0;
@@ -1851,8 +1838,8 @@ int gx_subsample_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint6
 
 int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_out) {
   if (!ctx || (cap && !out)) return GX_ERR_ORDER;
-  if (!ctx->countOn) return refuse(ctx, "gx_subsample_kept needs the samples' intervals kept (gx_set_count_in_peaks)");
-  if (ctx->phase == 1 || ctx->phase == 3) return refuse(ctx, "gx_subsample_kept: a sample is open");
+  if (int rc = guard_kept(ctx, "gx_subsample_kept", false)) return rc;
+  if (int rc = guard_closed(ctx, "gx_subsample_kept")) return rc;
   if (sample < 0 || (size_t)sample >= ctx->kept.size()) return refuse(ctx, "gx_subsample_kept: no such sample");
   if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
   HIPCHECK(hipSetDevice(ctx->device));
@@ -1863,7 +1850,7 @@ int gx_subsample_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold
 
 int gx_saturation(gx_ctx* ctx, const uint64_t* threshold, int n_points, uint64_t seed, unsigned flags, gx_sat_point* out) {
   if (!ctx || !threshold || n_points < 1 || !out || (flags & ~GX_SAT_CONTROLS)) return GX_ERR_ORDER;
-  if (!ctx->countOn) return refuse(ctx, "gx_saturation needs the samples' intervals kept (gx_set_count_in_peaks)");
+  if (int rc = guard_kept(ctx, "gx_saturation", false)) return rc;
   if (ctx->phase != 0 || !ctx->peaksReady) return refuse(ctx, "gx_saturation comes after gx_find_peaks, with no sample open");
   if (ctx->world > 1 || ctx->forceColl) return refuse(ctx, "gx_saturation: one context only (the re-call on several needs collectives between their children)");
   for (int j = 0; j < n_points; j++)

@@ -66,28 +66,14 @@ int cpx_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, u64
     ctx->err = (h[CPXC_STATUS] & CPX_ST_TABLE_FULL) ? "library complexity: the table ran full" : "library complexity: the list of frequent keys ran full";
     return GX_ERR_DEVICE;
   }
-  const u64 nBig = h[CPXC_NBIG];
-  std::vector<u32> big((size_t)nBig);
-  if (nBig) {
-    HIPCHECK(hipMemcpyAsync(big.data(), ctx->cpxBig.p, (size_t)nBig * 4, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::sort(big.begin(), big.end());   // (the list comes in the order of the races: nobody sees it)
-  }
+  std::vector<u32> big;
+  if (int rc = counted_list_read(ctx, ctx->cpxBig, h[CPXC_NBIG], [](u32 m) { return m; }, big)) return rc;
   r.N = h[CPXC_N];
   r.D = h[CPXC_D];
   u64 sumH = 0, sumMH = 0;
   for (u32 m = 1; m < CPX_BOUND; m++)
-    if (h[CPXC_WORDS + m]) {
-      r.mult.push_back(m);
-      r.keys.push_back(h[CPXC_WORDS + m]);
-    }
-  for (size_t i = 0; i < big.size(); i++) {
-    if (i && big[i] == big[i - 1]) r.keys.back()++;
-    else {
-      r.mult.push_back(big[i]);
-      r.keys.push_back(1);
-    }
-  }
+    if (h[CPXC_WORDS + m]) gx_sparse::append(r.mult, {&r.keys}, m, {h[CPXC_WORDS + m]});
+  for (u32 m : big) gx_sparse::append(r.mult, {&r.keys}, m, {1});
   for (size_t i = 0; i < r.mult.size(); i++) {
     sumH += r.keys[i];
     sumMH += r.mult[i] * r.keys[i];
@@ -99,25 +85,17 @@ int cpx_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, u64
   return GX_OK;
 }
 
-// every kept sample, through the staging the passes share (gx_host_count.h kept_stage)
+// every kept sample
 int complexity_kept(gx_ctx* ctx) {
-  const u32 nS = (u32)ctx->kept.size(), nChrom = ctx->nChrom;
   if (int rc = cpx_domain(ctx)) return rc;
-  std::vector<u64> nEv(nS, 0);
-  for (u32 k = 0; k < nS; k++) {
-    for (const gx_ctx::Seg& sg : ctx->kept[k].segs) nEv[k] += sg.n;
-    if (nEv[k] >> 31) return refuse(ctx, "library complexity: a sample of 2^31 events or more");
-  }
-  KeptIn in;
-  if (int rc = kept_stage(ctx, kept_views(ctx), 0, true, false, in)) return rc;
-  if (int rc = kept_send(ctx, in)) return rc;
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (a sample without events launches nothing: the staging area is free again)
-  std::vector<gx_ctx::CpxResult> res(nS);
-  for (u32 k = 0; k < nS; k++) {
-    if (int rc = cpx_pass(ctx, in.dCk + in.chunk0[k], (u32)(in.chunk0[k + 1] - in.chunk0[k]), in.dCh + (size_t)k * nChrom, nEv[k], 0, 0, res[k])) return rc;
-    res[k].rep = ctx->kept[k].rep;
-    res[k].ctrl = ctx->kept[k].ctrl;
-  }
+  const std::vector<KeptView> views = kept_views(ctx);
+  const std::vector<ViewSize> z = kept_sizes(views);
+  for (const ViewSize& v : z)
+    if (v.n >> 31) return refuse(ctx, "library complexity: a sample of 2^31 events or more");
+  std::vector<gx_ctx::CpxResult> res(views.size());
+  if (int rc = kept_each_view(ctx, views, [&](const CntChunk* dCk, u32 nCk, const CntChrom* dCh, size_t v) { return cpx_pass(ctx, dCk, nCk, dCh, z[v].n, 0, 0, res[v]); }))
+    return rc;
+  kept_stamp(ctx, res);
   ctx->cpx = std::move(res);
   ctx->cpxReady = true;
   return GX_OK;
@@ -131,20 +109,15 @@ int complexity_events(gx_ctx* ctx, const gx_event* ev, size_t n, u32 grid, int c
   if (capLog && (capLog < cpx_least_cap_log(n) || capLog > 32)) return refuse(ctx, "library complexity: a table of fewer than 2 n slots (or more than 2^32)");
   if (grid > CPX_MAX_GRID) return refuse(ctx, "library complexity: more than 65535 workgroups");
   std::vector<gx_ctx::Seg> segs;
-  if (n) {
-    POOLED(ctx, ctx->cpxEv, n * sizeof(gx_event));
-    HIPCHECK(hipMemcpyAsync(ctx->cpxEv.p, ev, n * sizeof(gx_event), hipMemcpyHostToDevice, ctx->stream));
-    segs.push_back({ctx->cpxEv.as<gx_event>(), n, nullptr, false});
-  }
-  KeptIn in;
-  if (int rc = kept_stage(ctx, {KeptView{&segs, nullptr}}, 0, true, false, in)) return rc;
-  if (int rc = kept_send(ctx, in)) return rc;
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (the events are the caller's; no events launch nothing)
-  return cpx_pass(ctx, in.dCk, (u32)in.chunk0[1], in.dCh, n, grid, capLog, r);
+  if (int rc = kept_upload(ctx, ev, n, false, segs)) return rc;
+  return kept_each_view(ctx, {KeptView{&segs, nullptr}}, [&](const CntChunk* dCk, u32 nCk, const CntChrom* dCh, size_t) { return cpx_pass(ctx, dCk, nCk, dCh, n, grid, capLog, r); });
 }
 
 // a result to the caller: min(cap, classes) pairs
-int cpx_give(const gx_ctx::CpxResult& r, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult, uint64_t* keys, size_t cap, size_t* n_classes) {
+int cpx_give(const gx_ctx::CpxResult& r, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult, uint64_t* keys, size_t cap,
+             size_t* n_classes) {
+  if (rep) *rep = r.rep;
+  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
   if (cap && (!mult || !keys)) return GX_ERR_ORDER;
   if (n_obs) *n_obs = r.N;
   if (n_distinct) *n_distinct = r.D;
@@ -159,21 +132,9 @@ int cpx_give(const gx_ctx::CpxResult& r, uint64_t* n_obs, uint64_t* n_distinct, 
 
 // b's pairs added to a's (both ascending in the multiplicity)
 void cpx_add(gx_ctx::CpxResult& a, const gx_ctx::CpxResult& b) {
-  gx_ctx::CpxResult o;
-  o.rep = a.rep;
-  o.ctrl = a.ctrl;
-  o.N = a.N + b.N;
-  o.D = a.D + b.D;
-  size_t i = 0, j = 0;
-  while (i < a.mult.size() || j < b.mult.size()) {
-    const bool ta = j == b.mult.size() || (i < a.mult.size() && a.mult[i] <= b.mult[j]);
-    const bool tb = i == a.mult.size() || (j < b.mult.size() && b.mult[j] <= a.mult[i]);
-    o.mult.push_back(ta ? a.mult[i] : b.mult[j]);
-    o.keys.push_back((ta ? a.keys[i] : 0) + (tb ? b.keys[j] : 0));
-    i += ta;
-    j += tb;
-  }
-  a = std::move(o);
+  a.N += b.N;
+  a.D += b.D;
+  gx_sparse::add(a.mult, {&a.keys}, b.mult, {&b.keys});
 }
 
 }  // namespace

@@ -419,10 +419,12 @@ struct gx_ctx {
   bool peaksReady = false;        // gx_find_peaks has called the peaks of the samples kept so far
   bool countsReady = false;       // ... and gx_count_in_peaks has counted them
   std::vector<KeptSample> kept;
-  // what a pass over kept events reads besides them (gx_host_count.h kept_stage): its staging area and the device's copy.  One
-  // pair serves all the passes: each drains the stream before it returns.
+  // what a pass over kept events reads besides them (gx_host_kept.h kept_stage): its staging area and the device's copy.  One
+  // pair serves all the passes: each drains the stream before it returns.  Likewise the one copy of a caller's events that the
+  // *_events hooks read (kept_upload).
   PinnedBuf keptStage;
   DevBuf keptIn;
+  DevBuf hookEv;
   u32 cntPk = 0;                  // peaks of the last count
   DevBuf cntIdx, cntDiff, cntRes;
   PinnedBuf cntHost;
@@ -487,7 +489,6 @@ struct gx_ctx {
     std::vector<uint64_t> mult, keys;   // h, sparse: keys[i] keys were seen mult[i] times (mult ascending)
   };
   DevBuf cpxTab, cpxCtl, cpxBig;  // the table (reused sample after sample), the control words + k_cpx_hist's histogram, its list
-  DevBuf cpxEv;                   // gx_complexity_events' copy of the caller's events
   std::vector<CpxResult> cpx;     // the last gx_complexity, per kept sample (until gx_reset)
   bool cpxReady = false;
   bool cpxUsed = false;           // k_cpx_insert ran since the last gx_reset
@@ -502,7 +503,6 @@ struct gx_ctx {
     std::vector<uint64_t> cn, cw, cb;       // [nChrom] intervals, weight, sum of w L
   };
   DevBuf ivsOut, ivsBig;          // the control words + the counters; the list of long lengths
-  DevBuf ivsEv;                   // gx_interval_stats_events' copy of the caller's events
   std::vector<IvsResult> ivs;     // the last gx_interval_stats, per kept sample (until gx_reset)
   bool ivsReady = false;
   bool ivsUsed = false;           // k_ivstat ran since the last gx_reset
@@ -545,14 +545,13 @@ struct gx_ctx {
   // each kept sample's depth inside the called peaks (gx_peak_signal / gx_peak_signal_events, gx_peaksig.h); nothing here exists
   // before the first call
   DevBuf psigSpace, psigRes;      // the peak space (one, cleared for sample after sample) and the records [sample][peak]
-  DevBuf psigEv;                  // gx_peak_signal_events' copy of the caller's events
   PinnedBuf psigHost, psigEvHost; // the last gx_peak_signal's records (until gx_reset); the last gx_peak_signal_events'
   size_t psigPk = 0;              // peaks of the last gx_peak_signal
   bool psigReady = false;
   // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
   // nothing here exists before the first call
   DevBuf subCnt, subOff;          // k_sub_count's counts per block, k_sub_scan's offsets
-  DevBuf subEv, subOut;           // gx_subsample_events' copy of the caller's events and its output
+  DevBuf subOut;                  // gx_subsample_events' output
   std::vector<DevBuf> subBufs;    // kept sample k's subsample: the child reads it in place until its gx_sample_end
   bool subUsed = false;           // k_sub_write ran since the last gx_reset
   gx_ctx* satChild = nullptr;     // the context gx_saturation re-calls the peaks on (until gx_reset / gx_destroy)

@@ -1,5 +1,5 @@
 // gx_host_depth.h -- the host side of the depth distribution (gx_depth.h): the bases that count, the one pass per closed sample
-// (and its one rerun with a longer list), the read-back, the sum over contexts.  (a part of gx_api.hip's translation unit)
+// (and its one rerun with a longer list: gx_host_kept.h counted_list), the read-back, the sum over contexts.  (a part of gx_api.hip's translation unit)
 #pragma once
 namespace {
 
@@ -56,8 +56,8 @@ int depth_sample(gx_ctx* ctx, int isCtrl) {
   r.rsq.assign(DEPTH_BOUND, 0);
   const size_t words = DPC_WORDS + 3 * (size_t)DEPTH_BOUND;
   std::vector<unsigned long long> h(words, 0);
-  u64 cap = ctx->knob.depthListCap > 0 ? (u64)ctx->knob.depthListCap : DEPTH_LIST_CAP;
-  u32 reruns = 0;
+  CountedList list{"depth distribution", "deep list", &ctx->depthDeep, sizeof(DepthDeep), &ctx->depthOut, words, DPC_STATUS, DPC_NDEEP, DEPTH_ST_LIST_FULL,
+                   DEPTH_ST_NEGATIVE, "depth distribution: a negative pileup", ctx->knob.depthListCap > 0 ? (u64)ctx->knob.depthListCap : DEPTH_LIST_CAP};
   const u32 nTiles = ctx->nTiles;
   if (nTiles && r.total) {
     phase_begin(ctx, isCtrl ? "c.depth" : "t.depth");   // (with -E regions the tight arrays, the zeroing, the pass or the two)
@@ -65,44 +65,25 @@ int depth_sample(gx_ctx* ctx, int isCtrl) {
     if (int rc = cov_input(ctx, P, in)) return rc;
     POOLED(ctx, ctx->depthOut, words * 8);
     const u32 grid = depth_grid(ctx);
-    for (;;) {
-      if (cap >> 32) return refuse(ctx, "depth distribution: a deep list of 2^32 entries or more");
-      POOLED(ctx, ctx->depthDeep, (size_t)std::max<u64>(cap, 1) * sizeof(DepthDeep));
-      HIPCHECK(hipMemsetAsync(ctx->depthOut.p, 0, words * 8, s));
-      if (!ctx->knob.depthPriv)
-        hipLaunchKernelGGL(k_depth_hist<false>, dim3(grid), dim3(DEPTH_NW * 64), 0, s, in, nTiles, ctx->depthOut.as<unsigned long long>(),
-                           ctx->depthDeep.as<DepthDeep>(), (u32)cap);
-      else
-        hipLaunchKernelGGL(k_depth_hist<true>, dim3(grid), dim3(DEPTH_NW * 64), 0, s, in, nTiles, ctx->depthOut.as<unsigned long long>(),
-                           ctx->depthDeep.as<DepthDeep>(), (u32)cap);
-      if (int rc__ = dbg_sync(ctx, "k_depth_hist")) return rc__;
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipMemcpyAsync(h.data(), ctx->depthOut.p, words * 8, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      if (h[DPC_STATUS] & DEPTH_ST_NEGATIVE) {
-        ctx->err = "depth distribution: a negative pileup";
-        return GX_ERR_DEVICE;
-      }
-      if (!(h[DPC_STATUS] & DEPTH_ST_LIST_FULL)) break;
-      if (reruns || h[DPC_NDEEP] <= cap) {   // (the counted size holds every entry: one rerun always suffices)
-        ctx->err = "depth distribution: the deep list ran full twice";
-        return GX_ERR_DEVICE;
-      }
-      cap = h[DPC_NDEEP];
-      reruns++;
-    }
+    if (int rc = counted_list(ctx, list, h, [&](u32 deepCap) -> int {
+          if (!ctx->knob.depthPriv)
+            hipLaunchKernelGGL(k_depth_hist<false>, dim3(grid), dim3(DEPTH_NW * 64), 0, s, in, nTiles, ctx->depthOut.as<unsigned long long>(),
+                               ctx->depthDeep.as<DepthDeep>(), deepCap);
+          else
+            hipLaunchKernelGGL(k_depth_hist<true>, dim3(grid), dim3(DEPTH_NW * 64), 0, s, in, nTiles, ctx->depthOut.as<unsigned long long>(),
+                               ctx->depthDeep.as<DepthDeep>(), deepCap);
+          if (int rc__ = dbg_sync(ctx, "k_depth_hist")) return rc__;
+          HIPCHECK(hipGetLastError());
+          return GX_OK;
+        }))
+      return rc;
     phase_end(ctx);
     ctx->depthUsed = true;
   }
-  ctx->depthLastCap = (size_t)cap;
-  ctx->depthLastReruns = reruns;
-  const u64 nDeep = h[DPC_NDEEP];
-  std::vector<DepthDeep> deep((size_t)nDeep);
-  if (nDeep) {
-    HIPCHECK(hipMemcpyAsync(deep.data(), ctx->depthDeep.p, (size_t)nDeep * sizeof(DepthDeep), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::sort(deep.begin(), deep.end(), [](const DepthDeep& a, const DepthDeep& b) { return a.v < b.v; });   // (the list comes in the order of the races)
-  }
+  ctx->depthLastCap = (size_t)list.cap;
+  ctx->depthLastReruns = list.reruns;
+  std::vector<DepthDeep> deep;
+  if (int rc = counted_list_read(ctx, ctx->depthDeep, h[DPC_NDEEP], [](const DepthDeep& d) { return d.v; }, deep)) return rc;
   u64 covered = 0;
   for (u32 d = 0; d < DEPTH_BOUND; d++) {
     r.bases[d] = h[DPC_WORDS + d];
@@ -110,13 +91,9 @@ int depth_sample(gx_ctx* ctx, int isCtrl) {
     r.rsq[d] = h[DPC_WORDS + 2 * (size_t)DEPTH_BOUND + d];
     covered += r.bases[d];
   }
-  for (size_t i = 0; i < deep.size(); i++) {
-    covered += deep[i].bases;
-    if (i && deep[i].v == deep[i - 1].v) r.deepBases.back() += deep[i].bases;
-    else {
-      r.deepV.push_back(deep[i].v);
-      r.deepBases.push_back(deep[i].bases);
-    }
+  for (const DepthDeep& d : deep) {
+    covered += d.bases;
+    gx_sparse::append(r.deepV, {&r.deepBases}, d.v, {d.bases});
   }
   r.maxV = h[DPC_VMAX];
   r.minV = covered ? (u64)(u32)~(u32)h[DPC_VMININV] : 0;
@@ -148,18 +125,7 @@ void depth_add(gx_ctx::DepthResult& a, const gx_ctx::DepthResult& b) {
     a.rsum[d] += b.rsum[d];
     a.rsq[d] += b.rsq[d];
   }
-  std::vector<uint64_t> v, n;
-  size_t i = 0, j = 0;
-  while (i < a.deepV.size() || j < b.deepV.size()) {
-    const bool ta = j == b.deepV.size() || (i < a.deepV.size() && a.deepV[i] <= b.deepV[j]);
-    const bool tb = i == a.deepV.size() || (j < b.deepV.size() && b.deepV[j] <= a.deepV[i]);
-    v.push_back(ta ? a.deepV[i] : b.deepV[j]);
-    n.push_back((ta ? a.deepBases[i] : 0) + (tb ? b.deepBases[j] : 0));
-    i += ta;
-    j += tb;
-  }
-  a.deepV = std::move(v);
-  a.deepBases = std::move(n);
+  gx_sparse::add(a.deepV, {&a.deepBases}, b.deepV, {&b.deepBases});
 }
 
 // a result to the caller: the three arrays whole (DEPTH_BOUND entries each, where asked for), min(cap, entries) deep pairs

@@ -1,5 +1,5 @@
 // gx_host_ivstat.h -- the host side of gx_interval_stats (gx_ivstat.h): the grid and the list sized for one sample, the one pass
-// (and its one rerun with a longer list), the read-back, the merged list and the three sums that must agree; the pass over the
+// (and its one rerun with a longer list: gx_host_kept.h counted_list), the read-back, the merged list and the three sums that must agree; the pass over the
 // kept samples and the one over a caller's events.  (a part of gx_api.hip's translation unit)
 #pragma once
 namespace {
@@ -43,8 +43,6 @@ int ivs_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, con
   const size_t words = IVC_WORDS + 2 * (size_t)IVS_BOUND + 3 * (size_t)nChrom;
   POOLED(ctx, ctx->ivsOut, words * 8);
   std::vector<unsigned long long> h(words, 0);
-  u64 cap = listCap ? listCap : IVS_LIST_CAP;
-  u32 reruns = 0;
   IvsArgs a;
   a.chunks = dCk;
   a.nChunks = nCk;
@@ -53,55 +51,29 @@ int ivs_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, con
   a.bases = dTb;
   a.nBase = nTb;
   a.out = ctx->ivsOut.as<unsigned long long>();
+  CountedList list{"interval lengths", "list", &ctx->ivsBig, sizeof(IvsBig), &ctx->ivsOut, words, IVC_STATUS, IVC_NBIG, IVS_ST_LIST_FULL, 0, nullptr,
+                   listCap ? listCap : IVS_LIST_CAP};
   phase_begin(ctx, "ivstat");
-  for (;;) {
-    if (cap >> 32) return refuse(ctx, "interval lengths: a list of 2^32 entries or more");
-    POOLED(ctx, ctx->ivsBig, (size_t)cap * sizeof(IvsBig));
-    a.big = ctx->ivsBig.as<IvsBig>();
-    a.bigCap = (u32)cap;
-    HIPCHECK(hipMemsetAsync(a.out, 0, words * 8, s));
-    hipLaunchKernelGGL(k_ivstat, dim3(grid ? grid : ivs_grid(nCk)), dim3(CNT_NT), 0, s, a);
-    if (int rc__ = dbg_sync(ctx, "k_ivstat")) return rc__;
-    HIPCHECK(hipGetLastError());
-    ctx->ivsUsed = true;
-    HIPCHECK(hipMemcpyAsync(h.data(), a.out, words * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    if (!(h[IVC_STATUS] & IVS_ST_LIST_FULL)) break;
-    if (reruns || h[IVC_NBIG] <= cap) {   // (the counted size holds every entry: one rerun always suffices)
-      ctx->err = "interval lengths: the list ran full twice";
-      return GX_ERR_DEVICE;
-    }
-    cap = h[IVC_NBIG];
-    reruns++;
-  }
+  if (int rc = counted_list(ctx, list, h, [&](u32 bigCap) -> int {
+        a.big = ctx->ivsBig.as<IvsBig>();
+        a.bigCap = bigCap;
+        hipLaunchKernelGGL(k_ivstat, dim3(grid ? grid : ivs_grid(nCk)), dim3(CNT_NT), 0, s, a);
+        if (int rc__ = dbg_sync(ctx, "k_ivstat")) return rc__;
+        HIPCHECK(hipGetLastError());
+        ctx->ivsUsed = true;
+        return GX_OK;
+      }))
+    return rc;
   phase_end(ctx);
-  ctx->ivsLastCap = (size_t)cap;
-  ctx->ivsLastReruns = reruns;
-  const u64 nBig = h[IVC_NBIG];
-  std::vector<IvsBig> big((size_t)nBig);
-  if (nBig) {
-    HIPCHECK(hipMemcpyAsync(big.data(), ctx->ivsBig.p, (size_t)nBig * sizeof(IvsBig), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::sort(big.begin(), big.end(), [](const IvsBig& x, const IvsBig& y) { return x.len < y.len; });   // (the list comes in the order of the races)
-  }
+  ctx->ivsLastCap = (size_t)list.cap;
+  ctx->ivsLastReruns = list.reruns;
+  std::vector<IvsBig> big;
+  if (int rc = counted_list_read(ctx, ctx->ivsBig, h[IVC_NBIG], [](const IvsBig& b) { return b.len; }, big)) return rc;
   r.nInv = h[IVC_NINV];
   r.wInv = h[IVC_WINV];
   for (u32 L = 0; L < IVS_BOUND; L++)
-    if (h[IVC_WORDS + L]) {
-      r.len.push_back(L);
-      r.n.push_back(h[IVC_WORDS + L]);
-      r.w.push_back(h[IVC_WORDS + IVS_BOUND + L]);
-    }
-  for (const IvsBig& b : big) {
-    if (!r.len.empty() && r.len.back() == b.len) {
-      r.n.back() += b.n;
-      r.w.back() += b.w;
-    } else {
-      r.len.push_back(b.len);
-      r.n.push_back(b.n);
-      r.w.push_back(b.w);
-    }
-  }
+    if (h[IVC_WORDS + L]) gx_sparse::append(r.len, {&r.n, &r.w}, L, {h[IVC_WORDS + L], h[IVC_WORDS + IVS_BOUND + L]});
+  for (const IvsBig& b : big) gx_sparse::append(r.len, {&r.n, &r.w}, b.len, {b.n, b.w});
   const unsigned long long* gChr = h.data() + IVC_WORDS + 2 * IVS_BOUND;
   u64 sumN = r.nInv, sumW = r.wInv, sumCn = 0, sumCw = 0;
   unsigned __int128 sumB = 0, sumCb = 0;
@@ -122,43 +94,30 @@ int ivs_pass(gx_ctx* ctx, const CntChunk* dCk, u32 nCk, const CntChrom* dCh, con
   return GX_OK;
 }
 
-// the views' chromosome tables behind kept_stage's front, then every view's pass
-int ivs_views(gx_ctx* ctx, const std::vector<KeptView>& views, const std::vector<u64>& nEv, u32 grid, u64 listCap, std::vector<gx_ctx::IvsResult>& res) {
+// the views' chromosomes by base in the staging's front, then every view's pass
+int ivs_views(gx_ctx* ctx, const std::vector<KeptView>& views, u32 grid, u64 listCap, std::vector<gx_ctx::IvsResult>& res) {
   const u32 nChrom = ctx->nChrom;
+  const std::vector<ViewSize> z = kept_sizes(views);
   // (the refusals come before the staging: nothing is allocated for a call that is refused)
-  for (size_t v = 0; v < views.size(); v++) {
-    u64 nCk = 0;
-    for (const gx_ctx::Seg& sg : *views[v].segs) nCk += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
-    if (int rc = ivs_refusals(ctx, nEv[v], nCk, grid, listCap)) return rc;
-  }
-  KeptIn in;
-  if (int rc = kept_stage(ctx, views, views.size() * std::max(1u, nChrom) * sizeof(IvsBase), true, false, in)) return rc;
-  IvsBase* tb = reinterpret_cast<IvsBase*>(in.front);
-  std::vector<u32> nTb(views.size());
-  for (size_t v = 0; v < views.size(); v++) nTb[v] = ivs_bases(ctx, views[v], tb + v * nChrom);
-  if (int rc = kept_send(ctx, in)) return rc;
-  HIPCHECK(hipStreamSynchronize(ctx->stream));   // (a sample without events launches nothing: the staging area is free again)
+  for (const ViewSize& v : z)
+    if (int rc = ivs_refusals(ctx, v.n, v.nCk, grid, listCap)) return rc;
   res.assign(views.size(), gx_ctx::IvsResult{});
-  const IvsBase* dTb = reinterpret_cast<const IvsBase*>(in.dFront);
-  for (size_t v = 0; v < views.size(); v++)
-    if (int rc = ivs_pass(ctx, in.dCk + in.chunk0[v], (u32)(in.chunk0[v + 1] - in.chunk0[v]), in.dCh + v * nChrom, dTb + v * nChrom, nTb[v], nEv[v],
-                          grid, listCap, res[v]))
-      return rc;
-  return GX_OK;
+  std::vector<u32> nTb(views.size());
+  const IvsBase* dTb = nullptr;
+  return kept_each_view(
+      ctx, views, views.size() * std::max(1u, nChrom) * sizeof(IvsBase),
+      [&](char* front, const char* dFront) {
+        for (size_t v = 0; v < views.size(); v++) nTb[v] = ivs_bases(ctx, views[v], reinterpret_cast<IvsBase*>(front) + v * nChrom);
+        dTb = reinterpret_cast<const IvsBase*>(dFront);
+      },
+      [&](const CntChunk* dCk, u32 nCk, const CntChrom* dCh, size_t v) { return ivs_pass(ctx, dCk, nCk, dCh, dTb + v * nChrom, nTb[v], z[v].n, grid, listCap, res[v]); });
 }
 
-// every kept sample, through the staging the passes share (gx_host_count.h kept_stage)
+// every kept sample
 int ivstat_kept(gx_ctx* ctx) {
-  const size_t nS = ctx->kept.size();
-  std::vector<u64> nEv(nS, 0);
-  for (size_t k = 0; k < nS; k++)
-    for (const gx_ctx::Seg& sg : ctx->kept[k].segs) nEv[k] += sg.n;
   std::vector<gx_ctx::IvsResult> res;
-  if (int rc = ivs_views(ctx, kept_views(ctx), nEv, 0, 0, res)) return rc;
-  for (size_t k = 0; k < nS; k++) {
-    res[k].rep = ctx->kept[k].rep;
-    res[k].ctrl = ctx->kept[k].ctrl;
-  }
+  if (int rc = ivs_views(ctx, kept_views(ctx), 0, 0, res)) return rc;
+  kept_stamp(ctx, res);
   ctx->ivs = std::move(res);
   ctx->ivsReady = true;
   return GX_OK;
@@ -168,20 +127,18 @@ int ivstat_kept(gx_ctx* ctx) {
 int ivstat_events(gx_ctx* ctx, const gx_event* ev, size_t n, u32 grid, u64 listCap, gx_ctx::IvsResult& r) {
   if (int rc = ivs_refusals(ctx, n, (n + CNT_CHUNK - 1) / CNT_CHUNK, grid, listCap)) return rc;
   std::vector<gx_ctx::Seg> segs;
-  if (n) {
-    POOLED(ctx, ctx->ivsEv, n * sizeof(gx_event));
-    HIPCHECK(hipMemcpyAsync(ctx->ivsEv.p, ev, n * sizeof(gx_event), hipMemcpyHostToDevice, ctx->stream));
-    segs.push_back({ctx->ivsEv.as<gx_event>(), n, nullptr, false});
-  }
+  if (int rc = kept_upload(ctx, ev, n, false, segs)) return rc;
   std::vector<gx_ctx::IvsResult> res;
-  if (int rc = ivs_views(ctx, {KeptView{&segs, nullptr}}, {(u64)n}, grid, listCap, res)) return rc;
+  if (int rc = ivs_views(ctx, {KeptView{&segs, nullptr}}, grid, listCap, res)) return rc;
   r = std::move(res[0]);
   return GX_OK;
 }
 
 // a result to the caller: min(cap, classes) lengths, min(chrom_cap, chromosomes) tallies
-int ivs_give(const gx_ctx::IvsResult& r, uint64_t* length, uint64_t* n, uint64_t* w120, size_t cap, size_t* n_classes, uint64_t* n_inverted,
-             uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120, uint64_t* cbases120, size_t chrom_cap) {
+int ivs_give(const gx_ctx::IvsResult& r, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120, size_t cap, size_t* n_classes,
+             uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120, uint64_t* cbases120, size_t chrom_cap) {
+  if (rep) *rep = r.rep;
+  if (is_ctrl) *is_ctrl = r.ctrl ? 1 : 0;
   if ((cap && (!length || !n || !w120)) || (chrom_cap && (!cn || !cw120 || !cbases120))) return GX_ERR_ORDER;
   if (n_classes) *n_classes = r.len.size();
   if (n_inverted) *n_inverted = r.nInv;
@@ -201,30 +158,14 @@ int ivs_give(const gx_ctx::IvsResult& r, uint64_t* length, uint64_t* n, uint64_t
 
 // b added to a (the lengths of both ascending; the same chromosome table)
 void ivs_add(gx_ctx::IvsResult& a, const gx_ctx::IvsResult& b) {
-  gx_ctx::IvsResult o;
-  o.rep = a.rep;
-  o.ctrl = a.ctrl;
-  o.nInv = a.nInv + b.nInv;
-  o.wInv = a.wInv + b.wInv;
-  size_t i = 0, j = 0;
-  while (i < a.len.size() || j < b.len.size()) {
-    const bool ta = j == b.len.size() || (i < a.len.size() && a.len[i] <= b.len[j]);
-    const bool tb = i == a.len.size() || (j < b.len.size() && b.len[j] <= a.len[i]);
-    o.len.push_back(ta ? a.len[i] : b.len[j]);
-    o.n.push_back((ta ? a.n[i] : 0) + (tb ? b.n[j] : 0));
-    o.w.push_back((ta ? a.w[i] : 0) + (tb ? b.w[j] : 0));
-    i += ta;
-    j += tb;
-  }
-  o.cn = b.cn;
-  o.cw = b.cw;
-  o.cb = b.cb;
+  a.nInv += b.nInv;
+  a.wInv += b.wInv;
+  gx_sparse::add(a.len, {&a.n, &a.w}, b.len, {&b.n, &b.w});
   for (size_t c = 0; c < std::min(a.cn.size(), b.cn.size()); c++) {
-    o.cn[c] += a.cn[c];
-    o.cw[c] += a.cw[c];
-    o.cb[c] += a.cb[c];
+    a.cn[c] += b.cn[c];
+    a.cw[c] += b.cw[c];
+    a.cb[c] += b.cb[c];
   }
-  a = std::move(o);
 }
 
 }  // namespace

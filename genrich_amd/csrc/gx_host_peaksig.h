@@ -118,11 +118,7 @@ int peak_signal_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_regio
   if (grid > 65535u) return refuse(ctx, "gx_peak_signal_events: more than 65535 workgroups");
   if (int rc = psig_check_peaks(ctx, peaks, nPk, summitOff)) return rc;
   std::vector<gx_ctx::Seg> segs;
-  if (n) {
-    POOLED(ctx, ctx->psigEv, n * sizeof(gx_event));
-    HIPCHECK(hipMemcpyAsync(ctx->psigEv.p, ev, n * sizeof(gx_event), hipMemcpyHostToDevice, ctx->stream));
-    segs.push_back({ctx->psigEv.as<gx_event>(), n, nullptr, false});
-  }
+  if (int rc = kept_upload(ctx, ev, n, false, segs)) return rc;
   std::vector<PsigPeak> pk(nPk);
   for (size_t k = 0; k < nPk; k++) pk[k] = PsigPeak{peaks[k].chrom, peaks[k].start, peaks[k].end, summitOff ? summitOff[k] : 0u};
   const int rc = psig_pass(ctx, {KeptView{&segs, nullptr}}, pk.data(), nPk, grid, ctx->psigEvHost);

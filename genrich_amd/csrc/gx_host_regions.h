@@ -1,5 +1,5 @@
 // gx_host_regions.h -- the host side of gx_count_in_regions (gx_regions.h): the regions put into tile space and ranked, the
-// count pass over the kept samples (gx_host_count.h keep_sample), the scans, the gather and the inverted intervals.
+// count pass over the kept samples (gx_host_kept.h keep_sample), the scans, the gather and the inverted intervals.
 // (a part of gx_api.hip's translation unit)
 #pragma once
 namespace {

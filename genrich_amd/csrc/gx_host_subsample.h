@@ -4,16 +4,13 @@
 #pragma once
 namespace {
 
-// one sample's pieces -> its chunk list and the events before each chunk, on the device (gx_host_count.h kept_stage); *n =
+// one sample's pieces -> its chunk list and the events before each chunk, on the device (gx_host_kept.h kept_stage); *n =
 // its events
 int sub_stage(gx_ctx* ctx, const std::vector<gx_ctx::Seg>& segs, const CntChunk** dCk, const u64** dFirst, u32* nCk, u64* n) {
+  const ViewSize z = kept_sizes({KeptView{&segs, nullptr}})[0];
+  const u64 nc = z.nCk;
+  *n = z.n;
   *nCk = 0;
-  *n = 0;
-  size_t nc = 0;
-  for (const gx_ctx::Seg& sg : segs) {
-    *n += sg.n;
-    nc += (sg.n + CNT_CHUNK - 1) / CNT_CHUNK;
-  }
   if (nc > 0xFFFFFFFFull / SUB_BPC) return refuse(ctx, "subsample: a sample of 2^32 events or more");
   *nCk = (u32)nc;
   if (!nc) return GX_OK;
