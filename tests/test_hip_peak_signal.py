@@ -18,6 +18,7 @@ import peaksig_cases as K
 import peaksig_ref as R
 from genrich_amd import synth
 from genrich_amd.lib import pack_events, peak_signal_geometry
+from ranks import ThreadAllreduce
 from test_hip_counts import Mem, _cli_inputs, _push
 from test_host_cli import _binary
 
@@ -215,35 +216,12 @@ def test_a_skipped_and_an_unsaved_chromosome():
     h.close()
 
 
-class _ThreadAllreduce:
-    """gx_set_collectives' sum over contexts that run side by side in threads of this process, as the command line's do"""
-
-    def __init__(self, world):
-        self.bar = threading.Barrier(world, timeout=120)
-        self.bufs = [None] * world
-
-    def callback(self, rank):
-        def cb(buf, n, _user):
-            try:
-                a = np.ctypeslib.as_array(buf, shape=(n,))
-                self.bufs[rank] = a.copy()
-                self.bar.wait()
-                total = np.sum(self.bufs, axis=0)
-                self.bar.wait()                     # (everyone has read every buffer)
-                a[:] = total
-                return 0
-            except Exception as e:                  # (never across the C boundary)
-                print("allreduce callback failed:", e)
-                return 1
-        return cb
-
-
 def test_owned_split_over_two_contexts():
     ev = synth.make_fragments(LENS, 300_000, 62, peak_every=20_000, tower_every=3_000_000)
     one, _ = _run(LENS, [(ev, None)])
     whole = _check(one, LENS, [(ev, 0, False, None)])[0]
     owns = [[1, 0, 1], [0, 1, 0]]
-    coll = _ThreadAllreduce(2)
+    coll = ThreadAllreduce(2)
     parts, errors = [None, None], []
 
     def rank(r):
