@@ -33,7 +33,7 @@ HOST_BIN = os.path.join(HERE, "genrich-amd")
 def build_host(force: bool = False) -> str:
     """The command-line host program (C++, g++): SAM/BAM ingest + options over the C ABI."""
     hd = os.path.dirname(HOST_SRC)
-    deps = [HOST_SRC, LIB] + [os.path.join(hd, f) for f in ("bgzf_reader.h", "gx_inflate.h", "gx_crc32.h")]
+    deps = [LIB] + sorted(os.path.join(hd, f) for f in os.listdir(hd) if f.endswith((".h", ".cpp")))  # (every part: none can be forgotten)
     if force or not os.path.exists(HOST_BIN) or os.path.getmtime(HOST_BIN) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", HOST_SRC, "-o", HOST_BIN, "-L" + HERE,
                                "-lgenrich_amd", "-lz", "-Wl,-rpath,$ORIGIN"])

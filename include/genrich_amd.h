@@ -169,7 +169,7 @@ long long gx_filter_saturation(const gx_event* events, size_t n, int n_chrom, co
  * "skipped due to overflow / underflow", the missing -b line, the length 0 towards the -x average (2558-2573) --
  * and not only their effect on the pileup (which gx_sample_end reproduces by itself): it counts starts and ends per
  * window as it pushes, asks for a window's exact state when one comes near 32,767, and keeps that window itself from
- * then on (genrich_amd/host/genrich_amd.cpp: HotWindows).  One pass over the pushed events; waits for their uploads.
+ * then on (genrich_amd/host/host_state.h: HotWindows).  One pass over the pushed events; waits for their uploads.
  * n <= 65536. */
 int gx_window_net(gx_ctx* ctx, uint32_t chrom, uint32_t pos0, uint32_t n, long long* net);
 

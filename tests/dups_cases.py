@@ -2,7 +2,7 @@
 
 The device decides a set of one alignment from "who held this key first" (gx_dups_first); a key that a multi-alignment set also
 holds is contested and is walked by the host in the reference's order, on tables that hold the contested keys only (findDups,
-genrich_amd/host/genrich_amd.cpp).  tests/synth.py's write_sam_dups gives only proper pairs a secondary alignment, and scores
+genrich_amd/host/host_dups.h).  tests/synth.py's write_sam_dups gives only proper pairs a secondary alignment, and scores
 it 3 below the best, so it is dropped unless -s is that large; here secondary alignments carry the primary's AS and survive
 without -s."""
 import numpy as np
