@@ -213,6 +213,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
                   const int32_t* bed_len) {
   if (!ctx || n <= 0 || !len) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
+  repro_drop(ctx);
   if (ctx->satChild) sat_drop(ctx);   // (its table is the old one)
   ctx->nChrom = (u32)n;
   ctx->len.assign(len, len + n);
@@ -297,6 +298,7 @@ int gx_set_keep_pileups(gx_ctx* ctx, int keep) {
 int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   if (!ctx || !owned || ctx->nChrom == 0) return GX_ERR_ORDER;
   if (ctx->phase != 0 || ctx->sample != 0) return GX_ERR_ORDER;  // the tile space changes: between runs only
+  repro_drop(ctx);
   if (ctx->satChild) sat_drop(ctx);   // (its mask is the old one)
   ctx->owned.assign(owned, owned + ctx->nChrom);
   ctx->covDirty = true;
@@ -344,6 +346,7 @@ int gx_reset(gx_ctx* ctx) {
   ctx->ivs.clear();
   ctx->ivsReady = ctx->ivsUsed = false;
   ctx->psigReady = false;   // (gx_peak_signal's records go with the peaks; the buffers stay)
+  repro_drop(ctx);          // (gx_reproducibility's calls and k_sub_split's bit)
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
@@ -943,7 +946,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u);
   return GX_OK;
 }
 
@@ -1883,6 +1886,112 @@ int gx_write_saturation(gx_ctx* ctx, FILE* out) {
   for (size_t j = 0; j < nP; j++)
     if (int rc = gx_saturation_overlap(full, ctx->nHostPeaks, ctx->satPeaks[j].data(), ctx->satPeaks[j].size(), &rec[j], &sub[j], &bp[j])) return rc;
   return gx_format_saturation(out, (int)nP, ctx->satPts.data(), rec.data(), sub.data(), bp.data(), ctx->nHostPeaks, ctx->peakBP);
+}
+
+int gx_subsample_split_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold,
+                              unsigned grid, gx_event* out, size_t cap, size_t* n_a) {
+  if (!ctx || (n && !ev) || (cap && !out)) return GX_ERR_ORDER;
+  if (int rc = guard_closed(ctx, "gx_subsample_split_events")) return rc;
+  if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
+  if (grid > SUB_MAX_GRID) return refuse(ctx, "subsample: more than 65535 workgroups");
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<gx_ctx::Seg> segs;
+  if (int rc = kept_upload(ctx, ev, n, packed != 0, segs)) return rc;
+  const CntChunk* dCk = nullptr;
+  const u64* dFirst = nullptr;
+  u32 nCk = 0;
+  u64 nEv = 0, nA = 0;
+  if (int rc = sub_stage(ctx, segs, &dCk, &dFirst, &nCk, &nEv)) return rc;
+  if (int rc = sub_split_pass(ctx, dCk, dFirst, nCk, nEv, subsample_key(seed, sample), threshold, grid, ctx->subOut, &nA)) return rc;
+  if (n_a) *n_a = (size_t)nA;
+  return sub_give(ctx, ctx->subOut, nEv, out, cap, nullptr);
+}
+
+int gx_subsample_split_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_a) {
+  if (!ctx || (cap && !out)) return GX_ERR_ORDER;
+  if (int rc = guard_kept(ctx, "gx_subsample_split_kept", false)) return rc;
+  if (int rc = guard_closed(ctx, "gx_subsample_split_kept")) return rc;
+  if (sample < 0 || (size_t)sample >= ctx->kept.size()) return refuse(ctx, "gx_subsample_split_kept: no such sample");
+  if (threshold > ((u64)1 << 32)) return refuse(ctx, "subsample: a threshold above 2^32");
+  HIPCHECK(hipSetDevice(ctx->device));
+  u64 n = 0, nA = 0;
+  if (int rc = sub_split_kept(ctx, (size_t)sample, seed, threshold, &n, &nA)) return rc;
+  if (n_a) *n_a = (size_t)nA;
+  return sub_give(ctx, ctx->subBufs[sample], n, out, cap, nullptr);
+}
+
+int gx_reproducibility(gx_ctx* ctx, uint64_t seed, unsigned flags, gx_repro_call* out, size_t cap, size_t* n_calls) {
+  if (!ctx || (cap && !out) || flags) return GX_ERR_ORDER;
+  if (int rc = guard_kept(ctx, "gx_reproducibility", false)) return rc;
+  if (ctx->phase != 0 || !ctx->peaksReady) return refuse(ctx, "gx_reproducibility comes after gx_find_peaks, with no sample open");
+  if (ctx->world > 1 || ctx->forceColl) return refuse(ctx, "gx_reproducibility: one context only (the calls on several need collectives between their children)");
+  HIPCHECK(hipSetDevice(ctx->device));
+  const int nR = ctx->sample;
+  std::vector<ReproRep> reps((size_t)nR);
+  for (size_t k = 0; k < ctx->kept.size(); k++) {
+    const gx_ctx::KeptSample& ks = ctx->kept[k];
+    if (ks.rep < 0 || ks.rep >= nR) continue;
+    (ks.ctrl ? reps[ks.rep].kc : reps[ks.rep].kt) = (int)k;
+  }
+  for (int r = 0; r < nR; r++)
+    if (reps[r].kt < 0) return refuse(ctx, "reproducibility: a replicate whose treatment was not kept");
+  if (int rc = sat_child(ctx)) return rc;
+  for (int r = 0; r < nR; r++)   // each treatment split once: both halves in its own buffer
+    if (int rc = sub_split_kept(ctx, (size_t)reps[r].kt, seed, (u64)1 << 31, &reps[r].n, &reps[r].nA)) return rc;
+  std::vector<gx_repro_call> calls;
+  std::vector<std::vector<ReproPart>> parts;
+  for (int r = 0; r < nR; r++) {
+    calls.push_back(gx_repro_call{GX_REPRO_ALONE, r, -1, 0, 0, 0, 0});
+    parts.push_back({ReproPart{r, -1}});
+  }
+  for (int r = 0; r < nR; r++)
+    for (int h = 0; h < 2; h++) {
+      calls.push_back(gx_repro_call{GX_REPRO_SELF, r, h, 0, 0, 0, 0});
+      parts.push_back({ReproPart{r, h}});
+    }
+  for (int h = 0; h < 2; h++) {
+    calls.push_back(gx_repro_call{GX_REPRO_POOLED, -1, h, 0, 0, 0, 0});
+    parts.emplace_back();
+    for (int r = 0; r < nR; r++) parts.back().push_back(ReproPart{r, h});
+  }
+  std::vector<std::vector<gx_peak>> peaks(calls.size());
+  for (size_t i = 0; i < calls.size(); i++)
+    if (int rc = repro_call(ctx, reps, parts[i], calls[i], peaks[i])) return rc;
+  if (n_calls) *n_calls = calls.size();
+  std::copy(calls.begin(), calls.begin() + std::min(cap, calls.size()), out);
+  ctx->reproCalls = std::move(calls);
+  ctx->reproPeaks = std::move(peaks);
+  ctx->reproSeed = seed;
+  return GX_OK;
+}
+
+int gx_get_reproducibility_peaks(gx_ctx* ctx, int call, gx_peak* out, size_t cap) {
+  if (!ctx || call < 0 || (size_t)call >= ctx->reproPeaks.size() || (cap && !out)) return GX_ERR_ORDER;
+  const size_t n = std::min(cap, ctx->reproPeaks[call].size());
+  if (n) memcpy(out, ctx->reproPeaks[call].data(), n * sizeof(gx_peak));
+  return GX_OK;
+}
+
+// (here, not in gx_emit.cpp, like the other writers over contexts: it reads one)
+int gx_write_reproducibility(gx_ctx* ctx, int pct, FILE* calls_file, FILE* metrics_file) {
+  if (!ctx || (!calls_file && !metrics_file) || ctx->reproCalls.empty() || !ctx->peaksReady || pct < 0 || pct > 100) return GX_ERR_ORDER;
+  const size_t nC = ctx->reproCalls.size();
+  const int nR = (int)((nC - 2) / 3);
+  const gx_peak* run = static_cast<const gx_peak*>(ctx->hPeaks.p);
+  std::vector<const gx_peak*> lists(nC);
+  for (size_t i = 0; i < nC; i++) lists[i] = ctx->reproPeaks[i].data();
+  gx_repro_figures fig;
+  std::vector<uint64_t> pairs((size_t)nR * (nR - 1) / 2 + 1), self((size_t)nR), inRun(nC), runSup(nC);
+  if (int rc = gx_reproducibility_figures(run, ctx->nHostPeaks, nR, ctx->reproCalls.data(), lists.data(), pct, &fig, pairs.data(), self.data(),
+                                          inRun.data(), runSup.data(), nullptr, nullptr))
+    return rc;
+  if (calls_file)
+    if (int rc = gx_format_reproducibility(calls_file, nR, ctx->reproCalls.data(), inRun.data(), runSup.data(), ctx->nHostPeaks, ctx->peakBP, pct,
+                                           ctx->reproSeed))
+      return rc;
+  if (metrics_file)
+    if (int rc = gx_format_reproducibility_metrics(metrics_file, &fig, pairs.data(), self.data())) return rc;
+  return GX_OK;
 }
 
 int gx_set_phase_timing(gx_ctx* ctx, int level) {

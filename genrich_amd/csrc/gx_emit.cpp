@@ -1,5 +1,5 @@
 // gx_emit.cpp -- host-side text emitters of the drop-in surface: ENCODE narrowPeak (-o), the
-// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the interval length and chromosome tables (--lengths, --chrom-stats), the strand cross-correlation tables (--xcor), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) and the saturation table (--saturation).  Pure formatting of arrays fetched through the
+// bedgraph-ish log (-f), the pileup log (-k), the binned coverage tracks (--coverage), the profile tables (--profile), the correlation matrix (--correlation), the fingerprint tables (--fingerprint), the library complexity tables (--complexity), the interval length and chromosome tables (--lengths, --chrom-stats), the strand cross-correlation tables (--xcor), the depth distribution tables (--depth), the per-peak signal table (--peak-signal) the saturation table (--saturation) and the reproducibility tables with their support walk and figures (--reproducibility).  Pure formatting of arrays fetched through the
 // C ABI (gx_get_peaks / gx_get_intervals); byte format follows the reference's printf calls:
 //   printPeak       Genrich.c:885-909      printLogHeader 674-717
 //   printInterval   770-803                printIntervalN 724-763
@@ -163,15 +163,20 @@ int gx_write_narrowpeak_group(gx_ctx* const* ctxs, int n_ctx, const char* const*
     std::stable_sort(pk.begin(), pk.end(), [](const gx_peak& a, const gx_peak& b) {
       return a.chrom != b.chrom ? a.chrom < b.chrom : a.start < b.start;
     });
-  const size_t n = pk.size();
+  return gx_format_narrowpeak(pk.data(), pk.size(), names, 0, out);
+}
+
+// ... the lines themselves, of a list: peak i is peak_<first_index + i>
+int gx_format_narrowpeak(const gx_peak* peaks, size_t n, const char* const* names, int first_index, FILE* out) {
+  if (n && (!peaks || !names || !out)) return GX_ERR_ORDER;
   for (size_t i = 0; i < n; i++) {
-    const gx_peak& k = pk[i];
+    const gx_peak& k = peaks[i];
     long start = (long)k.start, end = (long)k.end;
     // MIN((unsigned int)(1000.0f * signal / (end - start) + 0.5f), 1000): the float -> unsigned
     // conversion of an out-of-range value follows x86-64 gcc (64-bit cvttss2si, low 32 bits)
     float sc = 1000.0f * k.auc / (float)(end - start) + 0.5f;
     unsigned int u = (unsigned int)(long long)sc;
-    fprintf(out, "%s\t%ld\t%ld\tpeak_%d\t%d\t.\t%f\t%f", names[k.chrom], start, end, (int)i, u < 1000u ? u : 1000u, k.auc,
+    fprintf(out, "%s\t%ld\t%ld\tpeak_%d\t%d\t.\t%f\t%f", names[k.chrom], start, end, first_index + (int)i, u < 1000u ? u : 1000u, k.auc,
             k.p);
     if (k.q == GX_SKIP)
       fprintf(out, "\t-1\t%d\n", k.summit);
@@ -1191,6 +1196,165 @@ int gx_format_saturation(FILE* out, int n_points, const gx_sat_point* points, co
     else if (p.status == GX_ERR_EXPT) fprintf(out, "\tno_fragments\n");
     else fprintf(out, "\t%d\n", (int)p.status);
   }
+  return GX_OK;
+}
+
+// --reproducibility: which peaks of `a` a peak of `b` supports; two lists in gx_get_peaks order, one merge walk over the
+// overlapping pairs (whichever peak ends first cannot overlap what follows in the other list)
+int gx_peaks_supported(const gx_peak* a, size_t n_a, const gx_peak* b, size_t n_b, int pct, uint8_t* hit) {
+  if ((n_a && (!a || !hit)) || (n_b && !b) || pct < 0 || pct > 100) return GX_ERR_ORDER;
+  for (size_t i = 0; i < n_a; i++) hit[i] = 0;
+  size_t i = 0, j = 0;
+  while (i < n_a && j < n_b) {
+    const gx_peak &A = a[i], &B = b[j];
+    if (A.chrom != B.chrom) {
+      (A.chrom < B.chrom ? i : j)++;
+    } else if (A.end <= B.start) {
+      i++;
+    } else if (B.end <= A.start) {
+      j++;
+    } else {
+      const uint64_t ov = (uint64_t)std::min(A.end, B.end) - (uint64_t)std::max(A.start, B.start);
+      const uint64_t shorter = std::min((uint64_t)A.end - A.start, (uint64_t)B.end - B.start);
+      if (100 * ov >= (uint64_t)pct * shorter) hit[i] = 1;
+      if (A.end <= B.end) i++;
+      else j++;
+    }
+  }
+  return GX_OK;
+}
+
+// ... and the figures made of it.  The calls are gx_reproducibility's, in its order: ALONE r at r, SELF r h at R + 2 r + h,
+// POOLED h at 3 R + h.
+int gx_reproducibility_figures(const gx_peak* run, size_t n_run, int n_rep, const gx_repro_call* calls, const gx_peak* const* peaks, int pct,
+                               gx_repro_figures* fig, uint64_t* nt_pair, uint64_t* n_self, uint64_t* in_run, uint64_t* run_supported,
+                               uint8_t* conservative, uint8_t* optimal) {
+  if (n_rep < 1 || !calls || !peaks || !fig || (n_run && !run) || pct < 0 || pct > 100 || !n_self || (n_rep > 1 && !nt_pair)) return GX_ERR_ORDER;
+  const int R = n_rep, nC = 3 * R + 2;
+  for (int i = 0; i < nC; i++) {
+    const gx_repro_call& c = calls[i];
+    const bool ok = i < R ? c.kind == GX_REPRO_ALONE && c.rep == i
+                    : i < 3 * R ? c.kind == GX_REPRO_SELF && c.rep == (i - R) / 2 && c.half == (i - R) % 2
+                                : c.kind == GX_REPRO_POOLED && c.half == i - 3 * R;
+    if (!ok || (c.n_peaks && !peaks[i])) return GX_ERR_ORDER;
+  }
+  // the run's peaks against every call, and every call's against the run's
+  std::vector<std::vector<uint8_t>> sup((size_t)nC, std::vector<uint8_t>(n_run, 0));
+  std::vector<uint8_t> tmp;
+  for (int i = 0; i < nC; i++) {
+    const size_t n = (size_t)calls[i].n_peaks;
+    if (int rc = gx_peaks_supported(run, n_run, peaks[i], n, pct, sup[i].data())) return rc;
+    tmp.assign(n, 0);
+    if (int rc = gx_peaks_supported(peaks[i], n, run, n_run, pct, tmp.data())) return rc;
+    if (run_supported) run_supported[i] = (uint64_t)std::count(sup[i].begin(), sup[i].end(), 1);
+    if (in_run) in_run[i] = (uint64_t)std::count(tmp.begin(), tmp.end(), 1);
+  }
+  auto both = [&](int x, int y) {
+    uint64_t n = 0;
+    for (size_t k = 0; k < n_run; k++) n += sup[x][k] & sup[y][k];
+    return n;
+  };
+  *fig = gx_repro_figures{};
+  fig->n_rep = R;
+  fig->best_i = fig->best_j = -1;
+  for (int i = 0, at = 0; i < R; i++)
+    for (int j = i + 1; j < R; j++, at++) {
+      nt_pair[at] = both(i, j);
+      if (fig->best_i < 0 || nt_pair[at] > fig->nt) {   // (a tie: the first pair)
+        fig->nt = nt_pair[at];
+        fig->best_i = i;
+        fig->best_j = j;
+      }
+    }
+  fig->np = both(3 * R, 3 * R + 1);
+  for (int r = 0; r < R; r++) {   // ALONE r's peaks that both of its halves support
+    const size_t n = (size_t)calls[r].n_peaks;
+    std::vector<uint8_t> h0(n, 0), h1(n, 0);
+    for (int h = 0; h < 2; h++)
+      if (int rc = gx_peaks_supported(peaks[r], n, peaks[R + 2 * r + h], (size_t)calls[R + 2 * r + h].n_peaks, pct, (h ? h1 : h0).data())) return rc;
+    n_self[r] = 0;
+    for (size_t k = 0; k < n; k++) n_self[r] += h0[k] & h1[k];
+    fig->n_self_max = r ? std::max(fig->n_self_max, n_self[r]) : n_self[r];
+    fig->n_self_min = r ? std::min(fig->n_self_min, n_self[r]) : n_self[r];
+  }
+  const uint64_t hi = std::max(fig->np, fig->nt), lo = std::min(fig->np, fig->nt);
+  fig->rescue_na = R == 1 || lo == 0;
+  fig->self_na = R == 1 || fig->n_self_min == 0;
+  fig->rescue = fig->rescue_na ? 0.0 : (double)hi / (double)lo;
+  fig->self_consistency = fig->self_na ? 0.0 : (double)fig->n_self_max / (double)fig->n_self_min;
+  if (fig->rescue_na || fig->self_na)
+    fig->verdict = GX_REPRO_NA;
+  else {
+    const int good = (hi < 2 * lo) + (fig->n_self_max < 2 * fig->n_self_min);
+    fig->verdict = good == 2 ? GX_REPRO_PASS : good == 1 ? GX_REPRO_BORDERLINE : GX_REPRO_FAIL;
+  }
+  // the sets: the run's peaks counted in Nt, and the larger of those and Np's (a tie: the conservative set)
+  fig->n_conservative = R > 1 ? fig->nt : 0;
+  fig->optimal_is_pooled = fig->np > fig->n_conservative;
+  fig->n_optimal = std::max(fig->np, fig->n_conservative);
+  for (size_t k = 0; k < n_run; k++) {
+    const uint8_t cons = R > 1 ? sup[fig->best_i][k] & sup[fig->best_j][k] : 0, pool = sup[3 * R][k] & sup[3 * R + 1][k];
+    if (conservative) conservative[k] = cons;
+    if (optimal) optimal[k] = fig->optimal_is_pooled ? pool : cons;
+  }
+  return GX_OK;
+}
+
+static std::string repro_label(const gx_repro_call& c) {
+  if (c.kind == GX_REPRO_POOLED) return "pooled.pr" + std::to_string(c.half + 1);
+  std::string s = "t" + std::to_string(c.rep + 1);
+  return c.kind == GX_REPRO_SELF ? s + ".pr" + std::to_string(c.half + 1) : s;
+}
+
+int gx_reproducibility_label(const gx_repro_call* call, char* out, size_t cap) {
+  if (!call || !out || !cap) return GX_ERR_ORDER;
+  snprintf(out, cap, "%s", repro_label(*call).c_str());
+  return GX_OK;
+}
+
+// ... one row per call, under a comment line with the run's own peaks, the overlap asked for and the seed
+int gx_format_reproducibility(FILE* out, int n_rep, const gx_repro_call* calls, const uint64_t* in_run, const uint64_t* run_supported,
+                              uint64_t n_run, uint64_t run_bp, int pct, uint64_t seed) {
+  if (!out || n_rep < 1 || !calls || !in_run || !run_supported) return GX_ERR_ORDER;
+  fprintf(out, "# run: %llu peaks, %llu bp; overlap %d %%; seed %llu\n", (unsigned long long)n_run, (unsigned long long)run_bp, pct,
+          (unsigned long long)seed);
+  fprintf(out, "call\trep\thalf\tintervals\tpeaks\tpeak_bp\tin_run\trun_supported\tstatus\n");
+  for (int i = 0; i < 3 * n_rep + 2; i++) {
+    const gx_repro_call& c = calls[i];
+    fprintf(out, "%s", repro_label(c).c_str());
+    if (c.rep < 0) fprintf(out, "\tNA");
+    else fprintf(out, "\t%d", c.rep + 1);
+    if (c.half < 0) fprintf(out, "\tNA");
+    else fprintf(out, "\t%d", c.half + 1);
+    fprintf(out, "\t%llu\t%llu\t%llu\t%llu\t%llu", (unsigned long long)c.n_events, (unsigned long long)c.n_peaks, (unsigned long long)c.peak_bp,
+            (unsigned long long)in_run[i], (unsigned long long)run_supported[i]);
+    if (c.status == GX_OK) fprintf(out, "\tok\n");
+    else if (c.status == GX_ERR_EXPT) fprintf(out, "\tno_fragments\n");
+    else fprintf(out, "\t%d\n", (int)c.status);
+  }
+  return GX_OK;
+}
+
+int gx_format_reproducibility_metrics(FILE* out, const gx_repro_figures* fig, const uint64_t* nt_pair, const uint64_t* n_self) {
+  if (!out || !fig || fig->n_rep < 1 || !n_self || (fig->n_rep > 1 && !nt_pair)) return GX_ERR_ORDER;
+  static const char* const verdict[] = {"pass", "borderline", "fail", "NA"};
+  const int R = fig->n_rep;
+  fprintf(out, "figure\tvalue\n");
+  fprintf(out, "replicates\t%d\n", R);
+  for (int i = 0, at = 0; i < R; i++)
+    for (int j = i + 1; j < R; j++, at++) fprintf(out, "Nt.t%d.t%d\t%llu\n", i + 1, j + 1, (unsigned long long)nt_pair[at]);
+  if (R > 1) fprintf(out, "Nt\t%llu\n", (unsigned long long)fig->nt);
+  else fprintf(out, "Nt\tNA\n");
+  fprintf(out, "Np\t%llu\n", (unsigned long long)fig->np);
+  for (int r = 0; r < R; r++) fprintf(out, "N_self.t%d\t%llu\n", r + 1, (unsigned long long)n_self[r]);
+  if (fig->rescue_na) fprintf(out, "rescue_ratio\tNA\n");
+  else fprintf(out, "rescue_ratio\t%.6f\n", fig->rescue);
+  if (fig->self_na) fprintf(out, "self_consistency_ratio\tNA\n");
+  else fprintf(out, "self_consistency_ratio\t%.6f\n", fig->self_consistency);
+  fprintf(out, "verdict\t%s\n", verdict[fig->verdict >= 0 && fig->verdict <= 3 ? fig->verdict : 3]);
+  if (R > 1) fprintf(out, "conservative_peaks\t%llu\n", (unsigned long long)fig->n_conservative);
+  else fprintf(out, "conservative_peaks\tNA\n");
+  fprintf(out, "optimal_peaks\t%llu\n", (unsigned long long)fig->n_optimal);
   return GX_OK;
 }
 

@@ -557,6 +557,10 @@ struct gx_ctx {
   gx_ctx* satChild = nullptr;     // the context gx_saturation re-calls the peaks on (until gx_reset / gx_destroy)
   std::vector<gx_sat_point> satPts;             // the last gx_saturation, per point (until gx_reset)
   std::vector<std::vector<gx_peak>> satPeaks;   // ... and its peaks
+  bool splitUsed = false;         // k_sub_split ran since the last gx_reset
+  std::vector<gx_repro_call> reproCalls;        // the last gx_reproducibility, per call (until gx_reset)
+  std::vector<std::vector<gx_peak>> reproPeaks; // ... and its peaks
+  uint64_t reproSeed = 0;                       // ... and its seed
   // timing
   std::vector<Phase> phases;
   size_t nPhases = 0;

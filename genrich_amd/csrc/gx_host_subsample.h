@@ -1,5 +1,6 @@
 // gx_host_subsample.h -- the host side of the subsample (gx_subsample.h) and of the peak saturation curve made with it
-// (gx_saturation): the staging, the three launches, and the re-call of the peaks on a child context.
+// (gx_saturation): the staging, the three launches, and the re-call of the peaks on a child context; then the split of a sample
+// into both halves (k_sub_split) and the reproducibility calls made of the halves on the same child (gx_reproducibility).
 // (a part of gx_api.hip's translation unit)
 #pragma once
 namespace {
@@ -192,6 +193,118 @@ int sat_point(gx_ctx* ctx, u64 T, u64 seed, unsigned flags, gx_sat_point& pt, st
   pt.n_peaks = np;
   pt.peak_bp = bp;
   pt.genome_len = g;
+  peaks.resize(np);
+  if (np) rc = gx_get_peaks(ch, peaks.data(), np);
+  return rc;
+}
+
+// ---- both halves of a sample (k_sub_split) and the reproducibility calls made of them (gx_reproducibility) ----
+
+// sub_pass with k_sub_split as the third launch: all n events into `out`, half A in [0, *nA), half B behind it
+int sub_split_pass(gx_ctx* ctx, const CntChunk* dCk, const u64* dFirst, u32 nCk, u64 n, u64 key, u64 T, u32 grid, DevBuf& out, u64* nA) {
+  *nA = 0;
+  if (!nCk || !n) return GX_OK;
+  hipStream_t s = ctx->stream;
+  const u32 nBlocks = nCk * SUB_BPC;
+  POOLED(ctx, ctx->subCnt, (size_t)nBlocks * 4);
+  POOLED(ctx, ctx->subOff, ((size_t)nBlocks + 1) * 8);
+  POOLED(ctx, out, (size_t)n * sizeof(gx_event));
+  SubArgs a;
+  a.chunks = dCk;
+  a.first = dFirst;
+  a.nChunks = nCk;
+  a.key = key;
+  a.T = T;
+  a.blockCnt = ctx->subCnt.as<u32>();
+  a.blockOff = ctx->subOff.as<u64>();
+  a.out = out.as<uint4>();
+  const u32 g = grid ? grid : std::min(nBlocks, SUB_GRID);
+  phase_begin(ctx, "split");
+  hipLaunchKernelGGL(k_sub_count, dim3(g), dim3(SUB_NT), 0, s, a);
+  if (int rc__ = dbg_sync(ctx, "k_sub_count")) return rc__;
+  hipLaunchKernelGGL(k_sub_scan, dim3(1), dim3(SUB_SCAN_NT), 0, s, a.blockCnt, nBlocks, ctx->subOff.as<u64>());
+  if (int rc__ = dbg_sync(ctx, "k_sub_scan")) return rc__;
+  hipLaunchKernelGGL(k_sub_split, dim3(g), dim3(SUB_NT), 0, s, a);
+  if (int rc__ = dbg_sync(ctx, "k_sub_split")) return rc__;
+  phase_end(ctx);
+  HIPCHECK(hipGetLastError());
+  ctx->splitUsed = true;
+  u64 total = 0;
+  HIPCHECK(hipMemcpyAsync(&total, ctx->subOff.as<u64>() + nBlocks, 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (total > n) {
+    ctx->err = "subsample: more events kept than there are";
+    return GX_ERR_DEVICE;
+  }
+  *nA = total;
+  return GX_OK;
+}
+
+// kept sample k through the split, into its own buffer (ctx->subBufs[k])
+int sub_split_kept(gx_ctx* ctx, size_t k, u64 seed, u64 T, u64* n, u64* nA) {
+  if (ctx->subBufs.size() < ctx->kept.size()) ctx->subBufs.resize(ctx->kept.size());
+  const CntChunk* dCk = nullptr;
+  const u64* dFirst = nullptr;
+  u32 nCk = 0;
+  if (int rc = sub_stage(ctx, ctx->kept[k].segs, &dCk, &dFirst, &nCk, n)) return rc;
+  return sub_split_pass(ctx, dCk, dFirst, nCk, *n, subsample_key(seed, (u32)k), T, 0, ctx->subBufs[k], nA);
+}
+
+void repro_drop(gx_ctx* ctx) {
+  ctx->reproCalls.clear();
+  ctx->reproPeaks.clear();
+  ctx->splitUsed = false;
+}
+
+// one replicate's part in a call: whole (half < 0) or one of its halves
+struct ReproPart { int rep, half; };
+// a replicate as gx_reproducibility sees it: its treatment's and control's kept indices (-1: none), its events and half A's
+struct ReproRep { int kt = -1, kc = -1; u64 n = 0, nA = 0; };
+
+// one call: the parts as the replicates of a run on the child, each with its save mask and its control whole
+int repro_call(gx_ctx* ctx, const std::vector<ReproRep>& reps, const std::vector<ReproPart>& parts, gx_repro_call& call,
+               std::vector<gx_peak>& peaks) {
+  gx_ctx* ch = ctx->satChild;
+  peaks.clear();
+  call.status = GX_OK;
+  call.n_events = call.n_peaks = call.peak_bp = 0;
+  for (const ReproPart& p : parts) {
+    const ReproRep& R = reps[p.rep];
+    call.n_events += p.half < 0 ? R.n : p.half == 0 ? R.nA : R.n - R.nA;
+  }
+  int rc = gx_reset(ch);
+  for (size_t i = 0; !rc && i < parts.size(); i++) {
+    const ReproRep& R = reps[parts[i].rep];
+    const int half = parts[i].half;
+    rc = gx_sample_begin(ch, 0, ctx->kept[R.kt].save.data());
+    if (!rc && half < 0) rc = sat_push_whole(ch, ctx->kept[R.kt]);
+    else if (!rc) {
+      const u64 at = half ? R.nA : 0, m = half ? R.n - R.nA : R.nA;
+      if (m) rc = gx_push_events_device(ch, ctx->subBufs[R.kt].as<gx_event>() + at, (size_t)m);
+    }
+    if (!rc) rc = gx_sample_end(ch, nullptr, nullptr, nullptr);
+    if (rc) break;
+    if (R.kc >= 0) {
+      rc = gx_sample_begin(ch, 1, nullptr);
+      if (!rc) rc = sat_push_whole(ch, ctx->kept[R.kc]);
+      if (!rc) rc = gx_sample_end(ch, nullptr, nullptr, nullptr);
+    } else
+      rc = gx_sample_no_control(ch, nullptr);
+    if (!rc) rc = gx_pvalues(ch);
+  }
+  size_t np = 0;
+  uint64_t g = 0, bp = 0;
+  if (!rc) rc = gx_find_peaks(ch, &np, &g, &bp);
+  if (rc == GX_ERR_EXPT) {   // (the part left no analyzable fragment: a result)
+    call.status = GX_ERR_EXPT;
+    return GX_OK;
+  }
+  if (rc) {
+    ctx->err = "reproducibility: " + ch->err;
+    return rc;
+  }
+  call.n_peaks = np;
+  call.peak_bp = bp;
   peaks.resize(np);
   if (np) rc = gx_get_peaks(ch, peaks.data(), np);
   return rc;

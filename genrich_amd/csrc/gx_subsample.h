@@ -137,4 +137,86 @@ __global__ __launch_bounds__(SUB_NT) void k_sub_write(SubArgs a) {
   }
 }
 
+// k_sub_split -- both halves of a sample in one pass (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility):
+// a stable two-way partition.  Event i goes to half A iff its draw is below T, else to half B; both keep the kept order and
+// share one buffer of the sample's n events, A in [0, nA), B in [nA, n).  k_sub_count and k_sub_scan run before it as they do
+// before k_sub_write: blockOff[b] is A's offset of block b and blockOff[nBlocks] is nA, read here, so that no count comes
+// back to the host between the launches.  B needs no scan of its own: first[c] + b0 events lie before block b of chunk c and
+// blockOff[b] of them are A's, so B's part of the block starts at nA + first[c] + b0 - blockOff[b].  Inside a block the valid
+// positions pos = j * SUB_NT + threadIdx.x (those below ch.n - b0) are contiguous from 0, so an event with rankA of A's events
+// before it has pos - rankA of B's before it; rankA is k_sub_write's (ballot, popcount, the 32-entry scan).  Every event is
+// read once and stored once, 16 bytes each way; no workgroup waits for another, every loop is bounded by the chunk list, and
+// a place depends on the block offsets alone: the same bytes for every grid.
+// As compiled (gfx950, -O3; the compiler's resource-usage remarks) k_sub_split takes 72 VGPRs and no scratch: seven wavefronts
+// per SIMD, k_sub_write's step (66 VGPRs, seven as well).  It got there in three moves.  Written as k_sub_write is, with the
+// loads made unconditional, it took 76 to 81 and fell to six or five: the chunk's pointer, its count and the block offsets
+// came from vector loads (nothing tells the compiler that `out` does not alias them) and sat in vector registers, so they are
+// moved to scalar ones (sub_uni); a 64-bit select between the two halves' addresses cost two registers per event, so each
+// half has its own store off a uniform base; and the branch on the event form stands once around the eight loads, not inside
+// each, so that the packed form's loads are all in flight before the first is unpacked.  Asking for seven by
+// __launch_bounds__ instead spilled three registers.
+// a value that is the same in every lane, moved to scalar registers (a load the compiler cannot prove uniform lands in vector ones)
+__device__ __forceinline__ u32 sub_uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ u64 sub_uni(u64 v) { return ((u64)sub_uni((u32)(v >> 32)) << 32) | sub_uni((u32)v); }
+
+__global__ __launch_bounds__(SUB_NT) void k_sub_split(SubArgs a) {
+  __shared__ u32 cnt[SUB_ITEMS * SUB_NW], pre[SUB_ITEMS * SUB_NW];
+  const u32 nBlocks = a.nChunks * SUB_BPC;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const u64 nA = sub_uni(a.blockOff[nBlocks]);
+  for (u32 b = blockIdx.x; b < nBlocks; b += gridDim.x) {
+    const u32 c = b / SUB_BPC, b0 = (b % SUB_BPC) * SUB_BLOCK;
+    CntChunk ch;
+    ch.n = sub_uni(a.chunks[c].n);
+    if (b0 >= ch.n) continue;   // (uniform over the workgroup: an empty block)
+    ch.p = reinterpret_cast<const void*>(sub_uni((u64)reinterpret_cast<uintptr_t>(a.chunks[c].p)));
+    ch.packed = sub_uni(a.chunks[c].packed);
+    const u64 i0 = sub_uni(a.first[c]) + b0, offA = sub_uni(a.blockOff[b]), offB = nA + i0 - offA;
+    const u32 m = min(ch.n - b0, SUB_BLOCK);   // the block's events: its positions 0 .. m - 1
+    uint4 ev[SUB_ITEMS];
+    u32 at[SUB_ITEMS];   // A's events before this one in its wavefront's row; bit 31: the event is B's
+#pragma unroll
+    for (int j = 0; j < SUB_ITEMS; j++) {
+      const u32 pos = (u32)j * SUB_NT + threadIdx.x;
+      const bool k = pos < m && (u64)subsample_draw(a.key, i0 + pos) < a.T;
+      const unsigned long long inA = __ballot(k);
+      at[j] = (u32)__popcll(inA & ((1ull << lane) - 1)) | (k ? 0u : 0x80000000u);
+      if (lane == 0) cnt[j * SUB_NW + wv] = (u32)__popcll(inA);
+    }
+    // every event, unconditionally (a position past the end reads the block's last one): one branch on the form around the
+    // eight loads, which fly over the scan
+    if (ch.packed) {
+#pragma unroll
+      for (int j = 0; j < SUB_ITEMS; j++) ev[j] = kept_event(ch, b0 + min((u32)j * SUB_NT + threadIdx.x, m - 1));
+    } else {
+#pragma unroll
+      for (int j = 0; j < SUB_ITEMS; j++) ev[j] = kept_event(ch, b0 + min((u32)j * SUB_NT + threadIdx.x, m - 1));
+    }
+    __syncthreads();
+    if (wv == 0) {   // exclusive scan of the (row, wavefront) counts, row-major: the kept order
+      u32 v = lane < SUB_ITEMS * SUB_NW ? cnt[lane] : 0u;
+      const u32 mine = v;
+      for (int o = 1; o < SUB_ITEMS * SUB_NW; o <<= 1) {
+        const u32 u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+      }
+      if (lane < SUB_ITEMS * SUB_NW) pre[lane] = v - mine;
+    }
+    __syncthreads();
+    // a store per half: a uniform base and a place below SUB_BLOCK, i.e. one address register per event
+    uint4* const outA = a.out + offA;
+    uint4* const outB = a.out + offB;
+#pragma unroll
+    for (int j = 0; j < SUB_ITEMS; j++) {
+      const u32 pos = (u32)j * SUB_NT + threadIdx.x;
+      const u32 rankA = (pre[j * SUB_NW + wv] + (at[j] & 0x7FFFFFFFu)) & (SUB_BLOCK - 1);
+      if (pos < m) {
+        if (at[j] & 0x80000000u) outB[(pos - rankA) & (SUB_BLOCK - 1)] = ev[j];
+        else outA[rankA] = ev[j];
+      }
+    }
+    __syncthreads();   // (cnt and pre are the next block's as well)
+  }
+}
+
 }  // namespace gx

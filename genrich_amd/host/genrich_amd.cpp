@@ -152,6 +152,25 @@ void usage() {
   exit(EXIT_FAILURE);
 }
 
+// --help-reproducibility: the block of --reproducibility and its sub-options, in usage()'s form (to the same stream, with the same
+// exit status); it stands apart so that the -h text stays as recorded
+void usageReproducibility() {
+  fprintf(stderr,
+          "  --reproducibility FILE [--reproducibility-metrics FILE] [--reproducibility-overlap PCT] [--reproducibility-seed S]\n"
+          "                  [--reproducibility-peaks PREFIX]   the peaks called once more on every replicate alone, on two random\n"
+          "                  halves (pseudo-replicates) of every replicate drawn with seed S (1), and on the two pools of halves,\n"
+          "                  3 R + 2 calls for R replicates; the controls stay whole.  A TSV with one row per call -- t<rep>,\n"
+          "                  t<rep>.pr1, t<rep>.pr2, pooled.pr1, pooled.pr2: intervals, peaks, peak bp, the call's peaks that one of the\n"
+          "                  run's supports, the run's peaks that one of the call's supports, status; a peak supports another when\n"
+          "                  they share at least one base and PCT %% (50; 0 .. 100) of the shorter of the two.  The metrics file (it may\n"
+          "                  stand alone) has Nt per pair of replicates and the greatest, Np, N_self per replicate, the rescue and\n"
+          "                  self-consistency ratios, the verdict (pass, borderline, fail, NA) and the sizes of the conservative and\n"
+          "                  optimal sets; --reproducibility-peaks writes PREFIX.<call>.narrowPeak per call and the run's own -o lines\n"
+          "                  of the two sets as PREFIX.conservative.narrowPeak and PREFIX.optimal.narrowPeak; one device; not with -X,\n"
+          "                  -P or --events-only\n");
+  exit(EXIT_FAILURE);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -199,6 +218,12 @@ int main(int argc, char** argv) {
                                      {"lengths-metrics", required_argument, nullptr, 1031},
                                      {"lengths-cuts", required_argument, nullptr, 1032},
                                      {"chrom-stats", required_argument, nullptr, 1033},
+                                     {"reproducibility", required_argument, nullptr, 1039},
+                                     {"reproducibility-metrics", required_argument, nullptr, 1040},
+                                     {"reproducibility-overlap", required_argument, nullptr, 1041},
+                                     {"reproducibility-seed", required_argument, nullptr, 1042},
+                                     {"reproducibility-peaks", required_argument, nullptr, 1043},
+                                     {"help-reproducibility", no_argument, nullptr, 1044},
                                      {nullptr, 0, nullptr, 0}};
   int nThreads;  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
   {
@@ -316,6 +341,24 @@ int main(int argc, char** argv) {
         break;
       }
       case 1026: o.saturationControls = true; break;
+      case 1039: o.reproFile = optarg; break;
+      case 1040: o.reproMetricsFile = optarg; break;
+      case 1041: {
+        __int128 v;
+        if (!strictInt(optarg, 0, 100, &v)) die(optarg, ": --reproducibility-overlap takes an integer in [0, 100]");
+        o.reproPct = (int)v;
+        o.reproPctOpt = true;
+        break;
+      }
+      case 1042: {
+        __int128 v;
+        if (!strictInt(optarg, 0, (__int128)UINT64_MAX, &v)) die(optarg, ": --reproducibility-seed takes an integer in [0, 2^64 - 1]");
+        o.reproSeed = (uint64_t)v;
+        o.reproSeedOpt = true;
+        break;
+      }
+      case 1043: o.reproPrefix = optarg; break;
+      case 1044: usageReproducibility();
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -375,6 +418,12 @@ int main(int argc, char** argv) {
   if (o.saturationFile && (o.saturationSteps < 1 || o.saturationSteps > 100)) die("", "--saturation-steps must be in [1, 100]");
   // (the re-call on several contexts needs the collectives between their child contexts)
   if (o.saturationFile && o.devices.size() > 1) die("", "--saturation takes one device (not with --devices of more than one)");
+  // (the calls are made of this run's peaks and of the events the library keeps: none with -X, -P or --events-only)
+  if (o.reproOn() && !o.callsPeaks())
+    die("", "--reproducibility needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
+  if ((o.reproPctOpt || o.reproSeedOpt || o.reproPrefix) && !o.reproOn())
+    die("", "--reproducibility-overlap, --reproducibility-seed and --reproducibility-peaks need --reproducibility FILE or --reproducibility-metrics FILE");
+  if (o.reproOn() && o.devices.size() > 1) die("", "--reproducibility takes one device (not with --devices of more than one)");
   // the treatment / control lists, and the samples they name: one per -t file and per -c file that is not "null", known before
   // anything is read or written
   const std::vector<std::string> tFiles = splitList(o.inFile), cFiles = splitList(o.ctrlFile);
@@ -456,7 +505,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
+      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile || o.reproOn() || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
         check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
@@ -634,6 +683,7 @@ int main(int argc, char** argv) {
   if (o.depthFile || o.depthMetricsFile) writeDepth(S);
   if (o.xcorOn()) writeXcor(S);
   if (o.saturationFile) writeSaturation(S);
+  if (o.reproOn()) writeReproducibility(S, names);
   if (o.profileBed) writeProfile(S, profilePlan, sampleNames);
   writeFile(S, o.logFile, [&](FILE* f) {
     return gx_write_log_group(S.devs.ctx.data(), S.devs.owner.data(), S.sample, names.data(), nChrom, o.qvalOpt, o.peaksOpt, thr, f);

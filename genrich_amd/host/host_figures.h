@@ -520,6 +520,78 @@ void writeSaturation(State& S) {
             (double)pts[N - 1].n_peaks / (double)pts[N - 2].n_peaks);
 }
 
+// --reproducibility FILE [--reproducibility-metrics FILE] [--reproducibility-overlap PCT] [--reproducibility-seed S]
+// [--reproducibility-peaks PREFIX]: the peaks called once more on every replicate alone, on its two halves and on the two pools
+// of halves (gx_reproducibility), one row per call in FILE and the figures made of the lists in the metrics file; with the
+// prefix every call's narrowPeak and the run's own -o lines (their peak_N as in -o, so that they join with --counts) of the
+// conservative and the optimal set; with -v each call on stderr, then the figures and the verdict
+void writeReproducibility(State& S, const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  gx_ctx* g = S.devs.ctx[0];
+  const int nR = S.sample;
+  size_t nC = 3 * (size_t)nR + 2;
+  std::vector<gx_repro_call> calls(nC);
+  check(S, gx_reproducibility(g, o.reproSeed, 0u, calls.data(), calls.size(), &nC), g);   // (before a file is opened)
+  if (nC != calls.size()) die("", "--reproducibility: the library made other calls than this run's replicates ask for");
+  writeFiles(S, o.reproFile, o.reproMetricsFile, [&](FILE* a, FILE* b) { return gx_write_reproducibility(g, o.reproPct, a, b); });
+  if (!o.verbose && !o.reproPrefix) return;
+  // the lists once more on this side: the sets' members and -v's lines
+  size_t nRun = 0;
+  check(S, gx_peak_count(g, &nRun), g);
+  std::vector<gx_peak> run(nRun);
+  if (nRun) check(S, gx_get_peaks(g, run.data(), nRun), g);
+  std::vector<std::vector<gx_peak>> lists(nC);
+  std::vector<const gx_peak*> ptrs(nC);
+  for (size_t i = 0; i < nC; i++) {
+    lists[i].resize((size_t)calls[i].n_peaks);
+    if (!lists[i].empty()) check(S, gx_get_reproducibility_peaks(g, (int)i, lists[i].data(), lists[i].size()), g);
+    ptrs[i] = lists[i].data();
+  }
+  gx_repro_figures fig;
+  std::vector<uint64_t> pairs((size_t)nR * (nR - 1) / 2 + 1), self((size_t)nR), inRun(nC), runSup(nC);
+  std::vector<uint8_t> cons(nRun + 1), opt(nRun + 1);
+  check(S, gx_reproducibility_figures(run.data(), nRun, nR, calls.data(), ptrs.data(), o.reproPct, &fig, pairs.data(), self.data(), inRun.data(),
+                                      runSup.data(), cons.data(), opt.data()), g);
+  if (o.reproPrefix) {
+    char label[64];
+    for (size_t i = 0; i < nC; i++) {
+      check(S, gx_reproducibility_label(&calls[i], label, sizeof label), g);
+      const std::string path = std::string(o.reproPrefix) + "." + label + ".narrowPeak";
+      writeFile(S, path.c_str(), [&](FILE* f) { return gx_format_narrowpeak(lists[i].data(), lists[i].size(), names.data(), 0, f); });
+    }
+    const std::pair<const char*, const std::vector<uint8_t>*> sets[2] = {{"conservative", &cons}, {"optimal", &opt}};
+    for (const auto& st : sets) {
+      const std::string path = std::string(o.reproPrefix) + "." + st.first + ".narrowPeak";
+      writeFile(S, path.c_str(), [&](FILE* f) {
+        int rc = GX_OK;
+        for (size_t k = 0; k < nRun && rc == GX_OK; k++)
+          if ((*st.second)[k]) rc = gx_format_narrowpeak(&run[k], 1, names.data(), (int)k, f);
+        return rc;
+      });
+    }
+  }
+  if (!o.verbose) return;
+  char label[64];
+  for (size_t i = 0; i < nC; i++) {
+    check(S, gx_reproducibility_label(&calls[i], label, sizeof label), g);
+    fprintf(stderr, "  Reproducibility, %s: %llu intervals, %llu peaks (%llubp), %llu of them in the run's, %llu of the run's %zu supported%s\n", label,
+            (unsigned long long)calls[i].n_events, (unsigned long long)calls[i].n_peaks, (unsigned long long)calls[i].peak_bp,
+            (unsigned long long)inRun[i], (unsigned long long)runSup[i], nRun, calls[i].status ? " -- no analyzable fragments" : "");
+  }
+  static const char* const verdict[] = {"pass", "borderline", "fail", "NA"};
+  if (nR > 1)
+    fprintf(stderr, "  Reproducibility: Nt %llu (t%d, t%d), Np %llu, N_self %llu .. %llu\n", (unsigned long long)fig.nt, fig.best_i + 1, fig.best_j + 1,
+            (unsigned long long)fig.np, (unsigned long long)fig.n_self_min, (unsigned long long)fig.n_self_max);
+  else
+    fprintf(stderr, "  Reproducibility: one replicate: Np %llu, N_self %llu\n", (unsigned long long)fig.np, (unsigned long long)fig.n_self_max);
+  if (fig.verdict == GX_REPRO_NA)
+    fprintf(stderr, "  Reproducibility: verdict NA (%s)\n", nR > 1 ? "a count of 0" : "the ratios need two replicates");
+  else
+    fprintf(stderr, "  Reproducibility: rescue ratio %f, self-consistency ratio %f: verdict %s\n", fig.rescue, fig.self_consistency, verdict[fig.verdict]);
+  fprintf(stderr, "  Reproducibility: conservative set %llu peaks, optimal set %llu peaks\n", (unsigned long long)fig.n_conservative,
+          (unsigned long long)fig.n_optimal);
+}
+
 // --profile BED --profile-out PREFIX: each sample's pileup summed over bins around the BED's anchor sites.  The anchors go to
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one

@@ -52,6 +52,14 @@ struct Opts {
   uint64_t saturationSeed = 1;             // --saturation-seed S
   bool saturationSeedOpt = false;
   bool saturationControls = false;         // --saturation-controls: the controls are subsampled too
+  const char* reproFile = nullptr;         // --reproducibility FILE: the peaks called once more on every replicate, its halves and the pools of halves
+  const char* reproMetricsFile = nullptr;  // --reproducibility-metrics FILE: Nt, Np, N_self, the two ratios and the verdict (it may stand alone)
+  int reproPct = 50;                       // --reproducibility-overlap PCT: a peak supports another over PCT % of the shorter
+  bool reproPctOpt = false;
+  uint64_t reproSeed = 1;                  // --reproducibility-seed S
+  bool reproSeedOpt = false;
+  const char* reproPrefix = nullptr;       // --reproducibility-peaks PREFIX: every call's narrowPeak, the conservative and the optimal set
+  bool reproOn() const { return reproFile || reproMetricsFile; }
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;

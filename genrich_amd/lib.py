@@ -163,6 +163,14 @@ GX_SAT_CONTROLS = 1             # gx_saturation: the controls are subsampled at 
 GX_ERR_EXPT = -3                # a point of gx_saturation whose subsample left no analyzable fragment
 SAT_POINT_DTYPE = np.dtype([("threshold", "<u8"), ("n_total", "<u8"), ("n_kept", "<u8"), ("n_peaks", "<u8"), ("peak_bp", "<u8"),
                             ("genome_len", "<u8"), ("status", "<i4"), ("_pad", "<i4")])   # gx_sat_point
+GX_PATH_SPLIT = 268435456       # gx_path_info bit 28: k_sub_split ran (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility)
+GX_REPRO_ALONE, GX_REPRO_SELF, GX_REPRO_POOLED = 0, 1, 2          # gx_repro_call.kind
+REPRO_VERDICTS = ("pass", "borderline", "fail", "NA")              # GX_REPRO_PASS .. GX_REPRO_NA
+REPRO_CALL_DTYPE = np.dtype([("kind", "<i4"), ("rep", "<i4"), ("half", "<i4"), ("status", "<i4"), ("n_events", "<u8"), ("n_peaks", "<u8"),
+                             ("peak_bp", "<u8")])   # gx_repro_call
+REPRO_FIGURES_DTYPE = np.dtype([(k, "<i4") for k in ("n_rep", "best_i", "best_j", "verdict", "rescue_na", "self_na", "optimal_is_pooled", "_pad")]
+                               + [(k, "<u8") for k in ("nt", "np", "n_self_max", "n_self_min", "n_conservative", "n_optimal")]
+                               + [("rescue", "<f8"), ("self_consistency", "<f8")])   # gx_repro_figures
 
 
 GX_PATH_DEPTH = 33554432        # gx_path_info bit 25: k_depth_hist ran (gx_set_depth_hist)
@@ -424,6 +432,19 @@ _SIGS = {
     "gx_saturation_overlap": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "gx_format_saturation": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64],
     "gx_write_saturation": [C.c_void_p, C.c_void_p],
+    "gx_subsample_split_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint, C.c_void_p, C.c_size_t,
+                                  C.POINTER(C.c_size_t)],
+    "gx_subsample_split_kept": [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_reproducibility": [C.c_void_p, C.c_uint64, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_get_reproducibility_peaks": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
+    "gx_peaks_supported": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
+    "gx_reproducibility_figures": [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_reproducibility_label": [C.c_void_p, C.c_char_p, C.c_size_t],
+    "gx_format_reproducibility": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64],
+    "gx_format_reproducibility_metrics": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_format_narrowpeak": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_write_reproducibility": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_rccl_nranks": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_set_phase_filter": [C.c_void_p, C.c_char_p],
     "gx_set_phase_timing": [C.c_void_p, C.c_int],
@@ -1067,6 +1088,91 @@ def format_saturation(points, full_recovered, sub_in_full, shared_bp, n_full, fu
                                                           cols[2].ctypes.data, int(n_full), int(full_bp)))
 
 
+def peaks_supported(a, b, pct):
+    """hit[i] (uint8): peak a[i] is supported by a peak of b at `pct` percent of the shorter (gx_peaks_supported); two lists in
+    get_peaks() order; host-only."""
+    x, y = np.ascontiguousarray(a, dtype=PEAK_DTYPE), np.ascontiguousarray(b, dtype=PEAK_DTYPE)
+    hit = np.zeros(max(x.size, 1), dtype=np.uint8)
+    rc = load_library().gx_peaks_supported(x.ctypes.data if x.size else None, x.size, y.ctypes.data if y.size else None, y.size, int(pct),
+                                           hit.ctypes.data if x.size else None)
+    if rc:
+        raise RuntimeError(f"gx_peaks_supported: {rc}")
+    return hit[:x.size]
+
+
+def repro_calls(n_rep, n_events=None, n_peaks=None, peak_bp=None, status=None):
+    """gx_reproducibility's 3 R + 2 calls in its order, as REPRO_CALL_DTYPE records (the counts where given)."""
+    R = int(n_rep)
+    out = np.zeros(3 * R + 2, dtype=REPRO_CALL_DTYPE)
+    for r in range(R):
+        out[r] = (GX_REPRO_ALONE, r, -1, 0, 0, 0, 0)
+        for h in range(2):
+            out[R + 2 * r + h] = (GX_REPRO_SELF, r, h, 0, 0, 0, 0)
+    for h in range(2):
+        out[3 * R + h] = (GX_REPRO_POOLED, -1, h, 0, 0, 0, 0)
+    for name, col in (("n_events", n_events), ("n_peaks", n_peaks), ("peak_bp", peak_bp), ("status", status)):
+        if col is not None:
+            out[name] = col
+    return out
+
+
+def reproducibility_figures(run, calls, lists, pct):
+    """The figures of --reproducibility (gx_reproducibility_figures) from the run's peaks, the calls (REPRO_CALL_DTYPE, in
+    gx_reproducibility's order) and their peak lists: a dict with the REPRO_FIGURES_DTYPE record `fig` and the arrays nt_pair,
+    n_self, in_run, run_supported, conservative, optimal; host-only."""
+    lib = load_library()
+    run = np.ascontiguousarray(run, dtype=PEAK_DTYPE)
+    calls = np.ascontiguousarray(calls, dtype=REPRO_CALL_DTYPE)
+    R = (len(calls) - 2) // 3
+    lists = [np.ascontiguousarray(l, dtype=PEAK_DTYPE) for l in lists]
+    ptrs = (C.c_void_p * len(lists))(*[l.ctypes.data if l.size else None for l in lists])
+    fig = np.zeros(1, dtype=REPRO_FIGURES_DTYPE)
+    pair, n_self = np.zeros(max(R * (R - 1) // 2, 1), dtype=np.uint64), np.zeros(R, dtype=np.uint64)
+    in_run, run_sup = np.zeros(len(calls), dtype=np.uint64), np.zeros(len(calls), dtype=np.uint64)
+    cons, opt = np.zeros(max(run.size, 1), dtype=np.uint8), np.zeros(max(run.size, 1), dtype=np.uint8)
+    rc = lib.gx_reproducibility_figures(run.ctypes.data if run.size else None, run.size, R, calls.ctypes.data, ptrs, int(pct), fig.ctypes.data,
+                                        pair.ctypes.data, n_self.ctypes.data, in_run.ctypes.data, run_sup.ctypes.data, cons.ctypes.data,
+                                        opt.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_reproducibility_figures: {rc}")
+    return dict(fig=fig[0], nt_pair=pair[:R * (R - 1) // 2], n_self=n_self, in_run=in_run, run_supported=run_sup,
+                conservative=cons[:run.size], optimal=opt[:run.size])
+
+
+def repro_label(call):
+    """A call's label in the tables and file names (gx_reproducibility_label): t1, t1.pr2, pooled.pr1."""
+    c = np.ascontiguousarray(np.asarray(call, dtype=REPRO_CALL_DTYPE).reshape(1))
+    buf = C.create_string_buffer(64)
+    load_library().gx_reproducibility_label(c.ctypes.data, buf, 64)
+    return buf.value.decode()
+
+
+def format_reproducibility(calls, in_run, run_supported, n_run, run_bp, pct, seed) -> bytes:
+    """--reproducibility's call table (gx_format_reproducibility); host-only, needs no GPU."""
+    lib = load_library()
+    calls = np.ascontiguousarray(calls, dtype=REPRO_CALL_DTYPE)
+    a, b = np.ascontiguousarray(in_run, dtype=np.uint64), np.ascontiguousarray(run_supported, dtype=np.uint64)
+    return _to_tmpfile(lambda f: lib.gx_format_reproducibility(f, (len(calls) - 2) // 3, calls.ctypes.data, a.ctypes.data, b.ctypes.data,
+                                                               int(n_run), int(run_bp), int(pct), int(seed)))
+
+
+def format_reproducibility_metrics(figures) -> bytes:
+    """--reproducibility-metrics' table (gx_format_reproducibility_metrics) of what reproducibility_figures() gave; host-only."""
+    lib = load_library()
+    fig = np.ascontiguousarray(np.asarray(figures["fig"], dtype=REPRO_FIGURES_DTYPE).reshape(1))
+    pair = np.ascontiguousarray(np.append(figures["nt_pair"], 0), dtype=np.uint64)
+    n_self = np.ascontiguousarray(figures["n_self"], dtype=np.uint64)
+    return _to_tmpfile(lambda f: lib.gx_format_reproducibility_metrics(f, fig.ctypes.data, pair.ctypes.data, n_self.ctypes.data))
+
+
+def format_narrowpeak(peaks, names, first_index=0) -> bytes:
+    """-o's lines for a peak list (gx_format_narrowpeak); peak i is named peak_<first_index + i>; host-only."""
+    lib = load_library()
+    pk = np.ascontiguousarray(peaks, dtype=PEAK_DTYPE)
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    return _to_tmpfile(lambda f: lib.gx_format_narrowpeak(pk.ctypes.data if pk.size else None, pk.size, arr, int(first_index), f))
+
+
 def fp_geometry():
     """(n_classes, sub_log, lanes, grid) of k_fp_hist as the library was built (gx_fp_geometry): the value classes, log2 of the
     classes per octave, the lanes of a workgroup, the most workgroups of a launch by default."""
@@ -1209,6 +1315,7 @@ class Genrich:
 
     def reset(self):
         self._check(self.lib.gx_reset(self.ctx))
+        self._n_treat = 0
 
     def expect_fractional(self, on=True):
         """Hint: the run may hold fractional weights (Genrich's -s): pair records with a weight class from the first sample on."""
@@ -1263,6 +1370,8 @@ class Genrich:
             self._keep.append(sa)
             sp = sa.ctypes.data
         self._check(self.lib.gx_sample_begin(self.ctx, int(is_ctrl), sp))
+        if not is_ctrl:
+            self._n_treat = getattr(self, "_n_treat", 0) + 1   # (reproducibility() sizes its output by it)
 
     def push_events(self, ev):
         ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
@@ -1376,7 +1485,7 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran, 134217728 the cross-correlation kernels ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 268435456 the split kernel ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran, 134217728 the cross-correlation kernels ran)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value
@@ -1684,6 +1793,48 @@ class Genrich:
     def saturation_text(self) -> bytes:
         """--saturation's table of the last saturation() against this run's peaks (gx_write_saturation)."""
         return _to_tmpfile(lambda f: self.lib.gx_write_saturation(self.ctx, f))
+
+    # -- both halves of a sample and the reproducibility calls (include/genrich_amd.h, gx_reproducibility) -----------------
+    def subsample_split_events(self, events, seed, sample, threshold, grid=0, packed=False):
+        """(out, n_a): the events as sample `sample` split at `threshold` by the split kernel (gx_subsample_split_events): half A
+        in out[:n_a], half B behind it, both in order; always EVENT_DTYPE."""
+        ev = np.ascontiguousarray(events)
+        out = np.zeros(max(int(ev.size), 1), dtype=EVENT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_subsample_split_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, int(bool(packed)), int(seed),
+                                                       int(sample), int(threshold), int(grid), out.ctypes.data, ev.size, C.byref(n)))
+        return out[:ev.size], n.value
+
+    def subsample_split_kept(self, sample, seed, threshold, n):
+        """(out, n_a) of kept sample `sample` of `n` events (gx_subsample_split_kept)."""
+        out = np.zeros(max(int(n), 1), dtype=EVENT_DTYPE)
+        na = C.c_size_t(0)
+        self._check(self.lib.gx_subsample_split_kept(self.ctx, int(sample), int(seed), int(threshold), out.ctypes.data, int(n), C.byref(na)))
+        return out[:int(n)], na.value
+
+    def reproducibility(self, seed=1, flags=0):
+        """The peaks called once more on every replicate alone, on its two halves and on the two pools of halves
+        (gx_reproducibility), after find_peaks(): REPRO_CALL_DTYPE records, 3 R + 2 of them."""
+        n = C.c_size_t(0)
+        cap = 3 * max(getattr(self, "_n_treat", 0), 1) + 2
+        out = np.zeros(cap, dtype=REPRO_CALL_DTYPE)
+        self._check(self.lib.gx_reproducibility(self.ctx, int(seed), int(flags), out.ctypes.data, cap, C.byref(n)))
+        assert n.value <= cap, (n.value, cap)
+        self._repro_peaks = [int(p) for p in out["n_peaks"][:n.value]]
+        return out[:n.value]
+
+    def reproducibility_peaks(self, call):
+        """The peaks of one call of the last reproducibility() (gx_get_reproducibility_peaks), PEAK_DTYPE."""
+        n = self._repro_peaks[call]
+        out = np.zeros(n, dtype=PEAK_DTYPE)
+        self._check(self.lib.gx_get_reproducibility_peaks(self.ctx, int(call), out.ctypes.data if n else None, n))
+        return out
+
+    def reproducibility_text(self, pct=50):
+        """(calls, metrics): --reproducibility's two tables of the last reproducibility() against this run's peaks
+        (gx_write_reproducibility)."""
+        return (_to_tmpfile(lambda f: self.lib.gx_write_reproducibility(self.ctx, int(pct), f, None)),
+                _to_tmpfile(lambda f: self.lib.gx_write_reproducibility(self.ctx, int(pct), None, f)))
 
     # -- fingerprint of the samples' bins (include/genrich_amd.h, gx_coverage_fingerprint) -------------------------------
     def coverage_fingerprint(self):

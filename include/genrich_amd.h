@@ -778,6 +778,39 @@ int gx_saturation(gx_ctx* ctx, const uint64_t* threshold, int n_points, uint64_t
 int gx_get_saturation_peaks(gx_ctx* ctx, int point, gx_peak* out, size_t cap);
 int gx_saturation_thresholds(int n_points, uint64_t* threshold);
 
+/* ---- peak reproducibility over (pseudo-)replicates: the peaks called once more on every replicate alone, on two random
+ *      halves of every replicate and on the two pools of halves (no Genrich counterpart: what ENCODE's 3R + 2 further runs of
+ *      the caller on `samtools view -s` halves answer -- are these peaks one replicate's work?) ----
+ * The halves are the subsample's (above): event i of kept sample k is in half A iff its draw is below T, else in half B, so
+ * half A at T is exactly gx_subsample_kept(k, seed, T) and B is its complement, both in kept order.
+ *
+ * gx_subsample_split_events: the kernels (k_sub_count, k_sub_scan, k_sub_split: gx_subsample.h) over n events in host memory,
+ *   as gx_subsample_events takes them (the same argument rules and refusals): min(cap, n) events into out[], half A in
+ *   [0, *n_a), half B behind it, always 16-byte gx_event; the same bytes for every grid.  For tests and measurements.
+ * gx_subsample_split_kept: the same over kept sample `sample` of a context with gx_set_count_in_peaks on.
+ * gx_reproducibility: after gx_find_peaks, with gx_set_count_in_peaks on, no sample open and one context, else GX_ERR_ORDER
+ *   with a text; flags must be 0.  Each treatment is split once at T = 2^31 (its kept index is the draw's sample); controls
+ *   are never split.  Then 3R + 2 calls on gx_saturation's child context, in this order, R = the replicates:
+ *     GX_REPRO_ALONE r, r = 0 .. R-1: replicate r whole with its save mask and its control (or none), as a one-replicate run;
+ *     GX_REPRO_SELF r h, h = 0, 1:    half h of replicate r with the same control, as a one-replicate run;
+ *     GX_REPRO_POOLED h, h = 0, 1:    half h of EVERY replicate, each with its own control and save mask, combined as the run
+ *                                     combines its replicates: the run itself on half the treatment intervals.
+ *   With R = 1 all five are made: ALONE 0 is the run itself and POOLED h equals SELF 0 h.  out[i], i < min(cap, 3R + 2), and
+ *   *n_calls = 3R + 2: the call's kind, replicate (-1: pooled) and half (-1: alone), the treatment events pushed, its peaks and
+ *   their bases, and a status: GX_ERR_EXPT where the call left no analyzable fragment -- a result, with an empty list; every
+ *   other failure fails the whole call, with "reproducibility: " before the child's text.  The run's own peaks, counts and
+ *   complexity results stay as they are; calling again gives the same; gx_reset drops the result.
+ * gx_get_reproducibility_peaks: min(cap, n_peaks) peaks of call `call` of the last gx_reproducibility (gx_get_peaks order). */
+#define GX_REPRO_ALONE 0
+#define GX_REPRO_SELF 1
+#define GX_REPRO_POOLED 2
+typedef struct { int32_t kind, rep, half, status; uint64_t n_events, n_peaks, peak_bp; } gx_repro_call;
+int gx_subsample_split_events(gx_ctx* ctx, const void* ev, size_t n, int packed, uint64_t seed, uint32_t sample, uint64_t threshold,
+                              unsigned grid, gx_event* out, size_t cap, size_t* n_a);
+int gx_subsample_split_kept(gx_ctx* ctx, int sample, uint64_t seed, uint64_t threshold, gx_event* out, size_t cap, size_t* n_a);
+int gx_reproducibility(gx_ctx* ctx, uint64_t seed, unsigned flags, gx_repro_call* out, size_t cap, size_t* n_calls);
+int gx_get_reproducibility_peaks(gx_ctx* ctx, int call, gx_peak* out, size_t cap);
+
 /* ---- signal profiles around anchor sites per sample (no Genrich counterpart: the integral of gx_get_coverage, taken over
  *      strand-oriented windows around given positions instead of fixed genome-wide bins; the aggregate around transcription
  *      start sites is the TSS-enrichment curve) ----
@@ -1088,6 +1121,46 @@ int gx_saturation_overlap(const gx_peak* full, size_t n_full, const gx_peak* sub
 int gx_format_saturation(FILE* out, int n_points, const gx_sat_point* points, const uint64_t* full_recovered,
                          const uint64_t* sub_in_full, const uint64_t* shared_bp, uint64_t n_full, uint64_t full_bp);
 int gx_write_saturation(gx_ctx* ctx, FILE* out);
+/* --reproducibility (no Genrich counterpart).  All but the last: host only, no context.
+ * gx_peaks_supported: two peak lists in gx_get_peaks order (by chromosome, then start; no overlaps inside a list), in one
+ *   merge walk: hit[i] = 1 iff some b[j] on a[i]'s chromosome overlaps it by ov >= 1 bases with 100 * ov >= pct *
+ *   min(len a[i], len b[j]), in exact 64-bit integers.  pct: 0 .. 100 (else GX_ERR_ORDER); 0 = "touches", 50 = ENCODE's "half
+ *   of either peak", 100 = the shorter lies inside the longer.
+ * gx_reproducibility_figures: from the run's peaks, gx_reproducibility's 3 R + 2 calls (in its order, else GX_ERR_ORDER) and
+ *   their peak lists.  nt_pair[R (R-1) / 2], pairs i < j in row order: the run's peaks supported by both ALONE i and ALONE j;
+ *   Nt the greatest, with its pair (a tie: the first).  n_self[R]: ALONE r's peaks supported by both SELF r 0 and SELF r 1.
+ *   Np: the run's peaks supported by both pooled calls.  rescue = max(Np, Nt) / min(Np, Nt), self_consistency = max n_self /
+ *   min n_self; a ratio has no value (its _na = 1) with R = 1 or a minimum of 0.  The verdict, decided in integers as max <
+ *   2 * min: GX_REPRO_PASS both ratios below 2, GX_REPRO_BORDERLINE exactly one, GX_REPRO_FAIL neither, GX_REPRO_NA a ratio
+ *   without a value.  conservative[n_run]: the run's peaks counted in Nt (none with R = 1); optimal[n_run]: the larger of that
+ *   set and Np's (a tie: the conservative set).  in_run[3 R + 2]: the call's peaks supported by the run's; run_supported: the
+ *   run's peaks supported by the call's.  in_run, run_supported, conservative and optimal may be NULL, nt_pair with R = 1.
+ * gx_reproducibility_label: "t<rep>", "t<rep>.pr<half>", "pooled.pr<half>", replicates and halves counted from 1.
+ * gx_format_reproducibility: a comment line "# run: <n> peaks, <bp> bp; overlap <pct> %; seed <seed>", then a TSV, header "call
+ *   rep half intervals peaks peak_bp in_run run_supported status", one row per call; rep and half from 1, NA where the call
+ *   has none; status "ok" or, for GX_ERR_EXPT, "no_fragments" (another status: its number).
+ * gx_format_reproducibility_metrics: "figure value" rows: replicates, Nt.t<i>.t<j> per pair, Nt, Np, N_self.t<r>, rescue_ratio,
+ *   self_consistency_ratio (%.6f or NA), verdict, conservative_peaks, optimal_peaks (Nt and conservative_peaks: NA with R = 1).
+ * gx_format_narrowpeak: gx_write_narrowpeak_group's lines for a list; peak i is named peak_<first_index + i>.
+ * gx_write_reproducibility (gx_api.hip: it reads a context): the last gx_reproducibility against the run's own peaks; either
+ *   file may be NULL, not both. */
+#define GX_REPRO_PASS 0
+#define GX_REPRO_BORDERLINE 1
+#define GX_REPRO_FAIL 2
+#define GX_REPRO_NA 3
+typedef struct { int32_t n_rep, best_i, best_j, verdict, rescue_na, self_na, optimal_is_pooled, reserved;
+                 uint64_t nt, np, n_self_max, n_self_min, n_conservative, n_optimal;
+                 double rescue, self_consistency; } gx_repro_figures;
+int gx_peaks_supported(const gx_peak* a, size_t n_a, const gx_peak* b, size_t n_b, int pct, uint8_t* hit);
+int gx_reproducibility_figures(const gx_peak* run, size_t n_run, int n_rep, const gx_repro_call* calls, const gx_peak* const* peaks,
+                               int pct, gx_repro_figures* fig, uint64_t* nt_pair, uint64_t* n_self, uint64_t* in_run,
+                               uint64_t* run_supported, uint8_t* conservative, uint8_t* optimal);
+int gx_reproducibility_label(const gx_repro_call* call, char* out, size_t cap);
+int gx_format_reproducibility(FILE* out, int n_rep, const gx_repro_call* calls, const uint64_t* in_run, const uint64_t* run_supported,
+                              uint64_t n_run, uint64_t run_bp, int pct, uint64_t seed);
+int gx_format_reproducibility_metrics(FILE* out, const gx_repro_figures* fig, const uint64_t* nt_pair, const uint64_t* n_self);
+int gx_format_narrowpeak(const gx_peak* peaks, size_t n, const char* const* names, int first_index, FILE* out);
+int gx_write_reproducibility(gx_ctx* ctx, int pct, FILE* calls_file, FILE* metrics_file);
 int gx_write_pile_path(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, const char* expt_name,
                        const char* ctrl_name, const char* path, int append);
 int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
@@ -1186,6 +1259,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_DEPTH 33554432u /* bit 25: k_depth_hist ran since the last gx_reset (gx_set_depth_hist; a sample was closed with it on) */
 #define GX_PATH_IVSTAT 67108864u /* bit 26: k_ivstat ran since the last gx_reset (gx_interval_stats, gx_interval_stats_events) */
 #define GX_PATH_XCOR 134217728u /* bit 27: k_xc_set / k_xc_corr ran since the last gx_reset (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags) */
+#define GX_PATH_SPLIT 268435456u /* bit 28: k_sub_split ran since the last gx_reset (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
