@@ -167,6 +167,8 @@ int gx_create(gx_ctx** out, const gx_params* par) {
       fprintf(stderr, "k_tile workgroups: half %d, wide %d, fast %d\n", ctx->resTileHalf, ctx->resTile, ctx->resTileFast);
     HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scan_iv, STL_NT, 0));
     ctx->resSweep = std::max(1, std::min(nb, 4)) * ctx->numCU;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scan_iv_close_runs, STL_NT, 0));
+    ctx->resScanRuns = std::max(1, std::min(nb, 4)) * ctx->numCU;
     // level 1 of the pair sort: its persistent grids are what the device keeps resident (a multiple of NXCD, so that a chunk's
     // XCD class is the one a grid of one workgroup per chunk gave it)
     int nbA = 1 << 30;
@@ -349,6 +351,8 @@ int gx_reset(gx_ctx* ctx) {
   repro_drop(ctx);          // (gx_reproducibility's calls and k_sub_split's bit)
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
+  ctx->specRuns.valid = false;
+  ctx->overlapUsed = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
     ctx->statusSeen = 0;
@@ -359,6 +363,7 @@ int gx_reset(gx_ctx* ctx) {
 int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   if (!ctx || ctx->nChrom == 0) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
+  ctx->specRuns.valid = false;   // (a control or a further replicate: the sweep will not be the one the run pass was launched for)
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
     ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
@@ -741,6 +746,7 @@ int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* 
     src.nWords = (u32)(fa.looseStride - 2);
     src.haveMasks = true;
     src.hasSkip = false;
+    src.specOk = looseFast && !ctx->lateLooseUsed;   // (the run pass that rode in the scan's launch saw these very bits)
   } else {
     src.end = fa.end.as<u32>();
     src.p = fa.p.as<float>();
@@ -946,7 +952,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (ctx->looseSwept && ctx->overlapUsed ? GX_PATH_SWEEP_OVERLAP : 0u);
   return GX_OK;
 }
 

@@ -546,6 +546,57 @@ void launch_frag_close(gx_ctx* ctx, const Pileup& out) {
   hipLaunchKernelGGL(k_frag_select, dim3(1), dim3(1), 0, ctx->stream, ctx->closeSel);
 }
 
+// ---- what the sweep's run pass needs, shared by run_sweep and by the pass launched ahead of time (spec_runs) -----------------
+// persistent workgroups of a look-back kernel of the sweep (GX_SWEEP_GRID: tests)
+u32 sweep_grid(const gx_ctx* ctx, int resident) {
+  const u32 g = (u32)std::max(1, resident);
+  return ctx->knob.sweepGrid > 0 ? std::min(g, (u32)ctx->knob.sweepGrid) : g;
+}
+// the runs the sweep's arrays are sized for (never more runs than intervals)
+u32 sweep_run_cap(const gx_ctx* ctx, u32 nWords) {
+  const u64 capMin = ctx->knob.runCapMin > 0 ? (u64)ctx->knob.runCapMin : (u64)1 << 16;  // (tests: a tiny first guess)
+  // (first guess: one run per 256 intervals -- several times what a default threshold leaves on a genome --
+  // so that a single call does not pay for a second pass)
+  const u64 guess = ctx->knob.runCapMin > 0 ? capMin : std::max<u64>(capMin, (u64)nWords / 4);
+  return (u32)std::min<u64>(std::max<u64>(ctx->runCap, std::max<u64>(guess, 1)), (u64)nWords * 64);
+}
+// the run arrays for `cap` runs and the run pass's look-back granules (generation-tagged: never cleared between calls)
+int sweep_run_arrays(gx_ctx* ctx, u32 cap, u32 wChunks) {
+  HIPCHECK(ctx->swStart.ensure((size_t)cap * 4 + 16));
+  HIPCHECK(ctx->swEnd.ensure((size_t)cap * 4 + 16));
+  const size_t need = (size_t)2 * (wChunks + 8) * 8;
+  if (ctx->lbSweep.cap < need) {
+    HIPCHECK(ctx->lbSweep.ensure(need));
+    HIPCHECK(hipMemsetAsync(ctx->lbSweep.p, 0, ctx->lbSweep.cap, ctx->stream));
+  }
+  return GX_OK;
+}
+int sweep_next_gen(gx_ctx* ctx, u32* gen) {
+  if (++ctx->sweepGen >= (1u << 24)) {  // (the generation field wraps: start over with clean arrays)
+    ctx->sweepGen = 1;
+    if (ctx->lbSweep.cap) HIPCHECK(hipMemsetAsync(ctx->lbSweep.p, 0, ctx->lbSweep.cap, ctx->stream));
+    if (ctx->lbSweep2.cap) HIPCHECK(hipMemsetAsync(ctx->lbSweep2.p, 0, ctx->lbSweep2.cap, ctx->stream));
+  }
+  *gen = ctx->sweepGen;
+  return GX_OK;
+}
+RunsOut runs_out(gx_ctx* ctx, u32 cap) {
+  u32* misc = ctx->misc.as<u32>();
+  HostMail* dm = static_cast<HostMail*>(ctx->mailBuf.dp);
+  return RunsOut{ctx->swStart.as<u32>(), ctx->swEnd.as<u32>(), cap, misc + M_SWCOUNT, &dm->R, misc + M_TICKET3,
+                 reinterpret_cast<u64*>(misc + M_PEAKBP)};
+}
+// the chromosomes' first loose slots, from what the tile stage left (ChromStarts)
+ChromStarts chrom_starts(const gx_ctx* ctx) { return ChromStarts{ctx->dChrom.as<DChrom>(), ctx->tileSlot.as<u32>(), ctx->nChrom}; }
+
+// May the sweep's run pass ride in the scan's launch?  A treatment sample whose tile stage wrote the sweep's bits (lambda known
+// early), -p, one rank, built for the first time.  Whether the sweep will be the one this pass is for -- one replicate, no control,
+// the loose slots accepted -- only gx_find_peaks knows: run_sweep takes the pass or drops it.
+bool spec_runs_wanted(const gx_ctx* ctx, const BuildPlan& P) {
+  return P.closeInScan && P.wantEarly && !P.wantLate && !P.multiRank && !P.isCtrl && !P.fracPairs && !ctx->par.qval_opt && ctx->buildAttempt == 0 &&
+         ctx->sample == 0 && !ctx->knob.noSweepOverlap && !ctx->knob.noLoose && ctx->looseStride > 2;
+}
+
 // tile-local interval counts -> offsets (the pass over the tiles for fragLen -- deep-tile list, long first intervals --
 // rides in the scan), then the sample's closing: in the scan's own launch when lambda was known before the tile stage
 int scan_and_close(gx_ctx* ctx, const BuildPlan& P, Pileup& out) {
@@ -568,6 +619,7 @@ int scan_and_close(gx_ctx* ctx, const BuildPlan& P, Pileup& out) {
                        ctx->tileLastEnd.as<u32>(), ctx->dTileChrom.as<u32>(), ctx->dChrom.as<DChrom>(), nTiles, ctx->lbIv.as<u64>(),
                        ctx->lbIv.as<u64>() + P.tChunks + 1, so, ctx->dStatus.as<u32>(), close...);
   };
+  ctx->specRuns.valid = false;
   if (!P.closeInScan) scan(k_scan_iv);
   if (int rc__ = dbg_sync(ctx, "k_scan_iv")) return rc__;
   if (!P.closeInScan)
@@ -577,8 +629,31 @@ int scan_and_close(gx_ctx* ctx, const BuildPlan& P, Pileup& out) {
     // the general fragLen path or a changed lambda stands in the way, finish_scalars runs the separate kernels after all
     ctx->mail->nMerged = ctx->mail->closeState = 0;
     HostMail* dm = static_cast<HostMail*>(ctx->mailBuf.dp);
-    scan(k_scan_iv_close, CloseArgs{ctx->closeSel, nIv, (const u32*)&ctl->ok, ctx->dRisk.as<RiskBuf>(), mail_out(ctx), &dm->closeState,
-                                    ctx->closeSeq, nw_word(ctx, NW_CLOSE_TICKET)});
+    const CloseArgs ca{ctx->closeSel, nIv, (const u32*)&ctl->ok, ctx->dRisk.as<RiskBuf>(), mail_out(ctx), &dm->closeState,
+                       ctx->closeSeq, nw_word(ctx, NW_CLOSE_TICKET)};
+    if (spec_runs_wanted(ctx, P)) {
+      // ... and so does the sweep's run pass, in workgroups of its own behind the scan's: it needs the tile stage's bits only
+      const u32 nWords = (u32)(ctx->looseStride - 2), wChunks = (nWords + SW_CHUNK - 1) / SW_CHUNK;
+      const u32 cap = sweep_run_cap(ctx, nWords);
+      if (int rc__ = sweep_run_arrays(ctx, cap, wChunks)) return rc__;
+      u32 gen = 0;
+      if (int rc__ = sweep_next_gen(ctx, &gen)) return rc__;
+      // both halves resident together: each half's own bound, and if the two do not fit, half of the kernel's residency each
+      const u32 res = (u32)std::max(2, ctx->resScanRuns);
+      u32 gScan = std::min<u32>(P.tChunks, sweep_grid(ctx, ctx->resSweep)), gRun = std::min<u32>(wChunks, sweep_grid(ctx, ctx->resSweep));
+      if (gScan + gRun > res) {
+        gScan = std::min<u32>(gScan, res / 2);
+        gRun = std::min<u32>(gRun, res - gScan);
+      }
+      u64* lbS = ctx->lbSweep.as<u64>();
+      const RunHalf rh{SweepMasks{ctx->swMask.as<u64>(), nullptr, ctx->swMask.as<u64>() + ctx->looseStride, nWords}, chrom_starts(ctx),
+                       lbS, lbS + wChunks + 8, gen, runs_out(ctx, cap), gScan};
+      hipLaunchKernelGGL(k_scan_iv_close_runs, dim3(gScan + gRun), dim3(STL_NT), 0, ctx->stream, ctx->tileIvCount.as<u32>(),
+                         ctx->tileLastEnd.as<u32>(), ctx->dTileChrom.as<u32>(), ctx->dChrom.as<DChrom>(), nTiles, ctx->lbIv.as<u64>(),
+                         ctx->lbIv.as<u64>() + P.tChunks + 1, so, ctx->dStatus.as<u32>(), ca, rh);
+      ctx->specRuns = gx_ctx::SpecRuns{true, gen, cap, nWords, ctx->looseStride};
+    } else
+      scan(k_scan_iv_close, ca);
     if (int rc__ = dbg_sync(ctx, "k_close")) return rc__;
   }
   if (int rc__ = dbg_sync(ctx, "k_frag")) return rc__;
@@ -654,6 +729,7 @@ int finish_scalars(gx_ctx* ctx, int isCtrl) {
     ctx->closeSeq = 0;
     closed = ctx->mail->closeState == 1;
     if (!closed) {
+      ctx->specRuns.valid = false;   // (a deep tile, the general fragLen path, another lambda: the sweep's bits may not be final)
       launch_frag_close(ctx, ctx->expt);  // (closed in the scan: a treatment sample)
       if (int rc__ = dbg_sync(ctx, "k_frag (after k_close)")) return rc__;
     }
@@ -768,6 +844,7 @@ int close_sample(gx_ctx* ctx, Pileup& P, int isCtrl) {
   if (!isCtrl) ctx->looseOk = false;
   bool reuseSort = false;
   for (int attempt = 0; attempt < 12; attempt++) {
+    ctx->buildAttempt = attempt;
     int rc = build_pileup(ctx, P, isCtrl, reuseSort);
     reuseSort = false;
     if (rc) {

@@ -195,6 +195,9 @@ struct Knobs {
   int sbtTr = 0;          // GX_SBT_TR: 384 / 448: which instance of k_sbtile's dense launch runs (measurements; default: by the sample's density)
   int sbtGrid = 0;        // GX_SBT_GRID: persistent workgroups of k_sbtile's first launch (0: one per CU; a small number makes one workgroup run
                           // many bins in a row: tests, measurements)
+  int sweepGrid = 0;      // GX_SWEEP_GRID: persistent workgroups of the sweep's look-back kernels and of either half of k_scan_iv_close_runs
+                          // (0: as many as are resident together; tests: 1 makes one workgroup walk every chunk)
+  int noSweepOverlap = 0; // GX_NO_SWEEP_OVERLAP: the sweep's run pass behind the sample's closing (k_runs), as until round 25
   int s2Grid = 0;         // GX_S2_GRID: persistent workgroups of k_sort_a (per piece) and k_sort_b (0: as many as are resident together; a small
                           // number makes one workgroup run many chunks / pages in a row: tests, measurements)
   int fpAgg = 0;          // GX_FP_AGG: k_fp_hist aggregates equal classes inside the wavefront before LDS (measurements; default: an atomic pair per lane)
@@ -247,7 +250,7 @@ const KnobDef KNOBS[] = {
     {"GX_NO_DENSE_BH", &Knobs::noDenseBh, nullptr}, {"GX_REG_WINDOWS", &Knobs::regWindows, nullptr}, {"GX_QT_MULTI", &Knobs::qtMulti, nullptr}, {"GX_FORCE_COLL", &Knobs::forceColl, nullptr},
     {"GX_SBSHIFT", &Knobs::sbShift, nullptr}, {"GX_RUN_CAP_MIN", nullptr, &Knobs::runCapMin}, {"GX_BH_CAPLOG", &Knobs::bhCapLog, nullptr},
     {"GX_PT_JMAX", &Knobs::ptJmax, nullptr}, {"GX_FAULT", &Knobs::fault, nullptr}, {"GX_SBT_TR", &Knobs::sbtTr, nullptr}, {"GX_SBT_GRID", &Knobs::sbtGrid, nullptr},
-    {"GX_S2_GRID", &Knobs::s2Grid, nullptr},
+    {"GX_S2_GRID", &Knobs::s2Grid, nullptr}, {"GX_SWEEP_GRID", &Knobs::sweepGrid, nullptr}, {"GX_NO_SWEEP_OVERLAP", &Knobs::noSweepOverlap, nullptr},
     {"GX_FP_AGG", &Knobs::fpAgg, nullptr},
     {"GX_RANK_CAP_LOG", &Knobs::rankCapLog, nullptr},
     {"GX_RANK_LOOKUP", &Knobs::rankLookup, nullptr},
@@ -400,6 +403,16 @@ struct gx_ctx {
   u32 mailSeq = 0;          // mail_sync: the sequence number the next k_mail writes
   u32 statusSeen = 1;       // status bits read back since the device word was last cleared (1: not cleared yet)
   u64 runCap = 0, runSeen = 0;  // run_sweep: runs its arrays are sized for; runs of the last sweep
+  // the sweep's run pass launched ahead of time, in the scan's launch (k_scan_iv_close_runs: spec_runs); run_sweep's first
+  // attempt takes it when the sweep turns out to be the one it was launched for, and drops it in every other case
+  struct SpecRuns {
+    bool valid = false;
+    u32 gen = 0, cap = 0, nWords = 0;   // its generation number, the run arrays' capacity, the mask's words ...
+    size_t stride = 0;                  // ... and the words between the masks
+  } specRuns;
+  int buildAttempt = 0;         // close_sample: builds of the sample before this one (a rebuilt sample speculates nothing)
+  bool overlapUsed = false;     // the last gx_find_peaks took the speculative run pass (GX_PATH_SWEEP_OVERLAP)
+  int resScanRuns = 0;          // co-resident workgroups of k_scan_iv_close_runs
   bool phaseOpen = false;
   bool roctxOpen = false;       // (GX_ROCTX: the range of the open phase)
   int numCU = 0, resTile = 0, resTileHalf = 0, resTileFast = 0, resSweep = 0;  // co-resident workgroups per kernel class

@@ -20,6 +20,7 @@ struct SweepSrc {
   const u32* chromOff = nullptr;
   u32 nChrom = 0, nWords = 0;
   size_t mStride = 0;   // words between the sig / skip / brk masks in swMask
+  bool specOk = false;  // the run pass launched with the sample's scan (gx_ctx::SpecRuns) was for this very sweep
 };
 
 // callPeaks (Genrich.c:977-1069) on bit masks: runs of adjacent significant intervals -> candidates -> in-order AUC.
@@ -36,6 +37,10 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
   SweepMasks SM{ctx->swMask.as<u64>(), ctx->swMask.as<u64>() + S.mStride, ctx->swMask.as<u64>() + 2 * S.mStride, nWords};
   if (S.V) SM = SweepMasks{ctx->swMask.as<u64>(), nullptr, ctx->swMask.as<u64>() + S.mStride, nWords};
   u32 R = 0, nPeaks = 0;
+  // the run pass that rode in the scan's launch: taken by the first attempt, or dropped -- here, whatever follows
+  const gx_ctx::SpecRuns spec = ctx->specRuns;
+  ctx->specRuns.valid = false;
+  ctx->overlapUsed = false;
   ctx->peakBP = 0;
   ctx->nHostPeaks = 0;
   if (nWords) {
@@ -44,23 +49,11 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
     if (!S.haveMasks)
       hipLaunchKernelGGL(k_sig_mask, dim3(std::max(1u, std::min((nWords + 15) / 16, 4096u))), dim3(256), 0, s, S.p, S.q,
                          misc + M_NIV, ctx->par.thr, SM);
-    // look-back granules of the three one-pass compactions (generation-tagged: never cleared between calls)
-    {
-      const size_t need = (size_t)2 * (wChunks + 8) * 8;
-      if (ctx->lbSweep.cap < need) {
-        HIPCHECK(ctx->lbSweep.ensure(need));
-        HIPCHECK(hipMemsetAsync(ctx->lbSweep.p, 0, ctx->lbSweep.cap, s));
-      }
-    }
     for (int attempt = 0;; attempt++) {
-      // arrays for `cap` runs (never more runs than intervals)
-      const u64 capMin = ctx->knob.runCapMin > 0 ? (u64)ctx->knob.runCapMin : (u64)1 << 16;  // (tests: a tiny first guess)
-      // (first guess: one run per 256 intervals -- several times what a default threshold leaves on a genome --
-      // so that a single call does not pay for a second pass)
-      const u64 guess = ctx->knob.runCapMin > 0 ? capMin : std::max<u64>(capMin, (u64)nWords / 4);
-      const u32 cap = std::min<u64>(std::max<u64>(ctx->runCap, std::max<u64>(guess, 1)), (u64)nWords * 64);
-      HIPCHECK(ctx->swStart.ensure((size_t)cap * 4 + 16));
-      HIPCHECK(ctx->swEnd.ensure((size_t)cap * 4 + 16));
+      // arrays for `cap` runs, and the look-back granules of the three one-pass compactions (generation-tagged: never
+      // cleared between calls)
+      const u32 cap = sweep_run_cap(ctx, nWords);
+      if (int rc__ = sweep_run_arrays(ctx, cap, wChunks)) return rc__;
       HIPCHECK(ctx->headPos.ensure((size_t)cap * 4 + 16));
       HIPCHECK(ctx->cand.ensure((size_t)cap * sizeof(gx_peak)));
       HIPCHECK(ctx->valid.ensure((size_t)cap * 4 + 16));
@@ -75,12 +68,14 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
           HIPCHECK(hipMemsetAsync(ctx->lbSweep2.p, 0, ctx->lbSweep2.cap, s));
         }
       }
-      if (++ctx->sweepGen >= (1u << 24)) {  // (the generation field wraps: start over with clean arrays)
-        ctx->sweepGen = 1;
-        HIPCHECK(hipMemsetAsync(ctx->lbSweep.p, 0, ctx->lbSweep.cap, s));
-        HIPCHECK(hipMemsetAsync(ctx->lbSweep2.p, 0, ctx->lbSweep2.cap, s));
-      }
-      const u32 gen = ctx->sweepGen;
+      // (the speculative run pass is this sweep's: same capacity, same words, nothing rebuilt or rewritten since -- its runs,
+      // its counts and its generation number stand, and k_runs is not launched)
+      const bool specRuns = attempt == 0 && spec.valid && S.specOk && S.V && !S.qLut && spec.cap == cap && spec.nWords == nWords &&
+                            spec.stride == S.mStride && spec.gen == ctx->sweepGen;
+      u32 gen = spec.gen;
+      if (!specRuns)
+        if (int rc__ = sweep_next_gen(ctx, &gen)) return rc__;
+      ctx->overlapUsed = specRuns;
       u64* lbS = ctx->lbSweep.as<u64>();
       u64* lbE = lbS + wChunks + 8;
       u64* lbC = ctx->lbSweep2.as<u64>();
@@ -88,10 +83,16 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
       u32* runStart = ctx->swStart.as<u32>();
       u32* runEnd = ctx->swEnd.as<u32>();
       const u64* skipM = S.hasSkip ? SM.skip : (const u64*)nullptr;
-      const u32 gridP = (u32)std::max(1, ctx->resSweep);
+      const u32 gridP = sweep_grid(ctx, ctx->resSweep);
       // runs: count, place and write in one pass; the true count goes to the host, at most `cap` to the kernels
-      hipLaunchKernelGGL(k_runs, dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, lbS, lbE, gen, runStart, runEnd, cap,
-                         misc + M_SWCOUNT, &dm->R, misc + M_TICKET3, reinterpret_cast<u64*>(misc + M_PEAKBP), ctx->dStatus.as<u32>());
+      // (on the loose slots the chromosomes' starts come from the tile stage's table, as in the speculative pass)
+      if (specRuns) {
+      } else if (S.V)
+        hipLaunchKernelGGL(k_runs<true>, dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, chrom_starts(ctx), lbS, lbE, gen,
+                           runs_out(ctx, cap), ctx->dStatus.as<u32>());
+      else
+        hipLaunchKernelGGL(k_runs<false>, dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, ChromStarts{}, lbS, lbE, gen,
+                           runs_out(ctx, cap), ctx->dStatus.as<u32>());
       // candidates (chunks beyond the device-side run count leave at once)
       hipLaunchKernelGGL(k_cands, dim3(std::min<u32>(rChunks, gridP)), dim3(SW_NT), 0, s, SM, skipM, S.end, runStart, runEnd,
                          misc + M_SWCOUNT, ctx->par.max_gap, S.chromOff, nChrom, lbC, gen, ctx->headPos.as<u32>(), misc + M_NHEADS,

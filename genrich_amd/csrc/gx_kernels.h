@@ -1220,7 +1220,8 @@ struct IvScanOut {
 __device__ __forceinline__ void scan_iv_body(const u32* __restrict__ tileCount, const u32* __restrict__ tileLastEnd,
                                              const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms,
                                              u32 nTiles, u64* __restrict__ lbSum, u64* __restrict__ lbMax,
-                                             const IvScanOut& out, u32* __restrict__ st) {
+                                             const IvScanOut& out, u32* __restrict__ st, u32 wg, u32 nWg) {
+  // (wg of nWg: the workgroup's place among the scan's -- the launch's own, or its scan half: k_scan_iv_close_runs)
   __shared__ u32 scratch[8];
   __shared__ u64 s64[8];
   __shared__ u64 s_sum, s_max;
@@ -1228,7 +1229,7 @@ __device__ __forceinline__ void scan_iv_body(const u32* __restrict__ tileCount, 
   const bool slowFrag = out.ff->slow != 0;
   const bool firstTerms = slowFrag && out.fragAcc != nullptr;
   long long fhi = 0, flo = 0;
-  for (u32 id = blockIdx.x; id < nChunks; id += gridDim.x) {
+  for (u32 id = wg; id < nChunks; id += nWg) {
     const u32 tb = id * STL_CHUNK + threadIdx.x * STL_ITEMS;
     u32 c[STL_ITEMS];
     u64 key[STL_ITEMS];
@@ -1351,7 +1352,7 @@ __global__ __launch_bounds__(STL_NT) void k_scan_iv(const u32* __restrict__ tile
                                                     const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms,
                                                     u32 nTiles, u64* __restrict__ lbSum, u64* __restrict__ lbMax,
                                                     IvScanOut out, u32* __restrict__ st) {
-  scan_iv_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st);
+  scan_iv_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st, blockIdx.x, gridDim.x);
 }
 
 // One wavefront per tile walks the tile's loose slots (read only).  Closed form: the deep tiles of the list,
@@ -1708,23 +1709,29 @@ struct CloseArgs {
   u32 seq;
   u32* ticket;   // zero before the launch; left at zero
 };
-__global__ __launch_bounds__(STL_NT) void k_scan_iv_close(const u32* __restrict__ tileCount, const u32* __restrict__ tileLastEnd,
-                                                          const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms,
-                                                          u32 nTiles, u64* __restrict__ lbSum, u64* __restrict__ lbMax,
-                                                          IvScanOut out, u32* __restrict__ st, CloseArgs C) {
+__device__ __forceinline__ void scan_close_body(const u32* __restrict__ tileCount, const u32* __restrict__ tileLastEnd,
+                                                const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms, u32 nTiles,
+                                                u64* __restrict__ lbSum, u64* __restrict__ lbMax, const IvScanOut& out,
+                                                u32* __restrict__ st, const CloseArgs& C, u32 wg, u32 nWg) {
   __shared__ u32 s_last;
-  scan_iv_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st);
+  scan_iv_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st, wg, nWg);
   // (what the closing workgroup reads of the others: the interval count and the chromosomes' offsets -- agent-scope
   // stores -- and words only ever touched by atomics: fragLen's correction, the list count, LooseCtl::bad, the status)
   stores_done();
   __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(C.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+  if (threadIdx.x == 0) s_last = atomicAdd(C.ticket, 1u) == nWg - 1 ? 1u : 0u;
   __syncthreads();
   if (s_last) {  // block-uniform
     if (threadIdx.x == 0) *C.ticket = 0;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     close_body(C.sel, C.nIv, C.extra, C.rb, C.m, C.closeState, C.seq);
   }
+}
+__global__ __launch_bounds__(STL_NT) void k_scan_iv_close(const u32* __restrict__ tileCount, const u32* __restrict__ tileLastEnd,
+                                                          const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms,
+                                                          u32 nTiles, u64* __restrict__ lbSum, u64* __restrict__ lbMax,
+                                                          IvScanOut out, u32* __restrict__ st, CloseArgs C) {
+  scan_close_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st, C, blockIdx.x, gridDim.x);
 }
 
 }  // namespace gx

@@ -1250,6 +1250,15 @@ __device__ __forceinline__ void run_bits(const SweepMasks& M, u32 w, u64* starts
   *ends = sg & (~((sg >> 1) | (nextBit << 63)) | ((bk >> 1) | (nextBrk << 63)));
 }
 
+// ... with the word's chromosome starts, and the first bit of the next word's, handed in (ChromStarts)
+__device__ __forceinline__ void run_bits_brk(const SweepMasks& M, u32 w, u64 bk, u64 nextBrk, u64* starts, u64* ends) {
+  const u64 sg = M.sig[w];
+  const u64 prevBit = w ? M.sig[w - 1] >> 63 : 0ull;
+  const u64 nextBit = w + 1 < M.nWords ? M.sig[w + 1] & 1ull : 0ull;
+  *starts = sg & (~((sg << 1) | prevBit) | bk);
+  *ends = sg & (~((sg >> 1) | (nextBit << 63)) | ((bk >> 1) | (nextBrk << 63)));
+}
+
 // any bit of mask set in the interval-index range [lo, hi) ?
 __device__ __forceinline__ bool any_bit(const u64* __restrict__ mask, u32 lo, u32 hi) {
   if (lo >= hi) return false;
@@ -1660,23 +1669,74 @@ __device__ __forceinline__ u64 lookback_gen(u64* lb, u32 id, u64 aggregate, u32 
   return excl;
 }
 
+// The sweep on the loose slots: the chromosomes' first slots are tileSlot[first tile of the chromosome] -- what the
+// sample's closing also writes into SM.brk (close_body, frag_select_body), but known as soon as the tile stage has
+// run, so the run pass does not have to wait for the closing (k_scan_iv_close_runs).  chroms == nullptr: SM.brk.
+struct ChromStarts {
+  const DChrom* chroms = nullptr;
+  const u32* tileSlot = nullptr;
+  u32 nChrom = 0;
+};
+constexpr u32 RUN_NCH = 1024;   // chromosome starts a workgroup keeps in LDS (more: read where they lie, chunk by chunk)
+
+struct RunsOut {
+  u32* runStart;
+  u32* runEnd;
+  u32 cap;
+  u32* nRuns;       // min(total, cap)
+  u32* nRunsHost;   // total
+  u32* zeroMe;
+  u64* zeroBp;
+};
+
 // runs of adjacent significant intervals: starts and ends, counted, placed and written in one pass
-__global__ __launch_bounds__(SW_NT) void k_runs(SweepMasks M, u64* __restrict__ lbS, u64* __restrict__ lbE, u32 gen,
-                                                u32* __restrict__ runStart, u32* __restrict__ runEnd, u32 cap,
-                                                u32* __restrict__ nRuns /* min(total, cap) */, u32* __restrict__ nRunsHost /* total */,
-                                                u32* __restrict__ zeroMe, u64* __restrict__ zeroBp, u32* __restrict__ st) {
+// (wg of nWg: the workgroup's place among the run pass's -- the launch's own, or its run half: k_scan_iv_close_runs)
+template <bool TABLE>
+__device__ __forceinline__ void runs_body(const SweepMasks& M, const ChromStarts& CS, u64* __restrict__ lbS, u64* __restrict__ lbE,
+                                          u32 gen, const RunsOut& O, u32* __restrict__ st, u32 wg, u32 nWg) {
+  u32* __restrict__ runStart = O.runStart;
+  u32* __restrict__ runEnd = O.runEnd;
+  const u32 cap = O.cap;
   __shared__ u32 scratch[8];
   __shared__ u64 s_base[2];
+  // TABLE: the chunk's words of the chromosome-start mask, and the one behind them, made in LDS from the table
+  __shared__ u64 s_brk[TABLE ? SW_CHUNK + 1 : 1];
+  __shared__ u32 s_cstart[TABLE ? RUN_NCH : 1];
   const u32 nChunks = (M.nWords + SW_CHUNK - 1) / SW_CHUNK;
-  for (u32 id = blockIdx.x; id < nChunks; id += gridDim.x) {
+  const bool cached = TABLE && CS.nChrom <= RUN_NCH;
+  auto chrom_start = [&](u32 c) {  // ~0: the chromosome has no tile
+    const u32 tb = CS.chroms[c].tileBase;
+    return tb != NULL_TILE ? CS.tileSlot[tb] : ~0u;
+  };
+  if (cached && wg < nChunks) {
+    for (u32 c = threadIdx.x; c < CS.nChrom; c += SW_NT) s_cstart[c] = chrom_start(c);
+    // (the first chunk's barrier below orders these stores ahead of their readers)
+  }
+  for (u32 id = wg; id < nChunks; id += nWg) {
     const u32 w0 = id * SW_CHUNK + threadIdx.x * SW_ITEMS;
+    if (TABLE) {
+      for (u32 i = threadIdx.x; i < SW_CHUNK + 1; i += SW_NT) s_brk[i] = 0;
+      __syncthreads();
+      const u64 lo = (u64)id * SW_CHUNK * 64, hi = lo + (u64)(SW_CHUNK + 1) * 64;
+      for (u32 c = threadIdx.x; c < CS.nChrom; c += SW_NT) {
+        const u32 a = cached ? s_cstart[c] : chrom_start(c);
+        if (a != ~0u && a >= lo && a < hi) atomicOr((unsigned long long*)&s_brk[(a >> 6) - id * SW_CHUNK], 1ull << (a & 63));
+      }
+      __syncthreads();
+    }
     u64 stb[SW_ITEMS], enb[SW_ITEMS];
     u32 a = 0, b = 0;
 #pragma unroll
     for (int k = 0; k < SW_ITEMS; k++) {
       stb[k] = 0;
       enb[k] = 0;
-      if (w0 + k < M.nWords) run_bits(M, w0 + k, &stb[k], &enb[k]);
+      if (w0 + k < M.nWords) {
+        if (TABLE) {
+          const u32 l = threadIdx.x * SW_ITEMS + k;
+          run_bits_brk(M, w0 + k, s_brk[l], w0 + k + 1 < M.nWords ? s_brk[l + 1] & 1ull : 0ull, &stb[k], &enb[k]);
+        } else
+          run_bits(M, w0 + k, &stb[k], &enb[k]);
+      }
       a += __popcll(stb[k]);
       b += __popcll(enb[k]);
     }
@@ -1691,10 +1751,10 @@ __global__ __launch_bounds__(SW_NT) void k_runs(SweepMasks M, u64* __restrict__ 
         s_base[0] = ea;
         if (id == nChunks - 1) {
           const u32 total = (u32)ea + totA;
-          *nRuns = total > cap ? cap : total;
-          *nRunsHost = total;
-          *zeroMe = 0;
-          *zeroBp = 0;   // (k_peaks' sum of the peaks' lengths)
+          *O.nRuns = total > cap ? cap : total;
+          *O.nRunsHost = total;
+          *O.zeroMe = 0;
+          *O.zeroBp = 0;   // (k_peaks' sum of the peaks' lengths)
         }
       }
     }
@@ -1737,6 +1797,38 @@ __global__ __launch_bounds__(SW_NT) void k_runs(SweepMasks M, u64* __restrict__ 
     }
     __syncthreads();
   }
+}
+
+template <bool TABLE>
+__global__ __launch_bounds__(SW_NT) void k_runs(SweepMasks M, ChromStarts CS, u64* __restrict__ lbS, u64* __restrict__ lbE, u32 gen,
+                                                RunsOut O, u32* __restrict__ st) {
+  runs_body<TABLE>(M, CS, lbS, lbE, gen, O, st, blockIdx.x, gridDim.x);
+}
+
+// k_scan_iv_close and the sweep's run pass in ONE launch, side by side: the first nScan workgroups are the scan's (and
+// the last of THEM closes the sample), the ones behind them are k_runs<true>'s.  The run pass reads what the tile stage
+// wrote -- the significance words, tileSlot[] -- and nothing of the scan's or the closing's; the halves share no
+// look-back array and no counter, and neither waits for the other.  Both are persistent (each look-back relies on its
+// own half being resident): nScan + nRun <= what the device keeps resident of THIS kernel.
+struct RunHalf {
+  SweepMasks M;
+  ChromStarts CS;
+  u64* lbS;
+  u64* lbE;
+  u32 gen;
+  RunsOut O;
+  u32 nScan;
+};
+__global__ __launch_bounds__(STL_NT) void k_scan_iv_close_runs(const u32* __restrict__ tileCount, const u32* __restrict__ tileLastEnd,
+                                                               const u32* __restrict__ tileChrom, const DChrom* __restrict__ chroms,
+                                                               u32 nTiles, u64* __restrict__ lbSum, u64* __restrict__ lbMax,
+                                                               IvScanOut out, u32* __restrict__ st, CloseArgs C, RunHalf R) {
+  static_assert(STL_NT == SW_NT, "one workgroup size for both halves");
+  // (the run pass's workgroups first in the grid, or fewer of them -- one or two per CU --, measured: the launch is as long)
+  if (blockIdx.x < R.nScan)  // block-uniform
+    scan_close_body(tileCount, tileLastEnd, tileChrom, chroms, nTiles, lbSum, lbMax, out, st, C, blockIdx.x, R.nScan);
+  else
+    runs_body<true>(R.M, R.CS, R.lbS, R.lbE, R.gen, R.O, st, blockIdx.x - R.nScan, gridDim.x - R.nScan);
 }
 
 // candidates: the runs that open one (run_is_head), counted, placed and listed in one pass

@@ -163,6 +163,7 @@ GX_SAT_CONTROLS = 1             # gx_saturation: the controls are subsampled at 
 GX_ERR_EXPT = -3                # a point of gx_saturation whose subsample left no analyzable fragment
 SAT_POINT_DTYPE = np.dtype([("threshold", "<u8"), ("n_total", "<u8"), ("n_kept", "<u8"), ("n_peaks", "<u8"), ("peak_bp", "<u8"),
                             ("genome_len", "<u8"), ("status", "<i4"), ("_pad", "<i4")])   # gx_sat_point
+GX_PATH_SWEEP_OVERLAP = 536870912   # gx_path_info bit 29: the loose-slot sweep's run pass rode in the launch that closed the sample (k_scan_iv_close_runs): no k_runs launch
 GX_PATH_SPLIT = 268435456       # gx_path_info bit 28: k_sub_split ran (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility)
 GX_REPRO_ALONE, GX_REPRO_SELF, GX_REPRO_POOLED = 0, 1, 2          # gx_repro_call.kind
 REPRO_VERDICTS = ("pass", "borderline", "fail", "NA")              # GX_REPRO_PASS .. GX_REPRO_NA
@@ -1485,7 +1486,8 @@ class Genrich:
         events read in place, 1024 the control merge scored its intervals, 2048 BH's histogram from the pileup sums, 8192 q looked up
         where it is read, 16384 the loose slots swept with bits written late, 32768 -q on the loose slots, 65536 intervals kept for counting, 131072 counted in a region set,
         262144 pileups summed over coverage bins, 524288 pileups summed around anchors, 1048576 the Gram kernels ran,
-        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 268435456 the split kernel ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran, 134217728 the cross-correlation kernels ran)."""
+        2097152 the fingerprint kernel ran, 4194304 the rank kernel ran, 8388608 the complexity kernels ran, 16777216 the subsample kernels ran, 268435456 the split kernel ran, 33554432 the depth kernel ran, 67108864 the interval-length kernel ran, 134217728 the cross-correlation kernels ran,
+        536870912 the sweep's run pass ran beside the sample's closing scan)."""
         f = C.c_uint(0)
         self._check(self.lib.gx_path_info(self.ctx, C.byref(f)))
         return f.value

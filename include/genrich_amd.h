@@ -1260,6 +1260,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_IVSTAT 67108864u /* bit 26: k_ivstat ran since the last gx_reset (gx_interval_stats, gx_interval_stats_events) */
 #define GX_PATH_XCOR 134217728u /* bit 27: k_xc_set / k_xc_corr ran since the last gx_reset (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags) */
 #define GX_PATH_SPLIT 268435456u /* bit 28: k_sub_split ran since the last gx_reset (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility) */
+#define GX_PATH_SWEEP_OVERLAP 536870912u /* bit 29: ... GX_PATH_LOOSE_SWEEP whose run pass rode in the launch that scanned the tiles and closed the sample (k_scan_iv_close_runs), ahead of gx_find_peaks: the sweep launched no k_runs */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
