@@ -7,6 +7,7 @@
 #include "gx_host_build.h"
 #include "gx_host_sweep.h"
 #include "gx_host_stats.h"
+#include "gx_host_call.h"
 #include "gx_sparse.h"
 #include "gx_host_kept.h"
 #include "gx_host_count.h"
@@ -326,7 +327,6 @@ int gx_reset(gx_ctx* ctx) {
     recycle(ctx, pa.chromLooseOff); recycle(ctx, pa.keptV); recycle(ctx, pa.keptMeta);
   }
   ctx->reps.clear();
-  ctx->denseHistIdx = -1;
   ctx->pilesMade = false;
   ctx->sample = 0;
   ctx->phase = 0;
@@ -352,7 +352,7 @@ int gx_reset(gx_ctx* ctx) {
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
   ctx->specRuns.valid = false;
-  ctx->overlapUsed = false;
+  ctx->called.ran.overlap = false;
   if (ctx->statusSeen) {  // (a clean run leaves the status words at zero: no fill launch)
     HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 64, ctx->stream));
     ctx->statusSeen = 0;
@@ -648,7 +648,7 @@ int gx_pvalues(gx_ctx* ctx) {
     pa.ctrlConst = ctx->hScal.lambda;
     pa.loose = true;
     // (the tile stage wrote the sweep's significance bits, in loose-slot index space: LooseCtl)
-    pa.looseSweep = ctx->looseOk && (!ctx->par.qval_opt || ctx->built.wantLate) && !ctx->knob.noLoose;   // (-q: gx_find_peaks' qLoose)
+    pa.looseSweep = ctx->looseOk && (!ctx->par.qval_opt || (q_loose_may(ctx) && ctx->built.wantLate)) && !ctx->knob.noLoose;   // (-q: plan_call's LOOSE_Q)
     pa.latePending = pa.looseSweep && ctx->built.wantLate;   // (its bits are still to be written: k_loose_late, by gx_find_peaks)
     pa.looseStride = ctx->looseStride;
     if (pa.looseSweep) pa.chromLooseOff = std::move(ctx->chromLooseOff);
@@ -670,116 +670,32 @@ int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* 
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
   ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
-  hipStream_t s = ctx->stream;
-  u32* misc = ctx->misc.as<u32>();
-  // One replicate without a control, -p, and the tile stage left the sweep's bits on the loose slots (LooseCtl): the
-  // sweep walks them where they are -- no tight interval table is made unless somebody asks for it later
-  const bool looseFast = ctx->sample == 1 && ctx->reps.size() == 1 && ctx->reps[0].loose && ctx->reps[0].looseSweep &&
-                         !ctx->par.qval_opt;
-  // (one replicate, no control, unit weights, -q, one rank: the tight table's kernel sums "bp at pileup V" on its way -- BH's table
-  // of distinct p-values is made of those sums, not of a hash insertion per interval)
-  const bool packHist = ctx->par.qval_opt && ctx->sample == 1 && ctx->reps.size() == 1 && ctx->reps[0].ctrlIsConst && !ctx->sawFrac &&
-                        ctx->world <= 1 && !ctx->forceColl && !ctx->knob.noPackHist;
-  // (round 6) ... and with -q as well, where q is a function of the pileup like p: BH's histogram is summed from the loose slots, q
-  // tabulated by whole pileup (k_bh_small), the bits written from "q passes from this pileup on", the sweep as with -p -- no tight table
-  const bool qLoose = packHist && ctx->reps[0].loose && ctx->reps[0].looseSweep && (ctx->reps[0].latePending || ctx->reps[0].lateLoose) &&
-                      !ctx->knob.noQLoose && !ctx->qLooseBad && !ctx->hasBed;
-  ctx->qLooseUsed = false;
-  for (size_t r = 0; r < ctx->reps.size(); r++) {
-    if (ctx->reps[r].loose && !looseFast && !qLoose)
-      if (int rc = materialize_rep(ctx, (int)r, packHist)) return rc;
-    // (the Fisher combination of several replicates reuses the loose slots: the last replicate keeps what its pileup
-    // floats, if somebody asks for them, are made of)
-    if (ctx->sample > 1 && ctx->reps[r].pilesPending)
-      if (int rc = keep_loose_for_piles(ctx, (int)r)) return rc;
-  }
-  if (ctx->sample > 1 && (int)ctx->reps.size() == ctx->sample) {
-    if (int rc = combine_replicates(ctx)) return rc;
-  }
-  ctx->finalIdx = (int)ctx->reps.size() - 1;
-  PArray& fa = ctx->reps[ctx->finalIdx];
-  const u32 n = fa.n, nChrom = ctx->nChrom;
-  // genome length (findPeaks 1091-1101)
-  uint64_t g = ctx->par.genome_len;
-  const bool genomeOpt = g == 0;
-  if (genomeOpt) g = genome_len_for(ctx, fa.present);
-  ctx->genomeLenUsed = g;
-  ctx->mail->genome = g;
-  ctx->mail->n = n;
-  // genome length and interval count for the kernels that read them through pointers (BH, k_sig_mask): one tiny
-  // kernel instead of two copy launches, and none at all when the masks came with the p-values
-  const bool masksReady = looseFast || (ctx->maskIdx == ctx->finalIdx && ctx->maskN == n);
-  if (ctx->par.qval_opt || !masksReady)
-    hipLaunchKernelGGL(k_set_misc, dim3(1), dim3(1), 0, s, misc, (u32)M_NIV, (u32)M_GENOME, (u64)g, n);
-
-  ctx->lazyQUsed = false;
-  if (qLoose) {
-    if (int rc = loose_hist(ctx, fa, genomeOpt)) return rc;
-  } else if (ctx->par.qval_opt) {
-    if (int rc = bh_qvalues(ctx, fa, n, genomeOpt)) return rc;
-  }
-
-  // peak sweep
-  phase_begin(ctx, "sweep");
-  SweepSrc src{};
-  src.nChrom = nChrom;
-  if (qLoose || looseFast) {
-    // the sweep walks the loose slots; their bits are written now if lambda -- or, with -q, "q passes from this pileup on"
-    // (k_bh_small, above) -- came after the tile stage
-    ctx->lateLooseUsed = qLoose || fa.lateLoose || fa.latePending;
-    ctx->qLooseUsed = qLoose;
-    if (qLoose) HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, fa.looseStride * 8, s));   // (the significance words: a run before may have left its own)
-    if (qLoose || fa.latePending) {
-      hipLaunchKernelGGL(k_loose_late, dim3(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(8 * ctx->numCU)))), dim3(256), 0, s,
-                         ctx->tileSlot.as<u32>(), ctx->tileIvCount.as<u32>(), ctx->tileLastEnd.as<u32>(), ctx->nTiles,
-                         ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->looseCtl.as<LooseCtl>(), ctx->swMask.as<u64>(),
-                         qLoose ? (const u32*)(misc + M_VQ) : (const u32*)nullptr, qLoose ? ctx->dStatus.as<u32>() : (u32*)nullptr);
-      fa.latePending = false;
-      fa.lateLoose = true;
-    }
-    src.end = ctx->looseEnd.as<u32>();
-    src.V = ctx->looseV.as<int>();
-    src.p = ctx->pvLut.as<float>();
-    if (qLoose) src.qLut = ctx->qLut.as<float>();
-    src.chromOff = fa.chromLooseOff.as<u32>();
-    src.mStride = fa.looseStride;
-    src.nWords = (u32)(fa.looseStride - 2);
-    src.haveMasks = true;
-    src.hasSkip = false;
-    src.specOk = looseFast && !ctx->lateLooseUsed;   // (the run pass that rode in the scan's launch saw these very bits)
-  } else {
-    src.end = fa.end.as<u32>();
-    src.p = fa.p.as<float>();
-    src.q = ctx->par.qval_opt ? fa.q.as<float>() : (const float*)nullptr;
-    if (ctx->par.qval_opt && fa.qLazy) {
-      src.kq = ctx->bhKQ.as<u64>();
-      src.kqMask = ctx->bhLiveCap - 1;
-    }
-    src.chromOff = fa.chromOff.as<u32>();
-    src.nWords = (n + 63) / 64;
-    // the masks were filled by the pack kernels (p mode, one replicate) or by k_qlookup (q mode)
-    src.haveMasks = ctx->maskIdx == ctx->finalIdx && ctx->maskN == n;
-    src.mStride = src.haveMasks ? ctx->maskStride : (size_t)src.nWords + 2;
-    src.hasSkip = true;
-    HIPCHECK(ctx->swMask.ensure(src.mStride * 8 * 3));
-    // (whoever filled the sig / skip masks zeroed all three: the chromosome-start mask is still clear)
-    if (!src.haveMasks) HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, src.mStride * 8 * 3, s));
-  }
-  ctx->maskIdx = -1;
-  ctx->looseSwept = looseFast || qLoose;
+  const CallPlan& P = ctx->called;
   u32 nPeaks = 0;
-  const int rcSweep = run_sweep(ctx, src, &nPeaks);
-  phase_end(ctx);
-  if (qLoose && (ctx->mail->status & ST_Q_LOOSE)) {
-    // q turned out to be no threshold on the pileup (a table p(V) that is not monotone): once more, on the tight table -- and from now on
-    HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 4, s));
-    ctx->qLooseBad = true;
-    return gx_find_peaks(ctx, n_peaks, genome_len, peak_bp);
+  // (at most two plans: -q on the loose slots may be called off by the device, and the call is then planned again without it)
+  for (int attempt = 0;; attempt++) {
+    if (int rc = plan_call(ctx)) return rc;
+    if (int rc = call_tables(ctx, P)) return rc;
+    call_scalars(ctx, P);
+    if (int rc = call_bh(ctx, P)) return rc;
+    phase_begin(ctx, "sweep");
+    SweepSrc src;
+    if (int rc = call_sweep_source(ctx, P, src)) return rc;
+    bool synced = false;
+    const int rcSweep = run_sweep(ctx, src, &nPeaks, &synced);
+    phase_end(ctx);
+    if (attempt == 0 && P.walk == CallPlan::LOOSE_Q && synced && (ctx->mail->status & ST_Q_LOOSE)) {
+      // q turned out to be no threshold on the pileup (a table p(V) that is not monotone): once more, on the tight table -- and from now on
+      HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 4, ctx->stream));
+      ctx->qLooseBad = true;
+      continue;
+    }
+    if (rcSweep) return rcSweep;
+    break;
   }
-  if (rcSweep) return rcSweep;
   ctx->peaksReady = true;
   if (n_peaks) *n_peaks = nPeaks;
-  if (genome_len) *genome_len = g;
+  if (genome_len) *genome_len = P.g;
   if (peak_bp) *peak_bp = ctx->peakBP;
   return GX_OK;
 }
@@ -944,15 +860,20 @@ int gx_rccl_nranks(gx_ctx* ctx, int* n) {
 
 int gx_path_info(gx_ctx* ctx, unsigned* flags) {
   if (!ctx || !flags) return GX_ERR_ORDER;
-  *flags = (ctx->built.fused ? GX_PATH_FUSED : 0u) | (ctx->built.fused && ctx->built.pairs ? GX_PATH_PAIRS : 0u) | (ctx->denseBhUsed ? GX_PATH_DENSE_BH : 0u) | (ctx->rangeBhUsed ? GX_PATH_RANGE_BH : 0u) | (ctx->looseSwept ? GX_PATH_LOOSE_SWEEP : 0u) |
+  // the calling half's bits from the last call's plan and what its run told; the build half's from the last build's plan
+  const CallPlan& C = ctx->called;
+  const bool dense = C.exchange == CallPlan::X_DENSE && !C.ran.denseFellBack;
+  const bool range = C.exchange == CallPlan::X_RANGE || (C.exchange == CallPlan::X_DENSE && C.ran.denseFellBack);
+  const bool packHist = C.bh == CallPlan::BH_SMALL || (C.bh == CallPlan::BH_FROM_DENSE && !C.ran.tableGrew);
+  *flags = (ctx->built.fused ? GX_PATH_FUSED : 0u) | (ctx->built.fused && ctx->built.pairs ? GX_PATH_PAIRS : 0u) | (dense ? GX_PATH_DENSE_BH : 0u) | (range ? GX_PATH_RANGE_BH : 0u) | (C.looseSwept() ? GX_PATH_LOOSE_SWEEP : 0u) |
            (ctx->fellBack ? GX_PATH_FELL_BACK : 0u) | (ctx->ptGrew ? GX_PATH_PT_GREW : 0u) | (ctx->built.fused && ctx->built.fracPairs ? GX_PATH_FRAC_PAIRS : 0u) |
            (ctx->pilesMade ? GX_PATH_PILES_MADE : 0u) | (ctx->packedUsed ? GX_PATH_PACKED : 0u) | (ctx->mergePUsed ? GX_PATH_MERGE_P : 0u) |
-           (ctx->denseHistUsed ? GX_PATH_PACK_HIST : 0u) | (ctx->lazyQUsed ? GX_PATH_LAZY_Q : 0u) | (ctx->looseSwept && ctx->lateLooseUsed ? GX_PATH_LATE_LOOSE : 0u) | (ctx->qLooseUsed ? GX_PATH_Q_LOOSE : 0u) |
+           (packHist ? GX_PATH_PACK_HIST : 0u) | (C.lazyQ ? GX_PATH_LAZY_Q : 0u) | (C.looseSwept() && C.lateBits() ? GX_PATH_LATE_LOOSE : 0u) | (C.walk == CallPlan::LOOSE_Q ? GX_PATH_Q_LOOSE : 0u) |
            (ctx->countOn && !ctx->kept.empty() ? GX_PATH_COUNTS : 0u) | (ctx->regionsReady ? GX_PATH_REGION_COUNTS : 0u) |
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (ctx->looseSwept && ctx->overlapUsed ? GX_PATH_SWEEP_OVERLAP : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
   return GX_OK;
 }
 

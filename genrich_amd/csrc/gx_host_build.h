@@ -37,7 +37,7 @@ int pack_pileup(gx_ctx* ctx, Pileup& P) {
   const u32 nTiles = ctx->nTiles;
   HIPCHECK(pooled(ctx, P.ivV, P.ivEnd.cap));
   PackIn pin{ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->tileMeta.as<TileMeta>(), P.tileIvOff.as<u32>()};
-  hipLaunchKernelGGL(k_pack, dim3(std::max(1u, std::min((nTiles + 3) / 4, (u32)(8 * ctx->numCU)))), dim3(256), 0, s, pin, nTiles,
+  hipLaunchKernelGGL(k_pack, tile_grid(ctx, 8), dim3(256), 0, s, pin, nTiles,
                      P.ivEnd.as<u32>(), P.ivV.as<int>());
   if (int rc__ = dbg_sync(ctx, "k_pack")) return rc__;
   P.packed = true;
@@ -199,8 +199,7 @@ int plan_build(gx_ctx* ctx, int isCtrl, bool reuseSort) {
   // k_pack_pval's copy of every interval into the tight table.  One rank, a treatment sample, -p, no -E regions, the fused tile stage.
   // (-q as well, where q is a function of the pileup: unit weights, no control to come -- gx_find_peaks' qLoose; a control sample
   // that follows only finds the verdict unused)
-  const bool qLooseMay = ctx->par.qval_opt && !K.noQLoose && !ctx->qLooseBad && !ctx->sawFrac && !ctx->fracHint && !K.noPackHist;
-  P.wantLate = !P.wantEarly && !isCtrl && !P.multiRank && (!ctx->par.qval_opt || qLooseMay) && !ctx->hasBed && unit32 && !noLoose &&
+  P.wantLate = !P.wantEarly && !isCtrl && !P.multiRank && (!ctx->par.qval_opt || (q_loose_may(ctx) && !ctx->fracHint)) && !ctx->hasBed && unit32 && !noLoose &&
                !K.noLateLoose && fused && !forceSlowFrag;
   P.closeInScan = P.wantEarly && !P.multiRank;  // (k_scan_iv_close)
   P.looseCap = (size_t)2 * nEv + nTiles + ctx->nBedEdges + 16;  // slot t: records before + t (+ edges before)

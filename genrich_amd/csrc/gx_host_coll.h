@@ -230,7 +230,6 @@ int bh_range_exchange(gx_ctx* ctx, const BhTable& T, u32 Dlocal, u32 capLocal) {
     hipLaunchKernelGGL(k_bhx_scatter, dim3(std::max(1u, std::min((Dlocal + 255) / 256, 1024u))), dim3(256), 0, s, (const u32*)ctx->bhSortSlot.as<u32>(),
                        (const float*)ansIn, Dlocal, ctx->bhQ.as<float>());
   (void)T;
-  ctx->rangeBhUsed = true;
   return GX_OK;
 }
 

@@ -240,6 +240,44 @@ struct BuildPlan {
   u32 tChunks = 0;
   bool masks() const { return wantEarly || wantLate; }   // the sweep's masks are the loose slots'
 };
+// Every decision of one gx_find_peaks, made once (plan_call, gx_host_call.h) before anything is sized, cleared or launched;
+// the stages read it and nothing else decides.  The context keeps the last one (`called`), with what only the run could
+// tell (`ran`): gx_path_info reports the calling half's bits from it.
+struct CallPlan {
+  enum Walk { TIGHT, LOOSE_P, LOOSE_Q };             // what the sweep walks: the final array's tight table, or the loose slots
+  enum Bh { BH_NONE, BH_SMALL, BH_FROM_DENSE, BH_FROM_HIST };   // BH's table: none (-p); loose_hist + k_bh_small; from the "bp at V"
+                                                     // sums k_pack_pval<.., HIST> left; by k_bh_hist from the tight table
+  enum Exchange { X_NONE, X_DENSE, X_RANGE };        // the ranks' exchange of that table, as intended (X_DENSE may fall back: ran)
+  enum Masks { MASKS_TILE, MASKS_PACK, MASKS_BH, MASKS_SIG };   // who fills the sweep's masks: the tile stage (/ k_loose_late), the
+                                                     // pack kernel that wrote the tight table, BH, or the sweep's own k_sig_mask
+  Walk walk = TIGHT;
+  bool lateWrite = false;   // the loose slots' bits are still to be written (k_loose_late; LOOSE_Q: from "q passes from this pileup on")
+  bool lateBefore = false;  // ... were written behind the tile stage by a call before this one
+  bool packHist = false;    // the tight table's kernel sums BH's histogram on its way (k_pack_pval<.., HIST>)
+  u64 materialise = 0;      // reps[] entries (a bit each) whose tight table is made now
+  bool keepLoose = false;   // those whose pileup floats are pending keep what they are made of: the loose slots are about to be reused
+  bool combine = false;     // Fisher's method over the replicates (combine_replicates)
+  int finalIdx = -1;        // reps[] entry the peaks are called on
+  bool genomeOpt = false;   // the genome length is computed (no -L): BH's lengths must add up to it
+  u64 g = 0;
+  bool setMisc = false;     // k_set_misc: genome length and interval count for the kernels that read them through pointers
+  Bh bh = BH_NONE;
+  Exchange exchange = X_NONE;
+  int bhInst = 0;           // row of BH_INSTANCES (GX_BH_VARIANT, or the default)
+  bool lazyQ = false;       // q inside the candidates only (k_sig_from_p / k_q_fill_cands), the whole array on request
+  bool qtMulti = false;     // the chunked q-table kernels whatever the table's size (GX_QT_MULTI)
+  Masks masks = MASKS_SIG;
+  bool specOk = false;      // the run pass that rode in the scan's launch saw the very bits this sweep walks
+  bool qLooseBad = false;   // the second plan of a call: LOOSE_Q was called off (ST_Q_LOOSE)
+  struct Ran {
+    bool denseFellBack = false;  // a rank's region of the dense exchange overflowed: the range exchange ran instead
+    bool tableGrew = false;      // BH's table was full (ST_HASH_FULL) and made again, larger, by k_bh_hist
+    bool overlap = false;        // the sweep took the speculative run pass
+    bool lateWritten = false;    // k_loose_late ran
+  } ran;
+  bool looseSwept() const { return walk != TIGHT; }
+  bool lateBits() const { return lateBefore || ran.lateWritten; }
+};
 struct KnobDef { const char* name; int Knobs::*i; long long Knobs::*ll; };
 const KnobDef KNOBS[] = {
     {"GX_DEBUG", &Knobs::debug, nullptr}, {"GX_DEBUG_RETRY", &Knobs::debugRetry, nullptr}, {"GX_NO_SPIN", &Knobs::noSpin, nullptr},
@@ -330,13 +368,11 @@ struct gx_ctx {
                                 // k_sbtile<.., true>); on unit-weight data they give what the unit-weight instances give
   bool fusedOff = false;        // this sample: a super-bucket did not fit k_sbtile (the general chain runs instead)
   BuildPlan built;              // the last build's plan
+  CallPlan called;              // the last gx_find_peaks' plan, and what its run told
   bool earlyOwed = false;       // built.earlyColl, and this rank has not taken part in that all-reduce yet (poison_allreduce)
   bool earlyPending = false;
   int fusedBackoff[2] = {0, 0}; // treatment / control samples for which k_sbtile is not tried (after one that did not fit)
-  bool looseSwept = false;      // the last gx_find_peaks swept the loose slots
   bool pilesMade = false;       // pileup floats were written since the last gx_reset (ensure_piles)
-  int denseHistIdx = -1;        // the replicate whose "bp at V" histogram k_pack_pval<.., HIST> left in bhDense (and its deep values in the table)
-  bool denseHistUsed = false;   // ... and the last BH table was made from it
   bool mergePUsed = false;      // the last control merge wrote p-values into its loose slots (k_merge2<.., true>)
   DevBuf lbSweep, lbSweep2;     // look-back granules of the sweep's one-pass compactions (generation-tagged)
   u32 sweepGen = 0;
@@ -371,10 +407,7 @@ struct gx_ctx {
   bool satDone = false;         // this sample's events already went through the saturation filter
   long long satDropped = 0;     // ... which dropped this many of them (gx_saturation_dropped)
   bool qLooseBad = false;       // -q on the loose slots was called off once (ST_Q_LOOSE): this context takes the tight table from now on
-  bool qLooseUsed = false;      // the last gx_find_peaks: -q, the sweep on the loose slots (GX_PATH_Q_LOOSE)
-  DevBuf qLut;                  // ... its q by whole pileup (k_bh_small)
-  bool lateLooseUsed = false;   // ... and the replicate the sweep walked was such a sample (GX_PATH_LATE_LOOSE)
-  bool lazyQUsed = false;       // the last -q run took k_sig_from_p / k_q_fill_cands (GX_PATH_LAZY_Q)
+  DevBuf qLut;                  // -q on the loose slots: q by whole pileup (k_bh_small)
   bool bhLive = false;          // the table of the last -q run is still there, with {key, q} of every value (lazy q: ensure_q)
   u32 bhLiveCap = 0;
   int bhLiveIdx = -1;           // ... and it belongs to reps[bhLiveIdx]
@@ -396,8 +429,6 @@ struct gx_ctx {
   bool forceColl = false;       // GX_FORCE_COLL=1: run the collectives with a single rank too (tests)
   DevBuf bigBins;               // pair mode: the super-buckets k_sbtile's first launch leaves to its second
   DevBuf dColl, dCounts, dGather, bhDense, bhxSmall, bhxRecv, bhxKeys, bhxLens, bhxQ, bhxOut, bhxAns;
-  bool rangeBhUsed = false;     // the last gx_find_peaks took the range-partitioned BH exchange
-  bool denseBhUsed = false;     // the last gx_find_peaks exchanged the p-value histogram as one dense all-reduce
   int phaseLevel = 0;       // gx_set_phase_timing
   std::string phaseFilter = "tile";  // level 1: the one phase that is timed (gx_set_phase_filter)
   u32 mailSeq = 0;          // mail_sync: the sequence number the next k_mail writes
@@ -411,7 +442,6 @@ struct gx_ctx {
     size_t stride = 0;                  // ... and the words between the masks
   } specRuns;
   int buildAttempt = 0;         // close_sample: builds of the sample before this one (a rebuilt sample speculates nothing)
-  bool overlapUsed = false;     // the last gx_find_peaks took the speculative run pass (GX_PATH_SWEEP_OVERLAP)
   int resScanRuns = 0;          // co-resident workgroups of k_scan_iv_close_runs
   bool phaseOpen = false;
   bool roctxOpen = false;       // (GX_ROCTX: the range of the open phase)
@@ -642,6 +672,17 @@ enum { NW_WIDE = 0,        // tiles on wideList (k_tile_meta)
 u32* nw_word(const gx_ctx* ctx, int w) { return ctx->nWide.as<u32>() + w; }
 
 // GX_DEBUG=1: synchronise after every launch and say which kernel it was (hang / fault triage)
+// the grid of a kernel whose wavefronts stride over the tiles, four to a workgroup: at most perCU workgroups per CU
+dim3 tile_grid(const gx_ctx* ctx, int perCU) { return dim3(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(perCU * ctx->numCU)))); }
+
+// -q on the loose slots may be taken at all (one replicate without a control is gx_find_peaks' to see: plan_call): asked by
+// plan_build (the late bits are only wanted for it), gx_pvalues and plan_call.  k_bh_small inserts up to PV_WHOLE keys with an
+// unbounded probe: the table must have room for all of them (GX_BH_CAPLOG may start it smaller; the tight path grows it)
+bool q_loose_may(const gx_ctx* ctx) {
+  return ctx->par.qval_opt && !ctx->knob.noQLoose && !ctx->qLooseBad && !ctx->sawFrac && !ctx->knob.noPackHist &&
+         (1u << ctx->bhCapLog) >= 2u * PV_WHOLE;
+}
+
 int dbg_sync(gx_ctx* ctx, const char* what) {
   if (!ctx->knob.debug) return GX_OK;
   fprintf(stderr, "[gx] %s ...", what);

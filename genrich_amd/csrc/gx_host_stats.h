@@ -48,8 +48,42 @@ BhTable bh_table_of(gx_ctx* ctx, u32 cap) {
                  ctx->misc.as<u32>() + M_BHCOUNT};
 }
 
-// hist: the replicate is the run's only one, without a control, and -q follows (gx_find_peaks knows): its "bp at V" histogram is
-// made on the way (k_pack_pval<.., HIST>), for bh_qvalues
+// The instances of k_pack_pval, each named here and nowhere else (as SBT_INSTANCES): MASKS the sweep's masks on the way (-p),
+// HIST BH's "bp at V" histogram on the way (-q, one replicate without a control), TIGHT = false the histogram alone.
+using PackPvalKernel = decltype(&k_pack_pval<false>);
+struct PackPvalInstance { bool masks, hist, tight; PackPvalKernel fn; };
+const PackPvalInstance PACK_PVAL[] = {{true, false, true, k_pack_pval<true>}, {false, false, true, k_pack_pval<false>},
+                                      {false, true, true, k_pack_pval<false, true>}, {false, true, false, k_pack_pval<false, true, false>}};
+
+// ... and their launch.  hist: the table and the dense array are made ready for the sums first; as many workgroups as the CUs
+// hold at once -- seven, with the histogram's LDS and registers: an eighth would run behind the others
+int launch_pack_pval(gx_ctx* ctx, bool hist, bool tight, const PackIn& pin, u32* ivEnd, float* pOut, u64* sigM, u64* skipM) {
+  hipStream_t s = ctx->stream;
+  const PackPvalInstance* k = nullptr;
+  for (const PackPvalInstance& i : PACK_PVAL)
+    if (i.masks == (sigM != nullptr) && i.hist == hist && i.tight == tight) k = &i;
+  if (!k) {
+    ctx->err = "no k_pack_pval instance <" + std::to_string(sigM != nullptr) + ", " + std::to_string(hist) + ", " + std::to_string(tight) + ">";
+    return GX_ERR_DEVICE;
+  }
+  int perCU = 8;
+  if (hist) {
+    if (int rc = bh_table_prepare(ctx, 1u << ctx->bhCapLog)) return rc;
+    HIPCHECK(hipMemsetAsync(ctx->misc.as<u32>() + M_BHCOUNT, 0, 8, s));
+    HIPCHECK(ctx->bhDense.ensure(bhd_words(1) * 8));
+    HIPCHECK(hipMemsetAsync(ctx->bhDense.p, 0, bhd_words(1) * 8, s));
+    int nbH = 0;
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbH, k->fn, 256, 0));
+    perCU = std::max(1, std::min(nbH, 8));
+  }
+  hipLaunchKernelGGL(k->fn, tile_grid(ctx, perCU), dim3(256), 0, s, pin, ctx->nTiles, (const Scalars*)ctx->dScal.as<Scalars>(),
+                     (const float*)ctx->pvLut.as<float>(), ivEnd, pOut, ctx->par.thr, sigM, skipM, ctx->dStatus.as<u32>(),
+                     hist ? (const u32*)ctx->tilePrevEnd.as<u32>() : (const u32*)nullptr, hist ? ctx->bhDense.as<u64>() : (u64*)nullptr);
+  return GX_OK;
+}
+
+// hist: the replicate is the run's only one, without a control, and -q follows (plan_call knows): its "bp at V" histogram is
+// made on the way (k_pack_pval<.., HIST>), for BH's table
 int materialize_rep(gx_ctx* ctx, int idx, bool hist = false) {
   PArray& pa = ctx->reps[idx];
   if (!pa.loose) return GX_OK;
@@ -73,38 +107,13 @@ int materialize_rep(gx_ctx* ctx, int idx, bool hist = false) {
     ctx->maskN = n;
     ctx->maskStride = nWords + 2;
   }
-  {
-    const dim3 grid(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(8 * ctx->numCU))));
-    if (hist) {
-      const u32 cap = 1u << ctx->bhCapLog;
-      if (int rc = bh_table_prepare(ctx, cap)) return rc;
-      HIPCHECK(hipMemsetAsync(ctx->misc.as<u32>() + M_BHCOUNT, 0, 8, s));
-      HIPCHECK(ctx->bhDense.ensure(bhd_words(1) * 8));
-      HIPCHECK(hipMemsetAsync(ctx->bhDense.p, 0, bhd_words(1) * 8, s));
-      // (as many workgroups as the CUs hold at once -- seven, with the histogram's LDS and registers: an eighth would run behind the others)
-      int nbH = 0;
-      HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbH, k_pack_pval<false, true>, 256, 0));
-      const dim3 gridH(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(std::max(1, std::min(nbH, 8)) * ctx->numCU))));
-      hipLaunchKernelGGL((k_pack_pval<false, true>), gridH, dim3(256), 0, s, pin, ctx->nTiles, ctx->dScal.as<Scalars>(),
-                         ctx->pvLut.as<float>(), ctx->expt.ivEnd.as<u32>(), pa.p.as<float>(), ctx->par.thr, sigM, skipM,
-                         ctx->dStatus.as<u32>(), (const u32*)ctx->tilePrevEnd.as<u32>(), ctx->bhDense.as<u64>());
-    } else if (sigM)
-      hipLaunchKernelGGL((k_pack_pval<true>), grid, dim3(256), 0, s, pin, ctx->nTiles, ctx->dScal.as<Scalars>(),
-                         ctx->pvLut.as<float>(), ctx->expt.ivEnd.as<u32>(), pa.p.as<float>(), ctx->par.thr, sigM, skipM,
-                         ctx->dStatus.as<u32>());
-    else
-      hipLaunchKernelGGL((k_pack_pval<false>), grid, dim3(256), 0, s, pin, ctx->nTiles, ctx->dScal.as<Scalars>(),
-                         ctx->pvLut.as<float>(), ctx->expt.ivEnd.as<u32>(), pa.p.as<float>(), ctx->par.thr, sigM, skipM,
-                         ctx->dStatus.as<u32>());
-  }
+  if (int rc = launch_pack_pval(ctx, hist, true, pin, ctx->expt.ivEnd.as<u32>(), pa.p.as<float>(), sigM, skipM)) return rc;
   hipLaunchKernelGGL(k_pval_deep, dim3(256), dim3(256), 0, s, pin, ctx->fragSum.as<FragFix>(), ctx->fragList.as<u32>(),
                      ctx->dScal.as<Scalars>(), ctx->dDeep.as<DeepTab>(), pa.p.as<float>(), ctx->par.thr, sigM);
-  if (hist) {
+  if (hist)
     hipLaunchKernelGGL(k_deep_hist, dim3(64), dim3(256), 0, s, pin, ctx->fragSum.as<FragFix>(), ctx->fragList.as<u32>(),
                        (const u32*)ctx->tilePrevEnd.as<u32>(), (const float*)pa.p.as<float>(), bh_table_of(ctx, 1u << ctx->bhCapLog),
                        ctx->dStatus.as<u32>());
-    ctx->denseHistIdx = idx;
-  }
   if (int rc__ = dbg_sync(ctx, "k_pack_pval")) return rc__;
   phase_end(ctx);
   HIPCHECK(hipGetLastError());
@@ -132,14 +141,10 @@ int ensure_piles(gx_ctx* ctx, int idx) {
   // k_piles_from_loose reads nothing else: a null pointer says so)
   PackIn pin{pa.keptLoose ? (const u32*)nullptr : ctx->looseEnd.as<u32>(), pa.keptLoose ? pa.keptV.as<int>() : ctx->looseV.as<int>(),
              pa.keptLoose ? pa.keptMeta.as<TileMeta>() : ctx->tileMeta.as<TileMeta>(), pa.tileOff.as<u32>()};
-  const dim3 grid(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(8 * ctx->numCU))));
   // (the control value of a replicate without control is its lambda: saveLambda 1847-1876)
-  if (ctx->hasBed)
-    hipLaunchKernelGGL(k_piles_from_loose<true>, grid, dim3(256), 0, s, pin, ctx->nTiles, pa.ctrlConst, pa.expt.as<float>(),
-                       pa.ctrl.as<float>());
-  else
-    hipLaunchKernelGGL(k_piles_from_loose<false>, grid, dim3(256), 0, s, pin, ctx->nTiles, pa.ctrlConst, pa.expt.as<float>(),
-                       (float*)nullptr);
+  static constexpr decltype(&k_piles_from_loose<false>) PILES[2] = {k_piles_from_loose<false>, k_piles_from_loose<true>};   // [CTRL]
+  hipLaunchKernelGGL(PILES[ctx->hasBed], tile_grid(ctx, 8), dim3(256), 0, s, pin, ctx->nTiles, pa.ctrlConst, pa.expt.as<float>(),
+                     ctx->hasBed ? pa.ctrl.as<float>() : (float*)nullptr);
   if (int rc__ = dbg_sync(ctx, "k_piles_from_loose")) return rc__;
   pa.hasPiles = true;
   pa.pilesPending = false;
@@ -268,33 +273,24 @@ int merge_with_control(gx_ctx* ctx, PArray& pa) {
     ctx->maskIdx = (int)ctx->reps.size();
     ctx->maskStride = stride;
   }
+  const bool msk = sigM != nullptr;
   if (mergeP) {
-    hipLaunchKernelGGL(k_pairs_missed, dim3(std::max(1u, std::min((nTiles + 3) / 4, (u32)(4 * ctx->numCU)))), dim3(256), 0, s, ppi,
+    hipLaunchKernelGGL(k_pairs_missed, tile_grid(ctx, 4), dim3(256), 0, s, ppi,
                        ctx->tileIvCount.as<u32>(), ctx->fragList.as<u32>(), misc + M_TICKET, ctx->dScal.as<Scalars>(),
                        ctx->pairLogE.as<double>(), ctx->pairCtab.as<CtrlEntry>(), ctx->looseV.as<u32>(), ctx->dStatus.as<u32>(),
                        ctx->dRisk.as<RiskBuf>());
-    const dim3 grid(std::max(1u, std::min((nTiles + 3) / 4, (u32)(8 * ctx->numCU))));
-    if (sigM)
-      hipLaunchKernelGGL((k_pack_ep2<true>), grid, dim3(256), 0, s, ppi, ctx->looseV.as<float>(), nTiles, pa.end.as<u32>(), pa.p.as<float>(),
-                         ctx->par.thr, sigM, skipM);
-    else
-      hipLaunchKernelGGL((k_pack_ep2<false>), grid, dim3(256), 0, s, ppi, ctx->looseV.as<float>(), nTiles, pa.end.as<u32>(), pa.p.as<float>(),
-                         ctx->par.thr, sigM, skipM);
+    static constexpr decltype(&k_pack_ep2<false>) PACK_EP2[2] = {k_pack_ep2<false>, k_pack_ep2<true>};   // [MASKS]
+    hipLaunchKernelGGL(PACK_EP2[msk], tile_grid(ctx, 8), dim3(256), 0, s, ppi, (const float*)ctx->looseV.as<float>(), nTiles, pa.end.as<u32>(),
+                       pa.p.as<float>(), ctx->par.thr, sigM, skipM);
   } else {
-  {
-    const dim3 grid(std::max(1u, std::min((nTiles + 3) / 4, (u32)(8 * ctx->numCU))));
-    const bool msk = sigM != nullptr;
-#define GX_LAUNCH_PACK_PAIRS(K, M)                                                                                     \
-hipLaunchKernelGGL((k_pack_pairs<K, M>), grid, dim3(256), 0, s, ppi, nTiles, ctx->pairCtab.as<CtrlEntry>(),           \
-                   ctx->pairP2d.as<float>(), pa.end.as<u32>(), pa.expt.as<float>(), pa.ctrl.as<float>(),              \
-                   pa.p.as<float>(), ctx->par.thr, sigM, skipM, ctx->fragList.as<u32>(), misc + M_TICKET)
-    if (msk) GX_LAUNCH_PACK_PAIRS(false, true); else GX_LAUNCH_PACK_PAIRS(false, false);
-#undef GX_LAUNCH_PACK_PAIRS
-  }
-  hipLaunchKernelGGL(k_pack_pairs_full, dim3(std::max(1u, std::min((nTiles + 3) / 4, (u32)(4 * ctx->numCU)))), dim3(256), 0, s,
-                     ppi, ctx->fragList.as<u32>(), misc + M_TICKET, ctx->dScal.as<Scalars>(), ctx->pairLogE.as<double>(),
-                     ctx->pairCtab.as<CtrlEntry>(), (float*)nullptr, (float*)nullptr, pa.p.as<float>(), ctx->par.thr, sigM, skipM,
-                     ctx->dStatus.as<u32>(), ctx->dRisk.as<RiskBuf>());
+    static constexpr decltype(&k_pack_pairs<false, false>) PACK_PAIRS[2] = {k_pack_pairs<false, false>, k_pack_pairs<false, true>};   // [MASKS]
+    hipLaunchKernelGGL(PACK_PAIRS[msk], tile_grid(ctx, 8), dim3(256), 0, s, ppi, nTiles, (const CtrlEntry*)ctx->pairCtab.as<CtrlEntry>(),
+                       (const float*)ctx->pairP2d.as<float>(), pa.end.as<u32>(), pa.expt.as<float>(), pa.ctrl.as<float>(), pa.p.as<float>(),
+                       ctx->par.thr, sigM, skipM, ctx->fragList.as<u32>(), misc + M_TICKET);
+    hipLaunchKernelGGL(k_pack_pairs_full, tile_grid(ctx, 4), dim3(256), 0, s,
+                       ppi, ctx->fragList.as<u32>(), misc + M_TICKET, ctx->dScal.as<Scalars>(), ctx->pairLogE.as<double>(),
+                       ctx->pairCtab.as<CtrlEntry>(), (float*)nullptr, (float*)nullptr, pa.p.as<float>(), ctx->par.thr, sigM, skipM,
+                       ctx->dStatus.as<u32>(), ctx->dRisk.as<RiskBuf>());
   }
   if (int rc__ = dbg_sync(ctx, "k_pack_pairs")) return rc__;
   phase_end(ctx);
@@ -341,11 +337,10 @@ int make_pair_piles(gx_ctx* ctx, int idx) {
                   ctx->ctrl.tileIvOff.as<u32>(), pa.tileOff.as<u32>()};
   HIPCHECK(ctx->fragList.ensure((size_t)(nTiles + 1) * 4));
   HIPCHECK(hipMemsetAsync(misc + M_TICKET, 0, 4, s));
-  const dim3 grid(std::max(1u, std::min((nTiles + 3) / 4, (u32)(8 * ctx->numCU))));
-  hipLaunchKernelGGL((k_pack_pairs<true, false, true>), grid, dim3(256), 0, s, ppi, nTiles, ctx->pairCtab.as<CtrlEntry>(),
+  hipLaunchKernelGGL((k_pack_pairs<true, false, true>), tile_grid(ctx, 8), dim3(256), 0, s, ppi, nTiles, ctx->pairCtab.as<CtrlEntry>(),
                      ctx->pairP2d.as<float>(), (u32*)nullptr, pa.expt.as<float>(), pa.ctrl.as<float>(), (float*)nullptr, ctx->par.thr,
                      (u64*)nullptr, (u64*)nullptr, ctx->fragList.as<u32>(), misc + M_TICKET);
-  hipLaunchKernelGGL(k_pack_pairs_full, dim3(std::max(1u, std::min((nTiles + 3) / 4, (u32)(4 * ctx->numCU)))), dim3(256), 0, s,
+  hipLaunchKernelGGL(k_pack_pairs_full, tile_grid(ctx, 4), dim3(256), 0, s,
                      ppi, ctx->fragList.as<u32>(), misc + M_TICKET, ctx->dScal.as<Scalars>(), ctx->pairLogE.as<double>(),
                      ctx->pairCtab.as<CtrlEntry>(), pa.expt.as<float>(), pa.ctrl.as<float>(), (float*)nullptr, ctx->par.thr,
                      (u64*)nullptr, (u64*)nullptr, ctx->dStatus.as<u32>(), ctx->dRisk.as<RiskBuf>());
@@ -446,24 +441,42 @@ int combine_replicates(gx_ctx* ctx) {
   return GX_OK;
 }
 
+// The instances of k_bh_hist / k_qlookup (gx_stats.h), each named here and nowhere else: the workgroup, the entries and probes of
+// k_bh_hist's LDS table, log2 of k_qlookup's LDS cache, and either kernel's grid (so many workgroups per CU, or a fixed bound).
+// GX_BH_VARIANT names the row (0: rounds 2-5; 1: one workgroup per CU; 2: in between); a run without it takes the default.
+struct BhGrid { u32 perCU, fixed; u32 of(const gx_ctx* ctx) const { return perCU ? perCU * (u32)ctx->numCU : fixed; } };
+struct BhInstance {
+  u32 nt, ldsEntries, probes, cacheLog;
+  BhGrid histGrid, lookGrid;
+  decltype(&k_bh_hist<256, 2048, 8>) hist;
+  decltype(&k_qlookup<256, 11>) lookup;
+};
+#define GX_BH(NT, LT, PR, CL, HG, LG) {NT, LT, PR, CL, HG, LG, k_bh_hist<NT, LT, PR>, k_qlookup<NT, CL>}
+const BhInstance BH_INSTANCES[3] = {GX_BH(256, 2048, 8, 11, (BhGrid{0, 2048}), (BhGrid{0, 4096})), GX_BH(1024, 8192, 16, 14, (BhGrid{1, 0}), (BhGrid{1, 0})),
+                                    GX_BH(512, 4096, 16, 13, (BhGrid{3, 0}), (BhGrid{2, 0}))};
+#undef GX_BH
+int bh_instance(const gx_ctx* ctx) {
+  const int v = ctx->knob.bhVariant >= 0 ? ctx->knob.bhVariant : GX_BH_DEFAULT_VARIANT;
+  return v == 1 || v == 2 ? v : 0;
+}
+
+// the table {p -> bp} of the n intervals of `fa`, by a hash insertion per interval
+int launch_hist(gx_ctx* ctx, const BhInstance& I, const PArray& fa, u32 n, const BhTable& T) {
+  const size_t lds = bh_hist_lds((int)I.ldsEntries);
+  HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(I.hist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(I.hist, dim3(std::min(std::max(1u, (n + 4095) / 4096), I.histGrid.of(ctx))), dim3(I.nt), lds, ctx->stream,
+                     (const u32*)fa.end.as<u32>(), (const float*)fa.p.as<float>(), (const u32*)fa.chromOff.as<u32>(), ctx->nChrom,
+                     (const u32*)(ctx->misc.as<u32>() + M_NIV), T, ctx->dStatus.as<u32>());
+  return GX_OK;
+}
+
 // q of every interval of `fa` from the {key, q} table of the run (lookup 196-206), with the sweep's masks on the way (or without: nullptr)
-int qlookup_all(gx_ctx* ctx, PArray& fa, u32 cap, u64* sigMask, u64* skipMask) {
-  hipStream_t s = ctx->stream;
-  u32* misc = ctx->misc.as<u32>();
-  const int bhv = ctx->knob.bhVariant >= 0 ? ctx->knob.bhVariant : GX_BH_DEFAULT_VARIANT;
-  const u32 want = std::max(1u, (fa.n + 4095) / 4096);
-#define GX_QLOOKUP(NT, CL, GRID)                                                                                                      \
-  do {                                                                                                                                \
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_qlookup<NT, CL>), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                 (int)(8u << CL)));                                                                                   \
-    hipLaunchKernelGGL((k_qlookup<NT, CL>), dim3(std::min(want, (u32)(GRID))), dim3(NT), (size_t)(8u << CL), s, fa.p.as<float>(),     \
-                       misc + M_NIV, ctx->bhKQ.as<u64>(), cap - 1, fa.q.as<float>(), ctx->par.thr,                                  \
-                       sigMask, skipMask, ctx->dStatus.as<u32>());                              \
-  } while (0)
-  if (bhv == 1) GX_QLOOKUP(1024, 14, ctx->numCU);
-  else if (bhv == 2) GX_QLOOKUP(512, 13, 2 * ctx->numCU);
-  else GX_QLOOKUP(256, 11, 4096);
-#undef GX_QLOOKUP
+int qlookup_all(gx_ctx* ctx, const BhInstance& I, PArray& fa, u32 cap, u64* sigMask, u64* skipMask) {
+  const size_t lds = (size_t)(8u << I.cacheLog);
+  HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(I.lookup), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(I.lookup, dim3(std::min(std::max(1u, (fa.n + 4095) / 4096), I.lookGrid.of(ctx))), dim3(I.nt), lds, ctx->stream,
+                     (const float*)fa.p.as<float>(), (const u32*)(ctx->misc.as<u32>() + M_NIV), (const u64*)ctx->bhKQ.as<u64>(), cap - 1,
+                     fa.q.as<float>(), ctx->par.thr, sigMask, skipMask, ctx->dStatus.as<u32>());
   return GX_OK;
 }
 
@@ -476,28 +489,28 @@ int ensure_q(gx_ctx* ctx, PArray& pa, int idx) {
     return GX_ERR_ORDER;
   }
   HIPCHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->misc.as<u32>() + M_NIV), (int)pa.n, 1, ctx->stream));
-  if (int rc = qlookup_all(ctx, pa, ctx->bhLiveCap, nullptr, nullptr)) return rc;
+  if (int rc = qlookup_all(ctx, BH_INSTANCES[bh_instance(ctx)], pa, ctx->bhLiveCap, nullptr, nullptr)) return rc;
   pa.qLazy = false;
   return GX_OK;
 }
 
+// what every BH ends with: the table of this run stays, with {key, q} of every value, for the q-values nobody has asked for yet
+// (freed by the next run that wants the table: bh_release_live)
+void bh_keep_live(gx_ctx* ctx, u32 cap) {
+  ctx->bhDirty = false;
+  ctx->bhLive = true;
+  ctx->bhLiveCap = cap;
+  ctx->bhLiveIdx = ctx->finalIdx;
+}
+
 // -q on the loose slots: the "bp at pileup V" histogram that materialize_rep(.., hist) collects while it writes the tight table, without
 // the table (k_pack_pval<.., HIST, false>: reads the loose slots, writes nothing but the sums), then Benjamini-Hochberg on it
-int loose_hist(gx_ctx* ctx, PArray& pa, bool genomeOpt) {
+int loose_hist(gx_ctx* ctx, const CallPlan& P, PArray& pa) {
   hipStream_t s = ctx->stream;
   phase_begin(ctx, "pval");
   const u32 cap = 1u << ctx->bhCapLog;
-  if (int rc = bh_table_prepare(ctx, cap)) return rc;
-  HIPCHECK(hipMemsetAsync(ctx->misc.as<u32>() + M_BHCOUNT, 0, 8, s));
-  HIPCHECK(ctx->bhDense.ensure(bhd_words(1) * 8));
-  HIPCHECK(hipMemsetAsync(ctx->bhDense.p, 0, bhd_words(1) * 8, s));
   PackIn pin{ctx->looseEnd.as<u32>(), ctx->looseV.as<int>(), ctx->tileMeta.as<TileMeta>(), pa.tileOff.as<u32>()};
-  int nbH = 0;
-  HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbH, k_pack_pval<false, true, false>, 256, 0));
-  const dim3 gridH(std::max(1u, std::min((ctx->nTiles + 3) / 4, (u32)(std::max(1, std::min(nbH, 8)) * ctx->numCU))));
-  hipLaunchKernelGGL((k_pack_pval<false, true, false>), gridH, dim3(256), 0, s, pin, ctx->nTiles, ctx->dScal.as<Scalars>(),
-                     ctx->pvLut.as<float>(), (u32*)nullptr, (float*)nullptr, ctx->par.thr, (u64*)nullptr, (u64*)nullptr,
-                     ctx->dStatus.as<u32>(), (const u32*)ctx->tilePrevEnd.as<u32>(), ctx->bhDense.as<u64>());
+  if (int rc = launch_pack_pval(ctx, true, false, pin, nullptr, nullptr, nullptr, nullptr)) return rc;
   phase_end(ctx);
   // computeQval on ~100 distinct values, whole: one workgroup (k_bh_small) -- q by pileup, from which pileup on it passes, the values'
   // {key, q} in the run's table for whoever asks for the q array later (ensure_q)
@@ -509,101 +522,61 @@ int loose_hist(gx_ctx* ctx, PArray& pa, bool genomeOpt) {
   HIPCHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(misc + M_VQ + 1), ctx->knob.fault == 2 ? (int)0xFFFFFFFFu : 0, 1, s));
   hipLaunchKernelGGL(k_bh_small, dim3(1), dim3(1024), 0, s, (const u64*)ctx->bhDense.as<u64>(), ctx->pvLut.as<float>(), bh_table_of(ctx, cap),
                      ctx->bhKQ.as<u64>(), reinterpret_cast<const u64*>(misc + M_GENOME), ctx->par.thr, ctx->qLut.as<float>(), misc + M_VQ,
-                     misc + M_ALLONE, genomeOpt ? ctx->dStatus.as<u32>() : (u32*)nullptr, ctx->dStatus.as<u32>());
-  ctx->denseHistUsed = true;
+                     misc + M_ALLONE, P.genomeOpt ? ctx->dStatus.as<u32>() : (u32*)nullptr, ctx->dStatus.as<u32>());
   pa.qLazy = true;
-  ctx->lazyQUsed = true;
-  ctx->bhDirty = false;
-  ctx->bhLive = true;   // (freed by the next run that wants the table: bh_release_live)
-  ctx->bhLiveCap = cap;
-  ctx->bhLiveIdx = ctx->finalIdx;
+  bh_keep_live(ctx, cap);
   phase_end(ctx);
   return GX_OK;
 }
 
-// computeQval / saveQval (Genrich.c:352-401, 212-250) for the final p-array `fa` of n intervals: the genome-wide table
-// {p -> bp} (with several ranks: after the exchange, gx_host_coll.h), its sort and suffix scan, q per interval and the
-// sweep's masks on the way.  genomeOpt: the genome length was computed (not -L): the lengths must add up to it
-int bh_qvalues(gx_ctx* ctx, PArray& fa, u32 n, bool genomeOpt) {
+// computeQval / saveQval (Genrich.c:352-401, 212-250) for the final p-array `fa` of n intervals, in four pieces (bh_stage,
+// gx_host_call.h, runs them): the local table {p -> bp}, the ranks' exchange, its sort and suffix scan, q and the sweep's masks.
+
+// 1: this rank's table and its Dlocal distinct values.  From the "bp at V" sums k_pack_pval<.., HIST> left in bhDense (and the
+// deep values it left in the table), or by k_bh_hist.  A table too small (ST_HASH_FULL) is made again 8x larger, by k_bh_hist
+// whatever the first source was: the sums' table is materialize_rep's, and gone
+int bh_local_table(gx_ctx* ctx, const CallPlan& P, const PArray& fa, u32 n, BhTable& T, u32& Dlocal) {
   hipStream_t s = ctx->stream;
   u32* misc = ctx->misc.as<u32>();
-  const u32 nChrom = ctx->nChrom;
-  phase_begin(ctx, "bh");
-  u32 cap = 1u << ctx->bhCapLog;
-  auto bh_table = [&](u32 c) -> int { return bh_table_prepare(ctx, c); };
-  auto bh_grow = [&]() -> int {
-    if (ctx->bhCapLog >= 28) {
-      ctx->err = "p-value table full";
-      return GX_ERR_MEM;
-    }
-    ctx->bhCapLog += 3;
-    cap = 1u << ctx->bhCapLog;
-    ctx->bhDirty = true;  // (whatever the failed attempt left behind is wiped)
-    return GX_OK;
-  };
-  BhTable T{};
-  u32 Dlocal = 0;
-  // the instance of k_bh_hist / k_qlookup (gx_stats.h): LDS tables that hold a stretch of the genome's distinct values
-  const int bhv = ctx->knob.bhVariant >= 0 ? ctx->knob.bhVariant : GX_BH_DEFAULT_VARIANT;
-  auto launch_hist = [&]() -> int {
-    const u32 want = std::max(1u, (n + 4095) / 4096);
-#define GX_BH_HIST(NT, LT, PR, GRID)                                                                                                  \
-  do {                                                                                                                                \
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bh_hist<NT, LT, PR>), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                 (int)bh_hist_lds(LT)));                                                                              \
-    hipLaunchKernelGGL((k_bh_hist<NT, LT, PR>), dim3(std::min(want, (u32)(GRID))), dim3(NT), bh_hist_lds(LT), s, fa.end.as<u32>(),     \
-                       fa.p.as<float>(), fa.chromOff.as<u32>(), nChrom, misc + M_NIV, T, ctx->dStatus.as<u32>());                   \
-  } while (0)
-    if (bhv == 1) GX_BH_HIST(1024, 8192, 16, ctx->numCU);
-    else if (bhv == 2) GX_BH_HIST(512, 4096, 16, 3 * ctx->numCU);
-    else GX_BH_HIST(256, 2048, 8, 2048);
-#undef GX_BH_HIST
-    return GX_OK;
-  };
-  // (one replicate without a control: k_pack_pval<.., HIST> left "bp at V" in bhDense and the deep values in the table)
-  bool fromDense = ctx->denseHistIdx >= 0 && ctx->denseHistIdx == ctx->finalIdx && ctx->world <= 1 && !ctx->forceColl;
-  ctx->denseHistIdx = -1;
-  ctx->denseHistUsed = fromDense;
-  for (;;) {
+  for (bool fromDense = P.bh == CallPlan::BH_FROM_DENSE;; fromDense = false) {
+    const u32 cap = 1u << ctx->bhCapLog;
     if (fromDense) {
       T = bh_table_of(ctx, cap);
       HIPCHECK(hipMemsetAsync(misc + M_BHOVF, 0, 4, s));
       hipLaunchKernelGGL(k_bh_from_dense, dim3(256), dim3(256), 0, s, (const u64*)ctx->bhDense.as<u64>(), ctx->pvLut.as<float>(), 1u, T,
                          misc + M_BHOVF, ctx->dStatus.as<u32>());
-      if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, misc + M_BHCOUNT)) return rc__;
-      Dlocal = ctx->mail->nMerged;
-      if (!(ctx->mail->status & ST_HASH_FULL)) break;
-      if (ctx->mail->status != ST_HASH_FULL) return status_to_rc(ctx, ctx->mail->status & ~ST_HASH_FULL);
-      HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 4, s));   // (a table too small: once more from the tight intervals, into a larger one)
-      if (int rc = bh_grow()) return rc;
-      fromDense = false;
-      ctx->denseHistUsed = false;
-      continue;
+    } else {
+      if (int rc = bh_table_prepare(ctx, cap)) return rc;
+      HIPCHECK(hipMemsetAsync(misc + M_BHCOUNT, 0, 8, s));
+      T = bh_table_of(ctx, cap);
+      if (int rc__ = launch_hist(ctx, BH_INSTANCES[P.bhInst], fa, n, T)) return rc__;
+      if (int rc__ = dbg_sync(ctx, "k_bh_hist")) return rc__;
     }
-    if (int rc = bh_table(cap)) return rc;
-    HIPCHECK(hipMemsetAsync(misc + M_BHCOUNT, 0, 8, s));
-    T = bh_table_of(ctx, cap);
-    if (int rc__ = launch_hist()) return rc__;
-    if (int rc__ = dbg_sync(ctx, "k_bh_hist")) return rc__;
     if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, misc + M_BHCOUNT)) return rc__;
     Dlocal = ctx->mail->nMerged;
-    if (!(ctx->mail->status & ST_HASH_FULL)) break;
+    if (!(ctx->mail->status & ST_HASH_FULL)) return GX_OK;
     if (ctx->mail->status != ST_HASH_FULL) return status_to_rc(ctx, ctx->mail->status & ~ST_HASH_FULL);
-    HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 4, s));
-    if (int rc = bh_grow()) return rc;
+    HIPCHECK(hipMemsetAsync(ctx->dStatus.p, 0, 4, s));   // (a table too small: once more from the tight intervals, into a larger one)
+    if (ctx->bhCapLog >= 28) {
+      ctx->err = "p-value table full";
+      return GX_ERR_MEM;
+    }
+    ctx->bhCapLog += 3;
+    ctx->bhDirty = true;  // (whatever the failed attempt left behind is wiped)
+    ctx->called.ran.tableGrew = true;
   }
-  const bool multi = ctx->world > 1 || ctx->forceColl;
-  // (computeQval 377-382: checked when the genome length was computed -- not with -L)
-  u32* lenCheck = genomeOpt ? ctx->dStatus.as<u32>() : (u32*)nullptr;
-  u32 D = 0;
-  bool denseDone = false;
-  ctx->denseBhUsed = false;
-  ctx->rangeBhUsed = false;
+}
+
+// 2: the genome-wide table.  -> D: its distinct values on this rank (0: the range exchange has left every value's q in bhQ)
+int bh_exchange(gx_ctx* ctx, const CallPlan& P, const PArray& fa, u32 n, const BhTable& T, u32 Dlocal, u32& D) {
+  hipStream_t s = ctx->stream;
+  u32* misc = ctx->misc.as<u32>();
+  D = Dlocal;
+  if (P.exchange == CallPlan::X_NONE) return GX_OK;
   // One sample without a control: p is a function of the pileup, every rank holds the same table p(V), and the
   // genome-wide histogram is ONE all-reduce of a dense "bp at V" array (gx_stats.h: k_bh_dense_fill) -- decided by what
   // every rank knows alike
-  if (multi && ctx->sample == 1 && ctx->reps.size() == 1 && fa.ctrlIsConst && !ctx->bedGiven && (u32)std::max(1, ctx->world) <= 64 &&
-      !ctx->knob.noDenseBh) {
+  if (P.exchange == CallPlan::X_DENSE) {
     const u32 W = (u32)std::max(1, ctx->world);
     const size_t words = bhd_words(W);
     HIPCHECK(ctx->bhDense.ensure(words * 8));
@@ -622,89 +595,83 @@ int bh_qvalues(gx_ctx* ctx, PArray& fa, u32 n, bool genomeOpt) {
     HIPCHECK(hipStreamSynchronize(s));
     if (ctx->mail->bhOvf == 0) {
       D = ctx->mail->D;
-      denseDone = true;
-      ctx->denseBhUsed = true;
-    } else {
-      // some rank holds more values outside the table than its region takes: every rank saw it, all go back to their own
-      // tables and take the general exchange
-      hipLaunchKernelGGL(k_bh_clear, dim3(256), dim3(256), 0, s, T);
-      HIPCHECK(hipMemsetAsync(misc + M_BHCOUNT, 0, 8, s));
-      if (int rc__ = launch_hist()) return rc__;
-      if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, misc + M_BHCOUNT)) return rc__;
-      Dlocal = ctx->mail->nMerged;
+      return GX_OK;
     }
+    // some rank holds more values outside the table than its region takes: every rank saw it, all go back to their own
+    // tables and take the general exchange
+    ctx->called.ran.denseFellBack = true;
+    hipLaunchKernelGGL(k_bh_clear, dim3(256), dim3(256), 0, s, T);
+    HIPCHECK(hipMemsetAsync(misc + M_BHCOUNT, 0, 8, s));
+    if (int rc__ = launch_hist(ctx, BH_INSTANCES[P.bhInst], fa, n, T)) return rc__;
+    if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, misc + M_BHCOUNT)) return rc__;
+    Dlocal = ctx->mail->nMerged;
   }
-  bool rangeDone = false;
-  if (denseDone) {
-  } else if (multi) {
-    // a control / replicates: the range-partitioned exchange (gx_bhx.h) leaves every value's q in this rank's table
-    if (int rc = bh_range_exchange(ctx, T, Dlocal, cap)) return rc;
-    rangeDone = true;
-    D = 0;
-  } else
-    D = Dlocal;
-  if (D && !rangeDone) {
-    HIPCHECK(ctx->bhSortKeys.ensure((size_t)D * 4));
-    HIPCHECK(ctx->bhSortSlot.ensure((size_t)D * 4));
-    HIPCHECK(ctx->bhRaw.ensure((size_t)D * 4));
-    size_t tmpBytes = 0;
-    HIPCHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, ctx->bhOutKeys.as<u32>(), ctx->bhSortKeys.as<u32>(),
-                                       ctx->bhOutSlot.as<u32>(), ctx->bhSortSlot.as<u32>(), D, 0, 32, s));
-    HIPCHECK(ctx->bhTmp.ensure(tmpBytes + 16));
-    HIPCHECK(rocprim::radix_sort_pairs(ctx->bhTmp.p, tmpBytes, ctx->bhOutKeys.as<u32>(), ctx->bhSortKeys.as<u32>(),
-                                       ctx->bhOutSlot.as<u32>(), ctx->bhSortSlot.as<u32>(), D, 0, 32, s));
-    if (D <= 16384 && !ctx->knob.qtMulti) {
-      hipLaunchKernelGGL(k_qtable, dim3(1), dim3(1024), 0, s, ctx->bhSortKeys.as<u32>(), ctx->bhSortSlot.as<u32>(),
-                         ctx->bhLens.as<u64>(), D, reinterpret_cast<const u64*>(misc + M_GENOME), ctx->bhQ.as<float>(),
-                         ctx->bhRaw.as<float>(), misc + M_ALLONE, lenCheck);
-    } else {  // many distinct values (Fisher-combined replicates): the chunked kernels
-      const u32 nCh = (D + QT_CHUNK - 1) / QT_CHUNK;
-      HIPCHECK(ctx->bhDl.ensure((size_t)D * 8 + (size_t)nCh * 12 + 64));
-      u64* dl = ctx->bhDl.as<u64>();
-      u64* chunkSum = dl + D;
-      float* chunkMin = reinterpret_cast<float*>(chunkSum + nCh);
-      hipLaunchKernelGGL(k_qt_sums, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortSlot.as<u32>(), ctx->bhLens.as<u64>(), D, dl,
-                         chunkSum, (const u32*)nullptr);
-      hipLaunchKernelGGL(k_qt_raw, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortKeys.as<u32>(), dl, D,
-                         reinterpret_cast<const u64*>(misc + M_GENOME), chunkSum, ctx->bhRaw.as<float>(), chunkMin,
-                         (const u32*)nullptr, (const u64*)nullptr, 1u, 0u, lenCheck);
-      hipLaunchKernelGGL(k_qt_apply, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortSlot.as<u32>(), ctx->bhRaw.as<float>(), D,
-                         chunkMin, ctx->bhQ.as<float>(), misc + M_ALLONE, (const u32*)nullptr, (const u64*)nullptr, 1u, 0u);
-    }
-if (int rc__ = dbg_sync(ctx, "k_qtable")) return rc__;
+  // a control / replicates: the range-partitioned exchange (gx_bhx.h) leaves every value's q in this rank's table
+  D = 0;
+  return bh_range_exchange(ctx, T, Dlocal, T.capMask + 1);
+}
+
+// 3: the D values in order, their suffix sums, q by slot (bhQ): one workgroup, or the chunked kernels
+int bh_q_table(gx_ctx* ctx, const CallPlan& P, u32 D) {
+  hipStream_t s = ctx->stream;
+  u32* misc = ctx->misc.as<u32>();
+  // (computeQval 377-382: checked when the genome length was computed -- not with -L)
+  u32* lenCheck = P.genomeOpt ? ctx->dStatus.as<u32>() : (u32*)nullptr;
+  HIPCHECK(ctx->bhSortKeys.ensure((size_t)D * 4));
+  HIPCHECK(ctx->bhSortSlot.ensure((size_t)D * 4));
+  HIPCHECK(ctx->bhRaw.ensure((size_t)D * 4));
+  size_t tmpBytes = 0;
+  HIPCHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, ctx->bhOutKeys.as<u32>(), ctx->bhSortKeys.as<u32>(),
+                                     ctx->bhOutSlot.as<u32>(), ctx->bhSortSlot.as<u32>(), D, 0, 32, s));
+  HIPCHECK(ctx->bhTmp.ensure(tmpBytes + 16));
+  HIPCHECK(rocprim::radix_sort_pairs(ctx->bhTmp.p, tmpBytes, ctx->bhOutKeys.as<u32>(), ctx->bhSortKeys.as<u32>(),
+                                     ctx->bhOutSlot.as<u32>(), ctx->bhSortSlot.as<u32>(), D, 0, 32, s));
+  if (D <= 16384 && !P.qtMulti) {
+    hipLaunchKernelGGL(k_qtable, dim3(1), dim3(1024), 0, s, ctx->bhSortKeys.as<u32>(), ctx->bhSortSlot.as<u32>(),
+                       ctx->bhLens.as<u64>(), D, reinterpret_cast<const u64*>(misc + M_GENOME), ctx->bhQ.as<float>(),
+                       ctx->bhRaw.as<float>(), misc + M_ALLONE, lenCheck);
+  } else {  // many distinct values (Fisher-combined replicates): the chunked kernels
+    const u32 nCh = (D + QT_CHUNK - 1) / QT_CHUNK;
+    HIPCHECK(ctx->bhDl.ensure((size_t)D * 8 + (size_t)nCh * 12 + 64));
+    u64* dl = ctx->bhDl.as<u64>();
+    u64* chunkSum = dl + D;
+    float* chunkMin = reinterpret_cast<float*>(chunkSum + nCh);
+    hipLaunchKernelGGL(k_qt_sums, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortSlot.as<u32>(), ctx->bhLens.as<u64>(), D, dl,
+                       chunkSum, (const u32*)nullptr);
+    hipLaunchKernelGGL(k_qt_raw, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortKeys.as<u32>(), dl, D,
+                       reinterpret_cast<const u64*>(misc + M_GENOME), chunkSum, ctx->bhRaw.as<float>(), chunkMin,
+                       (const u32*)nullptr, (const u64*)nullptr, 1u, 0u, lenCheck);
+    hipLaunchKernelGGL(k_qt_apply, dim3(nCh), dim3(QT_NT), 0, s, ctx->bhSortSlot.as<u32>(), ctx->bhRaw.as<float>(), D,
+                       chunkMin, ctx->bhQ.as<float>(), misc + M_ALLONE, (const u32*)nullptr, (const u64*)nullptr, 1u, 0u);
   }
-  const bool lazyQ = !ctx->knob.noLazyQ;
+  return dbg_sync(ctx, "k_qtable");
+}
+
+// 4: {key, q} side by side, the sweep's significance / SKIP masks and q
+int bh_masks_and_q(gx_ctx* ctx, const CallPlan& P, PArray& fa, u32 n, const BhTable& T) {
+  hipStream_t s = ctx->stream;
+  u32* misc = ctx->misc.as<u32>();
   HIPCHECK(pooled(ctx, fa.q, (size_t)n * 4 + 16));
-  // q-values and, on the way, the sweep's significance / SKIP masks
-  {
-    const size_t stride = (size_t)((n + 63) / 64) + 2;
-    HIPCHECK(ctx->swMask.ensure(stride * 8 * 3));
-    HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, stride * 8 * 3, s));
-    ctx->maskIdx = ctx->finalIdx;
-    ctx->maskN = n;
-    ctx->maskStride = stride;
-    HIPCHECK(hipMemsetAsync(misc + M_PSTAR, 0xFF, 4, s));
-    hipLaunchKernelGGL(k_kq_build, dim3(256), dim3(256), 0, s, T, ctx->bhQ.as<float>(), ctx->bhKQ.as<u64>(), ctx->par.thr, misc + M_PSTAR);
-    if (lazyQ) {
-      // q never falls as p grows: the masks from one compare per interval; q itself inside the candidates (run_sweep: k_q_fill_cands)
-      // and for whoever asks for the array (ensure_q)
-      hipLaunchKernelGGL(k_sig_from_p, dim3(std::max(1u, std::min((n + 1023) / 1024, (u32)(8 * ctx->numCU)))), dim3(256), 0, s, fa.p.as<float>(),
-                         misc + M_NIV, misc + M_PSTAR, ctx->swMask.as<u64>(), ctx->swMask.as<u64>() + stride);
-    } else {
-      if (int rc__ = qlookup_all(ctx, fa, cap, ctx->swMask.as<u64>(), ctx->swMask.as<u64>() + stride)) return rc__;
-    }
+  const size_t stride = (size_t)((n + 63) / 64) + 2;
+  HIPCHECK(ctx->swMask.ensure(stride * 8 * 3));
+  HIPCHECK(hipMemsetAsync(ctx->swMask.p, 0, stride * 8 * 3, s));
+  ctx->maskIdx = ctx->finalIdx;
+  ctx->maskN = n;
+  ctx->maskStride = stride;
+  HIPCHECK(hipMemsetAsync(misc + M_PSTAR, 0xFF, 4, s));
+  hipLaunchKernelGGL(k_kq_build, dim3(256), dim3(256), 0, s, T, ctx->bhQ.as<float>(), ctx->bhKQ.as<u64>(), ctx->par.thr, misc + M_PSTAR);
+  if (P.lazyQ) {
+    // q never falls as p grows: the masks from one compare per interval; q itself inside the candidates (run_sweep: k_q_fill_cands)
+    // and for whoever asks for the array (ensure_q)
+    hipLaunchKernelGGL(k_sig_from_p, dim3(std::max(1u, std::min((n + 1023) / 1024, (u32)(8 * ctx->numCU)))), dim3(256), 0, s, fa.p.as<float>(),
+                       misc + M_NIV, misc + M_PSTAR, ctx->swMask.as<u64>(), ctx->swMask.as<u64>() + stride);
+  } else {
+    if (int rc__ = qlookup_all(ctx, BH_INSTANCES[P.bhInst], fa, T.capMask + 1, ctx->swMask.as<u64>(), ctx->swMask.as<u64>() + stride)) return rc__;
   }
-  fa.qLazy = lazyQ;
-  ctx->lazyQUsed = lazyQ;
-  ctx->bhDirty = false;
-  ctx->bhLive = true;   // (freed by the next run that wants the table: bh_release_live)
-  ctx->bhLiveCap = cap;
-  ctx->bhLiveIdx = ctx->finalIdx;
-  if (!lazyQ) bh_release_live(ctx);
-if (int rc__ = dbg_sync(ctx, "k_qlookup")) return rc__;
-  phase_end(ctx);
-  HIPCHECK(hipGetLastError());
-  return GX_OK;
+  fa.qLazy = P.lazyQ;
+  bh_keep_live(ctx, T.capMask + 1);
+  if (!P.lazyQ) bh_release_live(ctx);
+  return dbg_sync(ctx, "k_qlookup");
 }
 
 }  // namespace

@@ -28,7 +28,9 @@ struct SweepSrc {
 // far, with headroom), every kernel reads the counts on the device, the true run count comes back with the mail, and
 // only when it exceeds the guess is the sweep repeated with arrays that fit.  Counts travel through pinned memory
 // written by the kernels themselves, and the peak list is written straight into pinned host memory.
-int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
+// *synced: the sweep reached its synchronisation -- ctx->mail->status is this sweep's word, not an earlier one's
+int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut, bool* synced) {
+  *synced = false;
   hipStream_t s = ctx->stream;
   u32* misc = ctx->misc.as<u32>();
   HostMail* dm = static_cast<HostMail*>(ctx->mailBuf.dp);
@@ -40,7 +42,7 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
   // the run pass that rode in the scan's launch: taken by the first attempt, or dropped -- here, whatever follows
   const gx_ctx::SpecRuns spec = ctx->specRuns;
   ctx->specRuns.valid = false;
-  ctx->overlapUsed = false;
+  ctx->called.ran.overlap = false;
   ctx->peakBP = 0;
   ctx->nHostPeaks = 0;
   if (nWords) {
@@ -75,7 +77,7 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
       u32 gen = spec.gen;
       if (!specRuns)
         if (int rc__ = sweep_next_gen(ctx, &gen)) return rc__;
-      ctx->overlapUsed = specRuns;
+      ctx->called.ran.overlap = specRuns;
       u64* lbS = ctx->lbSweep.as<u64>();
       u64* lbE = lbS + wChunks + 8;
       u64* lbC = ctx->lbSweep2.as<u64>();
@@ -86,13 +88,10 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
       const u32 gridP = sweep_grid(ctx, ctx->resSweep);
       // runs: count, place and write in one pass; the true count goes to the host, at most `cap` to the kernels
       // (on the loose slots the chromosomes' starts come from the tile stage's table, as in the speculative pass)
-      if (specRuns) {
-      } else if (S.V)
-        hipLaunchKernelGGL(k_runs<true>, dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, chrom_starts(ctx), lbS, lbE, gen,
-                           runs_out(ctx, cap), ctx->dStatus.as<u32>());
-      else
-        hipLaunchKernelGGL(k_runs<false>, dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, ChromStarts{}, lbS, lbE, gen,
-                           runs_out(ctx, cap), ctx->dStatus.as<u32>());
+      static constexpr decltype(&k_runs<false>) RUNS[2] = {k_runs<false>, k_runs<true>};   // [TABLE]
+      if (!specRuns)
+        hipLaunchKernelGGL(RUNS[S.V != nullptr], dim3(std::min<u32>(wChunks, gridP)), dim3(SW_NT), 0, s, SM, S.V ? chrom_starts(ctx) : ChromStarts{},
+                           lbS, lbE, gen, runs_out(ctx, cap), ctx->dStatus.as<u32>());
       // candidates (chunks beyond the device-side run count leave at once)
       hipLaunchKernelGGL(k_cands, dim3(std::min<u32>(rChunks, gridP)), dim3(SW_NT), 0, s, SM, skipM, S.end, runStart, runEnd,
                          misc + M_SWCOUNT, ctx->par.max_gap, S.chromOff, nChrom, lbC, gen, ctx->headPos.as<u32>(), misc + M_NHEADS,
@@ -106,25 +105,16 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
       {
         const dim3 grid(std::max(1u, std::min((cap + 15) / 16, 16384u)));  // 16 candidates per workgroup and round
         const dim3 gridW(std::max(1u, std::min((cap + 3) / 4, (u32)(8 * ctx->numCU))));
-// (k_peak_both: the short candidates' workgroups first, the long candidates' behind them, one launch)
-#define GX_LAUNCH_PEAKS(Q, V, NSHORT, QPTR)                                                                               \
-  hipLaunchKernelGGL((k_peak_both<Q, V>), dim3((NSHORT) + gridW.x), dim3(256), 0, s, (u32)(NSHORT), ctx->candHdr.as<uint4>(), \
-                     S.end, S.p, QPTR, S.chromOff, nChrom, misc + M_NHEADS, ctx->longList.as<u32>(), misc + M_TICKET3,       \
-                     ctx->par.thr, ctx->par.min_auc, ctx->par.min_len, ctx->cand.as<gx_peak>(), ctx->valid.as<u32>())
-        if (S.V && S.qLut) {  // ... and q from its own table
-          const u32 nShortV = std::min<u32>(grid.x, (u32)(8 * ctx->numCU));
-          hipLaunchKernelGGL((k_peak_both<false, true, true>), dim3(nShortV + gridW.x), dim3(256), 0, s, nShortV, ctx->candHdr.as<uint4>(),
-                             S.end, S.p, reinterpret_cast<const float*>(S.V), S.chromOff, nChrom, misc + M_NHEADS, ctx->longList.as<u32>(),
-                             misc + M_TICKET3, ctx->par.thr, ctx->par.min_auc, ctx->par.min_len, ctx->cand.as<gx_peak>(),
-                             ctx->valid.as<u32>(), S.qLut);
-        } else if (S.V) {  // p from the table p(V) (`q` carries the exact pileups); every workgroup copies the table's compact form to LDS
-          const u32 nShortV = std::min<u32>(grid.x, (u32)(8 * ctx->numCU));
-          GX_LAUNCH_PEAKS(false, true, nShortV, reinterpret_cast<const float*>(S.V));
-        } else if (S.q)
-          GX_LAUNCH_PEAKS(true, false, grid.x, S.q);
-        else
-          GX_LAUNCH_PEAKS(false, false, grid.x, S.q);
-#undef GX_LAUNCH_PEAKS
+        // k_peak_both: the short candidates' workgroups first, the long candidates' behind them, one launch.  Its instances by
+        // [the sweep walks the loose slots][q is read]: on the loose slots p comes from the table p(V) (`q` carries the exact pileups; every
+        // workgroup copies the table's compact form to LDS) and q, if any, from its own table by pileup
+        static constexpr decltype(&k_peak_both<false, false>) PEAK_BOTH[2][2] = {{k_peak_both<false, false>, k_peak_both<true, false>},
+                                                                                 {k_peak_both<false, true>, k_peak_both<false, true, true>}};
+        const u32 nShort = S.V ? std::min<u32>(grid.x, (u32)(8 * ctx->numCU)) : grid.x;
+        hipLaunchKernelGGL(PEAK_BOTH[S.V != nullptr][S.V ? S.qLut != nullptr : S.q != nullptr], dim3(nShort + gridW.x), dim3(256), 0, s, nShort,
+                           (const uint4*)ctx->candHdr.as<uint4>(), S.end, S.p, S.V ? reinterpret_cast<const float*>(S.V) : S.q, S.chromOff, nChrom,
+                           (const u32*)(misc + M_NHEADS), (const u32*)ctx->longList.as<u32>(), (const u32*)(misc + M_TICKET3), ctx->par.thr,
+                           ctx->par.min_auc, ctx->par.min_len, ctx->cand.as<gx_peak>(), ctx->valid.as<u32>(), S.qLut);
       }
       // the peaks, in order, into pinned host memory; their number with them
       hipLaunchKernelGGL(k_peaks, dim3(std::min<u32>(rChunks, gridP)), dim3(SW_NT), 0, s, ctx->cand.as<gx_peak>(), ctx->valid.as<u32>(),
@@ -135,6 +125,7 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
       // synchronisation
       if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const u64*>(misc + M_PEAKBP)))
         return rc__;
+      *synced = true;
       R = ctx->mail->R;
       ctx->runSeen = R;
       if (R <= cap) break;
@@ -147,6 +138,7 @@ int run_sweep(gx_ctx* ctx, const SweepSrc& S, u32* nPeaksOut) {
     ctx->runCap = std::max<u64>(ctx->runCap, (u64)R + R / 4 + 1024);
   } else {
     if (int rc__ = mail_sync(ctx, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc__;
+    *synced = true;
   }
   if (R) nPeaks = ctx->mail->nPeaks;
   ctx->nHostPeaks = nPeaks;
