@@ -5,8 +5,7 @@
 // (0 inside -E regions: V_MARK intervals count 0), as an exact int64.
 //
 // k_cov_bins is tile-centric, like k_pack and k_merge2w: one wavefront per tile, which accounts for the tile's own bases
-// [pos0, min(pos0 + TILE, len)) -- the intervals that end inside the tile (the first clipped at pos0) and the tail behind its
-// last breakpoint at the next interval's pileup (loose slots: the next tile's carry; tight arrays: the next interval itself).
+// piece by piece (gx_pileup.h says what a tile's pieces are, in both forms of the pileup).
 // Every piece [s, e) of pileup v is FOUR adds into a per-wavefront LDS strip D of bin-to-bin differences, however many bins
 // it spans -- with bs / be its first / last bin, cs / ce its share of those two and v W the share of every bin between:
 //     D[bs] += cs;  D[bs + 1] += v W - cs;  D[be] += ce - v W;  D[be + 1] -= ce        (bs == be: D[bs] += c; D[bs + 1] -= c)
@@ -17,7 +16,7 @@
 // The strip holds COV_CAP bins: a whole tile's for W >= 8; a tile with more bins (W < 8) is done in passes of COV_CAP bins,
 // each of which reads the tile's intervals again (from the L2).
 #pragma once
-#include "gx_kernels.h"
+#include "gx_pileup.h"
 
 namespace gx {
 
@@ -26,25 +25,7 @@ constexpr u32 COV_CAP = 520;            // bins per pass: TILE / 8 + 1 (a bin cu
 constexpr u32 COV_MAX_W = 1u << 20;     // largest bin
 constexpr u64 COV_MAX_BINS = 1ull << 30;  // ... and most bins of a context (the chromosomes' first bins are 32-bit)
 
-struct CovIn {
-  const u32* end;          // interval ends (chromosome coordinates) and pileups (1/120 units, V_MARK inside -E regions):
-  const int* v;            // the sample's loose slots, or its tight arrays
-  const u32* tileIvOff;    // [nTiles + 1] tight offsets: tile t ends tileIvOff[t + 1] - tileIvOff[t] intervals
-  const TileMeta* meta;    // pos0 / len / flags of every tile; loose: tile t's first slot, and the pileup of its tail in
-                           // meta[t + 1].carry (no breakpoint lies between)
-  const u32* tileChrom;    // [nTiles] the tile's chromosome (k_sbtile's descriptors do not carry it)
-  u32 loose;               // 0: tight arrays (tile t's intervals start at tileIvOff[t]; with -E regions: no carry says V_MARK)
-  const u32* chromBin;     // [nChrom + 1] first bin of each chromosome in `bins`; [nChrom]: all bins
-  u32 nChrom;
-};
-
-__device__ __forceinline__ void cov_sync() {  // (LDS operations of one wavefront execute in order: keep the compiler from reordering them)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ __launch_bounds__(COV_NW * 64) void k_cov_bins(CovIn in, u32 nTiles, u32 W, unsigned long long* __restrict__ bins) {
+__global__ __launch_bounds__(COV_NW * 64) void k_cov_bins(PileIn in, u32 nTiles, u32 W, unsigned long long* __restrict__ bins) {
   __shared__ unsigned long long strip[COV_NW][COV_CAP + 2];
   const int wv = threadIdx.x >> 6, lane = lane_id();
   unsigned long long* D = strip[wv];
@@ -72,7 +53,7 @@ __global__ __launch_bounds__(COV_NW * 64) void k_cov_bins(CovIn in, u32 nTiles, 
       const u32 wlo = max(pos0, org);
       const u32 whi = (u32)min((u64)org + (u64)nb * W, (u64)tEnd);
       for (u32 j = lane; j < nb + 2; j += 64) D[j] = 0;
-      cov_sync();
+      pile_sync();
       u32 prevEnd = pos0;
       for (u32 base = 0; base <= n; base += 64) {   // (piece n is the tail)
         const u32 i = base + lane;
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(COV_NW * 64) void k_cov_bins(CovIn in, u32 nTiles, 
           }
         }
       }
-      cov_sync();
+      pile_sync();
       unsigned long long run = 0;
       for (u32 j0 = 0; j0 < nb; j0 += 64) {
         const u32 j = j0 + lane;
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(COV_NW * 64) void k_cov_bins(CovIn in, u32 nTiles, 
             atomicAdd(&bins[bin0 + b], x);
         }
       }
-      cov_sync();
+      pile_sync();
     }
   }
 }

@@ -9,11 +9,9 @@
 // and the smallest and the largest v met.  The bases at v = 0 are the host's complement (gx_host_depth.h): the tiles of a
 // chromosome the replicate's header does not list are never visited, as in k_cov_bins.
 //
-// k_depth_hist is tile-centric, one wavefront per tile, and walks a tile's pieces exactly as k_cov_bins does: the intervals
-// that end inside the tile, the first clipped at pos0, and the tail behind the last breakpoint at the next interval's pileup
-// (loose slots: the next tile's carry; tight arrays: the next interval itself; TM_LAST: no tail).  V_MARK and v == 0 pieces
-// are ignored.  A piece [s, e) of pileup v is ONE add of e - s to bases[d] of the workgroup's LDS table (and one each to
-// rsum / rsq when r != 0).
+// k_depth_hist is tile-centric, one wavefront per tile, and walks a tile's pieces (gx_pileup.h says what they are, in both
+// forms of the pileup).  A piece [s, e) of pileup v is ONE add of e - s to bases[d] of the workgroup's LDS table (and one each
+// to rsum / rsq when r != 0).
 // Contention: nearly every piece of a real track has d in 1 .. DEPTH_PRIV and r == 0, and their adds meet on DEPTH_PRIV LDS
 // words.  Measured against it (PRIV = true, GX_DEPTH_PRIV): those pieces summed in DEPTH_PRIV registers per lane, reduced over
 // the wavefront once, after its last tile, and added to LDS with one atomic per class and wavefront.  It gains nothing at
@@ -29,7 +27,7 @@
 // the host reallocates to the counted size and runs the pass once more.  No workgroup waits for another; every loop is bounded.
 // All of it integers: the result does not depend on the grid, the list's capacity or the order of the adds.
 #pragma once
-#include "gx_coverage.h"
+#include "gx_pileup.h"
 
 namespace gx {
 
@@ -48,7 +46,7 @@ enum { DEPTH_ST_LIST_FULL = 1, DEPTH_ST_NEGATIVE = 2 };
 struct DepthDeep { u32 v, bases; };   // one deep piece
 
 template <bool PRIV>
-__global__ __launch_bounds__(DEPTH_NW * 64) void k_depth_hist(CovIn in, u32 nTiles, unsigned long long* __restrict__ out,
+__global__ __launch_bounds__(DEPTH_NW * 64) void k_depth_hist(PileIn in, u32 nTiles, unsigned long long* __restrict__ out,
                                                               DepthDeep* __restrict__ deep, u32 deepCap) {
   __shared__ u32 lb[DEPTH_BOUND];
   __shared__ unsigned long long lr[DEPTH_BOUND], lq[DEPTH_BOUND];

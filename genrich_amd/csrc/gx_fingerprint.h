@@ -31,12 +31,6 @@ constexpr u32 FP_GRID = 768;             // most workgroups of a launch unless t
 constexpr u32 FP_MAX_GRID = 65535;       // ... and the most a caller may force along the bin axis (gx_fp_u64)
 // (gx_fp_geometry reports FP_NC, GX_FP_SUB_LOG, FP_NW * 64 and FP_GRID: the tests take the edges they probe from it)
 
-__device__ __forceinline__ unsigned long long fp_wave_sum(unsigned long long v) {   // (every lane has the wavefront's sum)
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // one value slot of a wavefront's step: `have` = this lane holds a value of the row
 template <bool AGG>
 __device__ __forceinline__ void fp_add(unsigned long long v, bool have, int lane, u32& zeros, u32* hc, unsigned long long* hs) {
@@ -55,7 +49,7 @@ __device__ __forceinline__ void fp_add(unsigned long long v, bool have, int lane
       const u32 kl = (u32)__shfl((int)k, leader, 64);
       const bool mine = live && k == kl;
       const unsigned long long same = __ballot(mine);
-      const unsigned long long s = fp_wave_sum(mine ? v : 0ull);
+      const unsigned long long s = wave_sum(mine ? v : 0ull);   // (every lane has it)
       if (lane == leader) {
         atomicAdd(&hc[kl], (u32)__popcll(same));
         atomicAdd(&hs[kl], s);

@@ -30,10 +30,11 @@ int cov_layout(gx_ctx* ctx) {
   return GX_OK;
 }
 
-// The closed sample's pileup as the passes over it read it (k_cov_bins, k_depth_hist), where close_sample left it.  Nothing has
-// stashed, merged or reused the loose slots yet; with -E regions the tight arrays are read (pack_pileup, which runs once per
-// pileup however many passes ask: what the control merge needs there anyway -- no carry says V_MARK).  chromBin stays the caller's.
-int cov_input(gx_ctx* ctx, Pileup& P, CovIn& in) {
+// The closed sample's pileup as all three passes over it read it (gx_pileup.h: k_cov_bins, k_depth_hist, k_profile), where
+// close_sample left it.  Nothing has stashed, merged or reused the loose slots yet; with -E regions the tight arrays are read
+// (pack_pileup, which runs once per pileup however many passes ask: what the control merge needs there anyway -- no carry says
+// V_MARK).  chromBin stays the coverage's.
+int pile_input(gx_ctx* ctx, Pileup& P, PileIn& in) {
   in.tileIvOff = P.tileIvOff.as<u32>();
   in.tileChrom = ctx->dTileChrom.as<u32>();
   in.nChrom = ctx->nChrom;
@@ -48,7 +49,7 @@ int cov_input(gx_ctx* ctx, Pileup& P, CovIn& in) {
   return GX_OK;
 }
 
-// gx_sample_end, coverage on: the sample's pileup (cov_input) summed into a bin array of its own
+// gx_sample_end, coverage on: the sample's pileup (pile_input) summed into a bin array of its own
 int cov_sample(gx_ctx* ctx, int isCtrl) {
   if (ctx->covDirty)
     if (int rc = cov_layout(ctx)) return rc;
@@ -62,8 +63,8 @@ int cov_sample(gx_ctx* ctx, int isCtrl) {
   if (nBins) {
     phase_begin(ctx, isCtrl ? "c.cover" : "t.cover");   // (the zeroing, with -E regions the tight arrays, the pass)
     HIPCHECK(hipMemsetAsync(cs.bins.p, 0, nBins * 8, s));
-    CovIn in{};
-    if (int rc = cov_input(ctx, P, in)) return rc;
+    PileIn in{};
+    if (int rc = pile_input(ctx, P, in)) return rc;
     in.chromBin = ctx->covChromBin.as<u32>();
     const u32 nTiles = ctx->nTiles;
     hipLaunchKernelGGL(k_cov_bins, dim3(std::max(1u, std::min((nTiles + COV_NW - 1) / COV_NW, (u32)(8 * ctx->numCU)))), dim3(COV_NW * 64), 0, s,

@@ -42,7 +42,7 @@ u32 depth_grid(const gx_ctx* ctx) {
   return std::max(1u, std::max(g, std::min(least, all)));
 }
 
-// gx_sample_end, the depth distribution on: one pass over the sample's pileup (cov_input); a second one, with a list of the
+// gx_sample_end, the depth distribution on: one pass over the sample's pileup (pile_input); a second one, with a list of the
 // counted size, when the deep list ran full -- the pileup is still where close_sample left it
 int depth_sample(gx_ctx* ctx, int isCtrl) {
   hipStream_t s = ctx->stream;
@@ -61,8 +61,8 @@ int depth_sample(gx_ctx* ctx, int isCtrl) {
   const u32 nTiles = ctx->nTiles;
   if (nTiles && r.total) {
     phase_begin(ctx, isCtrl ? "c.depth" : "t.depth");   // (with -E regions the tight arrays, the zeroing, the pass or the two)
-    CovIn in{};
-    if (int rc = cov_input(ctx, P, in)) return rc;
+    PileIn in{};
+    if (int rc = pile_input(ctx, P, in)) return rc;
     POOLED(ctx, ctx->depthOut, words * 8);
     const u32 grid = depth_grid(ctx);
     if (int rc = counted_list(ctx, list, h, [&](u32 deepCap) -> int {

@@ -20,7 +20,7 @@ int prof_layout(gx_ctx* ctx) {
   return GX_OK;
 }
 
-// gx_sample_end, profile on: the sample's pileup, where close_sample left it (cov_sample's three forms), summed around every
+// gx_sample_end, profile on: the sample's pileup, where close_sample left it (pile_input's three forms), summed around every
 // anchor -- the aggregate always, the matrix when one is kept
 int prof_sample(gx_ctx* ctx, int isCtrl) {
   if (ctx->profDirty)
@@ -39,16 +39,8 @@ int prof_sample(gx_ctx* ctx, int isCtrl) {
     return pool_failed(ctx);
   }
   phase_begin(ctx, isCtrl ? "c.profile" : "t.profile");   // (with -E regions the tight arrays, the pass, the column sums)
-  CovIn in{};
-  in.tileIvOff = P.tileIvOff.as<u32>();
-  if (ctx->hasBed) {
-    if (int rc = pack_pileup(ctx, P)) return rc;
-    in.end = P.ivEnd.as<u32>(); in.v = P.ivV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 0u;
-  } else if (P.inLoose) {   // (a control: scan_and_close has stashed it for its merge)
-    in.end = P.looseEnd.as<u32>(); in.v = P.looseV.as<int>(); in.meta = P.meta.as<TileMeta>(); in.loose = 1u;
-  } else {
-    in.end = ctx->looseEnd.as<u32>(); in.v = ctx->looseV.as<int>(); in.meta = ctx->tileMeta.as<TileMeta>(); in.loose = 1u;
-  }
+  PileIn in{};
+  if (int rc = pile_input(ctx, P, in)) return rc;
   hipLaunchKernelGGL(k_profile, dim3(grid), dim3(PROF_NW * 64), 0, s, in, ctx->nTiles, ctx->profDev.as<ProfAnchor>(), nA, ctx->profF,
                      ctx->profB, nb, ctx->profKeep ? ps.cells.as<unsigned long long>() : nullptr,
                      ctx->profPartial.as<unsigned long long>());

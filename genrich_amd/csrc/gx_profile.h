@@ -17,17 +17,17 @@
 // k_profile is anchor-centric: a tile-centric pass would have to find the anchors of its tile, and 20,000 windows of 4,000
 // bases touch 40,000 of hg38's 750,000 tiles.  One wavefront per anchor, grid-strided.  The host has resolved the first tile
 // of the anchor's chromosome (layout_tiles knows it: no search here); the window [lo, hi), clipped to [0, len), overlaps the
-// tiles lo / TILE .. (hi - 1) / TILE of it.  Each of them is walked as k_cov_bins walks its tile -- the intervals that end in
-// the tile, the first clipped at the tile's start, then the tail at the next tile's carry (loose slots) or the next interval
-// (tight arrays) -- and every piece, clipped to the window, is the same FOUR adds into a per-wavefront LDS strip of nb + 2
-// bin-to-bin differences whose origin is the window's start and whose width is B.  A 64-bit wave scan of the strip is the row
-// in ascending coordinates; for strand - it is read back mirrored, so that the stores of a row are coalesced on both strands.
+// tiles lo / TILE .. (hi - 1) / TILE of it.  Each of them is walked piece by piece (gx_pileup.h says what a tile's pieces
+// are, in both forms of the pileup), and every piece, clipped to the window, is the FOUR adds of gx_coverage.h into a
+// per-wavefront LDS strip of nb + 2 bin-to-bin differences whose origin is the window's start and whose width is B.  A 64-bit
+// wave scan of the strip is the row in ascending coordinates; for strand - it is read back mirrored, so that the stores of a
+// row are coalesced on both strands.
 // The aggregate costs no atomic: a wavefront keeps the sum of the rows it has made in registers (nb / 64 <= 16 words a lane),
 // the wavefronts of a workgroup add theirs through the strips when their anchors are done, and the workgroup stores one row
 // of `partial`, which k_profile_sum adds up column by column.
 // LDS: PROF_NW strips of 1026 words = 32,832 bytes, static.
 #pragma once
-#include "gx_coverage.h"
+#include "gx_pileup.h"
 
 namespace gx {
 
@@ -44,7 +44,7 @@ struct ProfAnchor {
   u32 len;     // the chromosome's length
 };
 
-__global__ __launch_bounds__(PROF_NW * 64) void k_profile(CovIn in, u32 nTiles, const ProfAnchor* __restrict__ anchors, u32 nAnchors,
+__global__ __launch_bounds__(PROF_NW * 64) void k_profile(PileIn in, u32 nTiles, const ProfAnchor* __restrict__ anchors, u32 nAnchors,
                                                           u32 F, u32 B, u32 nb, unsigned long long* __restrict__ cells /* or null */,
                                                           unsigned long long* __restrict__ partial /* [gridDim.x][nb] */) {
   __shared__ unsigned long long strip[PROF_NW][PROF_MAX_NB + 2];
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(PROF_NW * 64) void k_profile(CovIn in, u32 nTiles, 
       continue;
     }
     for (u32 j = lane; j < nb + 2; j += 64) D[j] = 0;
-    cov_sync();
+    pile_sync();
     const u32 t1 = A.tile0 + (u32)((chi - 1) >> TB);
     for (u32 t = A.tile0 + (u32)(clo >> TB); t <= t1 && t < nTiles; t++) {
       const TileMeta m = in.meta[t];
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(PROF_NW * 64) void k_profile(CovIn in, u32 nTiles, 
         if (prevEnd >= whi) break;   // (the pieces ascend: the rest of the tile lies behind the window)
       }
     }
-    cov_sync();
+    pile_sync();
     unsigned long long run = 0;
     for (u32 j0 = 0; j0 < nb; j0 += 64) {
       const u32 j = j0 + lane;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(PROF_NW * 64) void k_profile(CovIn in, u32 nTiles, 
       run = __shfl(x, 63, 64);
       if (j < nb) D[j] = x;
     }
-    cov_sync();
+    pile_sync();
 #pragma unroll
     for (int k = 0; k < PROF_SLOTS; k++) {
       const u32 j = (u32)k * 64 + lane;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(PROF_NW * 64) void k_profile(CovIn in, u32 nTiles, 
         acc[k] += x;
       }
     }
-    cov_sync();
+    pile_sync();
   }
   // (every wavefront gets here: the grid-stride loop has no other exit)
 #pragma unroll
