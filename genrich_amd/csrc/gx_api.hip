@@ -24,6 +24,7 @@
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
+#include "gx_host_summits.h"
 
 namespace {
 
@@ -348,6 +349,8 @@ int gx_reset(gx_ctx* ctx) {
   ctx->ivs.clear();
   ctx->ivsReady = ctx->ivsUsed = false;
   ctx->psigReady = false;   // (gx_peak_signal's records go with the peaks; the buffers stay)
+  ctx->sumRes.clear();      // (gx_peak_summits' summits too)
+  ctx->sumReady = false;
   repro_drop(ctx);          // (gx_reproducibility's calls and k_sub_split's bit)
   if (ctx->satChild || ctx->subUsed || !ctx->subBufs.empty()) sat_drop(ctx);   // (the child context goes; the buffers stay with the pool)
   ctx->peaksReady = false;
@@ -366,7 +369,7 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   ctx->specRuns.valid = false;   // (a control or a further replicate: the sweep will not be the one the run pass was launched for)
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
-    ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
+    ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = false;
     // (a further replicate: the previous one's loose slots, tile tables and p(V) table are about to be reused)
     for (size_t r = 0; r < ctx->reps.size(); r++)
       if (ctx->reps[r].loose || ctx->reps[r].pilesPending)
@@ -669,7 +672,7 @@ int gx_pvalues(gx_ctx* ctx) {
 int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* peak_bp) {
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
-  ctx->peaksReady = ctx->countsReady = ctx->psigReady = false;
+  ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = false;
   const CallPlan& P = ctx->called;
   u32 nPeaks = 0;
   // (at most two plans: -q on the loose slots may be called off by the device, and the call is then planned again without it)
@@ -1489,6 +1492,90 @@ int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const
 }
 
 int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out) { return gx_write_peak_signal_group(&ctx, 1, names, out); }
+
+int gx_peak_summits(gx_ctx* ctx, int prominence_pct, int height_pct, size_t* n) {
+  if (!ctx || !ctx->countOn || !ctx->peaksReady || ctx->phase != 0) return GX_ERR_ORDER;
+  if (prominence_pct < 0 || prominence_pct > 100 || height_pct < 0 || height_pct > 100) return refuse(ctx, "gx_peak_summits: a percentage outside 0..100");
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->sumReady = false;
+  if (int rc = peak_summits_kept(ctx, (u32)prominence_pct, (u32)height_pct)) return rc;
+  if (n) *n = ctx->sumRes.size();
+  return GX_OK;
+}
+
+int gx_get_peak_summits(gx_ctx* ctx, gx_summit* out, size_t cap) {
+  if (!ctx || !ctx->sumReady || (cap && !out)) return GX_ERR_ORDER;
+  if (const size_t m = std::min(cap, ctx->sumRes.size())) memcpy(out, ctx->sumRes.data(), m * sizeof(gx_summit));
+  return GX_OK;
+}
+
+int gx_peak_summits_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_region* peaks, size_t n_peaks, int prominence_pct, int height_pct,
+                           unsigned grid, unsigned run_cap, size_t list_cap, gx_summit* out, size_t cap, size_t* n_out) {
+  if (!ctx || ctx->nChrom == 0 || (n && !ev) || (n_peaks && !peaks) || (cap && !out)) return GX_ERR_ORDER;
+  if (int rc = guard_closed(ctx, "gx_peak_summits_events")) return rc;
+  if (prominence_pct < 0 || height_pct < 0) return refuse(ctx, "gx_peak_summits_events: a negative percentage");
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<gx_summit> res;
+  if (int rc = peak_summits_events(ctx, ev, n, peaks, n_peaks, (u32)prominence_pct, (u32)height_pct, grid, run_cap, list_cap, res)) return rc;
+  if (const size_t m = std::min(cap, res.size())) memcpy(out, res.data(), m * sizeof(gx_summit));
+  if (n_out) *n_out = res.size();
+  return GX_OK;
+}
+
+int gx_peak_summits_last(gx_ctx* ctx, unsigned* reruns, unsigned* big_peaks) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (reruns) *reruns = ctx->sumLastReruns;
+  if (big_peaks) *big_peaks = ctx->sumLastBig;
+  return GX_OK;
+}
+
+int gx_peak_summits_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_t* run_cap, uint64_t* list_min, uint32_t* list_per_peak,
+                             uint64_t* max_events) {
+  if (lanes) *lanes = SUM_NT;
+  if (grid) *grid = (int)SUM_GRID;
+  if (step_bases) *step_bases = PSIG_STEP;
+  if (run_cap) *run_cap = SUM_RUN_CAP;
+  if (list_min) *list_min = SUM_LIST_MIN;
+  if (list_per_peak) *list_per_peak = 2;
+  if (max_events) *max_events = PSIG_MAX_EVENTS - 1;
+  return GX_OK;
+}
+
+// (here, not in gx_emit.cpp, like the other writers over contexts that run their pass themselves)
+int gx_write_summits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out) {
+  if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
+  // the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group), their summits following them
+  std::vector<gx_peak> pk;
+  std::vector<gx_summit> sm;
+  for (int g = 0; g < n_ctx; g++) {
+    size_t k = 0, n = 0;
+    if (int rc = gx_peak_summits(ctxs[g], prominence_pct, height_pct, &n)) return rc;
+    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
+    const size_t at0 = pk.size(), s0 = sm.size();
+    pk.resize(at0 + k);
+    if (k)
+      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
+    sm.resize(s0 + n);
+    if (int rc = gx_get_peak_summits(ctxs[g], sm.data() + s0, n)) return rc;
+    for (size_t i = s0; i < sm.size(); i++) sm[i].peak += (uint32_t)at0;
+  }
+  std::vector<size_t> ord(pk.size()), rank(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+  if (n_ctx > 1)
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
+  std::vector<gx_region> reg(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) {
+    reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
+    rank[ord[i]] = i;
+  }
+  for (gx_summit& s : sm) s.peak = (uint32_t)rank[s.peak];
+  if (n_ctx > 1) std::sort(sm.begin(), sm.end(), [](const gx_summit& a, const gx_summit& b) { return a.peak != b.peak ? a.peak < b.peak : a.pos < b.pos; });
+  return gx_format_summits(out, names, reg.data(), reg.size(), sm.data(), sm.size());
+}
+
+int gx_write_summits(gx_ctx* ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out) {
+  return gx_write_summits_group(&ctx, 1, names, prominence_pct, height_pct, out);
+}
 
 int gx_complexity(gx_ctx* ctx, int* n_samples) {
   if (!ctx) return GX_ERR_ORDER;

@@ -263,6 +263,33 @@ int gx_format_peak_signal(FILE* out, const char* const* names, const gx_region* 
   return GX_OK;
 }
 
+// --summits (no Genrich counterpart): one row per summit of the pooled treatment depth, BED in its first six columns; host only,
+// no context.  The summits come ascending in (peak, pos), each peak's numbered from 1; the peaks' names are the narrowPeak's.
+int gx_format_summits(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const gx_summit* summits, size_t n) {
+  if (!out || (n && (!summits || !peaks || !names))) return GX_ERR_ORDER;
+  for (size_t i = 0; i < n; i++) {
+    const gx_summit& s = summits[i];
+    if (s.peak >= n_peaks || s.width == 0 || s.pos < (s.width - 1) / 2) return GX_ERR_ORDER;
+    const uint64_t a = s.pos - (s.width - 1) / 2;
+    if (a + s.width > (uint64_t)peaks[s.peak].end - peaks[s.peak].start) return GX_ERR_ORDER;
+    if (i && (summits[i - 1].peak > s.peak || (summits[i - 1].peak == s.peak && summits[i - 1].pos >= s.pos))) return GX_ERR_ORDER;
+  }
+  fprintf(out, "chr\tstart\tend\tname\theight\tstrand\tplateau_start\tplateau_end\tprominence\tpeak_start\tpeak_end\n");
+  size_t j = 0;
+  for (size_t i = 0; i < n; i++) {
+    const gx_summit& s = summits[i];
+    const gx_region& k = peaks[s.peak];
+    j = i && summits[i - 1].peak == s.peak ? j + 1 : 1;
+    const long at = (long)k.start + (long)s.pos, a = at - (long)((s.width - 1) / 2);
+    fprintf(out, "%s\t%ld\t%ld\tpeak_%u.%zu", names[k.chrom], at, at + 1, s.peak, j);
+    put_count(out, (long long)s.height120);
+    fprintf(out, "\t.\t%ld\t%ld", a, a + (long)s.width);
+    put_count(out, (long long)s.prominence120);
+    fprintf(out, "\t%ld\t%ld\n", (long)k.start, (long)k.end);
+  }
+  return GX_OK;
+}
+
 // --region-counts: one row per region in the caller's order, the contexts' counts added (a region lies on one chromosome, which
 // one context owns; the others count 0 there)
 int gx_write_region_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_region* regions,

@@ -38,6 +38,7 @@
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
+#include "gx_summits.h"
 
 using namespace gx;
 
@@ -591,6 +592,14 @@ struct gx_ctx {
   PinnedBuf psigHost, psigEvHost; // the last gx_peak_signal's records (until gx_reset); the last gx_peak_signal_events'
   size_t psigPk = 0;              // peaks of the last gx_peak_signal
   bool psigReady = false;
+  // the summits of the pooled treatment depth inside the called peaks (gx_peak_summits / gx_peak_summits_events, gx_summits.h):
+  // the peak space is psigSpace (each pass drains the stream); nothing here exists before the first call
+  DevBuf sumOut, sumFlag, sumList;            // the control words, the flagged peaks' run totals [peak], the summit list
+  DevBuf sumBig, sumScrStart, sumScrVal, sumScrBlk;   // the second launch: the flagged peaks, the HBM scratch of their runs and blocks
+  PinnedBuf sumMaxHost;                       // the samples' maxima, when the pooled events alone do not settle the domain
+  std::vector<gx_summit> sumRes;              // the last gx_peak_summits' summits, by (peak, pos) (until gx_reset)
+  bool sumReady = false;
+  u32 sumLastReruns = 0, sumLastBig = 0;      // the last pass: how often it ran again, the peaks its second launch took
   // subsamples of the kept samples' events and the peak saturation curve (gx_subsample_*, gx_saturation, gx_subsample.h);
   // nothing here exists before the first call
   DevBuf subCnt, subOff;          // k_sub_count's counts per block, k_sub_scan's offsets

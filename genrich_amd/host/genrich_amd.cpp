@@ -171,6 +171,21 @@ void usageReproducibility() {
   exit(EXIT_FAILURE);
 }
 
+// --help-summits: the block of --summits and its sub-options, likewise
+void usageSummits() {
+  fprintf(stderr,
+          "  --summits FILE [--summits-prominence PCT] [--summits-height PCT]   the local maxima of the treatments' pooled depth\n"
+          "                  (controls never; -E regions not masked) inside every called peak: a TSV, BED in its first six columns,\n"
+          "                  one row per summit -- chr, summit, summit + 1, peak_N.j (j = 1, 2, ... from left to right in peak_N of\n"
+          "                  -o), height, ., the plateau's start and end, prominence, the peak's start and end.  A plateau of equal\n"
+          "                  depth is a maximum when the depth is lower on both sides; the summit is its middle.  The prominence is\n"
+          "                  the height over the higher of the two lowest depths between the plateau and the nearest higher base (or\n"
+          "                  the peak's end) on either side.  The highest maximum of a peak is always reported, every other one\n"
+          "                  whose prominence is at least PCT %% (25; 0 .. 100) of its height and whose height is at least PCT %% (50;\n"
+          "                  0 .. 100) of the peak's highest; -v: the peaks with more than one summit; not with -X, -P or --events-only\n");
+  exit(EXIT_FAILURE);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -224,6 +239,10 @@ int main(int argc, char** argv) {
                                      {"reproducibility-seed", required_argument, nullptr, 1042},
                                      {"reproducibility-peaks", required_argument, nullptr, 1043},
                                      {"help-reproducibility", no_argument, nullptr, 1044},
+                                     {"summits", required_argument, nullptr, 1045},
+                                     {"summits-prominence", required_argument, nullptr, 1046},
+                                     {"summits-height", required_argument, nullptr, 1047},
+                                     {"help-summits", no_argument, nullptr, 1048},
                                      {nullptr, 0, nullptr, 0}};
   int nThreads;  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
   {
@@ -359,6 +378,22 @@ int main(int argc, char** argv) {
       }
       case 1043: o.reproPrefix = optarg; break;
       case 1044: usageReproducibility();
+      case 1045: o.summitsFile = optarg; break;
+      case 1046: {
+        __int128 v;
+        if (!strictInt(optarg, 0, 100, &v)) die(optarg, ": --summits-prominence takes an integer in [0, 100]");
+        o.summitsProminence = (int)v;
+        o.summitsProminenceOpt = true;
+        break;
+      }
+      case 1047: {
+        __int128 v;
+        if (!strictInt(optarg, 0, 100, &v)) die(optarg, ": --summits-height takes an integer in [0, 100]");
+        o.summitsHeight = (int)v;
+        o.summitsHeightOpt = true;
+        break;
+      }
+      case 1048: usageSummits();
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -385,6 +420,10 @@ int main(int argc, char** argv) {
   // (the signal is taken in the peaks this run calls, from the events the library keeps: none with -X, -P or --events-only)
   if (o.peakSignalFile && !o.callsPeaks())
     die("", "--peak-signal needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
+  // (the summits are taken in the peaks this run calls, from the events the library keeps: none with -X, -P or --events-only)
+  if (o.summitsFile && !o.callsPeaks())
+    die("", "--summits needs the peaks and the intervals of this run (not with -X, -P or --events-only)");
+  if ((o.summitsProminenceOpt || o.summitsHeightOpt) && !o.summitsFile) die("", "--summits-prominence and --summits-height need --summits FILE");
   if ((o.regionsBed != nullptr) != (o.regionCountsFile != nullptr)) die("", "--count-regions BED and --region-counts FILE need each other");
   // (the regions count the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.regionsBed && !o.buildsPileups()) die("", "--count-regions needs the intervals of this run (not with -P or --events-only)");
@@ -505,7 +544,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.peakSignalFile || o.regionsBed || o.complexityFile || o.saturationFile || o.reproOn() || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
+      if (o.countsFile || o.peakSignalFile || o.summitsFile || o.regionsBed || o.complexityFile || o.saturationFile || o.reproOn() || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
         check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
@@ -673,6 +712,7 @@ int main(int argc, char** argv) {
   }
   if (o.countsFile) writeCounts(S, names, sampleNames);
   if (o.peakSignalFile) writePeakSignal(S, names, (int)sampleNames.size());
+  if (o.summitsFile) writeSummits(S, names);
   if (o.regionsBed) writeRegionCounts(S, sampleNames);
   if (o.coveragePrefix) writeCoverage(S, names);
   if (o.correlationFile) writeCorrelation(S);

@@ -142,6 +142,36 @@ void writePeakSignal(State& S, const std::vector<const char*>& names, int nS) {
   }
 }
 
+// --summits FILE: every local maximum of the treatments' pooled depth inside the peaks just called that stands out by
+// --summits-prominence percent of its height and reaches --summits-height percent of the peak's highest
+// (gx_write_summits_group); with -v the peaks, the summits, the peaks with more than one, the most in one peak and the peaks
+// without pooled depth (no summit)
+void writeSummits(State& S, const std::vector<const char*>& names) {
+  writeFile(S, S.o.summitsFile, [&](FILE* f) {
+    return gx_write_summits_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), S.o.summitsProminence, S.o.summitsHeight, f);
+  });
+  if (!S.o.verbose) return;
+  size_t peaks = 0, summits = 0, multi = 0, most = 0, none = 0;
+  for (gx_ctx* g : S.devs.ctx) {
+    size_t k = 0, n = 0;
+    check(S, gx_peak_count(g, &k), g);
+    check(S, gx_peak_summits(g, S.o.summitsProminence, S.o.summitsHeight, &n), g);   // (the count; the writer's pass left the result)
+    std::vector<gx_summit> sm(n);
+    check(S, gx_get_peak_summits(g, sm.data(), n), g);
+    std::vector<size_t> per(k, 0);
+    for (const gx_summit& s : sm) per[s.peak]++;
+    for (size_t c : per) {
+      multi += c > 1;
+      none += c == 0;
+      most = std::max(most, c);
+    }
+    peaks += k;
+    summits += n;
+  }
+  fprintf(stderr, "  Summits in peaks: %zu peaks, %zu summits, %zu peaks with more than one, at most %zu in a peak, %zu peaks without pooled depth\n",
+          peaks, summits, multi, most, none);
+}
+
 // --count-regions BED --region-counts FILE: the same intervals counted in the BED's regions, which may overlap and come in any
 // order; exactly one output row per BED line, in the BED's order, so that the files of two runs line up.  The BED is read with
 // -E's rules (loadBED); a 4th column names the row, further columns are ignored (a narrowPeak file is valid input).

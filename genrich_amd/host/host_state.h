@@ -17,6 +17,7 @@ struct Opts {
              *bedFile = nullptr, *xFile = nullptr, *dupsFile = nullptr, *xchrom = nullptr,
              *countsFile = nullptr,  // --counts: each sample's intervals counted in the peaks (no Genrich counterpart)
              *peakSignalFile = nullptr,  // --peak-signal: each sample's own depth inside the peaks: height, summit, area
+             *summitsFile = nullptr,  // --summits: the local maxima of the treatments' pooled depth inside the peaks
              *regionsBed = nullptr, *regionCountsFile = nullptr,  // --count-regions BED --region-counts FILE: ... in given regions
              *coveragePrefix = nullptr,  // --coverage PREFIX: a binned bedGraph track per sample (no Genrich counterpart)
              *profileBed = nullptr, *profilePrefix = nullptr;  // --profile BED --profile-out PREFIX: signal around anchor sites
@@ -60,6 +61,8 @@ struct Opts {
   bool reproSeedOpt = false;
   const char* reproPrefix = nullptr;       // --reproducibility-peaks PREFIX: every call's narrowPeak, the conservative and the optimal set
   bool reproOn() const { return reproFile || reproMetricsFile; }
+  int summitsProminence = 25, summitsHeight = 50;   // --summits-prominence PCT, --summits-height PCT
+  bool summitsProminenceOpt = false, summitsHeightOpt = false;
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;

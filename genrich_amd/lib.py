@@ -50,6 +50,7 @@ class PeakCounts(NamedTuple):
 
 GX_PATH_REGION_COUNTS = 131072   # gx_path_info bit 17: gx_count_in_regions has counted since the last reset
 REGION_DTYPE = np.dtype([("chrom", "<u4"), ("start", "<u4"), ("end", "<u4")])   # gx_region
+SUMMIT_DTYPE = np.dtype([("peak", "<u4"), ("pos", "<u4"), ("width", "<u4"), ("pad", "<u4"), ("height", "<i8"), ("prominence", "<i8")])   # gx_summit
 
 
 class RegionCounts(NamedTuple):
@@ -326,6 +327,16 @@ _SIGS = {
     "gx_format_peak_signal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 7,
     "gx_write_peak_signal_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_peak_signal": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_peak_summits": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)],
+    "gx_get_peak_summits": [C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_peak_summits_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint, C.c_uint, C.c_size_t,
+                               C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_peak_summits_last": [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)],
+    "gx_peak_summits_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+    "gx_format_summits": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t],
+    "gx_write_summits_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "gx_write_summits": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "gx_set_coverage_bins": [C.c_void_p, C.c_uint32],
     "gx_coverage_samples": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_coverage_bin_count": [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)],
@@ -733,6 +744,29 @@ def format_peak_signal(names, peaks, samples) -> bytes:
     ctrl = (C.c_int * max(S, 1))(*[int(x.is_ctrl) for x in samples])
     cn = _c_names(list(names))
     return _to_tmpfile(lambda f: lib.gx_format_peak_signal(f, cn, reg.ctypes.data if reg.size else None, reg.size, S, rep, ctrl, *ptrs))
+
+
+def peak_summits_geometry():
+    """(lanes of a workgroup of k_summits, its most workgroups, bases a wavefront covers per step, the runs of a peak a
+    wavefront holds, the summit list's least first capacity, its entries per peak beyond that, the most events
+    peak_summits_events takes) -- gx_peak_summits_geometry; needs no GPU."""
+    lib = load_library()
+    lanes, grid, step, runs, most = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    lmin, lper = C.c_uint64(0), C.c_uint32(0)
+    rc = lib.gx_peak_summits_geometry(C.byref(lanes), C.byref(grid), C.byref(step), C.byref(runs), C.byref(lmin), C.byref(lper), C.byref(most))
+    if rc:
+        raise RuntimeError(f"gx_peak_summits_geometry: {rc}")
+    return lanes.value, grid.value, step.value, runs.value, lmin.value, lper.value, most.value
+
+
+def format_summits(names, peaks, summits) -> bytes:
+    """--summits' text (gx_format_summits) of `summits` (SUMMIT_DTYPE, ascending in (peak, pos)) in `peaks` (REGION_DTYPE, or
+    rows of (chrom, start, end)); host-only, needs no GPU."""
+    lib = load_library()
+    reg = _regions(peaks)
+    sm = np.ascontiguousarray(summits, dtype=SUMMIT_DTYPE)
+    cn = _c_names(list(names))
+    return _to_tmpfile(lambda f: lib.gx_format_summits(f, cn, reg.ctypes.data if reg.size else None, reg.size, sm.ctypes.data if sm.size else None, sm.size))
 
 
 def xcor_geometry():
@@ -1554,6 +1588,45 @@ class Genrich:
         """--peak-signal's text (gx_write_peak_signal) of this context; runs the pass."""
         cn = self._names(names)
         return _to_tmpfile(lambda f: self.lib.gx_write_peak_signal(self.ctx, cn, f))
+
+    # -- the summits of the pooled treatment depth inside the peaks (include/genrich_amd.h, gx_peak_summits) ---------------
+    def peak_summits(self, prominence_pct=25, height_pct=50):
+        """The summits (SUMMIT_DTYPE, ascending in (peak, pos)) of the kept treatments' pooled depth inside the peaks of the
+        last find_peaks (gx_peak_summits); needs set_count_in_peaks(True)."""
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_peak_summits(self.ctx, int(prominence_pct), int(height_pct), C.byref(n)))
+        out = np.zeros(n.value, dtype=SUMMIT_DTYPE)
+        self._check(self.lib.gx_get_peak_summits(self.ctx, out.ctypes.data if n.value else None, n.value))
+        return out
+
+    def peak_summits_events(self, events, peaks, prominence_pct=25, height_pct=50, grid=0, run_cap=0, list_cap=0):
+        """The summits of host events (EVENT_DTYPE) taken as one sample over this context's chromosome table, in the peaks
+        given (REGION_DTYPE or rows of (chrom, start, end): sorted, disjoint), by the same kernels (gx_peak_summits_events);
+        grid, run_cap, list_cap = 0: the library's."""
+        ev = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+        reg = _regions(peaks)
+        k = int(reg.size)
+        out = np.zeros(max(4096, 4 * k), dtype=SUMMIT_DTYPE)
+        for _ in range(2):
+            n = C.c_size_t(0)
+            self._check(self.lib.gx_peak_summits_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, reg.ctypes.data if k else None, k,
+                                                        int(prominence_pct), int(height_pct), int(grid), int(run_cap), int(list_cap),
+                                                        out.ctypes.data, out.size, C.byref(n)))
+            if n.value <= out.size:
+                break
+            out = np.zeros(n.value, dtype=SUMMIT_DTYPE)
+        return out[:n.value].copy()
+
+    def peak_summits_last(self):
+        """(how often the last summit pass ran again for a full list, the peaks its second launch took) -- gx_peak_summits_last."""
+        r, b = C.c_uint(0), C.c_uint(0)
+        self._check(self.lib.gx_peak_summits_last(self.ctx, C.byref(r), C.byref(b)))
+        return r.value, b.value
+
+    def summits_text(self, names, prominence_pct=25, height_pct=50) -> bytes:
+        """--summits' text (gx_write_summits) of this context; runs the pass."""
+        cn = self._names(names)
+        return _to_tmpfile(lambda f: self.lib.gx_write_summits(self.ctx, cn, int(prominence_pct), int(height_pct), f))
 
     # -- counting in a given region set (include/genrich_amd.h, gx_count_in_regions) ----------------------------------
     def count_in_regions(self, regions):

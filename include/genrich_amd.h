@@ -330,6 +330,56 @@ int gx_peak_signal_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_re
                           uint32_t* covered, int64_t* at_summit120);
 int gx_peak_signal_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_t* slot_pad, uint64_t* max_events);
 
+/* ---- sub-summits inside each called peak from the POOLED treatment depth (no Genrich counterpart: a narrowPeak line has one
+ *      summit, and a wide peak over two binding sites has two maxima) ----
+ * Pooled depth: the sum over all kept TREATMENT samples (controls never) of the depth gx_peak_signal defines: +w at s, -w at
+ * the clamped e, w = 120 / count; empty intervals add nothing, intervals with e < s add -w over [e, s); -E regions are not
+ * masked.  Per peak [ps, pe) that is d(x), x in [0, L), int64 in 1/120 units.
+ * A PLATEAU is a maximal run [a, b) of equal d.  It is a LOCAL MAXIMUM when d is strictly lower on both sides; a side that lies
+ * outside the peak counts as lower.  Per local maximum of height h:
+ *     pos    = a + (b - a - 1) / 2, the plateau's middle rounded down       width = b - a
+ *     prominence = h - max(baseL, baseR); a side's base is the minimum of d over the bases between the plateau and the nearest
+ *              base on that side with d > h strictly (none: up to the peak's end); a side whose range is empty (the plateau
+ *              touches the peak's edge) is left out of the max; both empty (the plateau is the whole peak): the base is 0.
+ *              For interior maxima this is scipy.signal.peak_prominences with wlen=None.
+ * Reported: the peak's highest local maximum when h > 0 (of equal maxima the leftmost); every other local maximum with h > 0
+ * and  prominence * 100 >= P * h  and  h * 100 >= R * hmax  -- integers, equality keeps the summit; P = prominence_pct, R =
+ * height_pct, both 0..100 (the command line's defaults, 25 and 50, are a choice, not a measurement).  A peak whose pooled
+ * depth is nowhere positive has no summit.  The summits are ordered by (peak, pos).  Exact integers: no figure depends on the
+ * launch geometry, the order of the adds, the push mode or the number of contexts.
+ * Domain: a pooled depth below 2^31 (1/120 units) at every base.  Fewer than 2^31 / 120 pooled treatment events cannot leave
+ * it; with more, the samples' own maxima per peak are taken first, and a peak in which they add up to 2^31 or more: GX_ERR_ORDER
+ * with a text.
+ *
+ * gx_peak_summits: after gx_find_peaks, with gx_set_count_in_peaks on (else GX_ERR_ORDER); a percentage outside 0..100:
+ *   GX_ERR_ORDER with a text.  gx_peak_signal's peak space is cleared once and every kept treatment's k_psig_scatter adds into
+ *   it; k_summits (gx_summits.h) gives a wavefront per peak; a peak with more runs than a wavefront's LDS holds is taken by a
+ *   second launch with an HBM scratch of the counted size; the summit list is read once more when it ran full.  *n: the
+ *   summits.  May be called again, with other percentages; no peak or no treatment is legal (no summit).  Under gx_set_owned a
+ *   context handles the peaks of the chromosomes it owns.  gx_get_peak_signal's result stays readable; gx_reset drops this
+ *   one.  Its phase is "summits".  Nothing of it is allocated or launched before the first call.
+ * gx_get_peak_summits: min(cap, n) summits of the last pass; peak is the index into gx_get_peaks, pos counts from its start.
+ * gx_peak_summits_events: the same kernels over n events in host memory, all ONE sample, in n_peaks peaks the caller gives, as
+ *   gx_peak_signal_events takes them and with its refusals (GX_ERR_ORDER with a text before anything is allocated or
+ *   launched); a percentage above 100 is refused likewise.  grid = 0: the library's geometry, else that many workgroups for
+ *   every kernel.  run_cap: the runs a wavefront holds before a peak goes to the second launch (0 or more than the library's:
+ *   the library's); list_cap: the list's first capacity (0: the library's).  min(cap, *n_out) summits are written.  It leaves
+ *   gx_get_peak_summits' result alone.
+ * gx_peak_summits_last: of the last pass of either kind, how often it ran again for a full list (0 or 1) and the peaks its
+ *   second launch took.
+ * gx_peak_summits_geometry: without a device: the lanes of a workgroup of k_summits (a wavefront of 64 per peak), its most
+ *   workgroups with grid = 0, the bases a wavefront covers per step, the runs a wavefront holds, the list's first capacity
+ *   max(list_min, list_per_peak * peaks), and the most events gx_peak_summits_events takes.  Any pointer may be NULL. */
+typedef struct { uint32_t peak, pos, width, pad; int64_t height120, prominence120; } gx_summit;
+int gx_peak_summits(gx_ctx* ctx, int prominence_pct, int height_pct, size_t* n);
+int gx_get_peak_summits(gx_ctx* ctx, gx_summit* out, size_t cap);
+int gx_peak_summits_events(gx_ctx* ctx, const gx_event* ev, size_t n, const gx_region* peaks, size_t n_peaks, int prominence_pct,
+                           int height_pct, unsigned grid, unsigned run_cap, size_t list_cap, gx_summit* out, size_t cap,
+                           size_t* n_out);
+int gx_peak_summits_last(gx_ctx* ctx, unsigned* reruns, unsigned* big_peaks);
+int gx_peak_summits_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_t* run_cap, uint64_t* list_min,
+                             uint32_t* list_per_peak, uint64_t* max_events);
+
 /* ---- binned coverage tracks per sample (no Genrich counterpart: -k, printPile Genrich.c:1697-1715, prints a replicate's pileups
  *      per run-length interval, the control's already scaled and floored; a track wants each sample's own pileup in bins) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_count_in_peaks: for replicate r its treatment, then its
@@ -903,6 +953,17 @@ int gx_format_peak_signal(FILE* out, const char* const* names, const gx_region* 
                           const uint32_t* const* summit, const uint32_t* const* covered, const int64_t* const* at_summit120);
 int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out);
 int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out);
+/* --summits (no Genrich counterpart).  gx_format_summits: host only, no context.  The header
+ * "chr\tstart\tend\tname\theight\tstrand\tplateau_start\tplateau_end\tprominence\tpeak_start\tpeak_end", then one row per summit
+ * (ascending in (peak, pos), else GX_ERR_ORDER): names[chrom], summit, summit + 1, peak_N.j with N the peak's index and j = 1,
+ * 2, ... from left to right within it, the height, ".", the plateau [start, end), the prominence, the peak's start and end --
+ * narrowPeak coordinates; height and prominence printed as --counts prints a count.  n == 0 is legal.
+ * gx_write_summits_group: runs gx_peak_summits on every context, merges their peaks as gx_write_narrowpeak_group does (the same
+ * peak_N) and formats.  gx_write_summits: one context. */
+int gx_format_summits(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const gx_summit* summits,
+                      size_t n);
+int gx_write_summits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out);
+int gx_write_summits(gx_ctx* ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out);
 /* --coverage (no Genrich counterpart; printPile 1697 is what -k prints instead): bedGraph without a header line.
  * gx_format_coverage: host only, no context.  One chromosome's bins (n_bins = ceil(len / bin_size) sums in 1/120 units) as lines
  * "chrom\tstart\tend\tvalue\n" that tile [0, len) with no gap and no overlap, zero runs included.  Adjacent bins are merged
