@@ -21,6 +21,7 @@
 #include "gx_host_complexity.h"
 #include "gx_host_ivstat.h"
 #include "gx_host_xcor.h"
+#include "gx_host_gcbias.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
@@ -75,6 +76,10 @@ int xc_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::XcResult& sum) {
   return group_sum(ctxs, n_ctx, sample, &gx_ctx::xc, any_goes,
                    [](const gx_ctx* c, const gx_ctx* c0, const auto& r, const auto& r0) { return c->xcLo == c0->xcLo && c->xcHi == c0->xcHi && same_sample(r, r0); },
                    xc_add, sum);
+}
+int gc_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::GcResult& sum) {
+  return group_sum(ctxs, n_ctx, sample, &gx_ctx::gcRes, [](const gx_ctx* c) { return c->gcReady; },
+                   [](const gx_ctx*, const gx_ctx*, const auto& r, const auto& r0) { return r.W == r0.W && same_sample(r, r0); }, gc_add, sum);
 }
 // The writers that run their pass themselves: on every context, which all report as many samples (*nS)
 int pass_on_all(gx_ctx* const* ctxs, int n_ctx, int (*pass)(gx_ctx*, int*), int* nS) {
@@ -208,6 +213,7 @@ void gx_destroy(gx_ctx* ctx) {
   for (hipEvent_t e : ctx->evPool) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->stageFree) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->xcStageFree) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->gcStageFree) if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
 
@@ -236,6 +242,7 @@ int gx_set_chroms(gx_ctx* ctx, int n, const uint32_t* len, const uint8_t* skip, 
   ctx->covDirty = true;
   ctx->profDirty = true;
   ctx->xcDirty = ctx->xcOn;
+  ctx->gcDirty = ctx->gcOn;   // (the genome is laid out again, empty: its bases are pushed again)
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -308,6 +315,7 @@ int gx_set_owned(gx_ctx* ctx, const uint8_t* owned) {
   ctx->covDirty = true;
   ctx->profDirty = true;
   ctx->xcDirty = ctx->xcOn;
+  ctx->gcDirty = ctx->gcOn;   // (the genome is laid out again, empty: its bases are pushed again)
   int rc = layout_tiles(ctx);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(ctx->stream));
@@ -341,6 +349,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_profile(ctx);    // (... and gx_set_profile's)
   drop_depth(ctx);      // (... and gx_set_depth_hist's)
   drop_xcor(ctx);       // (... and gx_set_xcor's)
+  drop_gcbias(ctx);     // (gx_gc_bias' results; the genome stays)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
@@ -876,7 +885,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->gcUsed ? GX_PATH_GC : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
   return GX_OK;
 }
 
@@ -1824,6 +1833,133 @@ int gx_write_xcor_group(gx_ctx* const* ctxs, int n_ctx, int read_len, FILE* curv
   if (metrics)
     if (int rc = gx_format_xcor_metrics(metrics, nS, rep.data(), ctrl.data(), N.data(), nP.data(), nM.data(), lo, hi, pc.data(), read_len)) return rc;
   return GX_OK;
+}
+
+int gx_set_genome(gx_ctx* ctx, int on) {
+  if (!ctx || ctx->nChrom == 0) return GX_ERR_ORDER;   // the table is known
+  if (int rc = guard_closed(ctx, "gx_set_genome")) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  HIPCHECK(hipStreamSynchronize(ctx->stream));
+  drop_gcbias(ctx);
+  if (!on) {   // off: the vectors go
+    ctx->gcOn = ctx->gcDirty = false;
+    ctx->gcVec.release();
+    ctx->gcAcgt.release();
+    ctx->gcDir.release();
+    ctx->gcPushed.clear();
+    return GX_OK;
+  }
+  if (int rc = gc_layout(ctx)) return rc;
+  ctx->gcOn = true;
+  return GX_OK;
+}
+
+int gx_push_sequence(gx_ctx* ctx, int chrom, uint64_t first_base, const char* bases, size_t n) {
+  if (!ctx || !ctx->gcOn || (n && !bases)) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  return gc_push(ctx, chrom, first_base, bases, n);
+}
+
+int gx_genome_info(gx_ctx* ctx, uint64_t* bases_pushed, uint64_t* gc, uint64_t* acgt) {
+  if (!ctx || !ctx->gcOn) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = gc_current(ctx)) return rc;
+  std::vector<gx_region> reg;
+  uint64_t pushed = 0;
+  for (u32 c = 0; c < ctx->nChrom; c++) {
+    pushed += ctx->gcPushed[c];
+    if (ctx->gcChrom[c].laid) reg.push_back(gx_region{c, 0, ctx->gcChrom[c].len});
+  }
+  std::vector<uint64_t> g(reg.size() + 1, 0), a(reg.size() + 1, 0);
+  if (int rc = gc_content(ctx, reg.data(), reg.size(), g.data(), a.data())) return rc;
+  uint64_t sg = 0, sa = 0;
+  for (size_t i = 0; i < reg.size(); i++) {
+    sg += g[i];
+    sa += a[i];
+  }
+  if (bases_pushed) *bases_pushed = pushed;
+  if (gc) *gc = sg;
+  if (acgt) *acgt = sa;
+  return GX_OK;
+}
+
+int gx_gc_content(gx_ctx* ctx, const gx_region* regions, size_t n, uint64_t* gc, uint64_t* acgt) {
+  if (!ctx || !ctx->gcOn || (n && (!regions || !gc || !acgt))) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  return gc_content(ctx, regions, n, gc, acgt);
+}
+
+int gx_gc_bias(gx_ctx* ctx, int window, int* n_samples) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (!ctx->gcOn) return refuse(ctx, "gx_gc_bias needs the genome (gx_set_genome)");
+  if (int rc = guard_kept(ctx, "gx_gc_bias", true)) return rc;
+  if (int rc = gc_check_window(ctx, window)) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  ctx->gcReady = false;
+  if (int rc = gc_bias_kept(ctx, (u32)window)) return rc;
+  if (n_samples) *n_samples = (int)ctx->gcRes.size();
+  return GX_OK;
+}
+
+int gx_get_gc_bias(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int* window, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn, uint64_t* Nw,
+                   uint64_t* n_unclassed, uint64_t* w_unclassed, size_t cap) {
+  if (!ctx || !ctx->gcReady || sample < 0 || (size_t)sample >= ctx->gcRes.size()) return GX_ERR_ORDER;
+  return gc_give(ctx->gcRes[sample], rep, is_ctrl, window, F, f_unclassed, Nn, Nw, n_unclassed, w_unclassed, cap);
+}
+
+// (the one over contexts lives here, not in gx_emit.cpp: it reads contexts)
+int gx_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, int* window, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn,
+                     uint64_t* Nw, uint64_t* n_unclassed, uint64_t* w_unclassed, size_t cap) {
+  gx_ctx::GcResult sum;
+  if (int rc = gc_sum(ctxs, n_ctx, sample, sum)) return rc;
+  return gc_give(sum, rep, is_ctrl, window, F, f_unclassed, Nn, Nw, n_unclassed, w_unclassed, cap);
+}
+
+int gx_gc_bias_events(gx_ctx* ctx, const void* ev, size_t n, int packed, int window, unsigned grid_expected, uint32_t tile_words, uint64_t flush_words,
+                      unsigned grid_observed, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn, uint64_t* Nw, uint64_t* n_unclassed,
+                      uint64_t* w_unclassed, size_t cap) {
+  if (!ctx || !ctx->gcOn || (n && !ev) || (cap && (!F || !Nn || !Nw))) return GX_ERR_ORDER;
+  if (int rc = guard_closed(ctx, "gx_gc_bias_events")) return rc;
+  if (int rc = gc_check_window(ctx, window)) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  gx_ctx::GcResult r;
+  if (int rc = gc_bias_events(ctx, ev, n, packed != 0, (u32)window, grid_expected, tile_words, flush_words, grid_observed, r)) return rc;
+  return gc_give(r, nullptr, nullptr, nullptr, F, f_unclassed, Nn, Nw, n_unclassed, w_unclassed, cap);
+}
+
+int gx_gc_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* min_tile_words, uint32_t* pad_words, uint32_t* block_bases,
+                   uint64_t* flush_words) {
+  static_assert(GC_MAX_WINDOW == GX_GC_MAX_WINDOW && GC_MIN_TILE == GX_GC_MIN_TILE, "the header's limits are the kernel's");
+  if (lanes) *lanes = (int)GC_NT;
+  if (grid) *grid = (int)GC_GRID;
+  if (tile_words) *tile_words = GC_TILE;
+  if (min_tile_words) *min_tile_words = GC_MIN_TILE;
+  if (pad_words) *pad_words = GC_PAD;
+  if (block_bases) *block_bases = GC_BLOCK_WORDS * 64;
+  if (flush_words) *flush_words = GC_FLUSH_WORDS;
+  return GX_OK;
+}
+
+int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || !out) return GX_ERR_ORDER;
+  int nS = 0;
+  for (int g = 0; g < n_ctx; g++) {
+    int n = 0;
+    if (int rc = gx_gc_bias(ctxs[g], window, &n)) return rc;
+    if (g && n != nS) return GX_ERR_ORDER;
+    nS = n;
+  }
+  std::vector<gx_ctx::GcResult> sums((size_t)nS);   // (each sample summed once; the writer reads the sums in place)
+  std::vector<int> rep, ctrl;
+  std::vector<uint64_t> fUn, nUn, wUn;
+  std::vector<const uint64_t*> pF, pN, pW;
+  for (int i = 0; i < nS; i++) {
+    const gx_ctx::GcResult& r = sums[i];
+    if (int rc = gc_sum(ctxs, n_ctx, i, sums[i])) return rc;
+    rep.push_back(r.rep); ctrl.push_back(r.ctrl); fUn.push_back(r.fUn); nUn.push_back(r.nUn); wUn.push_back(r.wUn);
+    pF.push_back(r.F.data()); pN.push_back(r.Nn.data()); pW.push_back(r.Nw.data());
+  }
+  return gx_format_gc_bias(out, nS, rep.data(), ctrl.data(), window, pF.data(), fUn.data(), pN.data(), pW.data(), nUn.data(), wUn.data());
 }
 
 uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index) { return subsample_draw(subsample_key(seed, sample), index); }

@@ -1501,4 +1501,98 @@ int gx_write_log_path(gx_ctx* ctx, int n_rep, const char* const* names, int n_ch
   return rc;
 }
 
+// --gc-bias (no Genrich counterpart): the window classes folded into 101 percent classes, k = (200 g + W) / (2 W) in integers
+// (halves up); per class ratio = (Nw[k] / sum Nw) / (F[k] / sum F) = double(Nw[k] * sum F) / double(F[k] * sum Nw), both
+// products exact (128 bits), each converted once (to_double); NaN where F[k] or sum Nw is 0.  Host only.
+int gx_gc_class(int window, int g) {
+  if (window < 1 || window > GX_GC_MAX_WINDOW || g < 0 || g > window) return -1;
+  return (200 * g + window) / (2 * window);
+}
+
+int gx_gc_metrics(int window, const uint64_t* F, uint64_t f_unclassed, const uint64_t* Nn, const uint64_t* Nw, uint64_t n_unclassed,
+                  uint64_t w_unclassed, gx_gc_metrics_t* out) {
+  if (!out || !F || !Nn || !Nw || window < 1 || window > GX_GC_MAX_WINDOW) return GX_ERR_ORDER;
+  gx_gc_metrics_t m{};
+  const double nan = std::nan("");
+  u128_t sF = 0, sN = 0, sW = 0, gF = 0, gW = 0;
+  for (int g = 0; g <= window; g++) {
+    if (Nw[g] < Nn[g] || (u128_t)Nw[g] > (u128_t)120 * Nn[g]) return GX_ERR_ORDER;   // (every interval weighs between 1/120 and 1)
+    const int k = gx_gc_class(window, g);
+    m.cls_windows[k] += F[g];
+    m.cls_intervals[k] += Nn[g];
+    m.cls_w120[k] += Nw[g];
+    sF += F[g];
+    sN += Nn[g];
+    sW += Nw[g];
+    gF += (u128_t)F[g] * (unsigned)g;
+    gW += (u128_t)Nw[g] * (unsigned)g;
+  }
+  if ((sF >> 64) || (sN >> 64) || (sW >> 64)) return GX_ERR_ORDER;
+  m.windows = (uint64_t)sF;
+  m.windows_unclassed = f_unclassed;
+  m.intervals = (uint64_t)sN;
+  m.intervals_unclassed = n_unclassed;
+  m.w120 = (uint64_t)sW;
+  m.w120_unclassed = w_unclassed;
+  m.mean_gc_genome = sF ? to_double(u256_of(gF)) / to_double(u256_of(sF * (unsigned)window)) : nan;
+  m.mean_gc_sample = sW ? to_double(u256_of(gW)) / to_double(u256_of(sW * (unsigned)window)) : nan;
+  m.ratio_min = m.ratio_max = nan;
+  m.ratio_min_class = m.ratio_max_class = -1;
+  for (int k = 0; k < GX_GC_CLASSES; k++) {
+    m.ratio[k] = nan;
+    if (!m.cls_windows[k] || !sW) continue;
+    m.ratio[k] = to_double(u256_of((u128_t)m.cls_w120[k] * sF)) / to_double(u256_of((u128_t)m.cls_windows[k] * sW));
+    if ((u128_t)100 * m.cls_windows[k] < sF) continue;   // (the extremes: among the classes that hold 1 % of the windows)
+    if (m.ratio_min_class < 0 || m.ratio[k] < m.ratio_min) {   // (ascending: the lowest class of the least ratio stays)
+      m.ratio_min = m.ratio[k];
+      m.ratio_min_class = k;
+    }
+    if (m.ratio_max_class < 0 || m.ratio[k] > m.ratio_max) {
+      m.ratio_max = m.ratio[k];
+      m.ratio_max_class = k;
+    }
+  }
+  *out = m;
+  return GX_OK;
+}
+
+// --gc-bias: one `#` line per sample, then its 101 rows
+int gx_format_gc_bias(FILE* out, int n_samples, const int* rep, const int* is_ctrl, int window, const uint64_t* const* F, const uint64_t* f_unclassed,
+                      const uint64_t* const* Nn, const uint64_t* const* Nw, const uint64_t* n_unclassed, const uint64_t* w_unclassed) {
+  if (!out || n_samples < 1 || !rep || !is_ctrl || !F || !f_unclassed || !Nn || !Nw || !n_unclassed || !w_unclassed) return GX_ERR_ORDER;
+  std::vector<gx_gc_metrics_t> m((size_t)n_samples);
+  for (int s = 0; s < n_samples; s++)
+    if (int rc = gx_gc_metrics(window, F[s], f_unclassed[s], Nn[s], Nw[s], n_unclassed[s], w_unclassed[s], &m[s])) return rc;
+  fprintf(out, "sample\tgc_percent\twindows\tintervals\tweight\tratio\n");
+  for (int s = 0; s < n_samples; s++) {
+    const char k = is_ctrl[s] ? 'c' : 't';
+    fprintf(out, "# %c%d\tW=%d\twindows=%llu\twindows_unclassed=%llu\tintervals=%llu\tintervals_unclassed=%llu\n", k, rep[s], window,
+            (unsigned long long)m[s].windows, (unsigned long long)m[s].windows_unclassed, (unsigned long long)m[s].intervals,
+            (unsigned long long)m[s].intervals_unclassed);
+    for (int c = 0; c < GX_GC_CLASSES; c++) {
+      fprintf(out, "%c%d\t%d\t%llu\t%llu", k, rep[s], c, (unsigned long long)m[s].cls_windows[c], (unsigned long long)m[s].cls_intervals[c]);
+      put_w120(out, m[s].cls_w120[c]);
+      put_cpx(out, m[s].ratio[c], "\t%.6f");
+      fprintf(out, "\n");
+    }
+  }
+  return GX_OK;
+}
+
+// --gc-peaks: the rows of --counts -- chr, start, end, peak_N in the order given -- then length, acgt, gc and gc / acgt
+int gx_format_gc_peaks(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const uint64_t* gc, const uint64_t* acgt) {
+  if (!out || (n_peaks && (!peaks || !names || !gc || !acgt))) return GX_ERR_ORDER;
+  for (size_t i = 0; i < n_peaks; i++)
+    if (gc[i] > acgt[i] || peaks[i].end < peaks[i].start || acgt[i] > peaks[i].end - peaks[i].start) return GX_ERR_ORDER;
+  fprintf(out, "chr\tstart\tend\tname\tlength\tacgt\tgc\tgc_fraction\n");
+  for (size_t i = 0; i < n_peaks; i++) {
+    const gx_region& k = peaks[i];
+    fprintf(out, "%s\t%ld\t%ld\tpeak_%d\t%ld\t%llu\t%llu", names[k.chrom], (long)k.start, (long)k.end, (int)i, (long)k.end - (long)k.start,
+            (unsigned long long)acgt[i], (unsigned long long)gc[i]);
+    put_cpx(out, acgt[i] ? (double)gc[i] / (double)acgt[i] : std::nan(""), "\t%.6f");
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
 }  // extern "C"

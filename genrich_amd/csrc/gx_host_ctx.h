@@ -35,6 +35,7 @@
 #include "gx_complexity.h"
 #include "gx_ivstat.h"
 #include "gx_xcor.h"
+#include "gx_gcbias.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
@@ -571,6 +572,29 @@ struct gx_ctx {
   int xcStageNext = 0;
   std::vector<XcResult> xc;         // until gx_reset
   bool xcUsed = false;              // k_xc_set / k_xc_corr ran since the last gx_reset
+  // the reference sequence as two bit vectors, GC bias per kept sample and GC content per interval (gx_set_genome /
+  // gx_push_sequence / gx_gc_bias / gx_gc_content, gx_gcbias.h); nothing here exists before gx_set_genome turns it on
+  struct GcResult {
+    int rep = 0;
+    bool ctrl = false;
+    u32 W = 0;
+    u64 fUn = 0, nUn = 0, wUn = 0;             // windows, intervals and weight that are not classed
+    std::vector<uint64_t> F, Nn, Nw;           // [W + 1]
+  };
+  bool gcOn = false;
+  bool gcDirty = false;             // the table changed since the layout (gx_set_chroms / gx_set_owned): laid out again, and empty
+  bool gcDirDirty = false;          // bases were pushed since the directory was built
+  std::vector<GcChrom> gcChrom;     // the layout
+  std::vector<uint64_t> gcPushed;   // per chromosome: the end of the furthest push
+  u64 gcWords = 0;                  // words of one vector
+  DevBuf gcVec, gcAcgt, gcDir, gcTab, gcSeq, gcOut;   // the two vectors, the directory, the table, gx_push_sequence's device buffer, a pass's counters
+  DevBuf gcAux;                     // a pass's small input: k_gc_expected's spans, k_gc_content's regions
+  PinnedBuf gcStage[2];             // pinned staging of gx_push_sequence (the caller's buffer is free on return)
+  hipEvent_t gcStageFree[2] = {nullptr, nullptr};
+  int gcStageNext = 0;
+  std::vector<GcResult> gcRes;      // the last gx_gc_bias, per kept sample (until gx_reset)
+  bool gcReady = false;
+  bool gcUsed = false;              // a kernel of gx_gcbias.h ran since the last gx_reset
   // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
   struct DepthResult {
     int rep = 0;

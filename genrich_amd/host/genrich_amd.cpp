@@ -34,6 +34,7 @@
 #include <zlib.h>
 
 #include <cctype>
+#include <chrono>
 #include <cerrno>
 #include <cfloat>
 #include <cmath>
@@ -71,6 +72,7 @@ static const float NOSCORE = -FLT_MAX;
 #include "host_dups.h"     // -r / -R
 #include "host_ingest.h"   // SAM / BAM decoding, the decode pipeline, the parallel state workers
 #include "host_peaklog.h"  // -P
+#include "host_genome.h"   // --genome: the FASTA reader
 #include "host_figures.h"  // --counts ... --profile
 
 namespace {
@@ -186,6 +188,29 @@ void usageSummits() {
   exit(EXIT_FAILURE);
 }
 
+// --help-gc: the block of --genome, --gc-bias and --gc-peaks, likewise
+void usageGc() {
+  fprintf(stderr,
+          "  --genome FASTA  the reference sequence the alignments were made against: plain text (any line width, CRLF, lower\n"
+          "                  case; N and the IUPAC codes are unknown bases) or gzip / BGZF; it goes to the device as two bits per\n"
+          "                  base.  A sequence the alignment files' headers do not name is skipped; one whose length differs from\n"
+          "                  its LN ends the run; a chromosome that is missing stays unknown (-v says so).  With --devices each\n"
+          "                  sequence goes to the device that owns its chromosome.  Needs --gc-bias or --gc-peaks\n"
+          "  --gc-bias FILE [--gc-window W]   each sample's GC bias (the fragment model of Benjamini & Speed, deepTools'\n"
+          "                  computeGCBias): every interval (-b line) is classed by the G + C among the W (200; 1 .. 4096) bases\n"
+          "                  from its start, whatever its own length, and so is EVERY window of the genome, not a sample of them;\n"
+          "                  a window with an unknown base, or one that runs past its chromosome, is not classed.  A TSV labelled\n"
+          "                  t<rep> / c<rep>: per sample a # line (W, the classed and unclassed windows and intervals), then per GC\n"
+          "                  percent 0 .. 100 the genome's windows, the sample's intervals, their weight and the ratio of the two\n"
+          "                  shares (NA where the genome has no such window).  -E regions are NOT masked on either side; -v: the\n"
+          "                  mean window GC of the sample and of the genome, the least and the greatest ratio among the classes\n"
+          "                  with 1 %% of the windows; works with -X, -z, -r, --devices; not with -P or --events-only\n"
+          "  --gc-peaks FILE the rows of --counts (chr, start, end, peak_N), then the peak's length, its known bases, the G + C\n"
+          "                  among them and their share (NA without known bases); needs --genome only; not with -X, -P (no\n"
+          "                  device context exists there) or --events-only\n");
+  exit(EXIT_FAILURE);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -243,6 +268,11 @@ int main(int argc, char** argv) {
                                      {"summits-prominence", required_argument, nullptr, 1046},
                                      {"summits-height", required_argument, nullptr, 1047},
                                      {"help-summits", no_argument, nullptr, 1048},
+                                     {"genome", required_argument, nullptr, 1049},
+                                     {"gc-bias", required_argument, nullptr, 1050},
+                                     {"gc-window", required_argument, nullptr, 1051},
+                                     {"gc-peaks", required_argument, nullptr, 1052},
+                                     {"help-gc", no_argument, nullptr, 1053},
                                      {nullptr, 0, nullptr, 0}};
   int nThreads;  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
   {
@@ -394,6 +424,17 @@ int main(int argc, char** argv) {
         break;
       }
       case 1048: usageSummits();
+      case 1049: o.genomeFile = optarg; break;
+      case 1050: o.gcBiasFile = optarg; break;
+      case 1051: {
+        __int128 v;
+        if (!strictInt(optarg, 1, GX_GC_MAX_WINDOW, &v)) die(optarg, ": --gc-window takes an integer in [1, 4096]");
+        o.gcWindow = (int)v;
+        o.gcWindowOpt = true;
+        break;
+      }
+      case 1052: o.gcPeaksFile = optarg; break;
+      case 1053: usageGc();
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -463,6 +504,14 @@ int main(int argc, char** argv) {
   if ((o.reproPctOpt || o.reproSeedOpt || o.reproPrefix) && !o.reproOn())
     die("", "--reproducibility-overlap, --reproducibility-seed and --reproducibility-peaks need --reproducibility FILE or --reproducibility-metrics FILE");
   if (o.reproOn() && o.devices.size() > 1) die("", "--reproducibility takes one device (not with --devices of more than one)");
+  if (o.gcBiasFile && !o.genomeFile) die("", "--gc-bias needs the reference sequence (--genome FASTA)");
+  if (o.gcPeaksFile && !o.genomeFile) die("", "--gc-peaks needs the reference sequence (--genome FASTA)");
+  if (o.gcWindowOpt && !o.gcBiasFile) die("", "--gc-window needs --gc-bias FILE");
+  if (o.genomeFile && !o.gcBiasFile && !o.gcPeaksFile) die("", "--genome needs --gc-bias FILE or --gc-peaks FILE");
+  // (the bias counts the events the library keeps: none with -P or --events-only; -X is fine)
+  if (o.gcBiasFile && !o.buildsPileups()) die("", "--gc-bias needs the intervals of this run (not with -P or --events-only)");
+  // (the content is taken in the peaks this run calls, on a device context: -P has neither)
+  if (o.gcPeaksFile && !o.callsPeaks()) die("", "--gc-peaks needs the peaks of this run on a device (not with -X, -P or --events-only)");
   // the treatment / control lists, and the samples they name: one per -t file and per -c file that is not "null", known before
   // anything is read or written
   const std::vector<std::string> tFiles = splitList(o.inFile), cFiles = splitList(o.ctrlFile);
@@ -544,7 +593,7 @@ int main(int argc, char** argv) {
       if (rc) die(g ? gx_last_error(g) : gx_strerror(rc), "");
       check(S, gx_set_keep_pileups(g, o.logFile || o.pileFile), g);  // only -f / -k print pileup values
       if (o.asDiff > 0.0f) check(S, gx_expect_fractional(g, 1), g);  // (-s: multimapping reads get weights 1/k)
-      if (o.countsFile || o.peakSignalFile || o.summitsFile || o.regionsBed || o.complexityFile || o.saturationFile || o.reproOn() || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile)
+      if (o.countsFile || o.peakSignalFile || o.summitsFile || o.regionsBed || o.complexityFile || o.saturationFile || o.reproOn() || o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile || o.gcBiasFile)
         check(S, gx_set_count_in_peaks(g, 1), g);
       D.ctx.push_back(g);
     }
@@ -590,6 +639,7 @@ int main(int argc, char** argv) {
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_depth_hist(g, 1), g);
   if (o.xcorOn())
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_xcor(g, o.xcorLo, o.xcorHi), g);
+  if (o.genomeFile) loadGenome(S);
   ProfilePlan profilePlan;
   if (o.profileBed) {
     profilePlan = planProfile(S);
@@ -722,6 +772,8 @@ int main(int argc, char** argv) {
   if (o.lengthsFile || o.lengthsMetricsFile || o.chromStatsFile) writeIntervalStats(S, names);
   if (o.depthFile || o.depthMetricsFile) writeDepth(S);
   if (o.xcorOn()) writeXcor(S);
+  if (o.gcBiasFile) writeGcBias(S);
+  if (o.gcPeaksFile) writeGcPeaks(S, names);
   if (o.saturationFile) writeSaturation(S);
   if (o.reproOn()) writeReproducibility(S, names);
   if (o.profileBed) writeProfile(S, profilePlan, sampleNames);

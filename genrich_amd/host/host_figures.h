@@ -450,6 +450,171 @@ void writeIntervalStats(State& S, const std::vector<const char*>& names) {
   }
 }
 
+// --genome FASTA: every sequence the run knows goes to the context that owns its chromosome, staging buffer by staging buffer
+// (host_genome.h strips it, gx_push_sequence packs it on the device).  A sequence the run does not know is skipped; one whose
+// length differs from the header's LN ends the run with both lengths; a chromosome of the run that the FASTA lacks stays
+// unknown, with one warning each under -v.  Plain text through a mapping; gzip and BGZF through the input stream's inflaters.
+struct GenomeSink {
+  State& S;
+  std::unordered_map<std::string, int> idx;
+  std::vector<uint8_t> seen;
+  int c = -1;
+  bool tooLong = false;
+  uint64_t nSeq = 0, nBases = 0;
+  std::string err;
+  explicit GenomeSink(State& s) : S(s), seen(s.chrom.size(), 0) {
+    for (size_t i = 0; i < S.chrom.size(); i++) idx.emplace(S.chrom[i].name, (int)i);
+  }
+  bool lengths(uint64_t fasta) {
+    err = S.chrom[c].name + ": the sequence in " + S.o.genomeFile + " has " + std::to_string(fasta) + (tooLong ? " bases or more" : " bases") +
+          ", the alignment files' header says " + std::to_string(S.chrom[c].len);
+    return false;
+  }
+  bool begin(const std::string& name) {
+    const auto it = idx.find(name);
+    if (it == idx.end() || S.chrom[it->second].skip) return false;
+    c = it->second;
+    if (seen[c]) {
+      err = name + ": twice in " + S.o.genomeFile;
+      c = -1;
+      return true;   // (bases() stops the reading)
+    }
+    seen[c] = 1;
+    tooLong = false;
+    nSeq++;
+    return true;
+  }
+  bool bases(uint64_t first, const char* p, size_t n) {
+    if (c < 0) return false;
+    const uint64_t len = S.chrom[c].len;
+    if (first + n > len) {   // (more may follow: end() knows the length)
+      tooLong = true;
+      return lengths(first + n);
+    }
+    if (n % 64 && first + n != len) return lengths(first + n);   // (a staging buffer that is not full is the sequence's last)
+    gx_ctx* g = S.devs.ctx[S.devs.owner[c]];
+    const int rc = gx_push_sequence(g, c, first, p, n);
+    if (rc) {
+      err = gx_last_error(g);
+      if (err.empty()) err = gx_strerror(rc);
+      return false;
+    }
+    nBases += n;
+    return true;
+  }
+  bool end(uint64_t length) {
+    if (c < 0) return false;
+    return length == S.chrom[c].len ? true : lengths(length);
+  }
+};
+
+void loadGenome(State& S) {
+  const Opts& o = S.o;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (gx_ctx* g : S.devs.ctx) check(S, gx_set_genome(g, 1), g);
+  GenomeSink sink(S);
+  const size_t chunk = (size_t)1 << 22;
+  unsigned char magic[2] = {0, 0};
+  {
+    FILE* f = fopen(o.genomeFile, "rb");
+    if (!f) die(o.genomeFile, ": cannot open file for reading");
+    const size_t k = fread(magic, 1, 2, f);
+    fclose(f);
+    if (!k) die(o.genomeFile, ": --genome: an empty file");
+  }
+  bool ok;
+  if (magic[0] == 0x1f && magic[1] == 0x8b) {
+    In in;
+    openRead(in, o.genomeFile, S.threads.sam.inflate);
+    ok = gxhost::genome_read_stream(in, o.genomeFile, chunk, sink, &sink.err);
+    checkIn(in);
+    in.close();
+  } else {
+    ok = gxhost::genome_read_plain(o.genomeFile, chunk, sink, &sink.err);
+  }
+  if (!ok) die("--genome: ", sink.err.c_str());
+  if (!o.verbose) return;
+  for (size_t i = 0; i < S.chrom.size(); i++)
+    if (!sink.seen[i] && !S.chrom[i].skip)
+      fprintf(stderr, "Warning! %s is not in %s: its bases are unknown to --gc-bias and --gc-peaks\n", S.chrom[i].name.c_str(), o.genomeFile);
+  uint64_t gc = 0, acgt = 0;
+  for (gx_ctx* g : S.devs.ctx) {
+    uint64_t a = 0, b = 0;
+    check(S, gx_genome_info(g, nullptr, &a, &b), g);   // (drains the device: the time below is the whole way)
+    gc += a;
+    acgt += b;
+  }
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  fprintf(stderr, "Genome %s: %llu sequences, %llu bases (%llu known, %llu G or C) in %.3f s\n", o.genomeFile, (unsigned long long)sink.nSeq,
+          (unsigned long long)sink.nBases, (unsigned long long)acgt, (unsigned long long)gc, sec);
+}
+
+// --gc-bias FILE: each sample's intervals (its -b lines) by the GC content of the --gc-window bases from their start, over the
+// genome's windows of that content, counted on the device (one pass per context and distinct set of chromosomes for the
+// genome's side, one per context and sample for the sample's; added): per sample a `#` line and 101 rows, labelled t<rep> /
+// c<rep>.  -E regions are not masked on either side.  With -v the mean window GC of the sample's intervals and of the genome, and
+// the least and the greatest ratio among the classes that hold at least 1 % of the windows
+void writeGcBias(State& S) {
+  const Opts& o = S.o;
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n(), W = o.gcWindow;
+  const int nS = agreedSamples(S, "--gc-bias: the devices kept different numbers of samples", [&](gx_ctx* g, int* n) { return gx_gc_bias(g, W, n); });
+  std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
+  std::vector<uint64_t> fUn((size_t)nS), nUn((size_t)nS), wUn((size_t)nS);
+  Columns cols(nS, 3);   // per window class: the genome's windows, the sample's intervals, their weight
+  for (int i = 0; i < nS; i++) {
+    uint64_t* a[3];
+    for (int k = 0; k < 3; k++) a[k] = cols.sized(i, k, (size_t)W + 1);
+    check(S, gx_gc_bias_group(ctxs, nCtx, i, &rep[i], &ctrl[i], nullptr, a[0], &fUn[i], a[1], a[2], &nUn[i], &wUn[i], (size_t)W + 1));
+  }
+  const std::vector<const uint64_t*> pF = cols.of(0), pN = cols.of(1), pW = cols.of(2);
+  writeFile(S, o.gcBiasFile, [&](FILE* f) {
+    return gx_format_gc_bias(f, nS, rep.data(), ctrl.data(), W, pF.data(), fUn.data(), pN.data(), pW.data(), nUn.data(), wUn.data());
+  });
+  if (!o.verbose) return;
+  for (int i = 0; i < nS; i++) {
+    gx_gc_metrics_t m;
+    check(S, gx_gc_metrics(W, pF[i], fUn[i], pN[i], pW[i], nUn[i], wUn[i], &m));
+    fprintf(stderr, "  GC bias, %s: mean window GC ", sampleLabel(rep[i], ctrl[i]).c_str());
+    if (std::isnan(m.mean_gc_sample)) fprintf(stderr, "NA");
+    else fprintf(stderr, "%f", m.mean_gc_sample);
+    if (std::isnan(m.mean_gc_genome)) fprintf(stderr, " (genome NA)");
+    else fprintf(stderr, " (genome %f)", m.mean_gc_genome);
+    if (m.ratio_min_class < 0) fprintf(stderr, ", ratio NA\n");
+    else fprintf(stderr, ", ratio %f at %d %% to %f at %d %% GC\n", m.ratio_min, m.ratio_min_class, m.ratio_max, m.ratio_max_class);
+  }
+}
+
+// --gc-peaks FILE: the rows of --counts (the contexts' peak lists merged in the order of -o, the same peak_N), then the peak's
+// length, its known bases, its G or C among them and their share, by rank differences on the context that owns the chromosome
+void writeGcPeaks(State& S, const std::vector<const char*>& names) {
+  std::vector<gx_region> reg;
+  std::vector<uint64_t> gc, acgt;
+  for (gx_ctx* g : S.devs.ctx) {
+    size_t k = 0;
+    check(S, gx_peak_count(g, &k), g);
+    std::vector<gx_peak> pk(k);
+    if (k) check(S, gx_get_peaks(g, pk.data(), k), g);
+    const size_t at = reg.size();
+    for (const gx_peak& p : pk) reg.push_back(gx_region{(uint32_t)p.chrom, (uint32_t)p.start, (uint32_t)p.end});
+    gc.resize(at + k);
+    acgt.resize(at + k);
+    check(S, gx_gc_content(g, reg.data() + at, k, gc.data() + at, acgt.data() + at), g);
+  }
+  std::vector<size_t> ord(reg.size());
+  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+  if (S.devs.n() > 1)
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return reg[a].chrom != reg[b].chrom ? reg[a].chrom < reg[b].chrom : reg[a].start < reg[b].start; });
+  std::vector<gx_region> r2;
+  std::vector<uint64_t> g2, a2;
+  for (size_t i : ord) {
+    r2.push_back(reg[i]);
+    g2.push_back(gc[i]);
+    a2.push_back(acgt[i]);
+  }
+  writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_format_gc_peaks(f, names.data(), r2.data(), r2.size(), g2.data(), a2.data()); });
+}
+
 // --xcor FILE / --xcor-metrics FILE: the strand cross-correlation of each sample's 5' ends, counted on the device when the
 // sample was closed (one pass per context, added): the curve, one row per sample and shift with the exact pair count and r, and
 // one row of figures per sample (fragment length, NSC, RSC), labelled t<rep> / c<rep>.  With -v the figures on stderr too, and

@@ -63,6 +63,11 @@ struct Opts {
   bool reproOn() const { return reproFile || reproMetricsFile; }
   int summitsProminence = 25, summitsHeight = 50;   // --summits-prominence PCT, --summits-height PCT
   bool summitsProminenceOpt = false, summitsHeightOpt = false;
+  const char* genomeFile = nullptr;        // --genome FASTA: the reference sequence, to the devices as two bit vectors
+  const char* gcBiasFile = nullptr;        // --gc-bias FILE: each sample's GC bias (observed over expected windows per GC percent)
+  int gcWindow = 200;                      // --gc-window W
+  bool gcWindowOpt = false;
+  const char* gcPeaksFile = nullptr;       // --gc-peaks FILE: the GC content of every called peak
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;

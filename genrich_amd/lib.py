@@ -145,6 +145,14 @@ GX_PATH_SPEARMAN = 4194304      # gx_path_info bit 22: k_rank ran (gx_coverage_r
 GX_PATH_COMPLEXITY = 8388608    # gx_path_info bit 23: k_cpx_insert ran (gx_complexity, gx_complexity_events)
 GX_PATH_IVSTAT = 67108864       # gx_path_info bit 26: k_ivstat ran (gx_interval_stats, gx_interval_stats_events)
 GX_PATH_XCOR = 134217728        # gx_path_info bit 27: k_xc_set / k_xc_corr ran (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags)
+GX_PATH_GC = 1073741824         # gx_path_info bit 30: a kernel of the genome / GC passes ran (gx_push_sequence, gx_gc_content, gx_gc_bias, gx_gc_bias_events)
+GC_MAX_WINDOW = 4096            # GX_GC_MAX_WINDOW
+GC_MIN_TILE = 64                # GX_GC_MIN_TILE
+GC_CLASSES = 101                # GX_GC_CLASSES
+GC_METRICS_DTYPE = np.dtype([(k, "<u8") for k in ("windows", "windows_unclassed", "intervals", "intervals_unclassed", "w120", "w120_unclassed")]
+                            + [(k, "<u8", (GC_CLASSES,)) for k in ("cls_windows", "cls_intervals", "cls_w120")] + [("ratio", "<f8", (GC_CLASSES,))]
+                            + [(k, "<f8") for k in ("mean_gc_genome", "mean_gc_sample", "ratio_min", "ratio_max")]
+                            + [("ratio_min_class", "<i4"), ("ratio_max_class", "<i4")])   # gx_gc_metrics_t
 TAG_DTYPE = np.dtype([("chrom", "<u4"), ("pos", "<u4"), ("strand", "<u4")])   # gx_tag; strand 1: +, 0: -
 XCOR_MAX_SHIFT = 4096           # GX_XCOR_MAX_SHIFT
 XCOR_MIN_TILE = 64              # GX_XCOR_MIN_TILE
@@ -214,6 +222,19 @@ class Xcor(NamedTuple):
     lo: int
     hi: int
     n11: list
+    rep: int = 0
+    is_ctrl: bool = False
+
+
+class GcBias(NamedTuple):
+    """One sample's GC tables (gx_get_gc_bias): F / Nn / Nw uint64[W + 1] per window class, and what is not classed."""
+    window: int
+    F: np.ndarray
+    f_unclassed: int
+    Nn: np.ndarray
+    Nw: np.ndarray
+    n_unclassed: int
+    w_unclassed: int
     rep: int = 0
     is_ctrl: bool = False
 
@@ -405,6 +426,23 @@ _SIGS = {
     "gx_format_xcor": [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
     "gx_format_xcor_metrics": [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_int],
     "gx_write_xcor_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gx_set_genome": [C.c_void_p, C.c_int],
+    "gx_push_sequence": [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t],
+    "gx_genome_info": [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3,
+    "gx_gc_content": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+    "gx_gc_bias": [C.c_void_p, C.c_int, C.POINTER(C.c_int)],
+    "gx_get_gc_bias": [C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t],
+    "gx_gc_bias_group": [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t],
+    "gx_gc_bias_events": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.c_uint64, C.c_uint, C.c_void_p,
+                          C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t],
+    "gx_gc_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 4 + [C.POINTER(C.c_uint64)],
+    "gx_gc_class": [C.c_int, C.c_int],
+    "gx_gc_metrics": [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+    "gx_format_gc_bias": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6,
+    "gx_format_gc_peaks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
+    "gx_write_gc_bias_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "gx_interval_stats": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_get_interval_lengths": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
@@ -851,6 +889,85 @@ def xcor_text(ctxs, read_len=0):
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
     return (_to_tmpfile(lambda f: lib.gx_write_xcor_group(arr, len(ctxs), int(read_len), f, None)),
             _to_tmpfile(lambda f: lib.gx_write_xcor_group(arr, len(ctxs), int(read_len), None, f)))
+
+
+def gc_geometry():
+    """(lanes, grid, tile_words, min_tile_words, pad_words, block_bases, flush_words) of the GC passes as the library was built
+    (gx_gc_geometry): the lanes of a workgroup of k_gc_expected, its most workgroups with grid = 0, its default and smallest words
+    per tile, the zero words around a chromosome, the bases per directory block, and the words a workgroup walks at most before
+    it adds its 32-bit counters to the 64-bit ones."""
+    lib = load_library()
+    lanes, grid, flush = C.c_int(0), C.c_int(0), C.c_uint64(0)
+    t, mt, pad, blk = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    lib.gx_gc_geometry(C.byref(lanes), C.byref(grid), C.byref(t), C.byref(mt), C.byref(pad), C.byref(blk), C.byref(flush))
+    return lanes.value, grid.value, t.value, mt.value, pad.value, blk.value, flush.value
+
+
+def gc_class(window, g):
+    """The percent class of g GC bases in a window of `window` (gx_gc_class; -1: out of range); host-only."""
+    return int(load_library().gx_gc_class(int(window), int(g)))
+
+
+def _gc_arrays(x):
+    return [np.ascontiguousarray(a, dtype=np.uint64) for a in (x.F, x.Nn, x.Nw)]
+
+
+def gc_metrics(x):
+    """gx_gc_metrics of a GcBias as one GC_METRICS_DTYPE record; host-only."""
+    lib = load_library()
+    F, Nn, Nw = _gc_arrays(x)
+    out = np.zeros(1, dtype=GC_METRICS_DTYPE)
+    ok = F.size == Nn.size == Nw.size == int(x.window) + 1
+    rc = lib.gx_gc_metrics(int(x.window), F.ctypes.data if ok else None, int(x.f_unclassed), Nn.ctypes.data, Nw.ctypes.data, int(x.n_unclassed),
+                           int(x.w_unclassed), out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"gx_gc_metrics: {rc}")
+    return out[0]
+
+
+def format_gc_bias(samples) -> bytes:
+    """--gc-bias' table for [GcBias] of one window (gx_format_gc_bias); host-only."""
+    lib = load_library()
+    rep = np.ascontiguousarray([x.rep for x in samples], dtype=np.int32)
+    ctrl = np.ascontiguousarray([int(x.is_ctrl) for x in samples], dtype=np.int32)
+    rows = [_gc_arrays(x) for x in samples]
+    ptrs = [(C.c_void_p * len(samples))(*[r[k].ctypes.data for r in rows]) for k in range(3)]
+    sc = [np.ascontiguousarray([getattr(x, k) for x in samples], dtype=np.uint64) for k in ("f_unclassed", "n_unclassed", "w_unclassed")]
+    return _to_tmpfile(lambda f: lib.gx_format_gc_bias(f, len(samples), rep.ctypes.data, ctrl.ctypes.data, int(samples[0].window), ptrs[0],
+                                                       sc[0].ctypes.data, ptrs[1], ptrs[2], sc[1].ctypes.data, sc[2].ctypes.data))
+
+
+def format_gc_peaks(names, regions, gc, acgt) -> bytes:
+    """--gc-peaks' table for regions (REGION_DTYPE) with their counts (gx_format_gc_peaks); host-only."""
+    lib = load_library()
+    reg = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+    g, a = np.ascontiguousarray(gc, dtype=np.uint64), np.ascontiguousarray(acgt, dtype=np.uint64)
+    nm = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    return _to_tmpfile(lambda f: lib.gx_format_gc_peaks(f, nm, reg.ctypes.data, reg.size, g.ctypes.data, a.ctypes.data))
+
+
+def _gc_result(call, window_cap=GC_MAX_WINDOW):
+    """A GcBias from call(rep, ctrl, window, F, f_un, Nn, Nw, n_un, w_un, cap)."""
+    rep, ctrl, w = C.c_int(0), C.c_int(0), C.c_int(0)
+    fu, nu, wu = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    F, Nn, Nw = (np.zeros(window_cap + 1, dtype=np.uint64) for _ in range(3))
+    call(C.byref(rep), C.byref(ctrl), C.byref(w), F.ctypes.data, C.byref(fu), Nn.ctypes.data, Nw.ctypes.data, C.byref(nu), C.byref(wu), window_cap + 1)
+    k = w.value + 1
+    return GcBias(w.value, F[:k].copy(), fu.value, Nn[:k].copy(), Nw[:k].copy(), nu.value, wu.value, rep.value, bool(ctrl.value))
+
+
+def gc_bias_group(ctxs, sample):
+    """GcBias of one sample added over the contexts of a run (gx_gc_bias_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _gc_result(lambda *a: ctxs[0]._check(lib.gx_gc_bias_group(arr, len(ctxs), int(sample), *a)))
+
+
+def gc_bias_text(ctxs, window=200) -> bytes:
+    """--gc-bias' table over the contexts of a run (gx_write_gc_bias_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_gc_bias_group(arr, len(ctxs), int(window), f)))
 
 
 def interval_stats_geometry():
@@ -1793,6 +1910,53 @@ class Genrich:
         self._check(self.lib.gx_xcor_tags(self.ctx, ln.ctypes.data, ln.size, t.ctypes.data if t.size else None, t.size, int(lo), int(hi), int(grid),
                                           int(tile_words), C.byref(N), C.byref(nP), C.byref(nM), C.byref(rej), n11.ctypes.data, n))
         return Xcor(N.value, nP.value, nM.value, rej.value, int(lo), int(hi), [int(x) for x in n11])
+
+    # -- the reference sequence, GC bias and GC content (include/genrich_amd.h, gx_set_genome) ------------------------------
+    def set_genome(self, on=True):
+        """Allocate and clear the two bit vectors for this context's chromosome table, or free them (gx_set_genome)."""
+        self._check(self.lib.gx_set_genome(self.ctx, int(bool(on))))
+
+    def push_sequence(self, chrom, first_base, bases):
+        """Plain sequence bytes of chromosome `chrom` from base `first_base` (a multiple of 64) on (gx_push_sequence)."""
+        b = bytes(bases)
+        self._check(self.lib.gx_push_sequence(self.ctx, int(chrom), int(first_base), b if b else None, len(b)))
+
+    def genome_info(self):
+        """(bases pushed, gc bits, acgt bits) of this context's genome (gx_genome_info)."""
+        p, g, a = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_genome_info(self.ctx, C.byref(p), C.byref(g), C.byref(a)))
+        return p.value, g.value, a.value
+
+    def gc_content(self, regions):
+        """(gc, acgt) uint64 arrays for regions (REGION_DTYPE), by rank differences (gx_gc_content)."""
+        reg = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+        g, a = np.zeros(max(reg.size, 1), dtype=np.uint64), np.zeros(max(reg.size, 1), dtype=np.uint64)
+        self._check(self.lib.gx_gc_content(self.ctx, reg.ctypes.data if reg.size else None, reg.size, g.ctypes.data, a.ctypes.data))
+        return g[:reg.size], a[:reg.size]
+
+    def gc_bias(self, window=200):
+        """The GC tables of every sample closed so far (gx_gc_bias); needs set_genome() and set_count_in_peaks(True).  Returns the
+        number of samples."""
+        n = C.c_int(0)
+        self._check(self.lib.gx_gc_bias(self.ctx, int(window), C.byref(n)))
+        return n.value
+
+    def get_gc_bias(self, sample):
+        """GcBias of one sample of the last gc_bias() (gx_get_gc_bias)."""
+        return _gc_result(lambda *a: self._check(self.lib.gx_get_gc_bias(self.ctx, int(sample), *a)))
+
+    def gc_bias_events(self, events, window=200, packed=False, grid_expected=0, tile_words=0, flush_words=0, grid_observed=0):
+        """GcBias of host events (EVENT_DTYPE; packed: EVENT8 records as pack_events gives them) taken as one sample over this
+        context's genome, by the kernels alone (gx_gc_bias_events); 0: the library's geometry."""
+        ev = np.ascontiguousarray(events)
+        W = int(window)
+        k = max(W, 0) + 1
+        F, Nn, Nw = (np.zeros(k, dtype=np.uint64) for _ in range(3))
+        fu, nu, wu = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_gc_bias_events(self.ctx, ev.ctypes.data if ev.size else None, ev.size, int(bool(packed)), W, int(grid_expected),
+                                               int(tile_words), int(flush_words), int(grid_observed), F.ctypes.data, C.byref(fu), Nn.ctypes.data,
+                                               Nw.ctypes.data, C.byref(nu), C.byref(wu), k))
+        return GcBias(W, F, fu.value, Nn, Nw, nu.value, wu.value)
 
     # -- lengths and chromosome tallies of the samples' intervals (include/genrich_amd.h, gx_interval_stats) --------------
     def interval_stats(self):

@@ -732,6 +732,94 @@ int gx_xcor_tags(gx_ctx* ctx, const uint32_t* lens, int n_chrom, const gx_tag* t
                  uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus, uint64_t* rejected, uint64_t* n11, size_t cap);
 int gx_xcor_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* pad_words_for_4096, uint64_t* flush_words);
 
+/* ---- the reference sequence, GC bias per sample and GC content per interval (no Genrich counterpart: deepTools' computeGCBias,
+ *      the fragment model of Benjamini & Speed, which otherwise wants another tool and another reading of the BAM and the
+ *      genome) ----
+ * THE GENOME, per context: two bit vectors, one bit per base.  gc has bit x set when base x is one of G C g c, acgt when it is
+ * one of A C G T a c g t.  Everything else is UNKNOWN: N, IUPAC codes, bases never pushed, positions past a chromosome's end.
+ * THE WINDOW of width W (1 .. GX_GC_MAX_WINDOW) at position x of a chromosome is [x, x + W).  It is CLASSED iff all W of its
+ * acgt bits are set; its class is then g, its gc bits, 0 <= g <= W.
+ * COUNTS, per sample, all exact uint64:
+ *     F[g]             the classed windows over all positions of the chromosomes that take part (saved, not skipped, owned);
+ *     f_unclassed      ... the positions of those chromosomes whose window is not classed
+ *     Nn[g], Nw[g]     the sample's intervals (exactly its -b lines, gx_set_count_in_peaks) whose window AT THE INTERVAL'S START
+ *                      is classed g, and their weight in 1/120 units; the interval's own length plays no part (deepTools'
+ *                      construction), so cut-site windows and inverted intervals count like the rest
+ *     n_unclassed, w_unclassed   the intervals whose window is not classed, and their weight
+ * -E regions are NOT masked on either side (as for gx_peak_signal).  The counts are the same for every launch geometry, split
+ * of the pushes and number of GPUs (a chromosome lives on one context: the contexts' counts add, gx_gc_bias_group).
+ * FIGURES (host, gx_gc_metrics): the classes folded into GX_GC_CLASSES percent classes, k = (200 g + W) / (2 W) in integers
+ * (halves up); ratio[k] = (Nw[k] / sum Nw) / (F[k] / sum F) = double(Nw[k] * sum F) / double(F[k] * sum Nw), both products exact
+ * 128-bit integers, each converted once (the leading 64 bits, then one rounding, as for gx_xcor_r); NaN ("NA") where F[k] or
+ * sum Nw is 0.
+ * LAYOUT AND LIMITS.  Every chromosome starts on a 512-base block; before and after each lie at least GX_GC_MAX_WINDOW / 64 + 1
+ * zero words.  Two vectors of (genome / 8) bytes and a rank directory of (genome / 64) bytes per context: 2 x 388 MB + 48 MB for
+ * hg38.  Refused with GX_ERR_ORDER and a text: a window outside 1 .. GX_GC_MAX_WINDOW; a genome of 2^37 bases or more.
+ *
+ * gx_set_genome: on != 0: the vectors for the context's table are allocated and cleared (every base unknown); 0: freed.  After
+ *   gx_set_chroms, with no sample open.  gx_set_chroms / gx_set_owned lay the vectors out again, EMPTY: the bases are pushed
+ *   again.  gx_reset keeps the genome and drops gx_gc_bias' results.  Off: nothing is allocated, launched or recorded.
+ * gx_push_sequence: n plain sequence bytes (no newlines) of chromosome chrom from base first_base on; any order, any split, at
+ *   any time; the caller's memory is free on return.  first_base must be a multiple of 64, and only a chromosome's last push
+ *   (first_base + n = its length) may have n % 64 != 0: every word has one writer.  The same stretch pushed twice is harmless.
+ *   GX_ERR_ORDER with a text: a chromosome outside the table, bases past its length, a first_base or an n that breaks the rule.
+ *   A chromosome that is skipped or not owned takes nothing, with no error, as tags do.
+ * gx_genome_info: the bases pushed (per chromosome the end of its furthest push, added) and the set bits of both vectors.
+ * gx_gc_content: for n intervals, the gc and the acgt bits in [start, min(end, length)); end <= start, a chromosome outside the
+ *   table or without words here: 0.
+ * gx_gc_bias: the tables of every closed kept sample (needs gx_set_count_in_peaks' keeping, no sample open, no peaks).  F is
+ *   computed once per distinct set of chromosomes among the samples (k_gc_expected), Nn / Nw by one pass per sample
+ *   (k_gc_observed).  gx_get_gc_bias: sample `sample` of the last gx_gc_bias, min(cap, W + 1) classes of each table; any
+ *   pointer may be NULL (the tables when cap is 0).  gx_gc_bias_group: that sample of every context, added.
+ * gx_gc_bias_events: the same kernels over the context's genome and n events in host memory (packed != 0: gx_event8 records),
+ *   taken as ONE sample that saves every chromosome.  grid_expected / tile_words / flush_words / grid_observed = 0: the
+ *   library's choices; else that many workgroups (at most 65535), words per tile of k_gc_expected (a multiple of
+ *   GX_GC_MIN_TILE from there to 1024) and words a workgroup of it walks at most between two flushes of its 32-bit counters
+ *   (from one tile to 2^25).  No sample open.  For tests and measurements.
+ * gx_gc_geometry: the lanes of a workgroup of k_gc_expected, its most workgroups with grid = 0, its default and smallest words
+ *   per tile, the zero words around a chromosome, the bases per directory block, and the flush bound (2^25 words x 64 windows
+ *   < 2^32).  Any pointer may be NULL. */
+#define GX_GC_MAX_WINDOW 4096
+#define GX_GC_MIN_TILE 64
+#define GX_GC_CLASSES 101
+int gx_set_genome(gx_ctx* ctx, int on);
+int gx_push_sequence(gx_ctx* ctx, int chrom, uint64_t first_base, const char* bases, size_t n);
+int gx_genome_info(gx_ctx* ctx, uint64_t* bases_pushed, uint64_t* gc, uint64_t* acgt);
+int gx_gc_content(gx_ctx* ctx, const gx_region* regions, size_t n, uint64_t* gc, uint64_t* acgt);
+int gx_gc_bias(gx_ctx* ctx, int window, int* n_samples);
+int gx_get_gc_bias(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int* window, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn, uint64_t* Nw,
+                   uint64_t* n_unclassed, uint64_t* w_unclassed, size_t cap);
+int gx_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, int* window, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn,
+                     uint64_t* Nw, uint64_t* n_unclassed, uint64_t* w_unclassed, size_t cap);
+int gx_gc_bias_events(gx_ctx* ctx, const void* ev, size_t n, int packed, int window, unsigned grid_expected, uint32_t tile_words, uint64_t flush_words,
+                      unsigned grid_observed, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn, uint64_t* Nw, uint64_t* n_unclassed,
+                      uint64_t* w_unclassed, size_t cap);
+int gx_gc_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* min_tile_words, uint32_t* pad_words, uint32_t* block_bases,
+                   uint64_t* flush_words);
+/* The figures and the tables (host only, gx_emit.cpp).  gx_gc_class: the percent class of g in a window of W (-1: out of range).
+ * gx_gc_metrics: the folded tables, the ratios, the mean window GC of the genome (sum g F[g] / (W sum F)) and of the sample's
+ * intervals (weighted: sum g Nw[g] / (W sum Nw)), and the least and the greatest ratio among the classes that hold at least 1 %
+ * of the classed windows (class -1 and NaN: none).  GX_ERR_ORDER: a table that contradicts itself (a weight outside
+ * Nn <= Nw <= 120 Nn).  gx_format_gc_bias: --gc-bias' table: a header, then per sample one `#` line (W, the classed and the
+ * unclassed windows and intervals) and GX_GC_CLASSES rows `sample gc_percent windows intervals weight ratio`; weights as --counts
+ * prints a count.  gx_format_gc_peaks: --gc-peaks' table: the rows of --counts (chr start end peak_N, in the order given), then
+ * length, acgt, gc and gc / acgt ("NA" when acgt is 0).  gx_write_gc_bias_group: gx_gc_bias on every context, the sums, the
+ * table. */
+typedef struct {
+  uint64_t windows, windows_unclassed, intervals, intervals_unclassed, w120, w120_unclassed;
+  uint64_t cls_windows[GX_GC_CLASSES], cls_intervals[GX_GC_CLASSES], cls_w120[GX_GC_CLASSES];
+  double ratio[GX_GC_CLASSES];
+  double mean_gc_genome, mean_gc_sample, ratio_min, ratio_max;
+  int32_t ratio_min_class, ratio_max_class;
+} gx_gc_metrics_t;
+int gx_gc_class(int window, int g);
+int gx_gc_metrics(int window, const uint64_t* F, uint64_t f_unclassed, const uint64_t* Nn, const uint64_t* Nw, uint64_t n_unclassed,
+                  uint64_t w_unclassed, gx_gc_metrics_t* out);
+int gx_format_gc_bias(FILE* out, int n_samples, const int* rep, const int* is_ctrl, int window, const uint64_t* const* F, const uint64_t* f_unclassed,
+                      const uint64_t* const* Nn, const uint64_t* const* Nw, const uint64_t* n_unclassed, const uint64_t* w_unclassed);
+int gx_format_gc_peaks(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const uint64_t* gc, const uint64_t* acgt);
+int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out);
+
 /* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
  *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
@@ -1322,6 +1410,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_XCOR 134217728u /* bit 27: k_xc_set / k_xc_corr ran since the last gx_reset (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags) */
 #define GX_PATH_SPLIT 268435456u /* bit 28: k_sub_split ran since the last gx_reset (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility) */
 #define GX_PATH_SWEEP_OVERLAP 536870912u /* bit 29: ... GX_PATH_LOOSE_SWEEP whose run pass rode in the launch that scanned the tiles and closed the sample (k_scan_iv_close_runs), ahead of gx_find_peaks: the sweep launched no k_runs */
+#define GX_PATH_GC 1073741824u /* bit 30: a kernel of the genome / GC passes ran since the last gx_reset (gx_push_sequence, gx_genome_info, gx_gc_content, gx_gc_bias, gx_gc_bias_events) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
