@@ -22,6 +22,7 @@
 #include "gx_host_ivstat.h"
 #include "gx_host_xcor.h"
 #include "gx_host_gcbias.h"
+#include "gx_host_motifs.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
@@ -350,6 +351,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_depth(ctx);      // (... and gx_set_depth_hist's)
   drop_xcor(ctx);       // (... and gx_set_xcor's)
   drop_gcbias(ctx);     // (gx_gc_bias' results; the genome stays)
+  drop_motifs(ctx);     // (gx_motif_scan_peaks' results; the motifs stay)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
@@ -378,7 +380,7 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   ctx->specRuns.valid = false;   // (a control or a further replicate: the sweep will not be the one the run pass was launched for)
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
-    ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = false;
+    ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = false;
     // (a further replicate: the previous one's loose slots, tile tables and p(V) table are about to be reused)
     for (size_t r = 0; r < ctx->reps.size(); r++)
       if (ctx->reps[r].loose || ctx->reps[r].pilesPending)
@@ -681,7 +683,7 @@ int gx_pvalues(gx_ctx* ctx) {
 int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* peak_bp) {
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
-  ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = false;
+  ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = false;
   const CallPlan& P = ctx->called;
   u32 nPeaks = 0;
   // (at most two plans: -q on the loose slots may be called off by the device, and the call is then planned again without it)
@@ -885,7 +887,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->gcUsed ? GX_PATH_GC : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->gcUsed ? GX_PATH_GC : 0u) | (ctx->motUsed ? GX_PATH_MOTIFS : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
   return GX_OK;
 }
 
@@ -1845,6 +1847,8 @@ int gx_set_genome(gx_ctx* ctx, int on) {
     ctx->gcOn = ctx->gcDirty = false;
     ctx->gcVec.release();
     ctx->gcAcgt.release();
+    ctx->gcAg.release();
+    ctx->seqOn = false;
     ctx->gcDir.release();
     ctx->gcPushed.clear();
     return GX_OK;
@@ -1960,6 +1964,214 @@ int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out
     pF.push_back(r.F.data()); pN.push_back(r.Nn.data()); pW.push_back(r.Nw.data());
   }
   return gx_format_gc_bias(out, nS, rep.data(), ctrl.data(), window, pF.data(), fUn.data(), pN.data(), pW.data(), nUn.data(), wUn.data());
+}
+
+int gx_set_genome_bases(gx_ctx* ctx, int on) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (int rc = guard_closed(ctx, "gx_set_genome_bases")) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  HIPCHECK(hipStreamSynchronize(ctx->stream));
+  return seq_set_bases(ctx, on != 0);
+}
+
+int gx_get_sequence(gx_ctx* ctx, int chrom, uint64_t start, size_t n, char* out) {
+  if (!ctx || !ctx->gcOn || (n && !out)) return GX_ERR_ORDER;
+  HIPCHECK(hipSetDevice(ctx->device));
+  return seq_get(ctx, chrom, start, n, out);
+}
+
+int gx_set_motifs(gx_ctx* ctx, const gx_motif* m, int n, const int16_t* scores) {
+  if (!ctx || (n > 0 && (!m || !scores))) return GX_ERR_ORDER;
+  return mot_set(ctx, m, n, scores);
+}
+
+int gx_motif_scan_regions(gx_ctx* ctx, const gx_region* regions, size_t n, unsigned grid, uint32_t step_words, uint32_t batch_motifs, size_t list_cap,
+                          gx_motif_hit* out, size_t cap, size_t* n_out, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev) {
+  if (!ctx || (n && !regions) || (cap && !out)) return GX_ERR_ORDER;
+  if (!ctx->seqOn) return refuse(ctx, "gx_motif_scan_regions needs the bases (gx_set_genome_bases)");
+  if (int rc = guard_closed(ctx, "gx_motif_scan_regions")) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<gx_motif_hit> hits;
+  std::vector<uint64_t> counts;
+  if (int rc = mot_pass(ctx, regions, n, MotGeometry{grid, step_words, batch_motifs, (u64)list_cap}, hits, counts)) return rc;
+  if (n_out) *n_out = hits.size();
+  if (const size_t k = std::min(cap, hits.size())) memcpy(out, hits.data(), k * sizeof(gx_motif_hit));
+  return windows || hits_fwd || hits_rev ? mot_give(counts, ctx->motMeta.size(), windows, hits_fwd, hits_rev, ctx->motMeta.size()) : GX_OK;
+}
+
+int gx_motif_scan_peaks(gx_ctx* ctx, size_t* n_hits) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (!ctx->seqOn) return refuse(ctx, "gx_motif_scan_peaks needs the bases (gx_set_genome_bases)");
+  if (ctx->phase != 0 || !ctx->peaksReady) return refuse(ctx, "gx_motif_scan_peaks comes after gx_find_peaks, with no sample open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = mot_scan_peaks(ctx)) return rc;
+  if (n_hits) *n_hits = ctx->motHits.size();
+  return GX_OK;
+}
+
+int gx_get_motif_hits(gx_ctx* ctx, gx_motif_hit* out, size_t cap) {
+  if (!ctx || !ctx->motReady || (cap && !out)) return GX_ERR_ORDER;
+  if (const size_t k = std::min(cap, ctx->motHits.size())) memcpy(out, ctx->motHits.data(), k * sizeof(gx_motif_hit));
+  return GX_OK;
+}
+
+int gx_get_motif_counts(gx_ctx* ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap) {
+  if (!ctx || !ctx->motReady) return GX_ERR_ORDER;
+  return mot_give(ctx->motCounts, ctx->motMeta.size(), windows, hits_fwd, hits_rev, cap);
+}
+
+int gx_motif_last(gx_ctx* ctx, uint32_t* reruns, uint32_t* batches) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (reruns) *reruns = ctx->motLastReruns;
+  if (batches) *batches = ctx->motLastBatches;
+  return GX_OK;
+}
+
+int gx_motif_scan_genome(gx_ctx* ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap) {
+  return gx_motif_scan_genome_group(&ctx, 1, windows, hits_fwd, hits_rev, cap);
+}
+
+// (the one over contexts lives here, not in gx_emit.cpp: it reads contexts)  Every context's pass is launched, with its read-back
+// queued on its stream, before the first is waited for: with several devices the passes run side by side.
+int gx_motif_scan_genome_group(gx_ctx* const* ctxs, int n_ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0]) return GX_ERR_ORDER;
+  std::vector<MotRun> runs((size_t)n_ctx);
+  for (int g = 0; g < n_ctx; g++) {
+    gx_ctx* ctx = ctxs[g];
+    if (!ctx || ctx->motMeta.size() != ctxs[0]->motMeta.size()) return GX_ERR_ORDER;
+    if (!ctx->seqOn) return refuse(ctx, "gx_motif_scan_genome needs the bases (gx_set_genome_bases)");
+    if (int rc = guard_closed(ctx, "gx_motif_scan_genome")) return rc;
+  }
+  int bad = GX_OK;
+  for (int g = 0; g < n_ctx && !bad; g++) {
+    gx_ctx* ctx = ctxs[g];
+    HIPCHECK(hipSetDevice(ctx->device));
+    if (int rc = gc_current(ctx)) return rc;
+    const std::vector<gx_region> reg = mot_genome_regions(ctx);
+    bad = mot_count_begin(ctx, reg.data(), reg.size(), runs[(size_t)g]);
+  }
+  std::vector<uint64_t> sum, counts;
+  for (int g = 0; g < n_ctx; g++) {   // (every pass that was launched is drained, also behind a failure: its buffers are the run's)
+    gx_ctx* ctx = ctxs[g];
+    HIPCHECK(hipSetDevice(ctx->device));
+    if (int rc = mot_count_end(ctx, runs[(size_t)g], counts)) return rc;
+    if (g == 0) sum = counts;
+    else
+      for (size_t k = 0; k < sum.size(); k++) sum[k] += counts[k];
+  }
+  if (bad) return bad;
+  return mot_give(sum, ctxs[0]->motMeta.size(), windows, hits_fwd, hits_rev, cap);
+}
+
+int gx_motif_grid(uint64_t units, uint32_t step_words, unsigned grid, unsigned* chosen) {
+  unsigned g = 0;
+  const char* why = "";
+  if (int rc = mot_grid(units, step_words ? step_words : MOT_STEP, grid, &g, &why)) return rc;
+  if (chosen) *chosen = g;
+  return GX_OK;
+}
+
+int gx_motif_geometry(int* lanes, int* grid, uint32_t* positions_per_step, uint32_t* step_words, uint32_t* batch_motifs, size_t* list_cap,
+                      uint64_t* flush_runs) {
+  if (lanes) *lanes = (int)MOT_NT;
+  if (grid) *grid = (int)MOT_GRID;
+  if (positions_per_step) *positions_per_step = 64;
+  if (step_words) *step_words = MOT_STEP;
+  if (batch_motifs) *batch_motifs = MOT_BATCH;
+  if (list_cap) *list_cap = (size_t)MOT_LIST_MIN;
+  if (flush_runs) *flush_runs = MOT_FLUSH_RUNS;
+  return GX_OK;
+}
+
+// the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group, as gx_write_summits_group merges them), each context's
+// hits following its peaks
+static int motif_group(gx_ctx* const* ctxs, int n_ctx, int n_motifs, bool, std::vector<gx_region>& reg, std::vector<uint32_t>& summit,
+                       std::vector<gx_motif_hit>& hits, std::vector<uint64_t>& cPeaks, std::vector<uint64_t>& cGenome) {
+  if (!ctxs || n_ctx < 1 || n_motifs < 0) return GX_ERR_ORDER;
+  const size_t nM = (size_t)n_motifs;
+  std::vector<gx_peak> pk;
+  cPeaks.assign(3 * nM, 0);
+  cGenome.assign(3 * nM, 0);
+  std::vector<uint64_t> one(3 * nM + 1, 0);
+  for (int g = 0; g < n_ctx; g++) {
+    if (!ctxs[g] || ctxs[g]->motMeta.size() != nM) return GX_ERR_ORDER;
+    size_t k = 0, n = ctxs[g]->motHits.size();
+    if (!ctxs[g]->motReady)   // (else the context holds the scan of these peaks with these motifs: nothing runs again)
+      if (int rc = gx_motif_scan_peaks(ctxs[g], &n)) return rc;
+    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
+    const size_t at0 = pk.size(), h0 = hits.size();
+    pk.resize(at0 + k);
+    if (k)
+      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
+    hits.resize(h0 + n);
+    if (int rc = gx_get_motif_hits(ctxs[g], hits.data() + h0, n)) return rc;
+    for (size_t i = h0; i < hits.size(); i++) hits[i].region += (uint32_t)at0;
+    if (int rc = gx_get_motif_counts(ctxs[g], one.data(), one.data() + nM, one.data() + 2 * nM, nM)) return rc;
+    for (size_t i = 0; i < 3 * nM; i++) cPeaks[i] += one[i];
+  }
+  std::vector<size_t> ord(pk.size()), rank(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+  if (n_ctx > 1)
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
+  reg.resize(pk.size());
+  summit.resize(pk.size());
+  for (size_t i = 0; i < ord.size(); i++) {
+    reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
+    summit[i] = pk[ord[i]].summit;
+    rank[ord[i]] = i;
+  }
+  for (gx_motif_hit& h : hits) h.region = (uint32_t)rank[h.region];
+  if (n_ctx > 1)
+    std::sort(hits.begin(), hits.end(), [](const gx_motif_hit& x, const gx_motif_hit& y) {
+      if (x.region != y.region) return x.region < y.region;
+      if (x.pos != y.pos) return x.pos < y.pos;
+      if (x.motif != y.motif) return x.motif < y.motif;
+      return x.strand < y.strand;
+    });
+  return GX_OK;
+}
+
+int gx_write_motifs_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_motif* motifs, const char* const* ids,
+                          const char* const* motif_names, const double* p_threshold, int n_motifs, FILE* hits_out, FILE* summary_out,
+                          uint64_t* counts_peaks, uint64_t* counts_genome, gx_motif_report* report) {
+  if (!hits_out && !summary_out) return GX_ERR_ORDER;
+  std::vector<gx_region> reg;
+  std::vector<uint32_t> summit;
+  std::vector<gx_motif_hit> hits;
+  std::vector<uint64_t> cP, cG;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = motif_group(ctxs, n_ctx, n_motifs, false, reg, summit, hits, cP, cG)) return rc;
+  const auto t1 = std::chrono::steady_clock::now();
+  const size_t nM = (size_t)n_motifs;
+  if (summary_out)
+    if (int rc = gx_motif_scan_genome_group(ctxs, n_ctx, cG.data(), cG.data() + nM, cG.data() + 2 * nM, nM)) return rc;
+  const auto t2 = std::chrono::steady_clock::now();
+  if (hits_out)
+    if (int rc = gx_format_motif_hits(hits_out, names, reg.data(), summit.data(), reg.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size()))
+      return rc;
+  if (summary_out)
+    if (int rc = gx_format_motif_summary(summary_out, reg.data(), reg.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size(), cP.data(), cG.data()))
+      return rc;
+  if (counts_peaks) std::copy(cP.begin(), cP.end(), counts_peaks);
+  if (counts_genome) std::copy(cG.begin(), cG.end(), counts_genome);
+  if (report) {
+    report->hits = hits.size();
+    report->peaks_with_hit = 0;
+    for (size_t i = 0; i < hits.size(); i++) report->peaks_with_hit += i == 0 || hits[i].region != hits[i - 1].region;
+    report->peaks_seconds = std::chrono::duration<double>(t1 - t0).count();
+    report->genome_seconds = std::chrono::duration<double>(t2 - t1).count();
+  }
+  return GX_OK;
+}
+
+int gx_write_motif_hits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_motif* motifs, const char* const* ids,
+                              const char* const* motif_names, const double* p_threshold, int n_motifs, FILE* out) {
+  return gx_write_motifs_group(ctxs, n_ctx, names, motifs, ids, motif_names, p_threshold, n_motifs, out, nullptr, nullptr, nullptr, nullptr);
+}
+
+int gx_write_motif_summary_group(gx_ctx* const* ctxs, int n_ctx, const gx_motif* motifs, const char* const* ids, const char* const* motif_names,
+                                 const double* p_threshold, int n_motifs, FILE* out) {
+  return gx_write_motifs_group(ctxs, n_ctx, nullptr, motifs, ids, motif_names, p_threshold, n_motifs, nullptr, out, nullptr, nullptr, nullptr);
 }
 
 uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index) { return subsample_draw(subsample_key(seed, sample), index); }

@@ -1595,4 +1595,146 @@ int gx_format_gc_peaks(FILE* out, const char* const* names, const gx_region* pea
   return GX_OK;
 }
 
+// --motifs (no Genrich counterpart): from a count matrix to scores in 1/128 bit against a uniform background and to the
+// threshold of a p-value, counted exactly over all 4^L L-mers.  Host only.
+static int motif_refuse(char* why, size_t cap, const char* text) {
+  if (why && cap) snprintf(why, cap, "%s", text);
+  return GX_ERR_ORDER;
+}
+
+int gx_motif_pssm(const uint32_t* counts, int width, double pseudocount, int16_t* scores, int32_t* smin, int32_t* smax, char* why, size_t cap) {
+  if (width < 1 || width > GX_MOTIF_MAX_WIDTH) return motif_refuse(why, cap, "the width must satisfy 1 <= L <= 32");
+  if (!counts || !scores) return GX_ERR_ORDER;
+  if (!(pseudocount >= 0.0) || !std::isfinite(pseudocount)) return motif_refuse(why, cap, "the pseudocount must be a number >= 0");
+  long long lo = 0, hi = 0;
+  for (int j = 0; j < width; j++) {
+    uint64_t N = 0;
+    for (int b = 0; b < 4; b++) {
+      if (counts[b * width + j] >> 31) return motif_refuse(why, cap, "a count of 2^31 or more");
+      N += counts[b * width + j];
+    }
+    long long cmin = 0, cmax = 0;
+    for (int b = 0; b < 4; b++) {
+      const double num = (double)counts[b * width + j] + 0.25 * pseudocount, den = (double)N + pseudocount;
+      if (!(den > 0.0) || !(num > 0.0)) return motif_refuse(why, cap, "a zero count without a pseudocount: the score would be minus infinity");
+      const double v = 128.0 * std::log2((num / den) / 0.25);
+      if (!(v > -40000.0 && v < 40000.0)) return motif_refuse(why, cap, "a score outside int16");
+      const long long s = std::llround(v);
+      if (s < -32768 || s > 32767) return motif_refuse(why, cap, "a score outside int16");
+      scores[4 * j + b] = (int16_t)s;
+      cmin = b ? std::min(cmin, s) : s;
+      cmax = b ? std::max(cmax, s) : s;
+    }
+    lo += cmin;
+    hi += cmax;
+  }
+  if (smin) *smin = (int32_t)lo;
+  if (smax) *smax = (int32_t)hi;
+  return GX_OK;
+}
+
+int gx_motif_threshold(const int16_t* scores, int width, double p, int32_t* threshold, int32_t* smin, int32_t* smax, double* p_achieved,
+                       int* unreachable) {
+  if (!scores || width < 1 || width > GX_MOTIF_MAX_WIDTH || !(p > 0.0) || !(p <= 1.0)) return GX_ERR_ORDER;
+  // K = floor(p * 4^L): p = M * 2^(e - 53) with a 53-bit integer M
+  int e = 0;
+  const uint64_t M = (uint64_t)std::ldexp(std::frexp(p, &e), 53);
+  const int sh = e - 53 + 2 * width;   // (at most 1 - 53 + 64)
+  const u128_t K = sh >= 0 ? (u128_t)M << sh : sh > -64 ? (u128_t)(M >> -sh) : (u128_t)0;
+  // dist[s - lo] = the L-mers of the columns so far whose score is s
+  long long lo = 0, hi = 0;
+  std::vector<u128_t> dist(1, (u128_t)1), next;
+  for (int j = 0; j < width; j++) {
+    const int16_t* c = scores + 4 * j;
+    const long long cmin = std::min(std::min(c[0], c[1]), std::min(c[2], c[3])), cmax = std::max(std::max(c[0], c[1]), std::max(c[2], c[3]));
+    next.assign((size_t)(hi + cmax - lo - cmin + 1), (u128_t)0);
+    for (size_t k = 0; k < dist.size(); k++)
+      if (dist[k])
+        for (int b = 0; b < 4; b++) next[k + (size_t)(c[b] - cmin)] += dist[k];
+    dist.swap(next);
+    lo += cmin;
+    hi += cmax;
+  }
+  // from the greatest score down: n_ge(s) = the sum from s on
+  u128_t nge = 0, at = 0;
+  long long t = hi + 1;
+  for (long long s = hi; s >= lo; s--) {
+    nge += dist[(size_t)(s - lo)];
+    if (nge > K) break;
+    t = s;
+    at = nge;
+  }
+  if (threshold) *threshold = (int32_t)t;
+  if (smin) *smin = (int32_t)lo;
+  if (smax) *smax = (int32_t)hi;
+  if (unreachable) *unreachable = t > hi ? 1 : 0;
+  if (p_achieved) *p_achieved = std::ldexp((double)at, -2 * width);   // (one rounding of the count; the division is exact)
+  return GX_OK;
+}
+
+static void put_motif_p(FILE* out, double p) {
+  if (std::isnan(p)) fprintf(out, "\tNA");
+  else fprintf(out, "\t%.3e", p);
+}
+
+// --motif-hits: one BED-like row per hit, in the order given
+int gx_format_motif_hits(FILE* out, const char* const* names, const gx_region* peaks, const uint32_t* summit_off, size_t n_peaks,
+                         const gx_motif* motifs, const char* const* ids, const char* const* motif_names, const double* p_threshold, int n_motifs,
+                         const gx_motif_hit* hits, size_t n_hits) {
+  if (!out || n_motifs < 0 || (n_hits && (!hits || !peaks || !summit_off || !names || !motifs || !ids || !motif_names || !p_threshold))) return GX_ERR_ORDER;
+  for (size_t i = 0; i < n_hits; i++) {
+    const gx_motif_hit& h = hits[i];
+    if (h.region >= n_peaks || h.motif >= n_motifs || h.strand > 1) return GX_ERR_ORDER;
+    if ((uint64_t)h.pos + motifs[h.motif].width > (uint64_t)peaks[h.region].end - peaks[h.region].start) return GX_ERR_ORDER;
+  }
+  fprintf(out, "chr\tstart\tend\tmotif\tscore\tstrand\tname\tpeak\toffset_from_summit\tp_threshold\n");
+  for (size_t i = 0; i < n_hits; i++) {
+    const gx_motif_hit& h = hits[i];
+    const gx_region& k = peaks[h.region];
+    const long L = (long)motifs[h.motif].width, at = (long)k.start + (long)h.pos;
+    fprintf(out, "%s\t%ld\t%ld\t%s\t%.4f\t%c\t%s\tpeak_%u\t%ld", names[k.chrom], at, at + L, ids[h.motif], (double)h.score / 128.0, h.strand ? '-' : '+',
+            motif_names[h.motif], h.region, (2 * at + L) / 2 - ((long)k.start + (long)summit_off[h.region]));
+    put_motif_p(out, p_threshold[h.motif]);
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
+// --motif-summary: one row per motif
+int gx_format_motif_summary(FILE* out, const gx_region* peaks, size_t n_peaks, const gx_motif* motifs, const char* const* ids,
+                            const char* const* motif_names, const double* p_threshold, int n_motifs, const gx_motif_hit* hits, size_t n_hits,
+                            const uint64_t* counts_peaks, const uint64_t* counts_genome) {
+  if (!out || n_motifs < 0 || (n_peaks && !peaks) || (n_hits && !hits) ||
+      (n_motifs && (!motifs || !ids || !motif_names || !p_threshold || !counts_peaks || !counts_genome)))
+    return GX_ERR_ORDER;
+  const size_t nM = (size_t)n_motifs;
+  // the peaks with any hit of a motif: the hits come sorted by region, so a motif's last region tells a new one
+  std::vector<uint64_t> withHit(nM, 0);
+  std::vector<uint64_t> last(nM, ~0ull);
+  for (size_t i = 0; i < n_hits; i++) {
+    const gx_motif_hit& h = hits[i];
+    if (h.region >= n_peaks || h.motif >= nM || (i && hits[i - 1].region > h.region)) return GX_ERR_ORDER;
+    if (last[h.motif] != h.region) {
+      last[h.motif] = h.region;
+      withHit[h.motif]++;
+    }
+  }
+  fprintf(out, "motif\tname\twidth\tthreshold\tp_threshold\tpeaks_scanned\tpeaks_with_hit\twindows_peaks\thits_peaks\twindows_genome\thits_genome\tenrichment\n");
+  for (size_t m = 0; m < nM; m++) {
+    uint64_t scanned = 0;
+    for (size_t k = 0; k < n_peaks; k++)
+      if (peaks[k].end > peaks[k].start && peaks[k].end - peaks[k].start >= motifs[m].width) scanned++;
+    const u128_t hp = (u128_t)counts_peaks[nM + m] + counts_peaks[2 * nM + m], hg = (u128_t)counts_genome[nM + m] + counts_genome[2 * nM + m];
+    const uint64_t wp = counts_peaks[m], wg = counts_genome[m];
+    fprintf(out, "%s\t%s\t%u\t%.4f", ids[m], motif_names[m], motifs[m].width, (double)motifs[m].threshold / 128.0);
+    put_motif_p(out, p_threshold[m]);
+    fprintf(out, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu", (unsigned long long)scanned, (unsigned long long)withHit[m], (unsigned long long)wp,
+            (unsigned long long)(uint64_t)hp, (unsigned long long)wg, (unsigned long long)(uint64_t)hg);
+    if (hg == 0 || wp == 0) fprintf(out, "\tNA");
+    else fprintf(out, "\t%.6f", to_double(mul128(hp, wg)) / to_double(mul128(hg, wp)));
+    fprintf(out, "\n");
+  }
+  return GX_OK;
+}
+
 }  // extern "C"

@@ -36,6 +36,7 @@
 #include "gx_ivstat.h"
 #include "gx_xcor.h"
 #include "gx_gcbias.h"
+#include "gx_motifs.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
@@ -595,6 +596,21 @@ struct gx_ctx {
   std::vector<GcResult> gcRes;      // the last gx_gc_bias, per kept sample (until gx_reset)
   bool gcReady = false;
   bool gcUsed = false;              // a kernel of gx_gcbias.h ran since the last gx_reset
+  // the sequence itself and the motifs scanned in it (gx_set_genome_bases / gx_set_motifs / gx_motif_scan_*, gx_motifs.h);
+  // nothing here exists before gx_set_genome_bases, gx_set_motifs and the first scan
+  bool seqOn = false;               // the third vector exists: gx_push_sequence fills all three (k_seq_pack3)
+  DevBuf gcAg;                      // ... laid out and cleared with the other two
+  DevBuf seqOut;                    // gx_get_sequence's letters
+  std::vector<MotMeta> motMeta;     // the motifs (gx_set_motifs) ...
+  std::vector<int> motTabs;         // ... and their tables [motif][MOT_TAB_WORDS], both strands packed
+  bool motDirty = false;            // ... are not on the device yet
+  DevBuf motTabDev, motMetaDev, motReg, motOut, motList;   // tables, metas, a pass's regions, its control words and counts, its hit list
+  PinnedBuf motHost;                // the count-only pass' words on their way back
+  std::vector<gx_motif_hit> motHits;            // the last gx_motif_scan_peaks' hits, sorted (until gx_reset)
+  std::vector<uint64_t> motCounts;              // ... and its counts [3][motif]
+  bool motReady = false;
+  bool motUsed = false;             // k_motif_scan ran since the last gx_reset
+  u32 motLastReruns = 0, motLastBatches = 0;    // the last pass: how often it ran again, its LDS batches
   // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
   struct DepthResult {
     int rep = 0;

@@ -39,6 +39,10 @@ int gc_layout(gx_ctx* ctx) {
       ctx->gcTab.ensure((size_t)ctx->nChrom * sizeof(GcChrom)) != hipSuccess)
     return pool_failed(ctx);
   hipStream_t s = ctx->stream;
+  if (ctx->seqOn) {   // (gx_set_genome_bases: the third vector, with the other two)
+    if (ctx->gcAg.ensure(bytes) != hipSuccess) return pool_failed(ctx);
+    HIPCHECK(hipMemsetAsync(ctx->gcAg.p, 0, bytes, s));
+  }
   HIPCHECK(hipMemsetAsync(ctx->gcVec.p, 0, bytes, s));
   HIPCHECK(hipMemsetAsync(ctx->gcAcgt.p, 0, bytes, s));
   HIPCHECK(hipMemcpyAsync(ctx->gcTab.p, ctx->gcChrom.data(), (size_t)ctx->nChrom * sizeof(GcChrom), hipMemcpyHostToDevice, s));
@@ -81,8 +85,13 @@ int gc_push(gx_ctx* ctx, int chrom, uint64_t first, const char* bases, size_t n)
     HIPCHECK(hipEventRecord(ctx->gcStageFree[k], s));
     const u64 groups = ((u64)take + 63) / 64 * 4;
     phase_begin(ctx, "gc.pack");
-    hipLaunchKernelGGL(k_gc_pack, dim3((unsigned)((groups + GC_NT - 1) / GC_NT)), dim3(GC_NT), 0, s, ctx->gcSeq.as<uint4>(), (u64)take,
-                       cc.off + (first + done) / 64, ctx->gcVec.as<unsigned long long>(), ctx->gcAcgt.as<unsigned long long>());
+    if (ctx->seqOn)
+      hipLaunchKernelGGL(k_seq_pack3, dim3((unsigned)((groups + GC_NT - 1) / GC_NT)), dim3(GC_NT), 0, s, ctx->gcSeq.as<uint4>(), (u64)take,
+                         cc.off + (first + done) / 64, ctx->gcVec.as<unsigned long long>(), ctx->gcAcgt.as<unsigned long long>(),
+                         ctx->gcAg.as<unsigned long long>());
+    else
+      hipLaunchKernelGGL(k_gc_pack, dim3((unsigned)((groups + GC_NT - 1) / GC_NT)), dim3(GC_NT), 0, s, ctx->gcSeq.as<uint4>(), (u64)take,
+                         cc.off + (first + done) / 64, ctx->gcVec.as<unsigned long long>(), ctx->gcAcgt.as<unsigned long long>());
     if (int rc__ = dbg_sync(ctx, "k_gc_pack")) return rc__;
     HIPCHECK(hipGetLastError());
     phase_end(ctx);

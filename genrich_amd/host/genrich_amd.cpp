@@ -66,6 +66,7 @@
 static const float NOSCORE = -FLT_MAX;
 
 // the program by stage, one translation unit; this file keeps the thread budget, usage(), the options and main
+#include "host_motifs.h"   // --motifs: the JASPAR reader
 #include "host_common.h"   // die, number parsing, output files, the input stream
 #include "host_state.h"    // options, chromosome table, device contexts, HotWindows
 #include "host_events.h"   // the alignments of a read name -> events (pairing, weighting, saveInterval)
@@ -211,6 +212,29 @@ void usageGc() {
   exit(EXIT_FAILURE);
 }
 
+// --help-motifs: the block of --motifs and its sub-options, likewise
+void usageMotifs() {
+  fprintf(stderr,
+          "  --motifs FILE   known motifs as JASPAR count matrices (`>ID NAME`, then four rows `A [ n n ... ]` .. `T [ ... ]`, or four\n"
+          "                  bare rows in the order A C G T; widths 1 .. 32, at most 4096 motifs), scanned on the device at every\n"
+          "                  position of every called peak on both strands.  Scores are log-odds against a uniform background in\n"
+          "                  1/128 bit; a motif's threshold is the least score that at most a share P of all 4^L L-mers reach,\n"
+          "                  counted exactly.  A window with an unknown base is not scanned; -E regions are NOT masked.  Needs\n"
+          "                  --genome FASTA and --motif-hits or --motif-summary; works with -z, --devices; not with -X, -P or\n"
+          "                  --events-only\n"
+          "  --motif-hits FILE   one BED-like row per hit in the order of -o, then position, motif, strand: chr, start, end, ID,\n"
+          "                  score (bits), strand, NAME, peak_N, the offset of the window's middle from the peak's summit and the\n"
+          "                  threshold's p\n"
+          "  --motif-summary FILE   one row per motif: ID, NAME, width, threshold (bits) and its p, the peaks long enough to scan and\n"
+          "                  those with a hit, the windows and hits (both strands) in the peaks and in the WHOLE genome (every\n"
+          "                  window of every chromosome that takes part, counted, not sampled) and the enrichment (hits per window in\n"
+          "                  the peaks over hits per window in the genome; NA without a hit in the genome)\n"
+          "  --motif-pvalue P (1e-4; 0 < P <= 1), --motif-pseudocount X (1; added to each column, a quarter to each base)\n"
+          "                  -v: the motifs read, those that cannot hit at P, the hits, the peaks with any, the three most enriched\n"
+          "                  motifs and the time of the genome pass\n");
+  exit(EXIT_FAILURE);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -273,6 +297,12 @@ int main(int argc, char** argv) {
                                      {"gc-window", required_argument, nullptr, 1051},
                                      {"gc-peaks", required_argument, nullptr, 1052},
                                      {"help-gc", no_argument, nullptr, 1053},
+                                     {"motifs", required_argument, nullptr, 1054},
+                                     {"motif-hits", required_argument, nullptr, 1055},
+                                     {"motif-summary", required_argument, nullptr, 1056},
+                                     {"motif-pvalue", required_argument, nullptr, 1057},
+                                     {"motif-pseudocount", required_argument, nullptr, 1058},
+                                     {"help-motifs", no_argument, nullptr, 1059},
                                      {nullptr, 0, nullptr, 0}};
   int nThreads;  // BGZF inflate threads and record decoders: --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores
   {
@@ -435,6 +465,24 @@ int main(int argc, char** argv) {
       }
       case 1052: o.gcPeaksFile = optarg; break;
       case 1053: usageGc();
+      case 1054: o.motifsFile = optarg; break;
+      case 1055: o.motifHitsFile = optarg; break;
+      case 1056: o.motifSummaryFile = optarg; break;
+      case 1057: {
+        char* end = nullptr;
+        o.motifPvalue = strtod(optarg, &end);
+        if (end == optarg || *end || !(o.motifPvalue > 0.0) || !(o.motifPvalue <= 1.0)) die(optarg, ": --motif-pvalue takes a number in (0, 1]");
+        o.motifPvalueOpt = true;
+        break;
+      }
+      case 1058: {
+        char* end = nullptr;
+        o.motifPseudo = strtod(optarg, &end);
+        if (end == optarg || *end || !(o.motifPseudo >= 0.0) || !std::isfinite(o.motifPseudo)) die(optarg, ": --motif-pseudocount takes a number >= 0");
+        o.motifPseudoOpt = true;
+        break;
+      }
+      case 1059: usageMotifs();
       case 1020: o.spearmanFile = optarg; break;
       case 1003: {  // --devices 0,1,2 or 0-7
         std::string list(optarg);
@@ -507,7 +555,13 @@ int main(int argc, char** argv) {
   if (o.gcBiasFile && !o.genomeFile) die("", "--gc-bias needs the reference sequence (--genome FASTA)");
   if (o.gcPeaksFile && !o.genomeFile) die("", "--gc-peaks needs the reference sequence (--genome FASTA)");
   if (o.gcWindowOpt && !o.gcBiasFile) die("", "--gc-window needs --gc-bias FILE");
-  if (o.genomeFile && !o.gcBiasFile && !o.gcPeaksFile) die("", "--genome needs --gc-bias FILE or --gc-peaks FILE");
+  if (o.motifsFile && !o.genomeFile) die("", "--motifs needs the reference sequence (--genome FASTA)");
+  if (o.motifsFile && !o.motifHitsFile && !o.motifSummaryFile) die("", "--motifs needs --motif-hits FILE or --motif-summary FILE");
+  if ((o.motifHitsFile || o.motifSummaryFile || o.motifPvalueOpt || o.motifPseudoOpt) && !o.motifsFile)
+    die("", "--motif-hits, --motif-summary, --motif-pvalue and --motif-pseudocount need --motifs FILE");
+  // (the motifs are scanned in the peaks this run calls, on a device context: -P has neither)
+  if (o.motifsFile && !o.callsPeaks()) die("", "--motifs needs the peaks of this run on a device (not with -X, -P or --events-only)");
+  if (o.genomeFile && !o.gcBiasFile && !o.gcPeaksFile && !o.motifsFile) die("", "--genome needs --gc-bias FILE or --gc-peaks FILE");
   // (the bias counts the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.gcBiasFile && !o.buildsPileups()) die("", "--gc-bias needs the intervals of this run (not with -P or --events-only)");
   // (the content is taken in the peaks this run calls, on a device context: -P has neither)
@@ -639,6 +693,7 @@ int main(int argc, char** argv) {
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_depth_hist(g, 1), g);
   if (o.xcorOn())
     for (gx_ctx* g : S.devs.ctx) check(S, gx_set_xcor(g, o.xcorLo, o.xcorHi), g);
+  if (o.motifsFile) loadMotifs(S);
   if (o.genomeFile) loadGenome(S);
   ProfilePlan profilePlan;
   if (o.profileBed) {
@@ -774,6 +829,7 @@ int main(int argc, char** argv) {
   if (o.xcorOn()) writeXcor(S);
   if (o.gcBiasFile) writeGcBias(S);
   if (o.gcPeaksFile) writeGcPeaks(S, names);
+  if (o.motifsFile) writeMotifs(S, names);
   if (o.saturationFile) writeSaturation(S);
   if (o.reproOn()) writeReproducibility(S, names);
   if (o.profileBed) writeProfile(S, profilePlan, sampleNames);

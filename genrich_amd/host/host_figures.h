@@ -512,6 +512,11 @@ void loadGenome(State& S) {
   const Opts& o = S.o;
   const auto t0 = std::chrono::steady_clock::now();
   for (gx_ctx* g : S.devs.ctx) check(S, gx_set_genome(g, 1), g);
+  if (o.motifsFile)   // (the scan needs the bases themselves: the third vector, and the motifs with it)
+    for (gx_ctx* g : S.devs.ctx) {
+      check(S, gx_set_genome_bases(g, 1), g);
+      check(S, gx_set_motifs(g, S.motifRecs.data(), (int)S.motifRecs.size(), S.motifScores.data()), g);
+    }
   GenomeSink sink(S);
   const size_t chunk = (size_t)1 << 22;
   unsigned char magic[2] = {0, 0};
@@ -613,6 +618,68 @@ void writeGcPeaks(State& S, const std::vector<const char*>& names) {
     a2.push_back(acgt[i]);
   }
   writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_format_gc_peaks(f, names.data(), r2.data(), r2.size(), g2.data(), a2.data()); });
+}
+
+// --motifs FILE: the JASPAR matrices (host_motifs.h) to scores and thresholds (gx_motif_pssm, gx_motif_threshold: host only), and
+// to every context.  A matrix the reader or the library refuses ends the run with its ID and the sentence; a motif that cannot
+// hit at --motif-pvalue stays in the run with one warning under -v and NA for its p.
+void loadMotifs(State& S) {
+  const Opts& o = S.o;
+  std::string err;
+  if (!gxhost::motifs_read_plain(o.motifsFile, S.motifs, &err)) die("--motifs: ", err.c_str());
+  size_t at = 0;
+  for (const gxhost::MotifRec& m : S.motifs) at += 4 * (size_t)m.width;
+  S.motifScores.assign(at, 0);
+  at = 0;
+  for (const gxhost::MotifRec& m : S.motifs) {
+    char why[160] = "";
+    int32_t t = 0;
+    double p = 0.0;
+    int unreachable = 0;
+    if (gx_motif_pssm(m.counts.data(), (int)m.width, o.motifPseudo, S.motifScores.data() + at, nullptr, nullptr, why, sizeof why) != GX_OK)
+      die("--motifs: ", (m.id + ": " + (why[0] ? why : "a matrix the library refuses")).c_str());
+    check(S, gx_motif_threshold(S.motifScores.data() + at, (int)m.width, o.motifPvalue, &t, nullptr, nullptr, &p, &unreachable));
+    if (unreachable && o.verbose)
+      fprintf(stderr, "Warning! motif %s cannot hit at --motif-pvalue %g: even its best score has more than that share of the %u-mers\n", m.id.c_str(),
+              o.motifPvalue, m.width);
+    S.motifRecs.push_back(gx_motif{m.width, (uint32_t)at, t});
+    S.motifP.push_back(unreachable ? std::nan("") : p);
+    at += 4 * (size_t)m.width;
+  }
+  if (o.verbose) fprintf(stderr, "Motifs %s: %zu matrices, p-value %g, pseudocount %g\n", o.motifsFile, S.motifs.size(), o.motifPvalue, o.motifPseudo);
+}
+
+// --motif-hits FILE / --motif-summary FILE: the motifs in the called peaks (k_motif_scan on the context that owns the
+// chromosome; the contexts' peak lists merged in the order of -o, the same peak_N) and, for the summary, counted over the whole
+// genome too.  With -v the hits, the peaks with any, the three most enriched motifs and the time of the genome pass
+void writeMotifs(State& S, const std::vector<const char*>& names) {
+  const Opts& o = S.o;
+  gx_ctx* const* ctxs = S.devs.ctx.data();
+  const int nCtx = (int)S.devs.n(), nM = (int)S.motifs.size();
+  std::vector<const char*> ids, mnames;
+  for (const gxhost::MotifRec& m : S.motifs) {
+    ids.push_back(m.id.c_str());
+    mnames.push_back(m.name.c_str());
+  }
+  // (one call for both files: the peaks are scanned once, the genome once and only for the summary)
+  std::vector<uint64_t> cp((size_t)3 * nM + 1, 0), cg((size_t)3 * nM + 1, 0);
+  gx_motif_report rep{};
+  writeFiles(S, o.motifHitsFile, o.motifSummaryFile, [&](FILE* hits, FILE* summary) {
+    return gx_write_motifs_group(ctxs, nCtx, names.data(), S.motifRecs.data(), ids.data(), mnames.data(), S.motifP.data(), nM, hits, summary, cp.data(),
+                                 cg.data(), &rep);
+  });
+  if (!o.verbose) return;
+  fprintf(stderr, "Motif hits: %llu in %llu peaks\n", (unsigned long long)rep.hits, (unsigned long long)rep.peaks_with_hit);
+  if (!o.motifSummaryFile) return;
+  std::vector<std::pair<double, int>> enr;
+  for (int m = 0; m < nM; m++) {
+    const double hp = (double)(cp[(size_t)nM + m] + cp[(size_t)2 * nM + m]), hg = (double)(cg[(size_t)nM + m] + cg[(size_t)2 * nM + m]);
+    if (hg > 0 && cp[m]) enr.push_back({(hp * (double)cg[m]) / (hg * (double)cp[m]), m});
+  }
+  std::sort(enr.begin(), enr.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) { return x.first != y.first ? x.first > y.first : x.second < y.second; });
+  for (size_t k = 0; k < enr.size() && k < 3; k++)
+    fprintf(stderr, "  Motif %s (%s): enrichment %f\n", S.motifs[enr[k].second].id.c_str(), S.motifs[enr[k].second].name.c_str(), enr[k].first);
+  fprintf(stderr, "  Motif summary: the peaks in %.3f s, the genome pass in %.3f s\n", rep.peaks_seconds, rep.genome_seconds);
 }
 
 // --xcor FILE / --xcor-metrics FILE: the strand cross-correlation of each sample's 5' ends, counted on the device when the

@@ -68,6 +68,11 @@ struct Opts {
   int gcWindow = 200;                      // --gc-window W
   bool gcWindowOpt = false;
   const char* gcPeaksFile = nullptr;       // --gc-peaks FILE: the GC content of every called peak
+  const char* motifsFile = nullptr;        // --motifs FILE: JASPAR count matrices, scanned in the called peaks on the device
+  const char* motifHitsFile = nullptr;     // --motif-hits FILE: every hit, BED-like
+  const char* motifSummaryFile = nullptr;  // --motif-summary FILE: per motif the peaks' and the genome's counts and the enrichment
+  double motifPvalue = 1e-4, motifPseudo = 1.0;   // --motif-pvalue P, --motif-pseudocount X
+  bool motifPvalueOpt = false, motifPseudoOpt = false;
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;
@@ -189,6 +194,11 @@ struct State {
   int sample = 0;
   uint64_t errCount = 0;
   HotWindows hot;            // (with a device: saveInterval's int16 checks)
+  // --motifs: the matrices read, their scores (row j: A C G T), the records the library takes and each threshold's achieved p
+  std::vector<gxhost::MotifRec> motifs;
+  std::vector<int16_t> motifScores;
+  std::vector<gx_motif> motifRecs;
+  std::vector<double> motifP;   // (NaN: the motif cannot hit)
 };
 
 void check(State& S, int rc, gx_ctx* which = nullptr) {

@@ -146,6 +146,12 @@ GX_PATH_COMPLEXITY = 8388608    # gx_path_info bit 23: k_cpx_insert ran (gx_comp
 GX_PATH_IVSTAT = 67108864       # gx_path_info bit 26: k_ivstat ran (gx_interval_stats, gx_interval_stats_events)
 GX_PATH_XCOR = 134217728        # gx_path_info bit 27: k_xc_set / k_xc_corr ran (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags)
 GX_PATH_GC = 1073741824         # gx_path_info bit 30: a kernel of the genome / GC passes ran (gx_push_sequence, gx_gc_content, gx_gc_bias, gx_gc_bias_events)
+GX_PATH_MOTIFS = 2147483648     # gx_path_info bit 31: k_motif_scan ran (gx_motif_scan_regions, gx_motif_scan_peaks, gx_motif_scan_genome)
+MOTIF_MAX_WIDTH = 32            # GX_MOTIF_MAX_WIDTH
+MOTIF_MAX = 4096                # GX_MOTIF_MAX
+MOTIF_SCALE = 128               # GX_MOTIF_SCALE
+MOTIF_DTYPE = np.dtype([("width", "<u4"), ("offset", "<u4"), ("threshold", "<i4")])   # gx_motif
+MOTIF_HIT_DTYPE = np.dtype([("region", "<u4"), ("pos", "<u4"), ("score", "<i4"), ("motif", "<u2"), ("strand", "u1"), ("pad", "u1")])   # gx_motif_hit
 GC_MAX_WINDOW = 4096            # GX_GC_MAX_WINDOW
 GC_MIN_TILE = 64                # GX_GC_MIN_TILE
 GC_CLASSES = 101                # GX_GC_CLASSES
@@ -443,6 +449,30 @@ _SIGS = {
     "gx_format_gc_bias": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6,
     "gx_format_gc_peaks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
     "gx_write_gc_bias_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "gx_set_genome_bases": [C.c_void_p, C.c_int],
+    "gx_get_sequence": [C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_void_p],
+    "gx_set_motifs": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_motif_scan_regions": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t,
+                              C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_motif_scan_peaks": [C.c_void_p, C.POINTER(C.c_size_t)],
+    "gx_get_motif_hits": [C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_get_motif_counts": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_motif_last": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "gx_motif_scan_genome": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_motif_scan_genome_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_motif_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_uint32)] * 3 + [C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)],
+    "gx_motif_grid": [C.c_uint64, C.c_uint32, C.c_uint, C.POINTER(C.c_uint)],
+    "gx_write_motifs_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p],
+    "gx_motif_pssm": [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_size_t],
+    "gx_motif_threshold": [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                           C.POINTER(C.c_double), C.POINTER(C.c_int)],
+    "gx_format_motif_hits": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                             C.c_void_p, C.c_size_t],
+    "gx_format_motif_summary": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                C.c_void_p, C.c_void_p],
+    "gx_write_motif_hits_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_write_motif_summary_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "gx_interval_stats": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_get_interval_lengths": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
@@ -968,6 +998,127 @@ def gc_bias_text(ctxs, window=200) -> bytes:
     lib = load_library()
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
     return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_gc_bias_group(arr, len(ctxs), int(window), f)))
+
+
+def motif_geometry():
+    """(lanes, grid, positions_per_step, step_words, batch_motifs, list_capacity, flush_runs) of the motif scan as the library was
+    built (gx_motif_geometry): the lanes of a workgroup of k_motif_scan, its most workgroups with grid = 0, the positions a wavefront
+    takes per step, the default runs of them per unit, the motifs per LDS batch, the first hit list's least capacity and the runs a
+    workgroup walks at most per batch (its 32-bit counters)."""
+    lib = load_library()
+    lanes, grid = C.c_int(0), C.c_int(0)
+    pos, step, batch = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    cap, flush = C.c_size_t(0), C.c_uint64(0)
+    lib.gx_motif_geometry(C.byref(lanes), C.byref(grid), C.byref(pos), C.byref(step), C.byref(batch), C.byref(cap), C.byref(flush))
+    return lanes.value, grid.value, pos.value, step.value, batch.value, cap.value, flush.value
+
+
+def motif_grid(units, step_words=0, grid=0):
+    """The workgroups a motif pass over `units` units of step_words runs takes (gx_motif_grid; host-only): the library's choice
+    with grid = 0, else `grid` itself; None when the library refuses it (a workgroup would walk more than the flush bound, or a
+    limit is broken)."""
+    g = C.c_uint(0)
+    rc = load_library().gx_motif_grid(int(units), int(step_words), int(grid), C.byref(g))
+    return None if rc else g.value
+
+
+def motif_pssm(counts, pseudocount=1.0):
+    """(scores int16[L, 4] in column order A C G T, smin, smax) of a count matrix counts[4, L] (rows A C G T) in 1/128 bit against
+    a uniform background (gx_motif_pssm); host-only.  ValueError with the library's sentence when it is refused."""
+    lib = load_library()
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.ndim != 2 or c.shape[0] != 4:
+        raise ValueError("counts must be [4, L]")
+    L = c.shape[1]
+    s = np.zeros((max(L, 1), 4), dtype=np.int16)
+    lo, hi = C.c_int32(0), C.c_int32(0)
+    why = C.create_string_buffer(256)
+    rc = lib.gx_motif_pssm(c.ctypes.data, L, float(pseudocount), s.ctypes.data, C.byref(lo), C.byref(hi), why, 256)
+    if rc:
+        raise ValueError(why.value.decode() or f"gx_motif_pssm: {rc}")
+    return s[:L], lo.value, hi.value
+
+
+def motif_threshold(scores, p):
+    """(threshold, smin, smax, p_achieved, unreachable) of scores int16[L, 4] for the p-value p in (0, 1], counted exactly over all
+    4^L L-mers (gx_motif_threshold); host-only."""
+    lib = load_library()
+    s = np.ascontiguousarray(scores, dtype=np.int16)
+    t, lo, hi = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    pa, un = C.c_double(0.0), C.c_int(0)
+    rc = lib.gx_motif_threshold(s.ctypes.data, s.shape[0], float(p), C.byref(t), C.byref(lo), C.byref(hi), C.byref(pa), C.byref(un))
+    if rc:
+        raise ValueError(f"gx_motif_threshold: {rc}")
+    return t.value, lo.value, hi.value, pa.value, bool(un.value)
+
+
+def pack_motifs(motifs):
+    """(MOTIF_DTYPE records, int16 scores) for [(scores int16[L, 4], threshold)], as gx_set_motifs takes them."""
+    rec = np.zeros(len(motifs), dtype=MOTIF_DTYPE)
+    flat, at = [], 0
+    for i, (s, t) in enumerate(motifs):
+        s = np.ascontiguousarray(s, dtype=np.int16).reshape(-1, 4)
+        rec[i] = (s.shape[0], at, int(t))
+        flat.append(s.reshape(-1))
+        at += s.size
+    return rec, (np.concatenate(flat) if flat else np.zeros(0, dtype=np.int16))
+
+
+def _motif_table_args(motifs, ids, motif_names, p_threshold):
+    rec, _ = pack_motifs(motifs)
+    p = np.ascontiguousarray(p_threshold, dtype=np.float64)
+    return rec, _c_names(list(ids)), _c_names(list(motif_names)), p
+
+
+def format_motif_hits(names, peaks, summit_off, motifs, ids, motif_names, p_threshold, hits) -> bytes:
+    """--motif-hits' table (gx_format_motif_hits) of `hits` (MOTIF_HIT_DTYPE, sorted) in `peaks` (REGION_DTYPE) with their summits'
+    offsets; motifs: [(scores, threshold)]; host-only."""
+    lib = load_library()
+    reg = np.ascontiguousarray(peaks, dtype=REGION_DTYPE)
+    so = np.ascontiguousarray(summit_off, dtype=np.uint32)
+    h = np.ascontiguousarray(hits, dtype=MOTIF_HIT_DTYPE)
+    rec, ci, cn, p = _motif_table_args(motifs, ids, motif_names, p_threshold)
+    nm = _c_names(names)
+    return _to_tmpfile(lambda f: lib.gx_format_motif_hits(f, nm, reg.ctypes.data, so.ctypes.data, reg.size, rec.ctypes.data, ci, cn, p.ctypes.data, len(rec),
+                                                          h.ctypes.data if h.size else None, h.size))
+
+
+def format_motif_summary(peaks, motifs, ids, motif_names, p_threshold, hits, counts_peaks, counts_genome) -> bytes:
+    """--motif-summary's table (gx_format_motif_summary); counts_*: uint64[3, motifs] windows, hits +, hits -; host-only."""
+    lib = load_library()
+    reg = np.ascontiguousarray(peaks, dtype=REGION_DTYPE)
+    h = np.ascontiguousarray(hits, dtype=MOTIF_HIT_DTYPE)
+    rec, ci, cn, p = _motif_table_args(motifs, ids, motif_names, p_threshold)
+    cp, cg = np.ascontiguousarray(counts_peaks, dtype=np.uint64), np.ascontiguousarray(counts_genome, dtype=np.uint64)
+    return _to_tmpfile(lambda f: lib.gx_format_motif_summary(f, reg.ctypes.data if reg.size else None, reg.size, rec.ctypes.data, ci, cn, p.ctypes.data, len(rec),
+                                                             h.ctypes.data if h.size else None, h.size, cp.ctypes.data, cg.ctypes.data))
+
+
+def motif_scan_genome_group(ctxs):
+    """uint64[3, motifs] (windows, hits +, hits -) of the genome pass added over the contexts of a run (gx_motif_scan_genome_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    n = ctxs[0].n_motifs
+    out = np.zeros((3, max(n, 1)), dtype=np.uint64)
+    ctxs[0]._check(lib.gx_motif_scan_genome_group(arr, len(ctxs), out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, n))
+    return out[:, :n]
+
+
+def motif_hits_text(ctxs, names, motifs, ids, motif_names, p_threshold) -> bytes:
+    """--motif-hits' table over the contexts of a run (gx_write_motif_hits_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    rec, ci, cn, p = _motif_table_args(motifs, ids, motif_names, p_threshold)
+    nm = _c_names(names)
+    return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_motif_hits_group(arr, len(ctxs), nm, rec.ctypes.data, ci, cn, p.ctypes.data, len(rec), f)))
+
+
+def motif_summary_text(ctxs, motifs, ids, motif_names, p_threshold) -> bytes:
+    """--motif-summary's table over the contexts of a run (gx_write_motif_summary_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    rec, ci, cn, p = _motif_table_args(motifs, ids, motif_names, p_threshold)
+    return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_motif_summary_group(arr, len(ctxs), rec.ctypes.data, ci, cn, p.ctypes.data, len(rec), f)))
 
 
 def interval_stats_geometry():
@@ -1957,6 +2108,77 @@ class Genrich:
                                                int(tile_words), int(flush_words), int(grid_observed), F.ctypes.data, C.byref(fu), Nn.ctypes.data,
                                                Nw.ctypes.data, C.byref(nu), C.byref(wu), k))
         return GcBias(W, F, fu.value, Nn, Nw, nu.value, wu.value)
+
+    # -- the sequence itself and the motif scan (include/genrich_amd.h, gx_set_genome_bases) --------------------------------
+    n_motifs = 0
+    _n_motif_hits = 0
+
+    def set_genome_bases(self, on=True):
+        """The third bit vector: from now on push_sequence keeps the bases themselves (gx_set_genome_bases); after set_genome(),
+        before the first push."""
+        self._check(self.lib.gx_set_genome_bases(self.ctx, int(bool(on))))
+
+    def get_sequence(self, chrom, start, n):
+        """n letters of chromosome `chrom` from base `start` on: ACGT, N for unknown and past the end (gx_get_sequence)."""
+        out = C.create_string_buffer(max(int(n), 1))
+        self._check(self.lib.gx_get_sequence(self.ctx, int(chrom), int(start), int(n), out))
+        return out.raw[:int(n)]
+
+    def set_motifs(self, motifs):
+        """The motifs to scan: [(scores int16[L, 4] in column order A C G T, threshold)] (gx_set_motifs); []: none."""
+        rec, flat = pack_motifs(motifs)
+        self._check(self.lib.gx_set_motifs(self.ctx, rec.ctypes.data if len(rec) else None, len(rec), flat.ctypes.data if len(rec) else None))
+        self.n_motifs = len(rec)
+
+    def _motif_counts(self):
+        return np.zeros((3, max(self.n_motifs, 1)), dtype=np.uint64)
+
+    def motif_scan_regions(self, regions, grid=0, step_words=0, batch_motifs=0, list_cap=0):
+        """(hits MOTIF_HIT_DTYPE sorted by (region, pos, motif, strand), counts uint64[3, motifs]: windows, hits +, hits -) of the
+        motifs in `regions` (REGION_DTYPE), by the kernel alone (gx_motif_scan_regions); 0: the library's geometry."""
+        reg = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+        cnt = self._motif_counts()
+        n = C.c_size_t(0)
+        args = (reg.ctypes.data if reg.size else None, reg.size, int(grid), int(step_words), int(batch_motifs), int(list_cap))
+        hits = np.empty(1 << 18, dtype=MOTIF_HIT_DTYPE)
+        for _ in range(2):   # (once more when there were more hits than the buffer held)
+            self._check(self.lib.gx_motif_scan_regions(self.ctx, *args, hits.ctypes.data, hits.size, C.byref(n), cnt[0].ctypes.data, cnt[1].ctypes.data,
+                                                       cnt[2].ctypes.data))
+            if n.value <= hits.size:
+                break
+            hits = np.empty(n.value, dtype=MOTIF_HIT_DTYPE)
+        return hits[:n.value].copy(), cnt[:, :self.n_motifs]
+
+    def motif_scan_peaks(self):
+        """Scan the peaks find_peaks left on this context (gx_motif_scan_peaks); returns the number of hits."""
+        n = C.c_size_t(0)
+        self._check(self.lib.gx_motif_scan_peaks(self.ctx, C.byref(n)))
+        self._n_motif_hits = n.value
+        return n.value
+
+    def get_motif_hits(self):
+        """The hits of the last motif_scan_peaks(), region = the peak's index (gx_get_motif_hits)."""
+        hits = np.zeros(self._n_motif_hits, dtype=MOTIF_HIT_DTYPE)
+        self._check(self.lib.gx_get_motif_hits(self.ctx, hits.ctypes.data if hits.size else None, hits.size))
+        return hits
+
+    def get_motif_counts(self):
+        """uint64[3, motifs] (windows, hits +, hits -) of the last motif_scan_peaks() (gx_get_motif_counts)."""
+        cnt = self._motif_counts()
+        self._check(self.lib.gx_get_motif_counts(self.ctx, cnt[0].ctypes.data, cnt[1].ctypes.data, cnt[2].ctypes.data, self.n_motifs))
+        return cnt[:, :self.n_motifs]
+
+    def motif_last(self):
+        """(reruns, batches) of the last motif scan (gx_motif_last)."""
+        r, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.gx_motif_last(self.ctx, C.byref(r), C.byref(b)))
+        return r.value, b.value
+
+    def motif_scan_genome(self):
+        """uint64[3, motifs] of the count-only pass over every chromosome that takes part (gx_motif_scan_genome)."""
+        cnt = self._motif_counts()
+        self._check(self.lib.gx_motif_scan_genome(self.ctx, cnt[0].ctypes.data, cnt[1].ctypes.data, cnt[2].ctypes.data, self.n_motifs))
+        return cnt[:, :self.n_motifs]
 
     # -- lengths and chromosome tallies of the samples' intervals (include/genrich_amd.h, gx_interval_stats) --------------
     def interval_stats(self):

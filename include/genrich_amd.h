@@ -820,6 +820,122 @@ int gx_format_gc_bias(FILE* out, int n_samples, const int* rep, const int* is_ct
 int gx_format_gc_peaks(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const uint64_t* gc, const uint64_t* acgt);
 int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out);
 
+/* ---- the sequence itself and known motifs scanned in the called peaks and in the genome (no Genrich counterpart: what HOMER's
+ *      findMotifsGenome -find, FIMO or MOODS do with the peak sequences cut out of the FASTA once more) ----
+ * THE SEQUENCE, per context: a third bit vector `ag` with the layout, the padding and the one-writer-per-word rule of gc and
+ * acgt; its bit is set for A G a g.  With gc it names a known base (acgt = 1): A = (gc 0, ag 1), C = (1, 0), G = (1, 1),
+ * T = (0, 0); the complement is the base with the ag bit flipped; a base whose acgt bit is 0 stays unknown.
+ * A MOTIF has a width L, 1 <= L <= GX_MOTIF_MAX_WIDTH, an L x 4 table of int16 scores s[j][b] in column order A C G T and an
+ * int32 threshold t; a context takes at most GX_MOTIF_MAX of them.
+ * THE WINDOW of motif m at position x of a region [start, end) on chromosome c is [x, x + L).  It is SCANNED iff start <= x,
+ * x + L <= min(end, len[c]) and all L of its acgt bits are set.  Its forward score is sum_j s[j][base(x + j)], its reverse score
+ * sum_j s[j][comp(base(x + L - 1 - j))].  A HIT is a scanned window and a strand whose score is >= t: both strands may hit at one
+ * x (a palindrome then reports two).
+ * COUNTS per motif, all exact uint64: windows (scanned), hits_fwd, hits_rev.  Over a set of regions every region is scanned on
+ * its own (overlapping regions count twice); over the genome the counts run over every chromosome that takes part (not
+ * skipped, owned, and saved by the last treatment sample begun; before any sample: every one), and add over contexts.
+ * THE HIT LIST: gx_motif_hit records; pos counts from the region's start; sorted by (region, pos, motif, strand).  -E regions
+ * are NOT masked (as for gx_peak_signal and gx_gc_bias).  No result depends on the launch geometry, the step, the motif batch,
+ * the list's capacity, the split of the pushes or the number of GPUs.
+ *
+ * gx_set_genome_bases: on != 0: after gx_set_genome(ctx, 1) and before any base is pushed (else GX_ERR_ORDER with a text): ag
+ *   is allocated and cleared, and from then on gx_push_sequence fills all three vectors (k_seq_pack3).  Off (the default):
+ *   nothing more is allocated and the pushes launch k_gc_pack as before.  gx_set_chroms / gx_set_owned lay ag out again, empty,
+ *   with the other two; gx_reset keeps it; gx_set_genome(ctx, 0) frees it.  gx_genome_info, gx_gc_content and gx_gc_bias* give
+ *   the same results with the bases on.
+ * gx_get_sequence: n letters of chromosome chrom from base start on (k_seq_unpack): upper-case A C G T, N for an unknown base
+ *   and for every position past the chromosome's end or on a chromosome without words here.  out holds n bytes (no terminator).
+ * gx_set_motifs: n motifs; motif i's table is the 4 * width int16 at scores + m[i].offset (row j: s[j][A], s[j][C], s[j][G],
+ *   s[j][T]).  A width outside 1 .. GX_MOTIF_MAX_WIDTH or more than GX_MOTIF_MAX motifs: GX_ERR_ORDER with a text.  n = 0 drops
+ *   them.  The results of the last gx_motif_scan_peaks go with the old motifs.
+ * gx_motif_scan_regions: k_motif_scan over n regions of the caller's (any order, overlapping, empty or inverted; a chromosome
+ *   outside the table or without words here scans nothing).  Needs the bases; no sample, no events and no peaks.  grid /
+ *   step_words / batch_motifs / list_cap = 0: the library's choices; else that many workgroups (at most 65535, and enough
+ *   that none walks more than the flush bound: gx_motif_grid), runs of 64 positions a wavefront takes per unit of work (1 .. 16), motifs per
+ *   LDS batch (1 .. 64) and entries of the first hit list (below 2^31; 0: one entry per 2048 positions of the regions and
+ *   motif, at least the geometry's least capacity and at most 2^24).  The list is counted: when it ran full the pass is run
+ *   once more with a list of the counted size; 2^31 hits or more are refused with a text.  out takes min(cap, *n_out) hits;
+ *   windows / hits_fwd / hits_rev take one count per motif set (NULL: not wanted; all three or none).  For tests and
+ *   measurements.
+ * gx_motif_scan_peaks: after gx_find_peaks, with no sample open, the bases on and motifs set (else GX_ERR_ORDER): the peaks
+ *   this context called are the regions (region = the peak's index in gx_get_peaks).  No peak or no motif is legal.  Nothing of
+ *   it is allocated or launched before the first call; its phase is "motifs".  gx_get_motif_hits: min(cap, *n_hits) of them;
+ *   gx_get_motif_counts: min(cap, motifs) of each count.  Until gx_reset, gx_set_motifs or the next sample.
+ * gx_motif_last: how often the last scan ran again (0 or 1) and its LDS batches.
+ * gx_motif_scan_genome: the count-only instance over every chromosome that takes part; min(cap, motifs) of each count.
+ *   gx_motif_scan_genome_group: the contexts' counts added (a chromosome lives on one context).
+ * gx_motif_geometry: the lanes of a workgroup of k_motif_scan, its most workgroups with grid = 0, the positions a wavefront
+ *   takes per step (64), the default runs per unit, the motifs per LDS batch, the first list's least capacity and the flush
+ *   bound: the runs a WORKGROUP walks at most per batch (its four wavefronts add to the same 32-bit LDS counters, at most 64 per
+ *   run: 2^25 x 64 = 2^31 < 2^32).  Any pointer may be NULL.  No device.
+ * gx_motif_grid: the grid a pass over `units` units of step_words runs (0: the default) takes: with grid = 0 the library's
+ *   choice in *chosen, else the caller's, or GX_ERR_ORDER when it is refused -- a step outside 1 .. 16, more than 65535
+ *   workgroups, 2^32 units or more, or a grid so small that a workgroup would walk more than the flush bound: a workgroup takes
+ *   four units per round, so it needs grid >= ceil(ceil(units / 4) / (2^25 / (4 step_words))).  No device, no context. */
+#define GX_MOTIF_MAX_WIDTH 32
+#define GX_MOTIF_MAX 4096
+#define GX_MOTIF_SCALE 128
+typedef struct { uint32_t width, offset; int32_t threshold; } gx_motif;
+typedef struct { uint32_t region, pos; int32_t score; uint16_t motif; uint8_t strand /* 0 +, 1 - */, pad; } gx_motif_hit;
+int gx_set_genome_bases(gx_ctx* ctx, int on);
+int gx_get_sequence(gx_ctx* ctx, int chrom, uint64_t start, size_t n, char* out);
+int gx_set_motifs(gx_ctx* ctx, const gx_motif* m, int n, const int16_t* scores);
+int gx_motif_scan_regions(gx_ctx* ctx, const gx_region* regions, size_t n, unsigned grid, uint32_t step_words, uint32_t batch_motifs, size_t list_cap,
+                          gx_motif_hit* out, size_t cap, size_t* n_out, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev);
+int gx_motif_scan_peaks(gx_ctx* ctx, size_t* n_hits);
+int gx_get_motif_hits(gx_ctx* ctx, gx_motif_hit* out, size_t cap);
+int gx_get_motif_counts(gx_ctx* ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap);
+int gx_motif_last(gx_ctx* ctx, uint32_t* reruns, uint32_t* batches);
+int gx_motif_scan_genome(gx_ctx* ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap);
+int gx_motif_scan_genome_group(gx_ctx* const* ctxs, int n_ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap);
+int gx_motif_geometry(int* lanes, int* grid, uint32_t* positions_per_step, uint32_t* step_words, uint32_t* batch_motifs, size_t* list_cap,
+                      uint64_t* flush_runs);
+int gx_motif_grid(uint64_t units, uint32_t step_words, unsigned grid, unsigned* chosen);
+/* From a count matrix to scores and a threshold (host only, gx_emit.cpp).
+ * gx_motif_pssm: counts[b * width + j] (rows A C G T, integers below 2^31) with column sums N_j and a pseudocount pc >= 0 give
+ *   scores[4 j + b] = llround(GX_MOTIF_SCALE * log2(((c + 0.25 pc) / (N_j + pc)) / 0.25)): 1/128 bit against a uniform background,
+ *   halves away from zero; *smin / *smax: the least and the greatest score an L-mer can have.  GX_ERR_ORDER with a sentence in
+ *   why[cap]: a width outside 1 .. 32, a count of 2^31 or more, a negative or non-finite pseudocount, a score that would be
+ *   minus infinity (a zero count with pc = 0, an empty column) or leaves int16.
+ * gx_motif_threshold: for p in (0, 1] let K = floor(p * 4^L) (exact: p is a double, K a 128-bit integer) and n_ge(t) the number
+ *   of the 4^L L-mers whose score is >= t (a dynamic program over the columns with 128-bit counts): *threshold = the least
+ *   integer t >= smin with n_ge(t) <= K; when even the greatest score has more than K L-mers, smax + 1 (the motif cannot hit) and
+ *   *unreachable = 1.  *p_achieved = n_ge(t) / 4^L.  The uniform background is a stated choice (HOMER's).
+ * gx_format_motif_hits: --motif-hits' table: a header, then one BED-like row per hit in the order given (sorted by region, pos,
+ *   motif, strand) `chr start end ID score strand NAME peak_N offset_from_summit p_threshold`: score = "%.4f" of
+ *   score / GX_MOTIF_SCALE (exact), offset_from_summit = the window's middle (2 start + L) / 2 minus the peak's summit
+ *   (summit_off[k] from the peak's start, narrowPeak column 10), signed; p_threshold "%.3e" ("NA": NaN).
+ * gx_format_motif_summary: --motif-summary's table: a header, then one row per motif `ID NAME width threshold p_threshold
+ *   peaks_scanned peaks_with_hit windows_peaks hits_peaks windows_genome hits_genome enrichment`: peaks_scanned = the peaks at
+ *   least as long as the motif, hits = both strands added, enrichment = (hits_peaks * windows_genome) / (hits_genome *
+ *   windows_peaks) from two exact 128-bit products, each converted once (as gx_gc_metrics' ratios), "%.6f"; "NA" when the
+ *   denominator is 0.  counts_peaks / counts_genome: [3][n_motifs] windows, hits_fwd, hits_rev.
+ * gx_write_motif_hits_group / gx_write_motif_summary_group: gx_motif_scan_peaks (and, for the summary, gx_motif_scan_genome) on
+ *   every context, the contexts' peaks merged into narrowPeak order as gx_write_summits_group does (the same peak_N), the table.
+ *   A context that still holds the scan of its peaks with these motifs (gx_motif_scan_peaks since the last gx_find_peaks and
+ *   gx_set_motifs) is not scanned again.  gx_write_motifs_group: both tables from ONE scan of the peaks and, with summary_out,
+ *   ONE genome pass (launched on every context before the first is waited for); either FILE may be NULL, not both; names may
+ *   be NULL without hits_out.  counts_peaks / counts_genome (NULL: not wanted) take [3][n_motifs] windows, hits_fwd, hits_rev
+ *   (the genome's zero without summary_out); *report (NULL: not wanted) the hits, the peaks with any, and the host's seconds
+ *   for the peaks' scans and for the genome pass. */
+typedef struct { uint64_t hits, peaks_with_hit; double peaks_seconds, genome_seconds; } gx_motif_report;
+int gx_motif_pssm(const uint32_t* counts, int width, double pseudocount, int16_t* scores, int32_t* smin, int32_t* smax, char* why, size_t cap);
+int gx_motif_threshold(const int16_t* scores, int width, double p, int32_t* threshold, int32_t* smin, int32_t* smax, double* p_achieved,
+                       int* unreachable);
+int gx_format_motif_hits(FILE* out, const char* const* names, const gx_region* peaks, const uint32_t* summit_off, size_t n_peaks,
+                         const gx_motif* motifs, const char* const* ids, const char* const* motif_names, const double* p_threshold, int n_motifs,
+                         const gx_motif_hit* hits, size_t n_hits);
+int gx_format_motif_summary(FILE* out, const gx_region* peaks, size_t n_peaks, const gx_motif* motifs, const char* const* ids,
+                            const char* const* motif_names, const double* p_threshold, int n_motifs, const gx_motif_hit* hits, size_t n_hits,
+                            const uint64_t* counts_peaks, const uint64_t* counts_genome);
+int gx_write_motifs_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_motif* motifs, const char* const* ids,
+                          const char* const* motif_names, const double* p_threshold, int n_motifs, FILE* hits_out, FILE* summary_out,
+                          uint64_t* counts_peaks, uint64_t* counts_genome, gx_motif_report* report);
+int gx_write_motif_hits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, const gx_motif* motifs, const char* const* ids,
+                              const char* const* motif_names, const double* p_threshold, int n_motifs, FILE* out);
+int gx_write_motif_summary_group(gx_ctx* const* ctxs, int n_ctx, const gx_motif* motifs, const char* const* ids, const char* const* motif_names,
+                                 const double* p_threshold, int n_motifs, FILE* out);
+
 /* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
  *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
@@ -1411,6 +1527,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_SPLIT 268435456u /* bit 28: k_sub_split ran since the last gx_reset (gx_subsample_split_events, gx_subsample_split_kept, gx_reproducibility) */
 #define GX_PATH_SWEEP_OVERLAP 536870912u /* bit 29: ... GX_PATH_LOOSE_SWEEP whose run pass rode in the launch that scanned the tiles and closed the sample (k_scan_iv_close_runs), ahead of gx_find_peaks: the sweep launched no k_runs */
 #define GX_PATH_GC 1073741824u /* bit 30: a kernel of the genome / GC passes ran since the last gx_reset (gx_push_sequence, gx_genome_info, gx_gc_content, gx_gc_bias, gx_gc_bias_events) */
+#define GX_PATH_MOTIFS 2147483648u /* bit 31: k_motif_scan ran since the last gx_reset (gx_motif_scan_regions, gx_motif_scan_peaks, gx_motif_scan_genome) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
