@@ -9,6 +9,7 @@
 #include "gx_host_stats.h"
 #include "gx_host_call.h"
 #include "gx_sparse.h"
+#include "gx_peak_merge.h"
 #include "gx_host_kept.h"
 #include "gx_host_count.h"
 #include "gx_host_regions.h"
@@ -82,8 +83,11 @@ int gc_sum(gx_ctx* const* ctxs, int n_ctx, int sample, gx_ctx::GcResult& sum) {
   return group_sum(ctxs, n_ctx, sample, &gx_ctx::gcRes, [](const gx_ctx* c) { return c->gcReady; },
                    [](const gx_ctx*, const gx_ctx*, const auto& r, const auto& r0) { return r.W == r0.W && same_sample(r, r0); }, gc_add, sum);
 }
-// The writers that run their pass themselves: on every context, which all report as many samples (*nS)
-int pass_on_all(gx_ctx* const* ctxs, int n_ctx, int (*pass)(gx_ctx*, int*), int* nS) {
+// The writers over contexts live in this file, not in gx_emit.cpp: they read contexts, and that file links on its own, against the
+// entries its stand-alone test programs define.  Those that run their pass themselves:
+// pass(ctx, &n) on every context, which all report as many samples (*nS)
+template <class Pass>
+int pass_on_all(gx_ctx* const* ctxs, int n_ctx, Pass pass, int* nS) {
   for (int g = 0; g < n_ctx; g++) {
     int n = 0;
     if (int rc = pass(ctxs[g], &n)) return rc;
@@ -1033,7 +1037,6 @@ int gx_depth_last(gx_ctx* ctx, size_t* list_capacity, int* reruns) {
   return GX_OK;
 }
 
-// (over contexts: here, not in gx_emit.cpp, like the complexity's -- it reads contexts)
 int gx_write_depth_group(gx_ctx* const* ctxs, int n_ctx, FILE* depth, FILE* metrics) {
   if (!ctxs || n_ctx < 1 || !ctxs[0] || (!depth && !metrics)) return GX_ERR_ORDER;
   const size_t nS = ctxs[0]->depth.size();
@@ -1123,8 +1126,6 @@ int gx_get_profile(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int64_t* agg
   return GX_OK;
 }
 
-// The writers over contexts live here, not in gx_emit.cpp: that file links on its own, against the entries its stand-alone
-// test programs define.
 int gx_write_profile_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, const char* const* sample_names, size_t n_anchors_counted,
                            FILE* out) {
   if (!ctxs || n_ctx < 1 || !out || n_samples < 0 || (n_samples && !sample_names)) return GX_ERR_ORDER;
@@ -1199,7 +1200,6 @@ int gx_gram_geometry(int* tile, int* lanes, int* grid) {
   return GX_OK;
 }
 
-// (the two over contexts live here, not in gx_emit.cpp, like the profile's group writers: they read contexts)
 int gx_coverage_gram_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* n_zero, gx_u128* sum, gx_u128* gram) {
   if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)GRAM_MAX_S || !sum || !gram) return GX_ERR_ORDER;
   Sums128 total((size_t)n_samples);
@@ -1267,7 +1267,6 @@ int gx_fp_geometry(int* n_classes, int* sub_log, int* lanes, int* grid) {
   return GX_OK;
 }
 
-// (the two over contexts live here, not in gx_emit.cpp, like the correlation's: they read contexts)
 int gx_coverage_fingerprint_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, uint64_t* n_bins, uint64_t* count, uint64_t* sum) {
   if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)FP_MAX_S || !count || !sum) return GX_ERR_ORDER;
   const size_t N = (size_t)n_samples * FP_NC;
@@ -1377,7 +1376,6 @@ int gx_coverage_rank_gram(gx_ctx* ctx, const gx_rank_lut* tables, int skip_zeros
   return GX_OK;
 }
 
-// (the two over contexts live here, not in gx_emit.cpp, like the correlation's: they read contexts)
 int gx_coverage_spearman_group(gx_ctx* const* ctxs, int n_ctx, int n_samples, int skip_zeros, uint64_t* n_ranked, gx_u128* sum, gx_u128* gram,
                                uint64_t* n_distinct) {
   if (!ctxs || n_ctx < 1 || n_samples < 1 || n_samples > (int)RK_MAX_S || !sum || !gram) return GX_ERR_ORDER;
@@ -1456,50 +1454,30 @@ int gx_peak_signal_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32_
   return GX_OK;
 }
 
-// (here, not in gx_emit.cpp, like the other writers over contexts that run their pass themselves)
 int gx_write_peak_signal_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out) {
   if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
   int nS = 0;
   if (int rc = pass_on_all(ctxs, n_ctx, gx_peak_signal, &nS)) return rc;
-  // the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group), their records following them
-  std::vector<gx_peak> pk;
+  gx_peak_merge::Merged m;
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  // every sample's five columns: the contexts' one after the other, then in the merged order
   std::vector<std::vector<int64_t>> area((size_t)nS), mx((size_t)nS), at((size_t)nS);
   std::vector<std::vector<uint32_t>> sm((size_t)nS), cov((size_t)nS);
   std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
-  for (int g = 0; g < n_ctx; g++) {
-    size_t k = 0;
-    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
-    const size_t at0 = pk.size();
-    pk.resize(at0 + k);
-    if (k)
-      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
-    for (int i = 0; i < nS; i++) {
-      area[i].resize(at0 + k); mx[i].resize(at0 + k); at[i].resize(at0 + k); sm[i].resize(at0 + k); cov[i].resize(at0 + k);
+  std::vector<const int64_t*> pa, pm, pt;
+  std::vector<const uint32_t*> ps, pc;
+  for (int i = 0; i < nS; i++) {
+    area[i].resize(m.size()); mx[i].resize(m.size()); at[i].resize(m.size()); sm[i].resize(m.size()); cov[i].resize(m.size());
+    for (int g = 0; g < n_ctx; g++) {
+      const size_t at0 = m.first[g];
       if (int rc = gx_get_peak_signal(ctxs[g], i, &rep[i], &ctrl[i], area[i].data() + at0, mx[i].data() + at0, sm[i].data() + at0, cov[i].data() + at0,
-                                      at[i].data() + at0, k))
+                                      at[i].data() + at0, m.first[g + 1] - at0))
         return rc;
     }
+    area[i] = permuted(m, area[i]); mx[i] = permuted(m, mx[i]); at[i] = permuted(m, at[i]); sm[i] = permuted(m, sm[i]); cov[i] = permuted(m, cov[i]);
+    pa.push_back(area[i].data()); pm.push_back(mx[i].data()); pt.push_back(at[i].data()); ps.push_back(sm[i].data()); pc.push_back(cov[i].data());
   }
-  std::vector<size_t> ord(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-  if (n_ctx > 1)
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
-  std::vector<gx_region> reg(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
-  std::vector<const int64_t*> pa((size_t)nS), pm((size_t)nS), pt((size_t)nS);
-  std::vector<const uint32_t*> ps((size_t)nS), pc((size_t)nS);
-  for (int i = 0; i < nS; i++) {
-    if (n_ctx > 1) {
-      std::vector<int64_t> a(ord.size()), m(ord.size()), t(ord.size());
-      std::vector<uint32_t> s(ord.size()), c(ord.size());
-      for (size_t j = 0; j < ord.size(); j++) {
-        a[j] = area[i][ord[j]]; m[j] = mx[i][ord[j]]; t[j] = at[i][ord[j]]; s[j] = sm[i][ord[j]]; c[j] = cov[i][ord[j]];
-      }
-      area[i].swap(a); mx[i].swap(m); at[i].swap(t); sm[i].swap(s); cov[i].swap(c);
-    }
-    pa[i] = area[i].data(); pm[i] = mx[i].data(); pt[i] = at[i].data(); ps[i] = sm[i].data(); pc[i] = cov[i].data();
-  }
-  return gx_format_peak_signal(out, names, reg.data(), reg.size(), nS, rep.data(), ctrl.data(), pa.data(), pm.data(), ps.data(), pc.data(), pt.data());
+  return gx_format_peak_signal(out, names, m.regions.data(), m.size(), nS, rep.data(), ctrl.data(), pa.data(), pm.data(), ps.data(), pc.data(), pt.data());
 }
 
 int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out) { return gx_write_peak_signal_group(&ctx, 1, names, out); }
@@ -1552,36 +1530,16 @@ int gx_peak_summits_geometry(int* lanes, int* grid, uint32_t* step_bases, uint32
   return GX_OK;
 }
 
-// (here, not in gx_emit.cpp, like the other writers over contexts that run their pass themselves)
 int gx_write_summits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out) {
   if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
-  // the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group), their summits following them
-  std::vector<gx_peak> pk;
-  std::vector<gx_summit> sm;
-  for (int g = 0; g < n_ctx; g++) {
-    size_t k = 0, n = 0;
-    if (int rc = gx_peak_summits(ctxs[g], prominence_pct, height_pct, &n)) return rc;
-    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
-    const size_t at0 = pk.size(), s0 = sm.size();
-    pk.resize(at0 + k);
-    if (k)
-      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
-    sm.resize(s0 + n);
-    if (int rc = gx_get_peak_summits(ctxs[g], sm.data() + s0, n)) return rc;
-    for (size_t i = s0; i < sm.size(); i++) sm[i].peak += (uint32_t)at0;
-  }
-  std::vector<size_t> ord(pk.size()), rank(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-  if (n_ctx > 1)
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
-  std::vector<gx_region> reg(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) {
-    reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
-    rank[ord[i]] = i;
-  }
-  for (gx_summit& s : sm) s.peak = (uint32_t)rank[s.peak];
-  if (n_ctx > 1) std::sort(sm.begin(), sm.end(), [](const gx_summit& a, const gx_summit& b) { return a.peak != b.peak ? a.peak < b.peak : a.pos < b.pos; });
-  return gx_format_summits(out, names, reg.data(), reg.size(), sm.data(), sm.size());
+  int none = 0;
+  if (int rc = pass_on_all(ctxs, n_ctx, [&](gx_ctx* c, int*) { return gx_peak_summits(c, prominence_pct, height_pct, nullptr); }, &none)) return rc;
+  gx_peak_merge::Merged m;
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  std::vector<std::vector<gx_summit>> own;
+  for (int g = 0; g < n_ctx; g++) own.push_back(ctxs[g]->sumRes);
+  const std::vector<gx_summit> sm = renumbered(m, own, &gx_summit::peak, gx_peak_merge::summit_less);
+  return gx_format_summits(out, names, m.regions.data(), m.size(), sm.data(), sm.size());
 }
 
 int gx_write_summits(gx_ctx* ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out) {
@@ -1628,7 +1586,6 @@ int gx_complexity_last(gx_ctx* ctx, size_t* capacity) {
   return GX_OK;
 }
 
-// (the two over contexts live here, not in gx_emit.cpp, like the fingerprint's: they read contexts)
 int gx_complexity_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_obs, uint64_t* n_distinct, uint64_t* mult,
                         uint64_t* keys, size_t cap, size_t* n_classes) {
   gx_ctx::CpxResult sum;
@@ -1704,7 +1661,6 @@ int gx_interval_stats_last(gx_ctx* ctx, size_t* list_capacity, int* reruns) {
   return GX_OK;
 }
 
-// (the two over contexts live here, not in gx_emit.cpp, like the complexity's: they read contexts)
 int gx_interval_stats_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* length, uint64_t* n, uint64_t* w120,
                             size_t cap, size_t* n_classes, uint64_t* n_inverted, uint64_t* w120_inverted, uint64_t* cn, uint64_t* cw120,
                             uint64_t* cbases120, size_t chrom_cap) {
@@ -1787,7 +1743,6 @@ int gx_get_xcor(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos
   return xc_give(ctx->xc[sample], ctx->xcLo, ctx->xcHi, rep, is_ctrl, n_pos, n_plus, n_minus, rejected, lo, hi, n11, cap);
 }
 
-// (the two over contexts live here, not in gx_emit.cpp: they read contexts)
 int gx_xcor_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, uint64_t* n_pos, uint64_t* n_plus, uint64_t* n_minus,
                   uint64_t* rejected, int* lo, int* hi, uint64_t* n11, size_t cap) {
   gx_ctx::XcResult sum;
@@ -1911,7 +1866,6 @@ int gx_get_gc_bias(gx_ctx* ctx, int sample, int* rep, int* is_ctrl, int* window,
   return gc_give(ctx->gcRes[sample], rep, is_ctrl, window, F, f_unclassed, Nn, Nw, n_unclassed, w_unclassed, cap);
 }
 
-// (the one over contexts lives here, not in gx_emit.cpp: it reads contexts)
 int gx_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int sample, int* rep, int* is_ctrl, int* window, uint64_t* F, uint64_t* f_unclassed, uint64_t* Nn,
                      uint64_t* Nw, uint64_t* n_unclassed, uint64_t* w_unclassed, size_t cap) {
   gx_ctx::GcResult sum;
@@ -1947,12 +1901,7 @@ int gx_gc_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* min_ti
 int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out) {
   if (!ctxs || n_ctx < 1 || !ctxs[0] || !out) return GX_ERR_ORDER;
   int nS = 0;
-  for (int g = 0; g < n_ctx; g++) {
-    int n = 0;
-    if (int rc = gx_gc_bias(ctxs[g], window, &n)) return rc;
-    if (g && n != nS) return GX_ERR_ORDER;
-    nS = n;
-  }
+  if (int rc = pass_on_all(ctxs, n_ctx, [&](gx_ctx* c, int* n) { return gx_gc_bias(c, window, n); }, &nS)) return rc;
   std::vector<gx_ctx::GcResult> sums((size_t)nS);   // (each sample summed once; the writer reads the sums in place)
   std::vector<int> rep, ctrl;
   std::vector<uint64_t> fUn, nUn, wUn;
@@ -1964,6 +1913,22 @@ int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out
     pF.push_back(r.F.data()); pN.push_back(r.Nn.data()); pW.push_back(r.Nw.data());
   }
   return gx_format_gc_bias(out, nS, rep.data(), ctrl.data(), window, pF.data(), fUn.data(), pN.data(), pW.data(), nUn.data(), wUn.data());
+}
+
+int gx_write_gc_peaks_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out) {
+  if (!ctxs || n_ctx < 1 || !names || !out) return GX_ERR_ORDER;
+  gx_peak_merge::Merged m;
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  // each context on its own peaks (it holds their chromosomes' bases), which are merged peaks rank[first[g] ..]
+  std::vector<uint64_t> gc(m.size()), acgt(m.size());
+  for (int g = 0; g < n_ctx; g++) {
+    std::vector<gx_region> own;
+    for (size_t j = m.first[g]; j < m.first[g + 1]; j++) own.push_back(m.regions[m.rank[j]]);
+    if (int rc = gx_gc_content(ctxs[g], own.data(), own.size(), gc.data() + m.first[g], acgt.data() + m.first[g])) return rc;
+  }
+  gc = permuted(m, gc);
+  acgt = permuted(m, acgt);
+  return gx_format_gc_peaks(out, names, m.regions.data(), m.size(), gc.data(), acgt.data());
 }
 
 int gx_set_genome_bases(gx_ctx* ctx, int on) {
@@ -2031,8 +1996,8 @@ int gx_motif_scan_genome(gx_ctx* ctx, uint64_t* windows, uint64_t* hits_fwd, uin
   return gx_motif_scan_genome_group(&ctx, 1, windows, hits_fwd, hits_rev, cap);
 }
 
-// (the one over contexts lives here, not in gx_emit.cpp: it reads contexts)  Every context's pass is launched, with its read-back
-// queued on its stream, before the first is waited for: with several devices the passes run side by side.
+// Every context's pass is launched, with its read-back queued on its stream, before the first is waited for: with several devices
+// the passes run side by side.
 int gx_motif_scan_genome_group(gx_ctx* const* ctxs, int n_ctx, uint64_t* windows, uint64_t* hits_fwd, uint64_t* hits_rev, size_t cap) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return GX_ERR_ORDER;
   std::vector<MotRun> runs((size_t)n_ctx);
@@ -2083,51 +2048,21 @@ int gx_motif_geometry(int* lanes, int* grid, uint32_t* positions_per_step, uint3
   return GX_OK;
 }
 
-// the contexts' peaks in narrowPeak order (gx_write_narrowpeak_group, as gx_write_summits_group merges them), each context's
-// hits following its peaks
-static int motif_group(gx_ctx* const* ctxs, int n_ctx, int n_motifs, bool, std::vector<gx_region>& reg, std::vector<uint32_t>& summit,
-                       std::vector<gx_motif_hit>& hits, std::vector<uint64_t>& cPeaks, std::vector<uint64_t>& cGenome) {
+// every context's scan of its peaks (run where the context does not hold it), the hits on the merged peaks, the counts added
+static int motif_group(gx_ctx* const* ctxs, int n_ctx, int n_motifs, gx_peak_merge::Merged& m, std::vector<gx_motif_hit>& hits,
+                       std::vector<uint64_t>& cPeaks) {
   if (!ctxs || n_ctx < 1 || n_motifs < 0) return GX_ERR_ORDER;
-  const size_t nM = (size_t)n_motifs;
-  std::vector<gx_peak> pk;
-  cPeaks.assign(3 * nM, 0);
-  cGenome.assign(3 * nM, 0);
-  std::vector<uint64_t> one(3 * nM + 1, 0);
+  cPeaks.assign(3 * (size_t)n_motifs, 0);
   for (int g = 0; g < n_ctx; g++) {
-    if (!ctxs[g] || ctxs[g]->motMeta.size() != nM) return GX_ERR_ORDER;
-    size_t k = 0, n = ctxs[g]->motHits.size();
+    if (!ctxs[g] || ctxs[g]->motMeta.size() != (size_t)n_motifs) return GX_ERR_ORDER;
     if (!ctxs[g]->motReady)   // (else the context holds the scan of these peaks with these motifs: nothing runs again)
-      if (int rc = gx_motif_scan_peaks(ctxs[g], &n)) return rc;
-    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
-    const size_t at0 = pk.size(), h0 = hits.size();
-    pk.resize(at0 + k);
-    if (k)
-      if (int rc = gx_get_peaks(ctxs[g], pk.data() + at0, k)) return rc;
-    hits.resize(h0 + n);
-    if (int rc = gx_get_motif_hits(ctxs[g], hits.data() + h0, n)) return rc;
-    for (size_t i = h0; i < hits.size(); i++) hits[i].region += (uint32_t)at0;
-    if (int rc = gx_get_motif_counts(ctxs[g], one.data(), one.data() + nM, one.data() + 2 * nM, nM)) return rc;
-    for (size_t i = 0; i < 3 * nM; i++) cPeaks[i] += one[i];
+      if (int rc = gx_motif_scan_peaks(ctxs[g], nullptr)) return rc;
+    for (size_t i = 0; i < cPeaks.size(); i++) cPeaks[i] += ctxs[g]->motCounts[i];
   }
-  std::vector<size_t> ord(pk.size()), rank(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-  if (n_ctx > 1)
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start; });
-  reg.resize(pk.size());
-  summit.resize(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) {
-    reg[i] = gx_region{pk[ord[i]].chrom, pk[ord[i]].start, pk[ord[i]].end};
-    summit[i] = pk[ord[i]].summit;
-    rank[ord[i]] = i;
-  }
-  for (gx_motif_hit& h : hits) h.region = (uint32_t)rank[h.region];
-  if (n_ctx > 1)
-    std::sort(hits.begin(), hits.end(), [](const gx_motif_hit& x, const gx_motif_hit& y) {
-      if (x.region != y.region) return x.region < y.region;
-      if (x.pos != y.pos) return x.pos < y.pos;
-      if (x.motif != y.motif) return x.motif < y.motif;
-      return x.strand < y.strand;
-    });
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  std::vector<std::vector<gx_motif_hit>> own;
+  for (int g = 0; g < n_ctx; g++) own.push_back(ctxs[g]->motHits);
+  hits = renumbered(m, own, &gx_motif_hit::region, gx_peak_merge::motif_hit_less);
   return GX_OK;
 }
 
@@ -2135,22 +2070,24 @@ int gx_write_motifs_group(gx_ctx* const* ctxs, int n_ctx, const char* const* nam
                           const char* const* motif_names, const double* p_threshold, int n_motifs, FILE* hits_out, FILE* summary_out,
                           uint64_t* counts_peaks, uint64_t* counts_genome, gx_motif_report* report) {
   if (!hits_out && !summary_out) return GX_ERR_ORDER;
-  std::vector<gx_region> reg;
-  std::vector<uint32_t> summit;
+  gx_peak_merge::Merged m;
   std::vector<gx_motif_hit> hits;
-  std::vector<uint64_t> cP, cG;
+  std::vector<uint64_t> cP;
   const auto t0 = std::chrono::steady_clock::now();
-  if (int rc = motif_group(ctxs, n_ctx, n_motifs, false, reg, summit, hits, cP, cG)) return rc;
+  if (int rc = motif_group(ctxs, n_ctx, n_motifs, m, hits, cP)) return rc;
   const auto t1 = std::chrono::steady_clock::now();
   const size_t nM = (size_t)n_motifs;
+  std::vector<uint64_t> cG(3 * nM, 0);
+  std::vector<uint32_t> summit;
+  for (const gx_peak& p : m.peaks) summit.push_back(p.summit);
   if (summary_out)
     if (int rc = gx_motif_scan_genome_group(ctxs, n_ctx, cG.data(), cG.data() + nM, cG.data() + 2 * nM, nM)) return rc;
   const auto t2 = std::chrono::steady_clock::now();
   if (hits_out)
-    if (int rc = gx_format_motif_hits(hits_out, names, reg.data(), summit.data(), reg.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size()))
+    if (int rc = gx_format_motif_hits(hits_out, names, m.regions.data(), summit.data(), m.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size()))
       return rc;
   if (summary_out)
-    if (int rc = gx_format_motif_summary(summary_out, reg.data(), reg.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size(), cP.data(), cG.data()))
+    if (int rc = gx_format_motif_summary(summary_out, m.regions.data(), m.size(), motifs, ids, motif_names, p_threshold, n_motifs, hits.data(), hits.size(), cP.data(), cG.data()))
       return rc;
   if (counts_peaks) std::copy(cP.begin(), cP.end(), counts_peaks);
   if (counts_genome) std::copy(cG.begin(), cG.end(), counts_genome);
@@ -2239,7 +2176,6 @@ int gx_get_saturation_peaks(gx_ctx* ctx, int point, gx_peak* out, size_t cap) {
   return GX_OK;
 }
 
-// (here, not in gx_emit.cpp, like the other writers over contexts: it reads one)
 int gx_write_saturation(gx_ctx* ctx, FILE* out) {
   if (!ctx || !out || ctx->satPts.empty() || !ctx->peaksReady) return GX_ERR_ORDER;
   const size_t nP = ctx->satPts.size();
@@ -2334,7 +2270,6 @@ int gx_get_reproducibility_peaks(gx_ctx* ctx, int call, gx_peak* out, size_t cap
   return GX_OK;
 }
 
-// (here, not in gx_emit.cpp, like the other writers over contexts: it reads one)
 int gx_write_reproducibility(gx_ctx* ctx, int pct, FILE* calls_file, FILE* metrics_file) {
   if (!ctx || (!calls_file && !metrics_file) || ctx->reproCalls.empty() || !ctx->peaksReady || pct < 0 || pct > 100) return GX_ERR_ORDER;
   const size_t nC = ctx->reproCalls.size();

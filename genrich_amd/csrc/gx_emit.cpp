@@ -13,6 +13,7 @@
 
 #include "../../include/genrich_amd.h"
 #include "gx_fp_class.h"
+#include "gx_peak_merge.h"
 
 namespace {
 
@@ -144,26 +145,32 @@ void put_fraction(FILE* out, double v) {
 }
 }  // namespace
 
+// gx_peak_merge.h's one function over contexts: their lists fetched (the only place that does), merged
+int gx_peak_merge::merged_peaks(gx_ctx* const* ctxs, int n_ctx, Merged& m) {
+  std::vector<std::vector<gx_peak>> own((size_t)std::max(n_ctx, 0));
+  std::vector<const gx_peak*> lists;
+  std::vector<size_t> n;
+  for (size_t g = 0; g < own.size(); g++) {
+    size_t k = 0;
+    if (int rc = gx_peak_count(ctxs[g], &k)) return rc;
+    own[g].resize(k);
+    if (k)
+      if (int rc = gx_get_peaks(ctxs[g], own[g].data(), k)) return rc;
+    lists.push_back(own[g].data());
+    n.push_back(k);
+  }
+  m = merge(lists.data(), n.data(), n.size());
+  return GX_OK;
+}
+
 extern "C" {
 
-// -o: one line per peak; peak_N numbers the peaks in output order (callPeaks' `count`).  Several contexts
-// (chromosomes sharded over GPUs): their peak lists are merged into chromosome-table order, then position --
-// the order in which the reference meets them (986, 925).
+// -o: one line per peak; peak_N numbers the peaks in output order (callPeaks' `count`): with several contexts (chromosomes
+// sharded over GPUs), that of their merged peak lists.
 int gx_write_narrowpeak_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out) {
-  std::vector<gx_peak> pk;
-  for (int g = 0; g < n_ctx; g++) {
-    size_t k = 0;
-    int rc = gx_peak_count(ctxs[g], &k);
-    if (rc) return rc;
-    const size_t at = pk.size();
-    pk.resize(at + k);
-    if (k && (rc = gx_get_peaks(ctxs[g], pk.data() + at, k))) return rc;
-  }
-  if (n_ctx > 1)
-    std::stable_sort(pk.begin(), pk.end(), [](const gx_peak& a, const gx_peak& b) {
-      return a.chrom != b.chrom ? a.chrom < b.chrom : a.start < b.start;
-    });
-  return gx_format_narrowpeak(pk.data(), pk.size(), names, 0, out);
+  gx_peak_merge::Merged m;
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  return gx_format_narrowpeak(m.peaks.data(), m.size(), names, 0, out);
 }
 
 // ... the lines themselves, of a list: peak i is peak_<first_index + i>
@@ -188,8 +195,8 @@ int gx_format_narrowpeak(const gx_peak* peaks, size_t n, const char* const* name
 
 int gx_write_narrowpeak(gx_ctx* ctx, const char* const* names, FILE* out) { return gx_write_narrowpeak_group(&ctx, 1, names, out); }
 
-// --counts (no Genrich counterpart): the rows of -o -- the same merge of the contexts' peak lists, the same peak_N -- with one
-// column per sample, n / 120 of its count (gx_count_in_peaks on every context first)
+// --counts (no Genrich counterpart): the rows of -o -- the merged peaks, the same peak_N -- with one column per sample, n / 120 of
+// its count (gx_count_in_peaks on every context first)
 static void put_count(FILE* out, long long n) {
   if (n % 120 == 0) fprintf(out, "\t%lld", n / 120);
   else fprintf(out, "\t%.2f", (double)n / 120.0);
@@ -197,35 +204,22 @@ static void put_count(FILE* out, long long n) {
 int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_samples,
                           const char* const* sample_names, FILE* out) {
   if (n_ctx < 1 || n_samples < 0 || (n_samples && !sample_names)) return GX_ERR_ORDER;
-  std::vector<gx_peak> pk;
-  std::vector<int64_t> cnt;   // [peak][sample], peaks in concatenation order
-  for (int g = 0; g < n_ctx; g++) {
-    size_t k = 0;
-    int rc = gx_peak_count(ctxs[g], &k);
-    if (rc) return rc;
-    const size_t at = pk.size();
-    pk.resize(at + k);
-    if (k && (rc = gx_get_peaks(ctxs[g], pk.data() + at, k))) return rc;
-    cnt.resize(pk.size() * (size_t)n_samples);
-    std::vector<int64_t> one(k);
-    for (int smp = 0; smp < n_samples; smp++) {
-      if ((rc = gx_get_peak_counts(ctxs[g], smp, nullptr, nullptr, one.data(), k, nullptr, nullptr))) return rc;
-      for (size_t i = 0; i < k; i++) cnt[(at + i) * n_samples + smp] = one[i];
-    }
+  gx_peak_merge::Merged m;
+  if (int rc = gx_peak_merge::merged_peaks(ctxs, n_ctx, m)) return rc;
+  std::vector<std::vector<int64_t>> cnt((size_t)n_samples);   // [sample][peak]
+  for (int smp = 0; smp < n_samples; smp++) {
+    cnt[smp].resize(m.size());
+    for (int g = 0; g < n_ctx; g++)
+      if (int rc = gx_get_peak_counts(ctxs[g], smp, nullptr, nullptr, cnt[smp].data() + m.first[g], m.first[g + 1] - m.first[g], nullptr, nullptr)) return rc;
+    cnt[smp] = permuted(m, cnt[smp]);
   }
-  std::vector<size_t> ord(pk.size());
-  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-  if (n_ctx > 1)
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {
-      return pk[a].chrom != pk[b].chrom ? pk[a].chrom < pk[b].chrom : pk[a].start < pk[b].start;
-    });
   fprintf(out, "chr\tstart\tend\tname");
   for (int smp = 0; smp < n_samples; smp++) fprintf(out, "\t%s", sample_names[smp]);
   fprintf(out, "\n");
-  for (size_t i = 0; i < ord.size(); i++) {
-    const gx_peak& k = pk[ord[i]];
+  for (size_t i = 0; i < m.size(); i++) {
+    const gx_region& k = m.regions[i];
     fprintf(out, "%s\t%ld\t%ld\tpeak_%d", names[k.chrom], (long)k.start, (long)k.end, (int)i);
-    for (int smp = 0; smp < n_samples; smp++) put_count(out, (long long)cnt[ord[i] * n_samples + smp]);
+    for (int smp = 0; smp < n_samples; smp++) put_count(out, (long long)cnt[smp][i]);
     fprintf(out, "\n");
   }
   return GX_OK;

@@ -237,12 +237,7 @@ int mot_pass(gx_ctx* ctx, const gx_region* reg, size_t n, MotGeometry g, std::ve
     HIPCHECK(hipStreamSynchronize(s));
   }
   // the records come in the order of the races
-  std::sort(hits.begin(), hits.end(), [](const gx_motif_hit& x, const gx_motif_hit& y) {
-    if (x.region != y.region) return x.region < y.region;
-    if (x.pos != y.pos) return x.pos < y.pos;
-    if (x.motif != y.motif) return x.motif < y.motif;
-    return x.strand < y.strand;
-  });
+  std::sort(hits.begin(), hits.end(), gx_peak_merge::by_peak(&gx_motif_hit::region, gx_peak_merge::motif_hit_less));
   return GX_OK;
 }
 

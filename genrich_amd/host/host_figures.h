@@ -590,34 +590,10 @@ void writeGcBias(State& S) {
   }
 }
 
-// --gc-peaks FILE: the rows of --counts (the contexts' peak lists merged in the order of -o, the same peak_N), then the peak's
-// length, its known bases, its G or C among them and their share, by rank differences on the context that owns the chromosome
+// --gc-peaks FILE: the rows of --counts (the same peak_N), then the peak's length, its known bases, its G or C among them and
+// their share, by rank differences on the context that owns the chromosome (gx_write_gc_peaks_group)
 void writeGcPeaks(State& S, const std::vector<const char*>& names) {
-  std::vector<gx_region> reg;
-  std::vector<uint64_t> gc, acgt;
-  for (gx_ctx* g : S.devs.ctx) {
-    size_t k = 0;
-    check(S, gx_peak_count(g, &k), g);
-    std::vector<gx_peak> pk(k);
-    if (k) check(S, gx_get_peaks(g, pk.data(), k), g);
-    const size_t at = reg.size();
-    for (const gx_peak& p : pk) reg.push_back(gx_region{(uint32_t)p.chrom, (uint32_t)p.start, (uint32_t)p.end});
-    gc.resize(at + k);
-    acgt.resize(at + k);
-    check(S, gx_gc_content(g, reg.data() + at, k, gc.data() + at, acgt.data() + at), g);
-  }
-  std::vector<size_t> ord(reg.size());
-  for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
-  if (S.devs.n() > 1)
-    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return reg[a].chrom != reg[b].chrom ? reg[a].chrom < reg[b].chrom : reg[a].start < reg[b].start; });
-  std::vector<gx_region> r2;
-  std::vector<uint64_t> g2, a2;
-  for (size_t i : ord) {
-    r2.push_back(reg[i]);
-    g2.push_back(gc[i]);
-    a2.push_back(acgt[i]);
-  }
-  writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_format_gc_peaks(f, names.data(), r2.data(), r2.size(), g2.data(), a2.data()); });
+  writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_write_gc_peaks_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), f); });
 }
 
 // --motifs FILE: the JASPAR matrices (host_motifs.h) to scores and thresholds (gx_motif_pssm, gx_motif_threshold: host only), and
@@ -650,8 +626,8 @@ void loadMotifs(State& S) {
 }
 
 // --motif-hits FILE / --motif-summary FILE: the motifs in the called peaks (k_motif_scan on the context that owns the
-// chromosome; the contexts' peak lists merged in the order of -o, the same peak_N) and, for the summary, counted over the whole
-// genome too.  With -v the hits, the peaks with any, the three most enriched motifs and the time of the genome pass
+// chromosome; the same peak_N as -o) and, for the summary, counted over the whole genome too.  With -v the hits, the peaks with
+// any, the three most enriched motifs and the time of the genome pass
 void writeMotifs(State& S, const std::vector<const char*>& names) {
   const Opts& o = S.o;
   gx_ctx* const* ctxs = S.devs.ctx.data();

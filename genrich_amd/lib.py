@@ -325,6 +325,7 @@ _SIGS = {
     "gx_get_peaks": [C.c_void_p, C.c_void_p, C.c_size_t],
     "gx_peak_count": [C.c_void_p, C.POINTER(C.c_size_t)],
     "gx_write_narrowpeak_path": [C.c_void_p, C.c_void_p, C.c_char_p],
+    "gx_write_narrowpeak_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_write_pile_path": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int],
     "gx_write_log_path": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_char_p],
     "gx_total_intervals": [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)],
@@ -449,6 +450,7 @@ _SIGS = {
     "gx_format_gc_bias": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6,
     "gx_format_gc_peaks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p],
     "gx_write_gc_bias_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "gx_write_gc_peaks_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "gx_set_genome_bases": [C.c_void_p, C.c_int],
     "gx_get_sequence": [C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_void_p],
     "gx_set_motifs": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
@@ -998,6 +1000,14 @@ def gc_bias_text(ctxs, window=200) -> bytes:
     lib = load_library()
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
     return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_gc_bias_group(arr, len(ctxs), int(window), f)))
+
+
+def gc_peaks_text(ctxs, names) -> bytes:
+    """--gc-peaks' table over the contexts of a run (gx_write_gc_peaks_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    nm = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_gc_peaks_group(arr, len(ctxs), nm, f)))
 
 
 def motif_geometry():

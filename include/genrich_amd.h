@@ -804,7 +804,8 @@ int gx_gc_geometry(int* lanes, int* grid, uint32_t* tile_words, uint32_t* min_ti
  * unclassed windows and intervals) and GX_GC_CLASSES rows `sample gc_percent windows intervals weight ratio`; weights as --counts
  * prints a count.  gx_format_gc_peaks: --gc-peaks' table: the rows of --counts (chr start end peak_N, in the order given), then
  * length, acgt, gc and gc / acgt ("NA" when acgt is 0).  gx_write_gc_bias_group: gx_gc_bias on every context, the sums, the
- * table. */
+ * table.  gx_write_gc_peaks_group: gx_gc_content on every context's own peaks, the table of the merged peaks (see
+ * gx_write_narrowpeak_group). */
 typedef struct {
   uint64_t windows, windows_unclassed, intervals, intervals_unclassed, w120, w120_unclassed;
   uint64_t cls_windows[GX_GC_CLASSES], cls_intervals[GX_GC_CLASSES], cls_w120[GX_GC_CLASSES];
@@ -818,6 +819,7 @@ int gx_gc_metrics(int window, const uint64_t* F, uint64_t f_unclassed, const uin
 int gx_format_gc_bias(FILE* out, int n_samples, const int* rep, const int* is_ctrl, int window, const uint64_t* const* F, const uint64_t* f_unclassed,
                       const uint64_t* const* Nn, const uint64_t* const* Nw, const uint64_t* n_unclassed, const uint64_t* w_unclassed);
 int gx_format_gc_peaks(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const uint64_t* gc, const uint64_t* acgt);
+int gx_write_gc_peaks_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out);
 int gx_write_gc_bias_group(gx_ctx* const* ctxs, int n_ctx, int window, FILE* out);
 
 /* ---- the sequence itself and known motifs scanned in the called peaks and in the genome (no Genrich counterpart: what HOMER's
@@ -911,7 +913,7 @@ int gx_motif_grid(uint64_t units, uint32_t step_words, unsigned grid, unsigned* 
  *   windows_peaks) from two exact 128-bit products, each converted once (as gx_gc_metrics' ratios), "%.6f"; "NA" when the
  *   denominator is 0.  counts_peaks / counts_genome: [3][n_motifs] windows, hits_fwd, hits_rev.
  * gx_write_motif_hits_group / gx_write_motif_summary_group: gx_motif_scan_peaks (and, for the summary, gx_motif_scan_genome) on
- *   every context, the contexts' peaks merged into narrowPeak order as gx_write_summits_group does (the same peak_N), the table.
+ *   every context, the table of the merged peaks (see gx_write_narrowpeak_group).
  *   A context that still holds the scan of its peaks with these motifs (gx_motif_scan_peaks since the last gx_find_peaks and
  *   gx_set_motifs) is not scanned again.  gx_write_motifs_group: both tables from ONE scan of the peaks and, with summary_out,
  *   ONE genome pass (launched on every context before the first is waited for); either FILE may be NULL, not both; names may
@@ -1116,9 +1118,13 @@ int gx_write_pile(gx_ctx* ctx, int rep, const char* const* names, int n_chrom, c
  *     peaks_opt = 0 is -X (logIntervals 837-878) */
 int gx_write_log(gx_ctx* ctx, int n_rep, const char* const* names, int n_chrom, int qval_opt, int peaks_opt,
                  float thr, FILE* out);
-/* The same for a run whose chromosomes are sharded over several contexts (one per GPU): peaks of all
- * contexts in chromosome-table order (peak_N numbering, Genrich.c:986, 925); owner[c] = index into ctxs of
- * the context that computed chromosome c. */
+/* The same for a run whose chromosomes are sharded over several contexts (one per GPU); owner[c] = index into ctxs of
+ * the context that computed chromosome c.
+ * THE MERGED PEAKS: every group writer with a row (or a group of rows) per called peak -- gx_write_narrowpeak_group,
+ * gx_write_counts_group, gx_write_peak_signal_group, gx_write_summits_group, gx_write_gc_peaks_group, gx_write_motifs_group --
+ * numbers the peaks alike: the contexts' lists (gx_get_peaks) concatenated in the order of ctxs, then, for n_ctx > 1,
+ * stable-sorted by (chrom, start) -- chromosome-table order, then position, the order in which the reference meets them
+ * (Genrich.c:986, 925); one context's list is taken as it is.  Merged peak i is peak_i in every file of a run. */
 int gx_write_narrowpeak_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, FILE* out);
 int gx_write_pile_group(gx_ctx* const* ctxs, const int* owner, int rep, const char* const* names, int n_chrom,
                         const char* expt_name, const char* ctrl_name, FILE* out);
@@ -1126,8 +1132,7 @@ int gx_write_log_group(gx_ctx* const* ctxs, const int* owner, int n_rep, const c
                        int qval_opt, int peaks_opt, float thr, FILE* out);
 int gx_write_narrowpeak_path(gx_ctx* ctx, const char* const* names, const char* path);
 /* --counts (no Genrich counterpart; after gx_count_in_peaks on every context): a header "chr\tstart\tend\tname" and one
- * column per sample (sample_names[i], n_samples of them), then one row per narrowPeak line (the same peak_N, contexts merged
- * as gx_write_narrowpeak_group does); a value n (1/120 units) is printed as n / 120 with %lld when n % 120 == 0, else with
+ * column per sample (sample_names[i], n_samples of them), then one row per narrowPeak line (the merged peaks); a value n (1/120 units) is printed as n / 120 with %lld when n % 120 == 0, else with
  * %.2f. */
 int gx_write_counts_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int n_samples,
                           const char* const* sample_names, FILE* out);
@@ -1149,8 +1154,8 @@ int gx_write_region_counts_path(gx_ctx* ctx, const char* const* names, const gx_
  * per sample the five columns <label>.max <label>.summit <label>.area <label>.covered <label>.at_summit, <label> = t<rep> or
  * c<rep>; then one row per peak in the order given: names[chrom], start, end, peak_N with N = k, and the samples' figures --
  * those in 1/120 units printed as --counts prints a count (n / 120 with %lld when n % 120 == 0, else %.2f), summit and covered
- * as they are.  n_peaks == 0 and n_samples == 0 are legal.  gx_write_peak_signal_group: runs gx_peak_signal on every context,
- * merges their peaks as gx_write_narrowpeak_group does (the same peak_N) and formats; contexts that differ in their samples:
+ * as they are.  n_peaks == 0 and n_samples == 0 are legal.  gx_write_peak_signal_group: runs gx_peak_signal on every context
+ * and formats the merged peaks; contexts that differ in their samples:
  * GX_ERR_ORDER.  gx_write_peak_signal: one context. */
 int gx_format_peak_signal(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, int n_samples,
                           const int* rep, const int* is_ctrl, const int64_t* const* area120, const int64_t* const* max120,
@@ -1162,8 +1167,7 @@ int gx_write_peak_signal(gx_ctx* ctx, const char* const* names, FILE* out);
  * (ascending in (peak, pos), else GX_ERR_ORDER): names[chrom], summit, summit + 1, peak_N.j with N the peak's index and j = 1,
  * 2, ... from left to right within it, the height, ".", the plateau [start, end), the prominence, the peak's start and end --
  * narrowPeak coordinates; height and prominence printed as --counts prints a count.  n == 0 is legal.
- * gx_write_summits_group: runs gx_peak_summits on every context, merges their peaks as gx_write_narrowpeak_group does (the same
- * peak_N) and formats.  gx_write_summits: one context. */
+ * gx_write_summits_group: runs gx_peak_summits on every context and formats the merged peaks.  gx_write_summits: one context. */
 int gx_format_summits(FILE* out, const char* const* names, const gx_region* peaks, size_t n_peaks, const gx_summit* summits,
                       size_t n);
 int gx_write_summits_group(gx_ctx* const* ctxs, int n_ctx, const char* const* names, int prominence_pct, int height_pct, FILE* out);
