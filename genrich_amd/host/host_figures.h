@@ -1,5 +1,5 @@
-// host_figures.h -- the figure writers (--counts ... --profile): the frame they share, then one function per figure, each with its
-// files and its -v lines.  (a part of genrich_amd.cpp's translation unit)
+// host_figures.h -- the figure writers (--counts ... --profile): the frame they share, then one function over the State per figure,
+// each with its files and its -v lines, then FIGURES, the table of them.  (a part of genrich_amd.cpp's translation unit)
 #pragma once
 namespace {
 
@@ -38,28 +38,6 @@ int agreedSamples(State& S, const char* sentence, F count, int expect = -1) {
 
 // a sample as the -v lines name it
 std::string sampleLabel(int rep, int ctrl) { return std::string(ctrl ? "control" : "experimental") + " file #" + std::to_string(rep); }
-
-// Chromosome name -> index.  A name that no header has gets an index behind the table (the library counts nothing there, its row
-// is zero) and its place behind the table's names.
-struct ChromNames {
-  std::vector<const char*> all;   // the table's names, then the unknown ones (good while the strings given to of() live)
-  std::unordered_map<std::string, uint32_t> idx;
-  ChromNames() = default;
-  explicit ChromNames(const std::vector<Chrom>& chrom) {
-    for (const Chrom& c : chrom) {
-      idx.emplace(c.name, (uint32_t)all.size());
-      all.push_back(c.name.c_str());
-    }
-  }
-  uint32_t of(const std::string& name) {
-    auto it = idx.find(name);
-    if (it == idx.end()) {
-      it = idx.emplace(name, (uint32_t)all.size()).first;
-      all.push_back(name.c_str());
-    }
-    return it->second;
-  }
-};
 
 // What a two-call getter fills (first call: the size; second: the data), kept for every sample at once because the formatters take
 // all samples: column k of sample i, and per column the pointers of all samples.
@@ -102,14 +80,13 @@ void reportCounted(State& S, int nS, const char* where, const char* ratio, Get g
 }
 
 // ---- the figures ------------------------------------------------------------------------------------------------------------
-// (`names`: the chromosome table's; `sampleNames`: the files that were read, in run order)
 // --counts: every sample's intervals (its -b lines) counted in the peaks just called, one column per sample in run order --
 // for replicate r its treatment, then its control when one was read; with -v the FRiP of each sample
-void writeCounts(State& S, const std::vector<const char*>& names, const std::vector<const char*>& sampleNames) {
-  const int nS = (int)sampleNames.size();
+void writeCounts(State& S) {
+  const int nS = (int)S.sampleNames.size();
   agreedSamples(S, "--counts: the library kept another number of samples than were read", gx_count_in_peaks, nS);
   writeFile(S, S.o.countsFile, [&](FILE* f) {
-    return gx_write_counts_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), nS, sampleNames.data(), f);
+    return gx_write_counts_group(S.devs.ctx.data(), (int)S.devs.n(), S.names.data(), nS, S.sampleNames.data(), f);
   });
   if (S.o.verbose) reportCounted(S, nS, "peaks", "FRiP", gx_get_peak_counts);
 }
@@ -117,10 +94,10 @@ void writeCounts(State& S, const std::vector<const char*>& names, const std::vec
 // --peak-signal FILE: every sample's own depth (its -b lines piled up, -E regions not masked) inside the peaks just called: one
 // row per narrowPeak line, five columns per sample (gx_write_peak_signal_group); with -v per sample the peaks in which it has no
 // depth at all and the peaks whose summit base is also the first base of its own maximum
-void writePeakSignal(State& S, const std::vector<const char*>& names, int nS) {
-  writeFile(S, S.o.peakSignalFile, [&](FILE* f) { return gx_write_peak_signal_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), f); });
+void writePeakSignal(State& S) {
+  writeFile(S, S.o.peakSignalFile, [&](FILE* f) { return gx_write_peak_signal_group(S.devs.ctx.data(), (int)S.devs.n(), S.names.data(), f); });
   if (!S.o.verbose) return;
-  for (int i = 0; i < nS; i++) {
+  for (int i = 0; i < (int)S.sampleNames.size(); i++) {
     size_t total = 0, empty = 0, shared = 0;
     int rep = 0, ctrl = 0;
     for (gx_ctx* g : S.devs.ctx) {
@@ -146,9 +123,9 @@ void writePeakSignal(State& S, const std::vector<const char*>& names, int nS) {
 // --summits-prominence percent of its height and reaches --summits-height percent of the peak's highest
 // (gx_write_summits_group); with -v the peaks, the summits, the peaks with more than one, the most in one peak and the peaks
 // without pooled depth (no summit)
-void writeSummits(State& S, const std::vector<const char*>& names) {
+void writeSummits(State& S) {
   writeFile(S, S.o.summitsFile, [&](FILE* f) {
-    return gx_write_summits_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), S.o.summitsProminence, S.o.summitsHeight, f);
+    return gx_write_summits_group(S.devs.ctx.data(), (int)S.devs.n(), S.names.data(), S.o.summitsProminence, S.o.summitsHeight, f);
   });
   if (!S.o.verbose) return;
   size_t peaks = 0, summits = 0, multi = 0, most = 0, none = 0;
@@ -181,6 +158,8 @@ void loadRegionRows(State& S, const char* fn, std::vector<RegionRow>& rows, std:
   In in;
   openRead(in, fn, S.threads.sam.inflate);
   while (in.gets(line.data(), (int)line.size())) {
+    // in the reference's order (5203-5213): a field is converted as soon as it has been cut off, and a missing one is reported
+    // with what strtok has left of the line, i.e. the name
     char* name = strtok(line.data(), "\t");
     if (!name) die(line.data(), ": poorly formatted BED record");
     char* a = strtok(nullptr, "\t");
@@ -208,8 +187,16 @@ void loadRegionRows(State& S, const char* fn, std::vector<RegionRow>& rows, std:
   checkIn(in);
   in.close();
 }
-void writeRegionCounts(State& S, const std::vector<const char*>& sampleNames) {
-  const int nS = (int)sampleNames.size();
+// -E FILE[,FILE...] (loadBED 5187-5238): the same three fields of every line of every file
+void loadBED(State& S, const char* files) {
+  std::string list(files);
+  std::vector<RegionRow> rows;
+  char* endFn = nullptr;  // (strtok_r as in the reference: the lines are cut up with strtok inside the loop)
+  for (char* fn = strtok_r(list.data(), ", ", &endFn); fn; fn = strtok_r(nullptr, ", ", &endFn)) loadRegionRows(S, fn, rows, nullptr);
+  for (const RegionRow& r : rows) S.xbed.push_back(BedRec{r.chrom, {r.start, r.end}});
+}
+void writeRegionCounts(State& S) {
+  const int nS = (int)S.sampleNames.size();
   ChromNames names(S.chrom);
   std::vector<gx_region> reg(S.regions.size());
   std::vector<const char*> regNames(S.regions.size());
@@ -222,7 +209,7 @@ void writeRegionCounts(State& S, const std::vector<const char*>& sampleNames) {
                 [&](gx_ctx* g, int* n) { return gx_count_in_regions(g, reg.data(), reg.size(), n); }, nS);
   writeFile(S, S.o.regionCountsFile, [&](FILE* f) {
     return gx_write_region_counts_group(S.devs.ctx.data(), (int)S.devs.n(), names.all.data(), reg.data(), regNames.data(), reg.size(), nS,
-                                        sampleNames.data(), f);
+                                        S.sampleNames.data(), f);
   });
   if (S.o.verbose) reportCounted(S, nS, "regions", "fraction", gx_get_region_counts);
 }
@@ -263,16 +250,16 @@ std::pair<int, int> leastAlike(const std::vector<double>& r, int nS) {
 
 // --coverage PREFIX: each sample's pileup in bins, one bedGraph file per sample -- PREFIX.t<rep>.bedgraph for a treatment,
 // PREFIX.c<rep>.bedgraph for a control that was read (.gz behind it with -z); with -v the mean of each track
-void writeCoverage(State& S, const std::vector<const char*>& names) {
+void writeCoverage(State& S) {
   const Opts& o = S.o;
-  const int nChrom = (int)names.size();
+  const int nChrom = (int)S.names.size();
   const int nS = agreedSamples(S, "--coverage: the devices closed different numbers of samples", gx_coverage_samples);
   const ClosedSamples L = closedSamples(S);
   std::vector<int64_t> sums;
   for (int i = 0; i < nS; i++) {
     const std::string path = std::string(o.coveragePrefix) + "." + L.labels[i] + ".bedgraph" + (o.gzOut ? ".gz" : "");
     writeFile(S, path.c_str(), [&](FILE* f) {
-      return gx_write_coverage_group(S.devs.ctx.data(), S.devs.owner.data(), i, names.data(), nChrom, o.coverageScale, f);
+      return gx_write_coverage_group(S.devs.ctx.data(), S.devs.owner.data(), i, S.names.data(), nChrom, o.coverageScale, f);
     });
     if (!o.verbose) continue;
     double total = 0.0;   // (sum120 / 120 over the chromosomes written)
@@ -402,11 +389,11 @@ void writeComplexity(State& S) {
 // of figures per sample (mean, sd, quantiles, mode, the shares of the --lengths-cuts classes), one row per chromosome with each
 // sample's intervals, weight, share and mean depth; labelled t<rep> / c<rep>.  With -j the intervals are cut-site windows, not
 // fragments, and the header says so.  With -v the median and mode, the shares and the fullest chromosome on stderr too
-void writeIntervalStats(State& S, const std::vector<const char*>& names) {
+void writeIntervalStats(State& S) {
   const Opts& o = S.o;
   gx_ctx* const* ctxs = S.devs.ctx.data();
   const int nCtx = (int)S.devs.n();
-  const size_t nC = names.size();
+  const size_t nC = S.names.size();
   const int nS = agreedSamples(S, "--lengths: the devices kept different numbers of samples", gx_interval_stats);
   std::vector<int> rep((size_t)nS), ctrl((size_t)nS);
   std::vector<uint64_t> nInv((size_t)nS), wInv((size_t)nS);
@@ -431,7 +418,7 @@ void writeIntervalStats(State& S, const std::vector<const char*>& names) {
   writeFile(S, o.chromStatsFile, [&](FILE* f) {
     std::vector<uint32_t> lens;
     for (const Chrom& ch : S.chrom) lens.push_back(ch.len);
-    return gx_format_chrom_stats(f, names.data(), lens.data(), (int)nC, nS, rep.data(), ctrl.data(), pcn.data(), pcw.data(), pcb.data());
+    return gx_format_chrom_stats(f, S.names.data(), lens.data(), (int)nC, nS, rep.data(), ctrl.data(), pcn.data(), pcw.data(), pcb.data());
   });
   if (!o.verbose) return;
   for (int i = 0; i < nS; i++) {
@@ -446,7 +433,7 @@ void writeIntervalStats(State& S, const std::vector<const char*>& names) {
     fprintf(stderr, "  Interval lengths%s, %s: %llu intervals, median %llu, mode %llu; shares", o.atacOpt ? " (cut-site windows)" : "",
             sampleLabel(rep[i], ctrl[i]).c_str(), (unsigned long long)m.n, (unsigned long long)m.median, (unsigned long long)m.mode);
     for (int k = 0; k <= nCuts; k++) fprintf(stderr, " %f", m.n ? m.share[k] : 0.0);
-    fprintf(stderr, "; most on %s (%f)\n", nC ? names[top] : "-", W ? (double)pcw[i][top] / (double)W : 0.0);
+    fprintf(stderr, "; most on %s (%f)\n", nC ? S.names[top] : "-", W ? (double)pcw[i][top] / (double)W : 0.0);
   }
 }
 
@@ -456,24 +443,22 @@ void writeIntervalStats(State& S, const std::vector<const char*>& names) {
 // unknown, with one warning each under -v.  Plain text through a mapping; gzip and BGZF through the input stream's inflaters.
 struct GenomeSink {
   State& S;
-  std::unordered_map<std::string, int> idx;
+  ChromNames names;
   std::vector<uint8_t> seen;
   int c = -1;
   bool tooLong = false;
   uint64_t nSeq = 0, nBases = 0;
   std::string err;
-  explicit GenomeSink(State& s) : S(s), seen(s.chrom.size(), 0) {
-    for (size_t i = 0; i < S.chrom.size(); i++) idx.emplace(S.chrom[i].name, (int)i);
-  }
+  explicit GenomeSink(State& s) : S(s), names(s.chrom), seen(s.chrom.size(), 0) {}
   bool lengths(uint64_t fasta) {
     err = S.chrom[c].name + ": the sequence in " + S.o.genomeFile + " has " + std::to_string(fasta) + (tooLong ? " bases or more" : " bases") +
           ", the alignment files' header says " + std::to_string(S.chrom[c].len);
     return false;
   }
   bool begin(const std::string& name) {
-    const auto it = idx.find(name);
-    if (it == idx.end() || S.chrom[it->second].skip) return false;
-    c = it->second;
+    const auto it = names.idx.find(name);
+    if (it == names.idx.end() || S.chrom[it->second].skip) return false;
+    c = (int)it->second;
     if (seen[c]) {
       err = name + ": twice in " + S.o.genomeFile;
       c = -1;
@@ -592,8 +577,8 @@ void writeGcBias(State& S) {
 
 // --gc-peaks FILE: the rows of --counts (the same peak_N), then the peak's length, its known bases, its G or C among them and
 // their share, by rank differences on the context that owns the chromosome (gx_write_gc_peaks_group)
-void writeGcPeaks(State& S, const std::vector<const char*>& names) {
-  writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_write_gc_peaks_group(S.devs.ctx.data(), (int)S.devs.n(), names.data(), f); });
+void writeGcPeaks(State& S) {
+  writeFile(S, S.o.gcPeaksFile, [&](FILE* f) { return gx_write_gc_peaks_group(S.devs.ctx.data(), (int)S.devs.n(), S.names.data(), f); });
 }
 
 // --motifs FILE: the JASPAR matrices (host_motifs.h) to scores and thresholds (gx_motif_pssm, gx_motif_threshold: host only), and
@@ -628,7 +613,7 @@ void loadMotifs(State& S) {
 // --motif-hits FILE / --motif-summary FILE: the motifs in the called peaks (k_motif_scan on the context that owns the
 // chromosome; the same peak_N as -o) and, for the summary, counted over the whole genome too.  With -v the hits, the peaks with
 // any, the three most enriched motifs and the time of the genome pass
-void writeMotifs(State& S, const std::vector<const char*>& names) {
+void writeMotifs(State& S) {
   const Opts& o = S.o;
   gx_ctx* const* ctxs = S.devs.ctx.data();
   const int nCtx = (int)S.devs.n(), nM = (int)S.motifs.size();
@@ -641,7 +626,7 @@ void writeMotifs(State& S, const std::vector<const char*>& names) {
   std::vector<uint64_t> cp((size_t)3 * nM + 1, 0), cg((size_t)3 * nM + 1, 0);
   gx_motif_report rep{};
   writeFiles(S, o.motifHitsFile, o.motifSummaryFile, [&](FILE* hits, FILE* summary) {
-    return gx_write_motifs_group(ctxs, nCtx, names.data(), S.motifRecs.data(), ids.data(), mnames.data(), S.motifP.data(), nM, hits, summary, cp.data(),
+    return gx_write_motifs_group(ctxs, nCtx, S.names.data(), S.motifRecs.data(), ids.data(), mnames.data(), S.motifP.data(), nM, hits, summary, cp.data(),
                                  cg.data(), &rep);
   });
   if (!o.verbose) return;
@@ -763,7 +748,7 @@ void writeSaturation(State& S) {
 // of halves (gx_reproducibility), one row per call in FILE and the figures made of the lists in the metrics file; with the
 // prefix every call's narrowPeak and the run's own -o lines (their peak_N as in -o, so that they join with --counts) of the
 // conservative and the optimal set; with -v each call on stderr, then the figures and the verdict
-void writeReproducibility(State& S, const std::vector<const char*>& names) {
+void writeReproducibility(State& S) {
   const Opts& o = S.o;
   gx_ctx* g = S.devs.ctx[0];
   const int nR = S.sample;
@@ -795,7 +780,7 @@ void writeReproducibility(State& S, const std::vector<const char*>& names) {
     for (size_t i = 0; i < nC; i++) {
       check(S, gx_reproducibility_label(&calls[i], label, sizeof label), g);
       const std::string path = std::string(o.reproPrefix) + "." + label + ".narrowPeak";
-      writeFile(S, path.c_str(), [&](FILE* f) { return gx_format_narrowpeak(lists[i].data(), lists[i].size(), names.data(), 0, f); });
+      writeFile(S, path.c_str(), [&](FILE* f) { return gx_format_narrowpeak(lists[i].data(), lists[i].size(), S.names.data(), 0, f); });
     }
     const std::pair<const char*, const std::vector<uint8_t>*> sets[2] = {{"conservative", &cons}, {"optimal", &opt}};
     for (const auto& st : sets) {
@@ -803,7 +788,7 @@ void writeReproducibility(State& S, const std::vector<const char*>& names) {
       writeFile(S, path.c_str(), [&](FILE* f) {
         int rc = GX_OK;
         for (size_t k = 0; k < nRun && rc == GX_OK; k++)
-          if ((*st.second)[k]) rc = gx_format_narrowpeak(&run[k], 1, names.data(), (int)k, f);
+          if ((*st.second)[k]) rc = gx_format_narrowpeak(&run[k], 1, S.names.data(), (int)k, f);
         return rc;
       });
     }
@@ -834,13 +819,6 @@ void writeReproducibility(State& S, const std::vector<const char*>& names) {
 // every context before the first sample (setProfile); PREFIX.profile.tsv has the mean signal per base and anchor at every
 // offset, one column per sample; with --profile-matrix a sample's PREFIX.t<rep>.matrix.tsv / PREFIX.c<rep>.matrix.tsv has one
 // row per BED line, in the BED's order; with -v the enrichment of each sample
-struct ProfilePlan {
-  ChromNames names;                    // the table's names, then those of chromosomes that no header names
-  std::vector<gx_anchor> anchors;
-  std::vector<gx_region> regions;
-  std::vector<const char*> rowNames;
-  size_t counted = 0;                  // anchors on chromosomes the run computes: known, not -e skipped, not empty
-};
 ProfilePlan planProfile(State& S) {
   ProfilePlan P;
   P.names = ChromNames(S.chrom);
@@ -860,12 +838,13 @@ ProfilePlan planProfile(State& S) {
   }
   return P;
 }
-void writeProfile(State& S, const ProfilePlan& P, const std::vector<const char*>& sampleNames) {
+void writeProfile(State& S) {
   const Opts& o = S.o;
-  const int nS = (int)sampleNames.size();
+  const ProfilePlan& P = S.profilePlan;
+  const int nS = (int)S.sampleNames.size();
   agreedSamples(S, "--profile: the library closed another number of samples than were read", gx_profile_samples, nS);
   writeFile(S, (std::string(o.profilePrefix) + ".profile.tsv").c_str(), [&](FILE* f) {
-    return gx_write_profile_group(S.devs.ctx.data(), (int)S.devs.n(), nS, sampleNames.data(), P.counted, f);
+    return gx_write_profile_group(S.devs.ctx.data(), (int)S.devs.n(), nS, S.sampleNames.data(), P.counted, f);
   });
   const uint32_t nb = (uint32_t)(2 * o.flank / o.profileBin);
   const ClosedSamples L = closedSamples(S, true);
@@ -895,5 +874,35 @@ void writeProfile(State& S, const ProfilePlan& P, const std::vector<const char*>
             edge ? (double)top * (2.0 * ne) / (double)edge : 0.0, P.counted);
   }
 }
+
+// ---- the table of figures ---------------------------------------------------------------------------------------------------
+// One row per figure, in the order they are written: when it is on, what it is made of besides the pileups, and its writer
+enum : unsigned { KEPT = 1, BINS = 2 };   // the library keeps the samples' intervals (gx_set_count_in_peaks); the coverage bins
+struct Figure { bool (*on)(const Opts&); unsigned madeOf; void (*write)(State&); };
+const Figure FIGURES[] = {
+    {[](const Opts& o) { return o.countsFile != nullptr; }, KEPT, writeCounts},
+    {[](const Opts& o) { return o.peakSignalFile != nullptr; }, KEPT, writePeakSignal},
+    {[](const Opts& o) { return o.summitsFile != nullptr; }, KEPT, writeSummits},
+    {[](const Opts& o) { return o.regionsBed != nullptr; }, KEPT, writeRegionCounts},
+    {[](const Opts& o) { return o.coveragePrefix != nullptr; }, BINS, writeCoverage},
+    {[](const Opts& o) { return o.correlationFile != nullptr; }, BINS, writeCorrelation},
+    {[](const Opts& o) { return o.spearmanFile != nullptr; }, BINS, writeSpearman},
+    {[](const Opts& o) { return o.fingerprintFile != nullptr; }, BINS, writeFingerprint},
+    {[](const Opts& o) { return o.complexityFile != nullptr; }, KEPT, writeComplexity},
+    {[](const Opts& o) { return o.lengthsOn(); }, KEPT, writeIntervalStats},
+    {[](const Opts& o) { return o.depthOn(); }, 0, writeDepth},
+    {[](const Opts& o) { return o.xcorOn(); }, 0, writeXcor},
+    {[](const Opts& o) { return o.gcBiasFile != nullptr; }, KEPT, writeGcBias},
+    {[](const Opts& o) { return o.gcPeaksFile != nullptr; }, 0, writeGcPeaks},
+    {[](const Opts& o) { return o.motifsFile != nullptr; }, 0, writeMotifs},
+    {[](const Opts& o) { return o.saturationFile != nullptr; }, KEPT, writeSaturation},
+    {[](const Opts& o) { return o.reproOn(); }, KEPT, writeReproducibility},
+    {[](const Opts& o) { return o.profileBed != nullptr; }, 0, writeProfile},
+};
+bool someFigureOf(const Opts& o, unsigned what) {
+  return std::any_of(std::begin(FIGURES), std::end(FIGURES), [&](const Figure& f) { return (f.madeOf & what) && f.on(o); });
+}
+bool keepsIntervals(const Opts& o) { return someFigureOf(o, KEPT); }
+bool Opts::binsOn() const { return someFigureOf(*this, BINS); }
 
 }  // namespace

@@ -26,6 +26,15 @@ struct PeakState {
   }
 };
 
+void logPeakParams(const Opts& o, uint64_t genomeLen, float thr) {   // -v: findPeaks 1103-1117, and callPeaksLog's
+  fprintf(stderr, "Peak-calling parameters:\n");
+  fprintf(stderr, "  Genome length: %ldbp\n", (long)genomeLen);
+  fprintf(stderr, "  Significance threshold: -log(%c) > %.3f\n", o.qvalOpt ? 'q' : 'p', thr);
+  fprintf(stderr, "  Min. AUC: %.3f\n", o.minAUC);
+  if (o.minLen) fprintf(stderr, "  Min. peak length: %dbp\n", o.minLen);
+  fprintf(stderr, "  Max. gap between sites: %dbp\n", o.maxGap);
+}
+
 void peaksOnly(State& S, float thr) {
   const Opts& o = S.o;
   In in;
@@ -151,12 +160,7 @@ void peaksOnly(State& S, float thr) {
       fprintf(stderr, " pileup calculation,\n  and the lengths were included");
       fprintf(stderr, " in the genome length %scalculation\n", o.qvalOpt ? "(and q-value) " : "");
     }
-    fprintf(stderr, "Peak-calling parameters:\n");
-    fprintf(stderr, "  Genome length: %ldbp\n", (long)genomeLen);
-    fprintf(stderr, "  Significance threshold: -log(%c) > %.3f\n", o.qvalOpt ? 'q' : 'p', thr);
-    fprintf(stderr, "  Min. AUC: %.3f\n", o.minAUC);
-    if (o.minLen) fprintf(stderr, "  Min. peak length: %dbp\n", o.minLen);
-    fprintf(stderr, "  Max. gap between sites: %dbp\n", o.maxGap);
+    logPeakParams(o, genomeLen, thr);
     fprintf(stderr, "Peaks identified: %d (%ldbp)\n", count, (long)peakBP);
   }
   checkIn(in);

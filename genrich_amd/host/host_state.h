@@ -26,6 +26,7 @@ struct Opts {
   int binSize = 50;             // --bin-size
   double coverageScale = 1.0;   // --coverage-scale
   bool binSizeOpt = false, coverageScaleOpt = false;
+  bool binsOn() const;                     // some figure that is made of the coverage bins is on (FIGURES, host_figures.h)
   const char* correlationFile = nullptr;   // --correlation FILE: the samples' Pearson matrix from the coverage bins
   bool corrSkipZeros = false;              // --corr-skip-zeros (both matrices)
   const char* spearmanFile = nullptr;      // --spearman FILE: the samples' Spearman matrix from the coverage bins
@@ -34,11 +35,13 @@ struct Opts {
   const char* complexityFile = nullptr;    // --complexity FILE: each sample's library complexity from its kept intervals
   const char* depthFile = nullptr;         // --depth FILE: each sample's per-base depth distribution from its pileup
   const char* depthMetricsFile = nullptr;  // --depth-metrics FILE: ... and the figures made of it
+  bool depthOn() const { return depthFile || depthMetricsFile; }
   const char* lengthsFile = nullptr;        // --lengths FILE: each sample's interval lengths from its kept intervals
   const char* lengthsMetricsFile = nullptr; // --lengths-metrics FILE: ... and the figures made of them
   const char* chromStatsFile = nullptr;     // --chrom-stats FILE: ... and its intervals per chromosome
   std::vector<uint64_t> lengthsCuts{150, 300, 500};   // --lengths-cuts A,B,...: the class borders of the metrics' shares
   bool lengthsCutsOpt = false;
+  bool lengthsOn() const { return lengthsFile || lengthsMetricsFile || chromStatsFile; }
   const char* xcorFile = nullptr;           // --xcor FILE: each sample's strand cross-correlation curve from its alignments' 5' ends
   const char* xcorMetricsFile = nullptr;    // --xcor-metrics FILE: ... and the figures made of it (fragment length, NSC, RSC)
   int xcorLo = -100, xcorHi = 600;          // --xcor-shifts LO,HI
@@ -80,6 +83,7 @@ struct Opts {
        qvalOpt = false, dupsOpt = false, peaksOpt = true, peaksOnly = false, sortOpt = true, verbose = false,
        eventsOnly = false;
   int device = 0;
+  int threads = 1;           // --threads N, else GENRICH_THREADS, else up to 16 of the machine's cores (parseOptions)
   std::vector<int> devices;  // --devices a,b,...: one context per GPU, chromosomes sharded by length
   // what a figure is made of: the run's intervals, pileups and alignments (none with -P or --events-only) ...
   bool buildsPileups() const { return !peaksOnly && !eventsOnly; }
@@ -169,9 +173,46 @@ struct HotWindows {
 };
 
 struct RegionRow { std::string chrom, name; uint32_t start, end; bool named; };   // a line of --count-regions' BED
+
+// Chromosome name -> index.  A name that no header has gets an index behind the table (the library counts nothing there, its row
+// is zero) and its place behind the table's names.
+struct ChromNames {
+  std::vector<const char*> all;   // the table's names, then the unknown ones (good while the strings given to of() live)
+  std::unordered_map<std::string, uint32_t> idx;
+  ChromNames() = default;
+  explicit ChromNames(const std::vector<Chrom>& chrom) {
+    for (const Chrom& c : chrom) {
+      idx.emplace(c.name, (uint32_t)all.size());
+      all.push_back(c.name.c_str());
+    }
+  }
+  uint32_t of(const std::string& name) {
+    auto it = idx.find(name);
+    if (it == idx.end()) {
+      it = idx.emplace(name, (uint32_t)all.size()).first;
+      all.push_back(name.c_str());
+    }
+    return it->second;
+  }
+};
+struct ProfilePlan {                   // --profile: what the anchors' BED becomes once the chromosome table is final (planProfile)
+  ChromNames names;                    // the table's names, then those of chromosomes that no header names
+  std::vector<gx_anchor> anchors;
+  std::vector<gx_region> regions;
+  std::vector<const char*> rowNames;
+  size_t counted = 0;                  // anchors on chromosomes the run computes: known, not -e skipped, not empty
+};
+
 struct State {
   Opts o;
   Threads threads;           // (set once, after the options)
+  std::vector<std::string> tFiles, cFiles;   // (what a stage leaves for those behind it, host_run.h:) the -t / -c lists ...
+  std::vector<const char*> sampleNames;      // ... and the files that are read, in run order (planSamples)
+  const char* controlOf(size_t r) const { return r < cFiles.size() && cFiles[r] != "null" ? cFiles[r].c_str() : nullptr; }
+  float thr = 0.0f;                          // -log10 of -p / -q (validate)
+  std::vector<const char*> names;            // the chromosome table's names, once it is final (scanHeaders)
+  ProfilePlan profilePlan;                   // (enablePasses)
+  size_t nPeaks = 0, peakBP = 0;             // (callPeaks)
   std::vector<Chrom> chrom;
   std::vector<std::string> xchr;
   std::vector<BedRec> xbed;
@@ -353,36 +394,6 @@ void sendChroms(State& S) {
       for (size_t i = 0; i < n; i++) owned[i] = D.owner[i] == (int)g;
       check(S, gx_set_owned(D.ctx[g], owned.data()), D.ctx[g]);
     }
-  }
-}
-
-void loadBED(State& S, const char* files) {  // loadBED 5187-5238
-  std::string list(files);
-  std::vector<char> line(65520);
-  char* endFn = nullptr;  // (strtok_r as in the reference: the lines are cut up with strtok inside the loop)
-  for (char* fn = strtok_r(list.data(), ", ", &endFn); fn; fn = strtok_r(nullptr, ", ", &endFn)) {
-    In in;
-    openRead(in, fn, S.threads.sam.inflate);
-    while (in.gets(line.data(), (int)line.size())) {
-      // in the reference's order (5203-5213): a field is converted as soon as it has been cut off, and a
-      // missing one is reported with what strtok has left of the line, i.e. the name
-      char* name = strtok(line.data(), "\t");
-      if (!name) die(line.data(), ": poorly formatted BED record");
-      char* a = strtok(nullptr, "\t");
-      if (!a) die(line.data(), ": poorly formatted BED record");
-      const int p0 = getInt(a);
-      char* b = strtok(nullptr, "\t\n");
-      if (!b) die(line.data(), ": poorly formatted BED record");
-      const int p1 = getInt(b);
-      if (p1 <= p0 || p0 < 0 || p1 < 0) {
-        char msg[512];
-        snprintf(msg, sizeof msg, "%s, %d - %d", name, p0, p1);
-        die(msg, ": poorly formatted BED record");
-      }
-      S.xbed.push_back(BedRec{name, {(uint32_t)p0, (uint32_t)p1}});
-    }
-    checkIn(in);
-  in.close();
   }
 }
 

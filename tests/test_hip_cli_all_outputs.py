@@ -5,10 +5,15 @@ and the order of its dispatch in place, which the per-figure tests exercise one 
 
 The input is the smallest on which every writer has something to say: two chromosomes of 20 kb and a third that no read touches,
 two replicates of a few hundred paired fragments (the first with a control, the second with `null`), a handful of unpaired
-alignments (-y) so that --xcor suggests an extension, one -E region, and a BED of ten lines for --count-regions and --profile with
-a line on a chromosome that no header names and lines on the minus strand."""
+alignments (-y) so that --xcor suggests an extension, one -E region, a BED of ten lines for --count-regions and --profile with
+a line on a chromosome that no header names and lines on the minus strand, a FASTA of the three chromosomes (seeded random bases
+with a short run of N) and three JASPAR motifs of width 6 to 8, loose enough (--motif-pvalue 0.01) to hit in the small peaks.
+
+Three -v lines carry a wall-clock time (--genome's, and --motif-summary's two): the seconds are masked before lines are compared."""
 import gzip
 import os
+import random
+import re
 import subprocess
 
 import pytest
@@ -39,10 +44,22 @@ FIGURES = {
     "xcor": (["--xcor", "xc.tsv", "--xcor-metrics", "xm.tsv", "--xcor-shifts", "-50,400", "--xcor-read-length", "50"], ["xc.tsv", "xm.tsv"],
              ["  Strand cross-correlation,", "  suggested -x"]),
     "saturation": (["--saturation", "sat.tsv", "--saturation-steps", "4", "--saturation-seed", "3"], ["sat.tsv"], ["  Saturation"]),
+    "summits": (["--summits", "sm.tsv", "--summits-prominence", "10", "--summits-height", "30"], ["sm.tsv"], ["  Summits in peaks:"]),
+    "reproducibility": (["--reproducibility", "rp.tsv", "--reproducibility-metrics", "rm.tsv", "--reproducibility-overlap", "40", "--reproducibility-seed", "3",
+                         "--reproducibility-peaks", "rpk"],
+                        ["rp.tsv", "rm.tsv"] + [f"rpk.{c}.narrowPeak" for c in ("t1", "t1.pr1", "t1.pr2", "t2", "t2.pr1", "t2.pr2", "pooled.pr1", "pooled.pr2",
+                                                                                "conservative", "optimal")], ["  Reproducibility"]),
+    "gc-bias": (["--genome", "g.fa", "--gc-bias", "gc.tsv", "--gc-window", "150"], ["gc.tsv"], ["Genome ", "  GC bias,"]),
+    "gc-peaks": (["--genome", "g.fa", "--gc-peaks", "gp.tsv"], ["gp.tsv"], ["Genome "]),
+    "motifs": (["--genome", "g.fa", "--motifs", "m.jaspar", "--motif-hits", "mh.tsv", "--motif-summary", "ms.tsv", "--motif-pvalue", "0.01",
+                "--motif-pseudocount", "0.5"], ["mh.tsv", "ms.tsv"], ["Genome ", "Motifs ", "Motif hits:", "  Motif "]),
     "profile": (["--profile", "sites.bed", "--profile-out", "prof", "--flank", "500", "--profile-bin", "20", "--profile-matrix"],
                 ["prof.profile.tsv"] + [f"prof.{s}.matrix.tsv" for s in SAMPLES], ["  Profile,"]),
 }
-PREFIXES = [p for _, _, ps in FIGURES.values() for p in ps]
+ONE_DEVICE = ["saturation", "reproducibility"]
+PREFIXES = sorted({p for _, _, ps in FIGURES.values() for p in ps})
+SECONDS = re.compile(r"\b\d+\.\d{3} s\b")
+MOTIFS = [("M6", "six", "ACGTGA"), ("M7", "seven", "TTGACCA"), ("M8", "eight", "GGATCCAT")]      # (ID, NAME, consensus)
 BASE = ["-v", "-y", "-p", "0.05", "-a", "20", "-t", "t0.sam,t1.sam", "-c", "c0.sam,null", "-E", "x.bed", "-o", "o.np"]
 BASE_FILES = ["o.np"]
 MORE = (["-f", "o.log", "-k", "o.pile", "-b", "o.bed"], ["o.log", "o.pile", "o.bed"])     # the combined runs write these as well
@@ -64,6 +81,16 @@ def _inputs(d):
     with open(os.path.join(d, "sites.bed"), "w") as f:
         for c, s, e, nm, st in BED:
             f.write(f"{c}\t{s}\t{e}\t{nm}\t0\t{st}\n")
+    rng = random.Random(7)
+    with open(os.path.join(d, "g.fa"), "w") as f:
+        for name, n in zip(NAMES, LENS):
+            seq = "".join(rng.choice("ACGT") for _ in range(n))
+            if name == "chrA":
+                seq = seq[:3000] + "N" * 40 + seq[3040:]
+            f.write(f">{name}\n" + "".join(seq[i:i + 60] + "\n" for i in range(0, n, 60)))
+    with open(os.path.join(d, "m.jaspar"), "w") as f:
+        for mid, name, cons in MOTIFS:          # 17 of 20 counts on the consensus base, one on each other
+            f.write(f">{mid} {name}\n" + "".join(f"{b} [ " + " ".join("17" if c == b else "1" for c in cons) + " ]\n" for b in "ACGT"))
     return sorted(os.listdir(d))
 
 
@@ -77,7 +104,7 @@ def _run(tmp, tag, opts, files, gz=False):
     made = sorted(set(os.listdir(d)) - set(inputs))
     assert made == sorted(f + (".gz" if gz else "") for f in files), (tag, made)
     read = (lambda p: gzip.open(p, "rb").read()) if gz else (lambda p: open(p, "rb").read())
-    return {f: read(os.path.join(d, f + (".gz" if gz else ""))) for f in files}, res.stderr.splitlines()
+    return {f: read(os.path.join(d, f + (".gz" if gz else ""))) for f in files}, SECONDS.sub("T s", res.stderr).splitlines()
 
 
 def _figure_lines(lines, prefixes):
@@ -121,11 +148,12 @@ def test_a_figure_alone_is_the_figure_of_the_combined_run(combined, name):
 
 
 def test_two_contexts_write_the_same_files(combined):
-    """(--saturation takes one device: every other figure)"""
-    sat_opts, sat_files, _ = FIGURES["saturation"]
-    opts = [o for o in combined["opts"] if o not in sat_opts] + ["--devices", "0,0"]
-    assert len(opts) == len(combined["opts"]) - len(sat_opts) + 2
-    files = [f for f in combined["files"] if f not in sat_files]
+    """(--saturation and --reproducibility take one device: every other figure)"""
+    one_opts = [o for n in ONE_DEVICE for o in FIGURES[n][0]]
+    one_files = [f for n in ONE_DEVICE for f in FIGURES[n][1]]
+    opts = [o for o in combined["opts"] if o not in one_opts] + ["--devices", "0,0"]
+    assert len(opts) == len(combined["opts"]) - len(one_opts) + 2
+    files = [f for f in combined["files"] if f not in one_files]
     out, _ = _run(combined["tmp"], "two", opts, files)
     for f in files:
         assert out[f] == combined["out"][f], f

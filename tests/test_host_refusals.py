@@ -1,7 +1,9 @@
-"""What the host program refuses before it reads or writes anything: every sentence of main's validation block, the malformed
-values of the four strict integer options, which sentence wins when an argv breaks two rules, -h's text and the line of
-GENRICH_THREADS_REPORT.  No GPU: every case ends before a device context is made.  Each case runs in an empty directory with
-relative file names and asserts exit status 1, the exact stderr and that the directory is still empty afterwards."""
+"""What the host program refuses before it reads or writes anything: every sentence of the validation block, the malformed
+values of the nine strict integer options (two of them lists) and of the three doubles, which sentence wins when an argv breaks two
+rules, the two refusals of --profile's BED that come just behind the block, -h's text and the line of GENRICH_THREADS_REPORT.
+No GPU: every case ends before a device context is made.  Each case runs in an empty directory with relative file names and asserts
+exit status 1, the exact stderr and that the directory is still empty afterwards."""
+import gzip
 import os
 import re
 import subprocess
@@ -38,13 +40,22 @@ NEEDS_PEAKS = [
     (["--counts", "c.tsv"], "--counts needs the peaks of this run (not with -P or -X)"),
     (["--peak-signal", "ps.tsv"], "--peak-signal needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
     (["--saturation", "sat.tsv"], "--saturation needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    (["--summits", "sm.tsv"], "--summits needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    (["--reproducibility", "rp.tsv"], "--reproducibility needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    (["--reproducibility-metrics", "rm.tsv"], "--reproducibility needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    (["--motifs", "m.jaspar", "--genome", "g.fa", "--motif-hits", "mh.tsv"], "--motifs needs the peaks of this run on a device (not with -X, -P or --events-only)"),
+    (["--gc-peaks", "gp.tsv", "--genome", "g.fa"], "--gc-peaks needs the peaks of this run on a device (not with -X, -P or --events-only)"),
 ]
+NEEDS_RUN.append((["--gc-bias", "gc.tsv", "--genome", "g.fa"], "--gc-bias needs the intervals of this run (not with -P or --events-only)"))
 
 CASES = {}
 for opts, msg in NEEDS_RUN + NEEDS_PEAKS:
     for via in ("P", "events") + (("X",) if (opts, msg) in NEEDS_PEAKS else ()):
         CASES[f"{opts[0]} via {via}"] = (VIA[via] + opts, msg)
 
+REPRO_NEED = ("--reproducibility-overlap, --reproducibility-seed and --reproducibility-peaks need --reproducibility FILE or "
+              "--reproducibility-metrics FILE")
+MOTIF_NEED = "--motif-hits, --motif-summary, --motif-pvalue and --motif-pseudocount need --motifs FILE"
 MANY = ",".join(f"t{i}.sam" for i in range(33))      # 33 samples
 CASES.update({
     # the sentences that do not depend on the kind of run, in the order of the block
@@ -92,6 +103,25 @@ CASES.update({
     "q-value above 1": (RUN + ["-q", "1.5"], "p-/q-value must be in (0,1]"),
     "coverage scale, not a number": (RUN + ["--coverage-scale", "x"], "x: cannot convert to float"),
     "65 devices": (RUN + ["--devices", "0-64"], "at most 64 devices"),
+    "summits prominence alone": (RUN + ["--summits-prominence", "30"], "--summits-prominence and --summits-height need --summits FILE"),
+    "summits height alone": (RUN + ["--summits-height", "30"], "--summits-prominence and --summits-height need --summits FILE"),
+    "reproducibility overlap alone": (RUN + ["--reproducibility-overlap", "30"], REPRO_NEED),
+    "reproducibility seed alone": (RUN + ["--reproducibility-seed", "3"], REPRO_NEED),
+    "reproducibility peaks alone": (RUN + ["--reproducibility-peaks", "rp"], REPRO_NEED),
+    "reproducibility on two devices": (RUN + ["--reproducibility", "rp.tsv", "--devices", "0,1"], "--reproducibility takes one device (not with --devices of more than one)"),
+    "reproducibility metrics on two devices": (RUN + ["--reproducibility-metrics", "rm.tsv", "--devices", "0,1"],
+                                               "--reproducibility takes one device (not with --devices of more than one)"),
+    "gc bias without genome": (RUN + ["--gc-bias", "gc.tsv"], "--gc-bias needs the reference sequence (--genome FASTA)"),
+    "gc peaks without genome": (RUN + ["--gc-peaks", "gp.tsv"], "--gc-peaks needs the reference sequence (--genome FASTA)"),
+    "gc window alone": (RUN + ["--gc-window", "100"], "--gc-window needs --gc-bias FILE"),
+    "gc window with gc peaks only": (RUN + ["--gc-peaks", "gp.tsv", "--genome", "g.fa", "--gc-window", "100"], "--gc-window needs --gc-bias FILE"),
+    "motifs without genome": (RUN + ["--motifs", "m.jaspar", "--motif-hits", "mh.tsv"], "--motifs needs the reference sequence (--genome FASTA)"),
+    "motifs without either output": (RUN + ["--motifs", "m.jaspar", "--genome", "g.fa"], "--motifs needs --motif-hits FILE or --motif-summary FILE"),
+    "motif hits alone": (RUN + ["--motif-hits", "mh.tsv"], MOTIF_NEED),
+    "motif summary alone": (RUN + ["--motif-summary", "ms.tsv"], MOTIF_NEED),
+    "motif pvalue alone": (RUN + ["--motif-pvalue", "0.001"], MOTIF_NEED),
+    "motif pseudocount alone": (RUN + ["--motif-pseudocount", "2"], MOTIF_NEED),
+    "genome alone": (RUN + ["--genome", "g.fa"], "--genome needs --gc-bias FILE or --gc-peaks FILE"),
     # two rules broken at once: the first of the block wins, and among the options' own values the first of the argv
     "counts with -P, and metrics without fingerprint": (VIA["P"] + ["--counts", "c.tsv", "--fingerprint-metrics", "fm.tsv"],
                                                         "--counts needs the peaks of this run (not with -P or -X)"),
@@ -112,12 +142,27 @@ CASES.update({
     "complexity hist alone and lengths cuts alone": (RUN + ["--lengths-cuts", "1", "--complexity-hist", "ch.tsv"], "--complexity-hist needs --complexity FILE"),
     "two malformed values": (RUN + ["--xcor-read-length", "0", "--saturation-seed", "x"], "0: --xcor-read-length takes a positive integer (at most 1000000)"),
     "a malformed value and a stray argument": (RUN + ["stray", "--saturation-seed", "x"], "x: --saturation-seed takes an integer in [0, 2^64 - 1]"),
+    "gc bias with -P and no genome": (VIA["P"] + ["--gc-bias", "gc.tsv"], "--gc-bias needs the reference sequence (--genome FASTA)"),
+    "summits with -X and its height": (VIA["X"] + ["--summits", "sm.tsv", "--summits-height", "40"],
+                                       "--summits needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    "summits height alone and counts with -X": (VIA["X"] + ["--summits-height", "40", "--counts", "c.tsv"], "--counts needs the peaks of this run (not with -P or -X)"),
+    "summits height alone and regions with -P": (VIA["P"] + ["--summits-height", "40", "--count-regions", "r.bed", "--region-counts", "rc.tsv"],
+                                                 "--summits-prominence and --summits-height need --summits FILE"),
+    "motifs with -P and no outputs": (VIA["P"] + ["--motifs", "m.jaspar", "--genome", "g.fa"], "--motifs needs --motif-hits FILE or --motif-summary FILE"),
+    "motifs with -X and gc bias with -P's sentence behind it": (VIA["X"] + ["--motifs", "m.jaspar", "--genome", "g.fa", "--motif-summary", "ms.tsv", "--gc-peaks", "gp.tsv"],
+                                                               "--motifs needs the peaks of this run on a device (not with -X, -P or --events-only)"),
+    "genome alone with -P": (VIA["P"] + ["--genome", "g.fa"], "--genome needs --gc-bias FILE or --gc-peaks FILE"),
+    "reproducibility with -X on two devices": (VIA["X"] + ["--reproducibility", "rp.tsv", "--devices", "0,1", "--reproducibility-seed", "2"],
+                                               "--reproducibility needs the peaks and the intervals of this run (not with -X, -P or --events-only)"),
+    "saturation and reproducibility on two devices": (RUN + ["--reproducibility", "rp.tsv", "--saturation", "sat.tsv", "--devices", "0,1"],
+                                                      "--saturation takes one device (not with --devices of more than one)"),
     "stray argument and no files": (["stray"], "stray: unknown command-line argument"),
     # a sign where the range reaches below zero is no malformed value: the argv gets as far as the validation block
     "xcor shifts with signs": (RUN + ["--xcor-shifts", "-5,+10"], "--xcor-shifts, --xcor-read-length and --xcor-unpaired need --xcor FILE or --xcor-metrics FILE"),
 })
 
-# the four strict integer options: empty, sign, trailing text, out of range, leading blank (and for the lists, their own rules)
+# the strict integer options: empty, sign, trailing text, trailing blank, out of range, beyond 64 bits, leading blank (and for the
+# lists, their own rules)
 BIG = "99999999999999999999"    # (beyond 64 bits)
 MALFORMED = {
     "--xcor-read-length": (": --xcor-read-length takes a positive integer (at most 1000000)", ["", "+36", "-36", "36x", "36 ", "0", "1000001", BIG, " 36", "x"]),
@@ -128,9 +173,37 @@ MALFORMED = {
     "--xcor-shifts": (": --xcor-shifts takes two integers LO,HI with -4096 <= LO <= HI <= 4096",
                       ["", "5", "5,", ",5", "5,6x", "5x,6", "5,6,7", "x", "-4097,0", "0,4097", BIG + ",5", "5," + BIG, " 5,6", "5, 6", "10,5", "- 5,6", "5,-+6"]),
 }
+PCT = ["", "+5", "-5", "5x", "5 ", "-1", "101", BIG, " 5", "x"]      # (an integer in [0, 100])
+MALFORMED.update({
+    "--reproducibility-overlap": (": --reproducibility-overlap takes an integer in [0, 100]", PCT),
+    "--reproducibility-seed": (": --reproducibility-seed takes an integer in [0, 2^64 - 1]", ["", "+1", "-1", "1x", "1 ", "18446744073709551616", BIG, " 1", "x"]),
+    "--summits-prominence": (": --summits-prominence takes an integer in [0, 100]", PCT),
+    "--summits-height": (": --summits-height takes an integer in [0, 100]", PCT),
+    "--gc-window": (": --gc-window takes an integer in [1, 4096]", ["", "+200", "-200", "200x", "200 ", "0", "4097", BIG, " 200", "x"]),
+    # the three doubles: strtod's whole argument (a leading blank is strtod's to skip), and for the motifs' two their ranges
+    "--coverage-scale": (": cannot convert to float", ["", "x", "1x", "1 "]),
+    "--motif-pvalue": (": --motif-pvalue takes a number in (0, 1]", ["", "x", "1x", "1 ", "nan", "inf", "-inf", "0", "-0.5", "1.0000001", "1e400"]),
+    "--motif-pseudocount": (": --motif-pseudocount takes a number >= 0", ["", "x", "1x", "1 ", "nan", "inf", "-1e-9", "-1", "1e400"]),
+})
 for opt, (tail, values) in MALFORMED.items():
     for v in values:
         CASES[f"{opt} {v!r}"] = (RUN + [opt, v], v + tail)
+# ... and the ends of their ranges are no malformed values: the argv gets as far as the sentence that asks for the figure
+ENDS = {
+    "--xcor-read-length": (["1", "1000000"], "--xcor-shifts, --xcor-read-length and --xcor-unpaired need --xcor FILE or --xcor-metrics FILE"),
+    "--saturation-seed": (["0", "18446744073709551615"], "--saturation-steps, --saturation-seed and --saturation-controls need --saturation FILE"),
+    "--reproducibility-overlap": (["0", "100"], REPRO_NEED),
+    "--reproducibility-seed": (["0", "18446744073709551615"], REPRO_NEED),
+    "--summits-prominence": (["0", "100"], "--summits-prominence and --summits-height need --summits FILE"),
+    "--summits-height": (["0", "100"], "--summits-prominence and --summits-height need --summits FILE"),
+    "--gc-window": (["1", "4096"], "--gc-window needs --gc-bias FILE"),
+    "--coverage-scale": (["nan", "inf", "-1", " 1", "1e400"], "--bin-size and --coverage-scale need --coverage PREFIX"),      # (any double)
+    "--motif-pvalue": (["1", "1e-300", " 0.5"], MOTIF_NEED),
+    "--motif-pseudocount": (["0", "1e300"], MOTIF_NEED),
+}
+for opt, (values, msg) in ENDS.items():
+    for v in values:
+        CASES[f"{opt} {v!r} is a value"] = (RUN + [opt, v], msg)
 
 
 def _binary():
@@ -151,6 +224,24 @@ def _run(argv, cwd, env=None):
 def test_refusal(name, tmp_path):
     argv, msg = CASES[name]
     assert _run(argv, tmp_path) == f"Error! {msg}\n"
+
+
+PROFILE = RUN + ["--profile", "a.bed", "--profile-out", "prof"]
+
+
+@pytest.mark.parametrize("lines, more, msg", [
+    (0, [], "a.bed: --profile: no anchors"),
+    (0, ["--profile-matrix", "--flank", "1048576", "--profile-bin", "2048"], "a.bed: --profile: no anchors"),
+    ((1 << 16) + 1, ["--profile-matrix", "--flank", "1048576", "--profile-bin", "2048"], "--profile-matrix: more than 2^26 cells (BED lines times bins)"),
+], ids=["no anchors", "no anchors, matrix", "2^26 cells and 1024 more"])
+def test_the_refusals_of_the_anchors(lines, more, msg, tmp_path):
+    """The two that come just behind the block, when --profile's BED has been read: the BED is the one file in the directory, and
+    it is still the only one afterwards.  (A BED without a line is a gzip of nothing: an empty plain file cannot be opened.  2^16
+    lines times 1024 bins are 2^26 cells, which are allowed: one line more)"""
+    (tmp_path / "a.bed").write_bytes(gzip.compress(b"chr1\t0\t1\n" * lines, 1))
+    res = subprocess.run([_binary()] + PROFILE + more, cwd=tmp_path, capture_output=True, text=True)
+    assert os.listdir(tmp_path) == ["a.bed"]
+    assert (res.returncode, res.stdout, res.stderr) == (1, "", f"Error! {msg}\n")
 
 
 @pytest.mark.parametrize("argv", [[], ["-t", "t.sam"], ["-P", "-o", "o.np"], ["-o", "o.np"], ["-P", "-f", "l.log"],
