@@ -24,6 +24,7 @@
 #include "gx_host_xcor.h"
 #include "gx_host_gcbias.h"
 #include "gx_host_motifs.h"
+#include "gx_host_kmers.h"
 #include "gx_host_subsample.h"
 #include "gx_host_depth.h"
 #include "gx_host_peaksig.h"
@@ -356,6 +357,7 @@ int gx_reset(gx_ctx* ctx) {
   drop_xcor(ctx);       // (... and gx_set_xcor's)
   drop_gcbias(ctx);     // (gx_gc_bias' results; the genome stays)
   drop_motifs(ctx);     // (gx_motif_scan_peaks' results; the motifs stay)
+  drop_kmers(ctx);      // (gx_kmer_count_peaks' results)
   ctx->gramUsed = false;
   ctx->fpUsed = false;
   ctx->rankUsed = false;
@@ -384,7 +386,7 @@ int gx_sample_begin(gx_ctx* ctx, int is_ctrl, const uint8_t* save) {
   ctx->specRuns.valid = false;   // (a control or a further replicate: the sweep will not be the one the run pass was launched for)
   if (!is_ctrl) {
     if (ctx->phase != 0) return GX_ERR_ORDER;
-    ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = false;
+    ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = ctx->kmReady = false;
     // (a further replicate: the previous one's loose slots, tile tables and p(V) table are about to be reused)
     for (size_t r = 0; r < ctx->reps.size(); r++)
       if (ctx->reps[r].loose || ctx->reps[r].pilesPending)
@@ -687,7 +689,7 @@ int gx_pvalues(gx_ctx* ctx) {
 int gx_find_peaks(gx_ctx* ctx, size_t* n_peaks, uint64_t* genome_len, uint64_t* peak_bp) {
   if (!ctx || ctx->phase != 0 || ctx->sample < 1) return GX_ERR_ORDER;
   HIPCHECK(hipSetDevice(ctx->device));
-  ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = false;
+  ctx->peaksReady = ctx->countsReady = ctx->psigReady = ctx->sumReady = ctx->motReady = ctx->kmReady = false;
   const CallPlan& P = ctx->called;
   u32 nPeaks = 0;
   // (at most two plans: -q on the loose slots may be called off by the device, and the call is then planned again without it)
@@ -891,7 +893,7 @@ int gx_path_info(gx_ctx* ctx, unsigned* flags) {
            (ctx->covW && !ctx->cov.empty() ? GX_PATH_COVERAGE : 0u) | (!ctx->prof.empty() ? GX_PATH_PROFILE : 0u) |
            (ctx->gramUsed ? GX_PATH_GRAM : 0u) | (ctx->fpUsed ? GX_PATH_FINGERPRINT : 0u) | (ctx->rankUsed ? GX_PATH_SPEARMAN : 0u) |
            (ctx->cpxUsed ? GX_PATH_COMPLEXITY : 0u) | (ctx->subUsed ? GX_PATH_SATURATION : 0u) | (ctx->depthUsed ? GX_PATH_DEPTH : 0u) | (ctx->ivsUsed ? GX_PATH_IVSTAT : 0u) |
-           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->gcUsed ? GX_PATH_GC : 0u) | (ctx->motUsed ? GX_PATH_MOTIFS : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
+           (ctx->xcUsed ? GX_PATH_XCOR : 0u) | (ctx->gcUsed ? GX_PATH_GC : 0u) | (ctx->motUsed ? GX_PATH_MOTIFS : 0u) | (ctx->kmUsed ? GX_PATH_KMERS : 0u) | (ctx->splitUsed ? GX_PATH_SPLIT : 0u) | (C.looseSwept() && C.ran.overlap ? GX_PATH_SWEEP_OVERLAP : 0u);
   return GX_OK;
 }
 
@@ -2109,6 +2111,147 @@ int gx_write_motif_hits_group(gx_ctx* const* ctxs, int n_ctx, const char* const*
 int gx_write_motif_summary_group(gx_ctx* const* ctxs, int n_ctx, const gx_motif* motifs, const char* const* ids, const char* const* motif_names,
                                  const double* p_threshold, int n_motifs, FILE* out) {
   return gx_write_motifs_group(ctxs, n_ctx, nullptr, motifs, ids, motif_names, p_threshold, n_motifs, nullptr, out, nullptr, nullptr, nullptr);
+}
+
+// ---- every k-mer of the peaks and of the genome counted (gx_kmers.h, gx_host_kmers.h) ----
+static int kmer_guard(gx_ctx* ctx, const char* fn, int k) {
+  if (!ctx->seqOn) return refuse(ctx, std::string(fn) + " needs the bases (gx_set_genome_bases)");
+  if (int rc = guard_closed(ctx, fn)) return rc;
+  return kmer_check_k(ctx, k);
+}
+
+int gx_kmer_count_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int k, unsigned grid, uint32_t step_words, uint64_t flush_runs,
+                          uint64_t* counts, uint64_t* windows) {
+  if (!ctx || (n && !regions)) return GX_ERR_ORDER;
+  if (int rc = kmer_guard(ctx, "gx_kmer_count_regions", k)) return rc;
+  HIPCHECK(hipSetDevice(ctx->device));
+  std::vector<uint64_t> c;
+  u64 w = 0;
+  if (int rc = kmer_pass(ctx, regions, n, (u32)k, KmerGeometry{grid, step_words, flush_runs}, c, &w, nullptr)) return rc;
+  if (counts) std::copy(c.begin(), c.end(), counts);
+  if (windows) *windows = w;
+  return GX_OK;
+}
+
+int gx_kmer_count_peaks(gx_ctx* ctx, int k, int flank, uint64_t* windows, uint64_t* regions_counted) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (int rc = kmer_guard(ctx, "gx_kmer_count_peaks", k)) return rc;
+  if (ctx->phase != 0 || !ctx->peaksReady) return refuse(ctx, "gx_kmer_count_peaks comes after gx_find_peaks, with no sample open");
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (int rc = kmer_count_peaks(ctx, (u32)k, flank)) return rc;
+  if (windows) *windows = ctx->kmWindows;
+  if (regions_counted) *regions_counted = ctx->kmRegions;
+  return GX_OK;
+}
+
+int gx_get_kmer_counts(gx_ctx* ctx, uint64_t* counts, size_t cap) {
+  if (!ctx || !ctx->kmReady || (cap && !counts)) return GX_ERR_ORDER;
+  if (const size_t n = std::min(cap, ctx->kmCounts.size())) std::copy(ctx->kmCounts.begin(), ctx->kmCounts.begin() + n, counts);
+  return GX_OK;
+}
+
+int gx_kmer_count_genome(gx_ctx* ctx, int k, uint64_t* counts, size_t cap, uint64_t* windows) {
+  return gx_kmer_count_genome_group(&ctx, 1, k, counts, cap, windows);
+}
+
+// Every context's pass is launched, with its read-back queued on its stream, before the first is waited for (as
+// gx_motif_scan_genome_group).
+int gx_kmer_count_genome_group(gx_ctx* const* ctxs, int n_ctx, int k, uint64_t* counts, size_t cap, uint64_t* windows) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || (cap && !counts)) return GX_ERR_ORDER;
+  std::vector<KmerRun> runs((size_t)n_ctx);
+  for (int g = 0; g < n_ctx; g++) {
+    if (!ctxs[g]) return GX_ERR_ORDER;
+    if (int rc = kmer_guard(ctxs[g], "gx_kmer_count_genome", k)) return rc;
+  }
+  int bad = GX_OK;
+  for (int g = 0; g < n_ctx && !bad; g++) {
+    gx_ctx* ctx = ctxs[g];
+    HIPCHECK(hipSetDevice(ctx->device));
+    if (int rc = gc_current(ctx)) return rc;
+    const std::vector<gx_region> reg = mot_genome_regions(ctx);
+    bad = kmer_begin(ctx, reg.data(), reg.size(), (u32)k, KmerGeometry{0, 0, 0}, runs[(size_t)g]);
+  }
+  std::vector<uint64_t> sum, c;
+  u64 wSum = 0;
+  for (int g = 0; g < n_ctx; g++) {   // (every pass that was launched is drained, also behind a failure: its buffers are the run's)
+    gx_ctx* ctx = ctxs[g];
+    HIPCHECK(hipSetDevice(ctx->device));
+    u64 w = 0;
+    if (int rc = kmer_end(ctx, runs[(size_t)g], c, &w)) return rc;
+    wSum += w;
+    if (sum.empty()) sum.assign((size_t)1 << (2 * k), 0);
+    for (size_t i = 0; i < sum.size() && i < c.size(); i++) sum[i] += c[i];
+  }
+  if (bad) return bad;
+  if (const size_t n = std::min(cap, sum.size())) std::copy(sum.begin(), sum.begin() + n, counts);
+  if (windows) *windows = wSum;
+  return GX_OK;
+}
+
+int gx_kmer_last(gx_ctx* ctx, int* path, uint32_t* flushes) {
+  if (!ctx) return GX_ERR_ORDER;
+  if (path) *path = (int)ctx->kmLastPath;
+  if (flushes) *flushes = ctx->kmLastFlushes;
+  return GX_OK;
+}
+
+int gx_kmer_force_hbm(gx_ctx* ctx, int on) {
+  if (!ctx) return GX_ERR_ORDER;
+  ctx->kmForceHbm = on != 0;
+  return GX_OK;
+}
+
+int gx_kmer_geometry(int* lanes, int* grid, uint32_t* positions_per_step, uint32_t* step_words, uint64_t* flush_runs, int* max_k, int* lds_max_k) {
+  if (lanes) *lanes = (int)MOT_NT;
+  if (grid) *grid = (int)MOT_GRID;
+  if (positions_per_step) *positions_per_step = 64;
+  if (step_words) *step_words = MOT_STEP;
+  if (flush_runs) *flush_runs = KMER_FLUSH_RUNS;
+  if (max_k) *max_k = (int)KMER_MAX_K;
+  if (lds_max_k) *lds_max_k = (int)KMER_LDS_MAX_K;
+  return GX_OK;
+}
+
+// --kmers' table over the contexts of a run: one count of every context's peaks, one genome pass launched on every context
+// before the first is waited for, the counts added
+int gx_write_kmers_group(gx_ctx* const* ctxs, int n_ctx, int k, int flank, int top, FILE* out, gx_kmer_report* report) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0] || !out || top < 0) return GX_ERR_ORDER;
+  if (k < 1 || k > (int)KMER_MAX_K) return refuse(ctxs[0], "kmers: k must satisfy 1 <= k <= 12");
+  const size_t nT = (size_t)1 << (2 * k);
+  std::vector<uint64_t> cP(nT, 0), cG(nT, 0);
+  uint64_t wP = 0, wG = 0, nReg = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int g = 0; g < n_ctx; g++) {
+    if (!ctxs[g]) return GX_ERR_ORDER;
+    uint64_t w = 0, r = 0;
+    if (int rc = gx_kmer_count_peaks(ctxs[g], k, flank, &w, &r)) return rc;
+    wP += w;
+    nReg += r;
+    for (size_t i = 0; i < nT; i++) cP[i] += ctxs[g]->kmCounts[i];
+  }
+  const auto t1 = std::chrono::steady_clock::now();
+  if (int rc = gx_kmer_count_genome_group(ctxs, n_ctx, k, cG.data(), nT, &wG)) return rc;
+  const auto t2 = std::chrono::steady_clock::now();
+  if (int rc = gx_format_kmers(out, k, flank, nReg, wP, wG, cP.data(), cG.data(), top)) return rc;
+  if (report) {
+    *report = gx_kmer_report{};
+    report->windows_peaks = wP;
+    report->windows_genome = wG;
+    report->regions_counted = nReg;
+    size_t n = 0;
+    if (int rc = gx_kmer_stats(k, cP.data(), wP, cG.data(), wG, nullptr, 0, &n)) return rc;
+    report->kmers_counted = n;
+    std::vector<gx_kmer_row> rows(std::max<size_t>(n, 1));
+    if (int rc = gx_kmer_stats(k, cP.data(), wP, cG.data(), wG, rows.data(), n, nullptr)) return rc;
+    report->n_top = (int)std::min<size_t>(n, 3);
+    for (int i = 0; i < report->n_top; i++) {
+      report->top_code[i] = rows[(size_t)i].code;
+      report->top_z[i] = rows[(size_t)i].z;
+    }
+    report->peaks_seconds = std::chrono::duration<double>(t1 - t0).count();
+    report->genome_seconds = std::chrono::duration<double>(t2 - t1).count();
+  }
+  return GX_OK;
 }
 
 uint32_t gx_subsample_draw(uint64_t seed, uint32_t sample, uint64_t index) { return subsample_draw(subsample_key(seed, sample), index); }

@@ -1731,4 +1731,83 @@ int gx_format_motif_summary(FILE* out, const gx_region* peaks, size_t n_peaks, c
   return GX_OK;
 }
 
+// --kmers (no Genrich counterpart): the strand collapse, the figures per canonical k-mer and the table.  Host only.
+uint32_t gx_kmer_revcomp(int k, uint32_t code) {
+  if (k < 1 || k > GX_KMER_MAX_K || (uint64_t)code >> (2 * k)) return 0xffffffffu;
+  uint32_t r = 0;
+  for (int j = 0; j < k; j++) {   // (the complement of digit b is 3 - b; the last base comes first)
+    r = (r << 2) | (3u - (code & 3u));
+    code >>= 2;
+  }
+  return r;
+}
+
+int gx_kmer_stats(int k, const uint64_t* counts_peaks, uint64_t windows_peaks, const uint64_t* counts_genome, uint64_t windows_genome,
+                  gx_kmer_row* rows, size_t cap, size_t* n_rows) {
+  if (k < 1 || k > GX_KMER_MAX_K || !counts_peaks || !counts_genome || (cap && !rows)) return GX_ERR_ORDER;
+  const uint32_t nT = 1u << (2 * k);
+  const uint64_t Wp = windows_peaks, Wg = windows_genome;
+  std::vector<gx_kmer_row> all;
+  for (uint32_t c = 0; c < nT; c++) {
+    const uint32_t rc = gx_kmer_revcomp(k, c);
+    if (rc < c) continue;   // (its canonical k-mer is rc)
+    const u128_t cp128 = (u128_t)counts_peaks[c] + (rc != c ? counts_peaks[rc] : 0), cg128 = (u128_t)counts_genome[c] + (rc != c ? counts_genome[rc] : 0);
+    if (cp128 > Wp || cg128 > Wg) return GX_ERR_ORDER;
+    const uint64_t cp = (uint64_t)cp128, cg = (uint64_t)cg128;
+    if (!cp) continue;
+    gx_kmer_row r{c, rc, cp, cg, std::nan(""), std::nan("")};
+    if (cg) {
+      r.enrichment = to_double(mul128(cp, Wg)) / to_double(mul128(cg, Wp));
+      if (cg != Wg)
+        r.z = diff256(mul128(cp, Wg), mul128(cg, Wp), nullptr) / std::sqrt(to_double(mul128((u128_t)Wp * cg, (u128_t)(Wg - cg))));
+    }
+    all.push_back(r);
+  }
+  std::sort(all.begin(), all.end(), [](const gx_kmer_row& a, const gx_kmer_row& b) {
+    const bool na = std::isnan(a.z), nb = std::isnan(b.z);
+    if (na != nb) return nb;
+    if (!na && a.z != b.z) return a.z > b.z;
+    if (a.count_peaks != b.count_peaks) return a.count_peaks > b.count_peaks;
+    return a.code < b.code;
+  });
+  if (n_rows) *n_rows = all.size();
+  if (const size_t n = std::min(cap, all.size())) std::copy(all.begin(), all.begin() + n, rows);
+  return GX_OK;
+}
+
+static void put_kmer(FILE* out, int k, uint32_t code) {
+  char s[GX_KMER_MAX_K + 1];
+  for (int j = 0; j < k; j++) s[j] = "ACGT"[(code >> (2 * (k - 1 - j))) & 3u];
+  s[k] = '\0';
+  fputs(s, out);
+}
+
+int gx_format_kmers(FILE* out, int k, int flank, uint64_t regions_counted, uint64_t windows_peaks, uint64_t windows_genome,
+                    const uint64_t* counts_peaks, const uint64_t* counts_genome, int top) {
+  if (!out || top < 0) return GX_ERR_ORDER;
+  size_t n = 0;
+  if (int rc = gx_kmer_stats(k, counts_peaks, windows_peaks, counts_genome, windows_genome, nullptr, 0, &n)) return rc;
+  std::vector<gx_kmer_row> rows(std::max<size_t>(n, 1));
+  if (int rc = gx_kmer_stats(k, counts_peaks, windows_peaks, counts_genome, windows_genome, rows.data(), n, nullptr)) return rc;
+  fprintf(out, "# k=%d flank=", k);
+  if (flank < 0) fprintf(out, "whole");
+  else fprintf(out, "%d", flank);
+  fprintf(out, " regions=%llu windows_peaks=%llu windows_genome=%llu kmers=%zu\n", (unsigned long long)regions_counted, (unsigned long long)windows_peaks,
+          (unsigned long long)windows_genome, n);
+  fprintf(out, "kmer\trevcomp\tcount_peaks\tcount_genome\tenrichment\tz\n");
+  const size_t shown = top ? std::min<size_t>(n, (size_t)top) : n;
+  for (size_t i = 0; i < shown; i++) {
+    const gx_kmer_row& r = rows[i];
+    put_kmer(out, k, r.code);
+    fputc('\t', out);
+    put_kmer(out, k, r.revcomp);
+    fprintf(out, "\t%llu\t%llu", (unsigned long long)r.count_peaks, (unsigned long long)r.count_genome);
+    if (std::isnan(r.enrichment)) fprintf(out, "\tNA");
+    else fprintf(out, "\t%.6f", r.enrichment);
+    if (std::isnan(r.z)) fprintf(out, "\tNA\n");
+    else fprintf(out, "\t%.4f\n", r.z);
+  }
+  return GX_OK;
+}
+
 }  // extern "C"

@@ -37,6 +37,7 @@
 #include "gx_xcor.h"
 #include "gx_gcbias.h"
 #include "gx_motifs.h"
+#include "gx_kmers.h"
 #include "gx_subsample.h"
 #include "gx_depth.h"
 #include "gx_peaksig.h"
@@ -611,6 +612,17 @@ struct gx_ctx {
   bool motReady = false;
   bool motUsed = false;             // k_motif_scan ran since the last gx_reset
   u32 motLastReruns = 0, motLastBatches = 0;    // the last pass: how often it ran again, its LDS batches
+  // every k-mer of the peaks and of the genome counted (gx_kmer_count_*, gx_kmers.h); nothing here exists before the first pass
+  DevBuf kmTable, kmOut, kmReg;     // the 4^k counters in table-index order, the control words, a pass's regions
+  PinnedBuf kmHost;                 // the table and the control words on their way back
+  std::vector<uint64_t> kmCounts;   // the last gx_kmer_count_peaks' counts in the public order (until gx_reset) ...
+  uint64_t kmWindows = 0, kmRegions = 0;   // ... its windows and the regions that hold at least k bases
+  u32 kmK = 0;
+  bool kmReady = false;
+  bool kmUsed = false;              // k_kmer_count ran since the last gx_reset
+  bool kmForceHbm = false;          // gx_kmer_force_hbm: every k takes the global-atomic path (for measurements)
+  bool kmLdsSet = false;            // the LDS instance may take 64 KiB
+  u32 kmLastPath = 0, kmLastFlushes = 0;   // the last pass: 0 LDS, 1 HBM; the flushes before a workgroup's end
   // the depth distribution of every closed sample's pileup (gx_set_depth_hist, gx_depth.h); the results live on the host
   struct DepthResult {
     int rep = 0;

@@ -91,6 +91,24 @@ int mot_grid(u64 nUnits, u32 step, unsigned grid, unsigned* chosen, const char**
   return GX_OK;
 }
 
+// The regions that have a position at all (on a chromosome of the table that is laid out, clamped to its length) as MotRegion
+// records with the units before each; the units of all (2^32 or more: the caller's mot_grid refuses), their positions added to
+// *positions.  Shared with the k-mer pass (gx_host_kmers.h).
+u64 mot_resolve(const gx_ctx* ctx, const gx_region* reg, size_t n, u32 step, std::vector<MotRegion>& rs, u64* positions) {
+  u64 nUnits = 0;
+  for (size_t i = 0; i < n && !(nUnits >> 32); i++) {
+    if (reg[i].chrom >= ctx->nChrom) continue;
+    const GcChrom& cc = ctx->gcChrom[reg[i].chrom];
+    const u32 e = std::min(reg[i].end, cc.len);
+    if (!cc.laid || reg[i].start >= e) continue;
+    rs.push_back(MotRegion{cc.off, reg[i].start, e, (u32)i, (u32)nUnits});
+    *positions += e - reg[i].start;
+    const u64 runs = ((u64)(e - reg[i].start) + 63) / 64;
+    nUnits += (runs + step - 1) / step;
+  }
+  return nUnits;
+}
+
 // a pass that is set up: its arguments, its grid, what must live until the stream is drained
 struct MotRun {
   MotArgs a{};
@@ -114,17 +132,7 @@ int mot_setup(gx_ctx* ctx, const gx_region* reg, size_t n, MotGeometry g, MotRun
   const char* why = "";
   if (mot_grid(0, g.step, g.grid, &r.grid, &why)) return refuse(ctx, why);   // (the step and the grid, before anything is done)
   if (int rc = gc_current(ctx)) return rc;
-  u64 nUnits = 0;
-  for (size_t i = 0; i < n && !(nUnits >> 32); i++) {
-    if (reg[i].chrom >= ctx->nChrom) continue;
-    const GcChrom& cc = ctx->gcChrom[reg[i].chrom];
-    const u32 e = std::min(reg[i].end, cc.len);
-    if (!cc.laid || reg[i].start >= e) continue;
-    r.rs.push_back(MotRegion{cc.off, reg[i].start, e, (u32)i, (u32)nUnits});
-    r.positions += e - reg[i].start;
-    const u64 runs = ((u64)(e - reg[i].start) + 63) / 64;
-    nUnits += (runs + g.step - 1) / g.step;
-  }
+  const u64 nUnits = mot_resolve(ctx, reg, n, g.step, r.rs, &r.positions);
   if (mot_grid(nUnits, g.step, g.grid, &r.grid, &why)) return refuse(ctx, why);
   if (!nM || r.rs.empty()) return GX_OK;
   hipStream_t s = ctx->stream;

@@ -153,6 +153,38 @@ __device__ __forceinline__ u32 mot_window(const unsigned long long* __restrict__
   return (u32)(sh ? (lo >> sh) | (hi << (64u - sh)) : lo);
 }
 
+// The front end k_motif_scan shares with k_kmer_count (gx_kmers.h).
+// the region of unit u (unit0 <= u, the last such): a bounded binary search
+__device__ __forceinline__ MotRegion mot_unit_region(const MotRegion* __restrict__ reg, u32 nReg, u32 u) {
+  u32 lo = 0, hi = nReg;
+  for (int it = 0; it < 32 && lo + 1 < hi; it++) {
+    const u32 mid = (lo + hi) >> 1;
+    if (reg[mid].unit0 <= u) lo = mid;
+    else hi = mid;
+  }
+  return reg[lo];
+}
+// a lane's position in run k of unit u of its region: x, the bases from x to the region's end (0: none) and the 32 bits of each
+// vector from x on; false (wave-uniform) when the run lies behind the region's end
+struct MotLane { u64 x; u32 room, wg, wp, wa; };
+__device__ __forceinline__ bool mot_run_lane(const unsigned long long* __restrict__ gc, const unsigned long long* __restrict__ ag,
+                                             const unsigned long long* __restrict__ acgt, const MotRegion& rg, u32 u, u32 step, u32 k, u32 lane,
+                                             MotLane& L) {
+  const u64 first = (u64)rg.start + ((u64)(u - rg.unit0) * step + k) * 64u;   // the run's first position
+  if (first >= rg.end) return false;
+  L.x = first + lane;
+  L.room = L.x < rg.end ? (u32)(rg.end - L.x) : 0u;
+  L.wg = L.wp = L.wa = 0;
+  if (L.room) {
+    const u64 w = rg.off + (L.x >> 6);
+    const u32 sh = (u32)(L.x & 63u);
+    L.wg = mot_window(gc, w, sh);
+    L.wp = mot_window(ag, w, sh);
+    L.wa = mot_window(acgt, w, sh);
+  }
+  return true;
+}
+
 template <bool LIST>
 __global__ __launch_bounds__(MOT_NT) void k_motif_scan(MotArgs a) {
   extern __shared__ int mot_lds[];
@@ -174,26 +206,12 @@ __global__ __launch_bounds__(MOT_NT) void k_motif_scan(MotArgs a) {
       const u64 u64u = u0 + wave;
       if (u64u >= a.nUnits) continue;   // (wave-uniform)
       const u32 u = (u32)u64u;
-      u32 lo = 0, hi = a.nReg;   // the region of unit u (unit0 <= u, the last such)
-      for (int it = 0; it < 32 && lo + 1 < hi; it++) {
-        const u32 mid = (lo + hi) >> 1;
-        if (a.reg[mid].unit0 <= u) lo = mid;
-        else hi = mid;
-      }
-      const MotRegion rg = a.reg[lo];
+      const MotRegion rg = mot_unit_region(a.reg, a.nReg, u);
       for (u32 k = 0; k < a.step; k++) {
-        const u64 first = (u64)rg.start + ((u64)(u - rg.unit0) * a.step + k) * 64u;   // the run's first position
-        if (first >= rg.end) break;   // (wave-uniform)
-        const u64 x = first + lane;
-        const u32 room = x < rg.end ? (u32)(rg.end - x) : 0u;   // bases from x to the region's end
-        u32 wg = 0, wp = 0, wa = 0;
-        if (room) {
-          const u64 w = rg.off + (x >> 6);
-          const u32 sh = (u32)(x & 63u);
-          wg = mot_window(a.gc, w, sh);
-          wp = mot_window(a.ag, w, sh);
-          wa = mot_window(a.acgt, w, sh);
-        }
+        MotLane ln;
+        if (!mot_run_lane(a.gc, a.ag, a.acgt, rg, u, a.step, k, lane, ln)) break;   // (wave-uniform)
+        const u64 x = ln.x;
+        const u32 room = ln.room, wg = ln.wg, wp = ln.wp, wa = ln.wa;
         for (u32 m = 0; m < nb; m++) {
           const MotMeta mm = meta[m];
           const u32 L = mm.width, mask = L >= 32u ? ~0u : (1u << L) - 1u;

@@ -236,6 +236,24 @@ Threads splitThreads(int n) {
   exit(EXIT_FAILURE);
 }
 
+// --help-kmers: the block of --kmers and its sub-options, likewise
+[[noreturn]] void usageKmers() {
+  fprintf(stderr,
+          "  --kmers FILE [--kmer-k K] [--kmer-flank N] [--kmer-top N]   the K-mers (8; 1 .. 12) that are over-represented in the\n"
+          "                  called peaks: every window of K known bases of every peak -- whole, or with --kmer-flank the N bases to\n"
+          "                  either side of its summit -- counted on the device, and every window of the WHOLE genome (every\n"
+          "                  chromosome that takes part; counted, not sampled or shuffled) as the background.  A K-mer and its\n"
+          "                  reverse complement are one row (the smaller of the two names it; a palindrome counts once).  A TSV: a #\n"
+          "                  line (k, flank, the regions counted, the windows of the peaks and of the genome, the K-mers counted in\n"
+          "                  the peaks), then kmer, revcomp, count_peaks, count_genome, enrichment (the peaks' share over the\n"
+          "                  genome's) and z, the binomial z-score of count_peaks among the peaks' windows at the genome's rate; the\n"
+          "                  N (100; 0: all) rows of highest z.  Overlapping windows are not independent: z ranks K-mers, it is not a\n"
+          "                  p-value.  A window with an unknown base is not counted; overlapping regions count twice; -E regions\n"
+          "                  are NOT masked.  Needs --genome FASTA; works with -z, --devices and next to every other output; not\n"
+          "                  with -X, -P or --events-only; -v: the windows, the three top K-mers and the genome pass's seconds\n");
+  exit(EXIT_FAILURE);
+}
+
 }  // namespace
 
 #include "host_options.h"  // the table of long options, parseOptions (behind the thread budget and the usage texts, which they call)

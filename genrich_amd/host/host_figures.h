@@ -497,11 +497,10 @@ void loadGenome(State& S) {
   const Opts& o = S.o;
   const auto t0 = std::chrono::steady_clock::now();
   for (gx_ctx* g : S.devs.ctx) check(S, gx_set_genome(g, 1), g);
-  if (o.motifsFile)   // (the scan needs the bases themselves: the third vector, and the motifs with it)
-    for (gx_ctx* g : S.devs.ctx) {
-      check(S, gx_set_genome_bases(g, 1), g);
-      check(S, gx_set_motifs(g, S.motifRecs.data(), (int)S.motifRecs.size(), S.motifScores.data()), g);
-    }
+  if (o.motifsFile || o.kmersFile)   // (the scan and the k-mers need the bases themselves: the third vector)
+    for (gx_ctx* g : S.devs.ctx) check(S, gx_set_genome_bases(g, 1), g);
+  if (o.motifsFile)   // (... and the motifs with it)
+    for (gx_ctx* g : S.devs.ctx) check(S, gx_set_motifs(g, S.motifRecs.data(), (int)S.motifRecs.size(), S.motifScores.data()), g);
   GenomeSink sink(S);
   const size_t chunk = (size_t)1 << 22;
   unsigned char magic[2] = {0, 0};
@@ -641,6 +640,30 @@ void writeMotifs(State& S) {
   for (size_t k = 0; k < enr.size() && k < 3; k++)
     fprintf(stderr, "  Motif %s (%s): enrichment %f\n", S.motifs[enr[k].second].id.c_str(), S.motifs[enr[k].second].name.c_str(), enr[k].first);
   fprintf(stderr, "  Motif summary: the peaks in %.3f s, the genome pass in %.3f s\n", rep.peaks_seconds, rep.genome_seconds);
+}
+
+// --kmers FILE [--kmer-k K] [--kmer-flank N] [--kmer-top N]: every K-mer of the called peaks (whole, or N bases to either side of
+// the summit) counted on the device that owns the chromosome, and of the whole genome (k_kmer_count); the strands collapsed, the
+// enrichment and the z-score per canonical K-mer, the N highest.  With -v the windows, the three top K-mers and the genome pass's
+// seconds
+void writeKmers(State& S) {
+  const Opts& o = S.o;
+  gx_kmer_report rep{};
+  writeFile(S, o.kmersFile, [&](FILE* f) {
+    return gx_write_kmers_group(S.devs.ctx.data(), (int)S.devs.n(), o.kmerK, o.kmerFlankOpt ? o.kmerFlank : -1, o.kmerTop, f, &rep);
+  });
+  if (!o.verbose) return;
+  fprintf(stderr, "K-mers (k = %d): %llu windows in %llu regions of the peaks, %llu in the genome, %llu canonical k-mers counted\n", o.kmerK,
+          (unsigned long long)rep.windows_peaks, (unsigned long long)rep.regions_counted, (unsigned long long)rep.windows_genome,
+          (unsigned long long)rep.kmers_counted);
+  for (int i = 0; i < rep.n_top; i++) {
+    char s[GX_KMER_MAX_K + 1];
+    for (int j = 0; j < o.kmerK; j++) s[j] = "ACGT"[(rep.top_code[i] >> (2 * (o.kmerK - 1 - j))) & 3u];
+    s[o.kmerK] = '\0';
+    if (std::isnan(rep.top_z[i])) fprintf(stderr, "  K-mer %s: z NA\n", s);
+    else fprintf(stderr, "  K-mer %s: z %.4f\n", s, rep.top_z[i]);
+  }
+  fprintf(stderr, "  K-mers: the peaks in %.3f s, the genome pass in %.3f s\n", rep.peaks_seconds, rep.genome_seconds);
 }
 
 // --xcor FILE / --xcor-metrics FILE: the strand cross-correlation of each sample's 5' ends, counted on the device when the
@@ -895,6 +918,7 @@ const Figure FIGURES[] = {
     {[](const Opts& o) { return o.gcBiasFile != nullptr; }, KEPT, writeGcBias},
     {[](const Opts& o) { return o.gcPeaksFile != nullptr; }, 0, writeGcPeaks},
     {[](const Opts& o) { return o.motifsFile != nullptr; }, 0, writeMotifs},
+    {[](const Opts& o) { return o.kmersFile != nullptr; }, 0, writeKmers},
     {[](const Opts& o) { return o.saturationFile != nullptr; }, KEPT, writeSaturation},
     {[](const Opts& o) { return o.reproOn(); }, KEPT, writeReproducibility},
     {[](const Opts& o) { return o.profileBed != nullptr; }, 0, writeProfile},

@@ -138,6 +138,11 @@ const LongOpt LONG_OPTS[] = {
     {"motif-pvalue", required_argument, real(&Opts::motifPvalue, &Opts::motifPvalueOpt, [](double p) { return p > 0.0 && p <= 1.0; }, ": --motif-pvalue takes a number in (0, 1]")},
     {"motif-pseudocount", required_argument, real(&Opts::motifPseudo, &Opts::motifPseudoOpt, [](double x) { return x >= 0.0 && std::isfinite(x); }, ": --motif-pseudocount takes a number >= 0")},
     {"help-motifs", no_argument, help(usageMotifs)},
+    {"kmers", required_argument, path(&Opts::kmersFile)},
+    {"kmer-k", required_argument, strict(&Opts::kmerK, &Opts::kmerKOpt, 1, GX_KMER_MAX_K, ": --kmer-k takes an integer in [1, 12]")},
+    {"kmer-flank", required_argument, strict(&Opts::kmerFlank, &Opts::kmerFlankOpt, 0, 1000000000, ": --kmer-flank takes an integer in [0, 1000000000]")},
+    {"kmer-top", required_argument, strict(&Opts::kmerTop, &Opts::kmerTopOpt, 0, 16777216, ": --kmer-top takes an integer in [0, 16777216] (0: all)")},
+    {"help-kmers", no_argument, help(usageKmers)},
 };
 const int LONG_BASE = 1000;   // what getopt_long returns for row i: LONG_BASE + i (above every character of the short options)
 

@@ -76,7 +76,11 @@ void validate(State& S) {
     die("", "--motif-hits, --motif-summary, --motif-pvalue and --motif-pseudocount need --motifs FILE");
   // (the motifs are scanned in the peaks this run calls, on a device context: -P has neither)
   if (o.motifsFile && !o.callsPeaks()) die("", "--motifs needs the peaks of this run on a device (not with -X, -P or --events-only)");
-  if (o.genomeFile && !o.gcBiasFile && !o.gcPeaksFile && !o.motifsFile) die("", "--genome needs --gc-bias FILE or --gc-peaks FILE");
+  if (o.kmersFile && !o.genomeFile) die("", "--kmers needs the reference sequence (--genome FASTA)");
+  if ((o.kmerKOpt || o.kmerFlankOpt || o.kmerTopOpt) && !o.kmersFile) die("", "--kmer-k, --kmer-flank and --kmer-top need --kmers FILE");
+  // (the k-mers are counted in the peaks this run calls, on a device context: -P has neither)
+  if (o.kmersFile && !o.callsPeaks()) die("", "--kmers needs the peaks of this run on a device (not with -X, -P or --events-only)");
+  if (o.genomeFile && !o.gcBiasFile && !o.gcPeaksFile && !o.motifsFile && !o.kmersFile) die("", "--genome needs --gc-bias FILE or --gc-peaks FILE");
   // (the bias counts the events the library keeps: none with -P or --events-only; -X is fine)
   if (o.gcBiasFile && !o.buildsPileups()) die("", "--gc-bias needs the intervals of this run (not with -P or --events-only)");
   // (the content is taken in the peaks this run calls, on a device context: -P has neither)

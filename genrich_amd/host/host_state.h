@@ -76,6 +76,9 @@ struct Opts {
   const char* motifSummaryFile = nullptr;  // --motif-summary FILE: per motif the peaks' and the genome's counts and the enrichment
   double motifPvalue = 1e-4, motifPseudo = 1.0;   // --motif-pvalue P, --motif-pseudocount X
   bool motifPvalueOpt = false, motifPseudoOpt = false;
+  const char* kmersFile = nullptr;         // --kmers FILE: the k-mers of the called peaks against the whole genome
+  int kmerK = 8, kmerFlank = -1, kmerTop = 100;   // --kmer-k K, --kmer-flank N (none: the whole peaks), --kmer-top N (0: all)
+  bool kmerKOpt = false, kmerFlankOpt = false, kmerTopOpt = false;
   uint64_t genomeLen = 0;
   int extend = 0, minMapQ = 0, minLen = 0, maxGap = 100, atacLen5 = 100, atacLen3 = 0;
   float asDiff = 0.0f, pqvalue = 0.01f, minAUC = 200.0f;

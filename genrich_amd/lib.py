@@ -147,6 +147,10 @@ GX_PATH_IVSTAT = 67108864       # gx_path_info bit 26: k_ivstat ran (gx_interval
 GX_PATH_XCOR = 134217728        # gx_path_info bit 27: k_xc_set / k_xc_corr ran (gx_set_xcor with a sample closed, gx_push_tags, gx_xcor_tags)
 GX_PATH_GC = 1073741824         # gx_path_info bit 30: a kernel of the genome / GC passes ran (gx_push_sequence, gx_gc_content, gx_gc_bias, gx_gc_bias_events)
 GX_PATH_MOTIFS = 2147483648     # gx_path_info bit 31: k_motif_scan ran (gx_motif_scan_regions, gx_motif_scan_peaks, gx_motif_scan_genome)
+GX_PATH_KMERS = 4096            # gx_path_info bit 12: k_kmer_count ran (gx_kmer_count_regions, gx_kmer_count_peaks, gx_kmer_count_genome)
+KMER_MAX_K = 12                 # GX_KMER_MAX_K
+KMER_LDS_MAX_K = 7              # GX_KMER_LDS_MAX_K
+KMER_ROW_DTYPE = np.dtype([("code", "<u4"), ("revcomp", "<u4"), ("count_peaks", "<u8"), ("count_genome", "<u8"), ("enrichment", "<f8"), ("z", "<f8")])   # gx_kmer_row
 MOTIF_MAX_WIDTH = 32            # GX_MOTIF_MAX_WIDTH
 MOTIF_MAX = 4096                # GX_MOTIF_MAX
 MOTIF_SCALE = 128               # GX_MOTIF_SCALE
@@ -475,6 +479,18 @@ _SIGS = {
                                 C.c_void_p, C.c_void_p],
     "gx_write_motif_hits_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "gx_write_motif_summary_group": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "gx_kmer_count_regions": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)],
+    "gx_kmer_count_peaks": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "gx_get_kmer_counts": [C.c_void_p, C.c_void_p, C.c_size_t],
+    "gx_kmer_count_genome": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)],
+    "gx_kmer_count_genome_group": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)],
+    "gx_kmer_last": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)],
+    "gx_kmer_force_hbm": [C.c_void_p, C.c_int],
+    "gx_kmer_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                         C.POINTER(C.c_int)],
+    "gx_kmer_stats": [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "gx_format_kmers": [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int],
+    "gx_write_kmers_group": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "gx_interval_stats": [C.c_void_p, C.POINTER(C.c_int)],
     "gx_get_interval_lengths": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
@@ -555,6 +571,7 @@ def load_library(path: str = os.environ.get("GENRICH_AMD_LIB", LIB_PATH)):
     lib.gx_filter_saturation.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     lib.gx_fp_class.restype, lib.gx_fp_class.argtypes = C.c_uint32, [C.c_uint64]
     lib.gx_subsample_draw.restype, lib.gx_subsample_draw.argtypes = C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint64]
+    lib.gx_kmer_revcomp.restype, lib.gx_kmer_revcomp.argtypes = C.c_uint32, [C.c_int, C.c_uint32]
     lib.gx_fp_class_lo.restype, lib.gx_fp_class_lo.argtypes = C.c_uint64, [C.c_uint32]
     lib.gx_fp_class_hi.restype, lib.gx_fp_class_hi.argtypes = C.c_uint64, [C.c_uint32]
     _lib = lib
@@ -1129,6 +1146,70 @@ def motif_summary_text(ctxs, motifs, ids, motif_names, p_threshold) -> bytes:
     arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
     rec, ci, cn, p = _motif_table_args(motifs, ids, motif_names, p_threshold)
     return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_motif_summary_group(arr, len(ctxs), rec.ctypes.data, ci, cn, p.ctypes.data, len(rec), f)))
+
+
+def kmer_geometry():
+    """(lanes, grid, positions_per_step, step_words, flush_runs, max_k, lds_max_k) of the k-mer count as the library was built
+    (gx_kmer_geometry); host-only."""
+    lib = load_library()
+    lanes, grid, mk, lk = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    pos, step, flush = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    lib.gx_kmer_geometry(C.byref(lanes), C.byref(grid), C.byref(pos), C.byref(step), C.byref(flush), C.byref(mk), C.byref(lk))
+    return lanes.value, grid.value, pos.value, step.value, flush.value, mk.value, lk.value
+
+
+def kmer_revcomp(k, code):
+    """The code of the reverse complement of a k-mer's code (gx_kmer_revcomp); None where the library refuses; host-only."""
+    r = load_library().gx_kmer_revcomp(int(k), int(code))
+    return None if r == 0xffffffff else r
+
+
+def _kmer_tables(k, counts_peaks, counts_genome):
+    cp = np.ascontiguousarray(counts_peaks, dtype=np.uint64)
+    cg = np.ascontiguousarray(counts_genome, dtype=np.uint64)
+    if cp.size != 4 ** int(k) or cg.size != 4 ** int(k):
+        raise ValueError("kmers: a table of 4^k counts")
+    return cp, cg
+
+
+def kmer_stats(k, counts_peaks, windows_peaks, counts_genome, windows_genome):
+    """KMER_ROW_DTYPE rows, one per canonical k-mer counted in the peaks, sorted as --kmers prints them (gx_kmer_stats); host-only."""
+    lib = load_library()
+    cp, cg = _kmer_tables(k, counts_peaks, counts_genome)
+    n = C.c_size_t(0)
+    rc = lib.gx_kmer_stats(int(k), cp.ctypes.data, int(windows_peaks), cg.ctypes.data, int(windows_genome), None, 0, C.byref(n))
+    if rc:
+        raise RuntimeError(f"gx_kmer_stats: {rc}")
+    rows = np.zeros(max(n.value, 1), dtype=KMER_ROW_DTYPE)
+    rc = lib.gx_kmer_stats(int(k), cp.ctypes.data, int(windows_peaks), cg.ctypes.data, int(windows_genome), rows.ctypes.data, n.value, None)
+    if rc:
+        raise RuntimeError(f"gx_kmer_stats: {rc}")
+    return rows[:n.value]
+
+
+def format_kmers(k, flank, regions_counted, windows_peaks, windows_genome, counts_peaks, counts_genome, top=100) -> bytes:
+    """--kmers' table (gx_format_kmers); host-only."""
+    lib = load_library()
+    cp, cg = _kmer_tables(k, counts_peaks, counts_genome)
+    return _to_tmpfile(lambda f: lib.gx_format_kmers(f, int(k), int(flank), int(regions_counted), int(windows_peaks), int(windows_genome), cp.ctypes.data,
+                                                     cg.ctypes.data, int(top)))
+
+
+def kmer_count_genome_group(ctxs, k):
+    """(counts uint64[4^k], windows) of the genome pass added over the contexts of a run (gx_kmer_count_genome_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    out = np.zeros(4 ** int(k), dtype=np.uint64)
+    w = C.c_uint64(0)
+    ctxs[0]._check(lib.gx_kmer_count_genome_group(arr, len(ctxs), int(k), out.ctypes.data, out.size, C.byref(w)))
+    return out, w.value
+
+
+def kmers_text(ctxs, k, flank=-1, top=100) -> bytes:
+    """--kmers' table over the contexts of a run (gx_write_kmers_group)."""
+    lib = load_library()
+    arr = (C.c_void_p * len(ctxs))(*[c.ctx for c in ctxs])
+    return _to_tmpfile(lambda f: ctxs[0]._check(lib.gx_write_kmers_group(arr, len(ctxs), int(k), int(flank), int(top), f, None)))
 
 
 def interval_stats_geometry():
@@ -2189,6 +2270,49 @@ class Genrich:
         cnt = self._motif_counts()
         self._check(self.lib.gx_motif_scan_genome(self.ctx, cnt[0].ctypes.data, cnt[1].ctypes.data, cnt[2].ctypes.data, self.n_motifs))
         return cnt[:, :self.n_motifs]
+
+    # -- every k-mer counted (include/genrich_amd.h, gx_kmer_count_regions) --------------------------------------------------
+    _kmer_k = 0
+
+    def kmer_count_regions(self, regions, k, grid=0, step_words=0, flush_runs=0):
+        """(counts uint64[4^k] in the public order, windows) of the k-mers of `regions` (REGION_DTYPE), by the kernel alone
+        (gx_kmer_count_regions); 0: the library's geometry."""
+        reg = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
+        out = np.zeros(4 ** int(k) if 1 <= int(k) <= KMER_MAX_K else 1, dtype=np.uint64)
+        w = C.c_uint64(0)
+        self._check(self.lib.gx_kmer_count_regions(self.ctx, reg.ctypes.data if reg.size else None, reg.size, int(k), int(grid), int(step_words),
+                                                   int(flush_runs), out.ctypes.data, C.byref(w)))
+        return out, w.value
+
+    def kmer_count_peaks(self, k, flank=-1):
+        """Count the k-mers of the peaks find_peaks left on this context (gx_kmer_count_peaks): (windows, regions counted)."""
+        w, r = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.gx_kmer_count_peaks(self.ctx, int(k), int(flank), C.byref(w), C.byref(r)))
+        self._kmer_k = int(k)
+        return w.value, r.value
+
+    def get_kmer_counts(self):
+        """uint64[4^k] of the last kmer_count_peaks() (gx_get_kmer_counts)."""
+        out = np.zeros(4 ** self._kmer_k, dtype=np.uint64)
+        self._check(self.lib.gx_get_kmer_counts(self.ctx, out.ctypes.data, out.size))
+        return out
+
+    def kmer_count_genome(self, k):
+        """(counts uint64[4^k], windows) over every chromosome that takes part (gx_kmer_count_genome)."""
+        out = np.zeros(4 ** int(k) if 1 <= int(k) <= KMER_MAX_K else 1, dtype=np.uint64)
+        w = C.c_uint64(0)
+        self._check(self.lib.gx_kmer_count_genome(self.ctx, int(k), out.ctypes.data, out.size, C.byref(w)))
+        return out, w.value
+
+    def kmer_last(self):
+        """(path: 0 LDS, 1 HBM; flushes before a workgroup's end) of the last k-mer pass (gx_kmer_last)."""
+        p, f = C.c_int(0), C.c_uint32(0)
+        self._check(self.lib.gx_kmer_last(self.ctx, C.byref(p), C.byref(f)))
+        return p.value, f.value
+
+    def kmer_force_hbm(self, on=True):
+        """Every k takes the global-atomic path (gx_kmer_force_hbm): for measurements; no result changes."""
+        self._check(self.lib.gx_kmer_force_hbm(self.ctx, 1 if on else 0))
 
     # -- lengths and chromosome tallies of the samples' intervals (include/genrich_amd.h, gx_interval_stats) --------------
     def interval_stats(self):

@@ -938,6 +938,77 @@ int gx_write_motif_hits_group(gx_ctx* const* ctxs, int n_ctx, const char* const*
 int gx_write_motif_summary_group(gx_ctx* const* ctxs, int n_ctx, const gx_motif* motifs, const char* const* ids, const char* const* motif_names,
                                  const double* p_threshold, int n_motifs, FILE* out);
 
+/* ---- every k-mer of the called peaks counted against the whole genome (no Genrich counterpart: the counting step that HOMER,
+ *      MEME-ChIP or DREME begin with, over the peak sequences cut out of the FASTA once more and a sampled background) ----
+ * Needs the bases (gx_set_genome_bases); no sample, no motif.
+ * k is 1 .. GX_KMER_MAX_K.  THE WINDOW at position x of a region [start, end) on chromosome c is [x, x + k).  It is COUNTED iff
+ * start <= x, x + k <= min(end, len[c]) and all k acgt bits are set (the motif block's SCANNED rule with L = k).
+ * THE CODE of a window is sum_j b(x + j) * 4^(k - 1 - j) with A 0, C 1, G 2, T 3: lexicographic order, the first base most
+ * significant.  The device counts FORWARD codes only: counts[4^k] and windows, all exact uint64.
+ * STRAND COLLAPSE happens on the host: the canonical k-mer of a code is the smaller of the code and its reverse complement
+ * (gx_kmer_revcomp); its count is counts[c] + counts[rc(c)], or counts[c] alone for a palindrome.
+ * Over a set of regions every region is counted on its own: overlapping regions count twice.  -E regions are NOT masked.  No
+ * result depends on the launch geometry, the step, the flush bound, the table path, the split of the pushes or the number of
+ * GPUs.  After every pass the host checks sum(counts) == windows; a mismatch is GX_ERR_ARR with a text, not a result.
+ * Two paths: k <= GX_KMER_LDS_MAX_K counts in 4^k 32-bit LDS counters per workgroup, flushed to the 64-bit table; above it 64-bit
+ * global atomics go straight into the table (gx_kmers.h).
+ *
+ * gx_kmer_count_regions: k_kmer_count over n regions of the caller's (any order, overlapping, empty or inverted; a chromosome
+ *   outside the table, skipped or not owned counts nothing).  grid / step_words / flush_runs = 0: the library's choices; else
+ *   that many workgroups (chosen or refused exactly as gx_motif_grid does), runs of 64 positions per unit (1 .. 16), and the runs
+ *   a workgroup walks at most between two flushes of its LDS counters (1 .. 2^25; kept per round of four units, a round alone is
+ *   always walked).  counts takes 4^k values (NULL: not wanted), windows one.  k outside 1 .. 12, no bases, a sample open or a
+ *   refused geometry: GX_ERR_ORDER with a text.  For tests and measurements.
+ * gx_kmer_count_peaks: after gx_find_peaks, with no sample open and the bases on (else GX_ERR_ORDER): the peaks this context
+ *   called are the regions; flank < 0: the whole peaks; flank >= 0: [max(start, summit - flank), min(end, summit + flank + 1))
+ *   with the summit of narrowPeak's column 10.  *regions_counted: the regions that hold at least k bases.  No peak is legal.
+ *   Nothing of it is allocated or launched before the first call; its phase is "kmers".  gx_get_kmer_counts: min(cap, 4^k) of
+ *   the counts.  Until gx_reset, the next sample or the next call.
+ * gx_kmer_count_genome: the pass over every chromosome that takes part (the rule of gx_motif_scan_genome); min(cap, 4^k) counts.
+ *   gx_kmer_count_genome_group: every context's pass is launched before the first is waited for; the counts are added.
+ * gx_kmer_last: the path of the last pass (0 LDS, 1 HBM) and the flushes its workgroups made before their end.
+ * gx_kmer_force_hbm: on: every k takes the HBM path (for measurements of the 7 | 8 split); it changes no result.
+ * gx_kmer_geometry: the lanes of a workgroup, the most workgroups with grid = 0, the positions per step (64), the default runs
+ *   per unit, the flush bound, GX_KMER_MAX_K and GX_KMER_LDS_MAX_K as the library was built.  Needs no device. */
+#define GX_KMER_MAX_K 12
+#define GX_KMER_LDS_MAX_K 7
+int gx_kmer_count_regions(gx_ctx* ctx, const gx_region* regions, size_t n, int k, unsigned grid, uint32_t step_words, uint64_t flush_runs,
+                          uint64_t* counts, uint64_t* windows);
+int gx_kmer_count_peaks(gx_ctx* ctx, int k, int flank, uint64_t* windows, uint64_t* regions_counted);
+int gx_get_kmer_counts(gx_ctx* ctx, uint64_t* counts, size_t cap);
+int gx_kmer_count_genome(gx_ctx* ctx, int k, uint64_t* counts, size_t cap, uint64_t* windows);
+int gx_kmer_count_genome_group(gx_ctx* const* ctxs, int n_ctx, int k, uint64_t* counts, size_t cap, uint64_t* windows);
+int gx_kmer_last(gx_ctx* ctx, int* path, uint32_t* flushes);
+int gx_kmer_force_hbm(gx_ctx* ctx, int on);
+int gx_kmer_geometry(int* lanes, int* grid, uint32_t* positions_per_step, uint32_t* step_words, uint64_t* flush_runs, int* max_k, int* lds_max_k);
+/* Host only (gx_emit.cpp); no context, no device.
+ * gx_kmer_revcomp: the code of the reverse complement of `code` (k outside 1 .. 12 or a code of 4^k or more: 0xffffffff).
+ * gx_kmer_stats: one row per canonical k-mer with count_peaks > 0.  With cp, cg its counts in the peaks and in the genome (both
+ *   strands added, a palindrome once) and Wp, Wg the windows: enrichment = (cp * Wg) / (cg * Wp), two exact 128-bit products each
+ *   converted to double once (NaN when cg is 0); z = (cp * Wg - cg * Wp) / sqrt(Wp * cg * (Wg - cg)), the numerator an exact
+ *   signed integer, the radicand an exact integer, each converted once, then sqrt, then one division (NaN when cg is 0 or
+ *   equals Wg): the binomial z-score of cp among Wp draws at rate cg / Wg.  Overlapping windows are not independent: z ranks
+ *   k-mers, it is not a p-value.  Sorted by z descending with NaN last, then count_peaks descending, then code ascending.
+ *   *n_rows: the rows there are; min(cap, *n_rows) are written.  A canonical count above its windows: GX_ERR_ORDER.
+ * gx_format_kmers: --kmers' table: `# k=K flank=F regions=N windows_peaks=Wp windows_genome=Wg kmers=M` (F = whole for a
+ *   negative flank, M the rows there are), the header `kmer revcomp count_peaks count_genome enrichment z`, then the first `top`
+ *   rows (0: all); enrichment "%.6f", z "%.4f", NA for NaN.
+ * gx_write_kmers_group: gx_kmer_count_peaks on every context, gx_kmer_count_genome_group, the counts added, the table. */
+typedef struct { uint32_t code, revcomp; uint64_t count_peaks, count_genome; double enrichment, z; } gx_kmer_row;
+typedef struct {
+  uint64_t windows_peaks, windows_genome, regions_counted, kmers_counted;
+  double peaks_seconds, genome_seconds;
+  uint32_t top_code[3];
+  double top_z[3];
+  int n_top;
+} gx_kmer_report;
+uint32_t gx_kmer_revcomp(int k, uint32_t code);
+int gx_kmer_stats(int k, const uint64_t* counts_peaks, uint64_t windows_peaks, const uint64_t* counts_genome, uint64_t windows_genome,
+                  gx_kmer_row* rows, size_t cap, size_t* n_rows);
+int gx_format_kmers(FILE* out, int k, int flank, uint64_t regions_counted, uint64_t windows_peaks, uint64_t windows_genome,
+                    const uint64_t* counts_peaks, const uint64_t* counts_genome, int top);
+int gx_write_kmers_group(gx_ctx* const* ctxs, int n_ctx, int k, int flank, int top, FILE* out, gx_kmer_report* report);
+
 /* ---- depth distribution of each sample's pileup (no Genrich counterpart: what deepTools' plotCoverage estimates from a
  *      million sampled positions, what `samtools depth | awk` or mosdepth's distribution file take from another pass) ----
  * A sample = every gx_sample_end of the run, in call order, as for gx_get_coverage.  For one closed sample on one context:
@@ -1532,6 +1603,7 @@ int gx_set_knob(gx_ctx* ctx, const char* name, const char* value);
 #define GX_PATH_SWEEP_OVERLAP 536870912u /* bit 29: ... GX_PATH_LOOSE_SWEEP whose run pass rode in the launch that scanned the tiles and closed the sample (k_scan_iv_close_runs), ahead of gx_find_peaks: the sweep launched no k_runs */
 #define GX_PATH_GC 1073741824u /* bit 30: a kernel of the genome / GC passes ran since the last gx_reset (gx_push_sequence, gx_genome_info, gx_gc_content, gx_gc_bias, gx_gc_bias_events) */
 #define GX_PATH_MOTIFS 2147483648u /* bit 31: k_motif_scan ran since the last gx_reset (gx_motif_scan_regions, gx_motif_scan_peaks, gx_motif_scan_genome) */
+#define GX_PATH_KMERS 4096u /* bit 12: k_kmer_count ran since the last gx_reset (gx_kmer_count_regions, gx_kmer_count_peaks, gx_kmer_count_genome) */
 #define GX_PATH_FRAC_PAIRS 128u /* bit 7: ... and the pair records carried a weight class (k_sort_a<FRAC> / k_sbtile<.., FRAC>: -s multimapping) */
 int gx_path_info(gx_ctx* ctx, unsigned* flags);
 
